@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json metric: 2D slices/s of the ACDC U-Net + InfoNCE training step.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -12,16 +12,22 @@ RAdam.  One step = forward of 16 + 32 slices, supervised KL loss, InfoNCE loss, 
 optimizer step (+ gradient all-reduce over RCCL when N > 1).  Inputs are resident in HBM.
 `value` = (n_l + n_unl) * world / step_time  (dataset slices consumed per second).
 
-Extra JSON objects (see DESIGN.md "Measurement"):
+A plain run sets up, warms up, times the steps, writes --dump-outputs if asked and prints the line.
+With --full it also fills these JSON objects (see DESIGN.md "Measurement"); otherwise they are null / empty:
   roofline     -- dominant conv kernel family: algorithmic FLOP / HIP-event time of its launches,
                   collected in a separate single-stream instrumented pass of the same step AFTER the
                   timed region
+  kernels      -- the same pass's table of every conv kernel family
   cpu_baseline -- the oracle's CPU restatement of the same step (kind "port") on a bounded sample
+
+--dump-outputs DIR writes what the last timed step left to its caller as DIR/<name>.npy (see dump_outputs);
+the inputs, the initial weights and the per-step augmentation are seeded, so two builds can be compared file by file.
 """
 from __future__ import annotations
 
 import argparse
 import json
+import random
 import re
 import os
 import sys
@@ -32,11 +38,14 @@ REPO = Path(__file__).resolve().parent
 sys.path.insert(0, str(REPO / "contrast-you_amd"))
 sys.path.insert(0, str(REPO))
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
 PEAK_BF16_TFLOPS = 2500.0  # MI355X dense bf16 MFMA (MI355X_MICROARCH.md, chip-level parameters)
 PEAK_HBM_BPS = 8.0e12      # HBM3E peak (same table)
+DUMP_BUDGET = 64 << 20     # bytes: every file of --dump-outputs together
+DUMP_CAP = 1 << 18         # elements: a larger tensor is dumped as a fixed sample of this many
 
 
 class _Transforms:
@@ -234,6 +243,46 @@ def kernel_roofline(ctx, device, steps: int = 3):
     return roof, detail
 
 
+def dump_outputs(ctx, metrics, out_dir: str):
+    """--dump-outputs: what the last timed step leaves to its caller -- the updated parameters and BatchNorm buffers of
+    the model and the hook's projector, the parameter gradients of that step -- and the epoch's meter values, one .npy
+    per array (f32; integer buffers and meter values as f64).  A tensor of more than DUMP_CAP elements is written as
+    the flat values at DUMP_CAP positions drawn by a generator seeded with its size, the same positions in every run."""
+    arrays = {}
+
+    def add(name, t):
+        t = t.detach()
+        if t.numel() > DUMP_CAP:
+            g = torch.Generator().manual_seed(t.numel())
+            idx = torch.randperm(t.numel(), generator=g)[:DUMP_CAP].sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        arrays[name] = t.cpu().numpy().astype(np.float32 if t.is_floating_point() else np.float64)
+
+    model, hook = ctx["model"], ctx["hook"]
+    for name, p in model.named_parameters():
+        add(f"param.{name}", p)
+        if p.grad is not None:
+            add(f"grad.{name}", p.grad)
+    for name, b in model.named_buffers():
+        add(f"buffer.{name}", b)
+    for i, p in enumerate(hook.parameters()):
+        add(f"param.hook.{i}", p)
+        if p.grad is not None:
+            add(f"grad.hook.{i}", p.grad)
+    for group, d in metrics.items():
+        for k, v in d.items():
+            if isinstance(v, (int, float)):
+                arrays[f"metric.{group}.{k}"] = np.array(v, dtype=np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the budget of {DUMP_BUDGET}")
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out / (re.sub(r"[^\w.-]", "_", name) + ".npy"), a)  # (hook meter groups are named "infonce/Conv5/...")
+    return len(arrays), total
+
+
 def cpu_baseline(hw: int, max_channel: int):
     """oracle step (CPU restatement, kind=port) on a bounded sample: 2 labeled + 2 unlabeled slices"""
     from oracle import losses as ol
@@ -287,9 +336,18 @@ def main():
                     help="c2 (default, the BASELINE metric's config): semi-supervised step; c4: the same step at 8 "
                          "classes, 256 x 256, fp16 autocast + GradScaler; c5: encoder pre-training, 256 slices x 2 "
                          "views per GPU, until=Conv5, global negatives")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the instrumented single-stream pass (roofline, kernels) "
+                         "and the oracle's CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: leave out the instrumented pass")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (at most 64 MB)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not a.full:
+        a.no_cpu_baseline = a.no_roofline = True
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -323,6 +381,10 @@ def main():
             print(f"[bench +{time.perf_counter() - t_start:7.1f}s] {msg}", file=sys.stderr, flush=True)
 
     t_start = time.perf_counter()
+    # the epochers draw each step's augmentation seed from `random` (the infonce hook's point sampling from numpy):
+    # seeded, the same arguments give the same steps in every run
+    random.seed(0)
+    np.random.seed(0)
     if a.workload == "c5":
         n_c5 = a.n_unlabeled if a.n_unlabeled != 16 else 256
         ctx = build_step_c5(device, rank, n_c5, a.hw, a.max_channel)
@@ -355,6 +417,9 @@ def main():
         dt = tt.item()
     metrics = ep.get_metric()
     note(f"timed {a.steps} steps: {dt / a.steps * 1e3:.2f} ms/step")
+    if a.dump_outputs and rank == 0:  # (before the instrumented pass of --full, which trains on)
+        n, nbytes = dump_outputs(ctx, metrics, a.dump_outputs)
+        note(f"wrote {n} arrays, {nbytes / 2**20:.1f} MB, to {a.dump_outputs}")
 
     roof, detail = (None, {})
     if not a.no_roofline:

@@ -84,7 +84,13 @@ def _stream() -> int:
 
 
 class PinnedRing:
-    """small ring of pinned host buffers for sync-free H2D copies of per-step parameters"""
+    """small ring of pinned host buffers for sync-free H2D copies of per-step parameters.
+
+    A non-blocking copy reads its pinned buffer when the stream reaches it, and nothing in a step makes the host wait
+    for the GPU: a host running more than a ring's worth of uploads ahead would overwrite a buffer whose copy has not
+    run yet (another step's augmentation parameters then reach the kernels).  Each slot therefore carries an event
+    recorded behind its copy, and the host waits on it before refilling the slot -- it blocks only when it is that
+    far ahead, where the GPU has a ring's worth of work queued anyway."""
 
     def __init__(self, slots: int = 16):
         self._slots, self._bufs, self._i = slots, {}, 0
@@ -93,12 +99,21 @@ class PinnedRing:
         key = (tuple(host.shape), host.dtype)
         ring = self._bufs.get(key)
         if ring is None:
-            ring = self._bufs[key] = [torch.empty(host.shape, dtype=host.dtype).pin_memory()
+            ring = self._bufs[key] = [[torch.empty(host.shape, dtype=host.dtype).pin_memory(), None]
                                       for _ in range(self._slots)]
         self._i = (self._i + 1) % self._slots
-        buf = ring[self._i]
+        slot = ring[self._i]
+        buf, done = slot
+        capturing = torch.cuda.is_current_stream_capturing()
+        if done is not None and not capturing:
+            done.synchronize()  # the copy that last read this buffer has run
         buf.copy_(host)
-        return buf.to(device, non_blocking=True)
+        out = buf.to(device, non_blocking=True)
+        if out.is_cuda and not capturing:
+            if done is None:
+                done = slot[1] = torch.cuda.Event()
+            done.record(torch.cuda.current_stream(out.device))
+        return out
 
 
 pinned = PinnedRing()

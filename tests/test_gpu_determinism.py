@@ -73,3 +73,18 @@ def test_conv_family_is_bit_reproducible(geom):
         else:
             for a, b in zip(ref, cur):
                 assert torch.equal(a, b)
+
+
+def test_pinned_uploads_survive_a_host_running_ahead():
+    """per-step host parameters (augmentation theta / gamma, labels, sampled rows) go up through cyhip.ops.pinned without
+    a host sync; with the stream held by a spin kernel, four rings' worth of uploads of one shape must each arrive with
+    the values handed in -- a refilled slot must not change what an earlier, still queued copy delivers"""
+    from cyhip import _lib, ops
+
+    dev = torch.device("cuda:0")
+    n = 4 * 16
+    _lib.call("cy_debug_spin", 20000, ops._stream())  # 20 ms: the uploads below are all enqueued behind it
+    outs = [ops.pinned.upload(torch.full((16, 6), float(i)), dev) for i in range(n)]
+    torch.cuda.synchronize()
+    bad = [i for i, o in enumerate(outs) if not torch.equal(o.cpu(), torch.full((16, 6), float(i)))]
+    assert not bad, f"{len(bad)} of {n} uploads delivered another upload's values, e.g. {bad[:5]}"

@@ -11,7 +11,7 @@ cd /tmp && export TMPDIR=/tmp
   rocprofv3 -M --kernel-trace --stats --output-format csv -d $OUT/single -- python3 $ROOT/bench.py --steps 16 --warmup 4 --no-cpu-baseline --no-roofline > $OUT/single.log 2>&1 )
 cd $ROOT
 python tools/family_times.py $OUT/single 20 > $OUT/family.txt
-python bench.py --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err
 cat $OUT/family.txt
 python - <<PY
 import json
