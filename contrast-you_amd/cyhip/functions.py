@@ -9,6 +9,7 @@ nearest-upsample and channel concat are addressing modes of the consuming conv).
 """
 from __future__ import annotations
 
+import contextlib
 import os
 from typing import List, Optional
 
@@ -244,6 +245,127 @@ def _bn_flags(bn: nn.BatchNorm2d):
     return use_batch, update
 
 
+# ---- the steps of ConvChainFn.backward --------------------------------------------------------------------------
+
+def _backward_accs(ctx, ys: List[Tensor]) -> Optional[list]:
+    """the accumulators for the backward sums of the block's BatchNorms (a None entry: a fresh one is taken), or None
+    on the partial-row path (CY_BN_ACC=0, or more than 1024 channels)"""
+    accs, ctx.bwd_accs = ctx.bwd_accs, None  # (a second backward through the same node gets fresh accumulators)
+    if not (ops.BN_ACC and all(y.shape[1] <= 1024 for y in ys)):
+        return None
+    return accs if accs is not None else [None] * len(ys)
+
+
+def _pooled_grad(out: Tensor, dout: Optional[Tensor], dpooled: Tensor, y: Tensor, coef, accs: Optional[list]):
+    """(dA of the block's last BatchNorm, its partial rows or None) when the block also wrote MaxPool2d(2) of its
+    output: the pooled branch's gradient through the arg-max of `out` plus the skip branch's `dout`.  The same launch
+    adds that BatchNorm's backward sums: into its accumulator while vacant (BnAccBuf's rule), else into a fresh one;
+    as partial rows on the partial-row path."""
+    if dpooled.dtype != out.dtype:
+        dpooled = dpooled.to(out.dtype)
+    add = None if dout is None else ops.to_nhwc(dout if dout.dtype == out.dtype else dout.to(out.dtype))
+    if accs is None:
+        return ops.maxpool2_bwd_bn(out, ops.to_nhwc(dpooled), add, y, *coef)
+    acc = accs[-1] if accs[-1] is not None and accs[-1].vacant() else None
+    da, acc = ops.maxpool2_bwd_bn_acc(out, ops.to_nhwc(dpooled), add, y, coef[0], acc)
+    if acc is not None:
+        acc.filled(da)
+        accs[-1] = acc
+    return da, None
+
+
+def _bn_relu_grad(ctx, i: int, da: Tensor, params, y: Tensor, coef, accs: Optional[list], partials: Optional[Tensor],
+                  split: Optional[int]):
+    """backward of relu(bn(y)) of conv i at `da`: (data gradient of the conv or None, dy, dgamma, dbeta).  The
+    BatchNorm's backward sums come from partial rows (legacy path) or an accumulator: a producer's, if it holds the sums
+    of exactly `da` (BnAccBuf's rule), else the reduce launch's.  Where the layer has a launch plan for it, the data
+    gradient takes the BatchNorm + ReLU backward into its load path (conv3x3_dgrad_bn: one launch instead of two)."""
+    need = ctx.needs_input_grad
+    w, g, b = params[3 * i: 3 * i + 3]
+    need_g, need_b = need[4 + 3 * i], need[5 + 3 * i]
+    # parameter gradients are accumulated straight into .grad when it is a live f32 buffer (flat-buffer optimizer);
+    # otherwise they are returned to autograd as usual
+    gsink = ops.grad_sink(g) if (need_g and need_b) else None
+    bsink = ops.grad_sink(b) if gsink is not None else None
+    pgrads = dict(dgamma_out=gsink if bsink is not None else None, dbeta_out=bsink, want_param_grads=need_g or need_b)
+    if accs is None:
+        return (None, *ops.bn_relu_bwd(da, y, *coef, ctx.batch_flags[i], partials=partials, **pgrads))
+    acc, done = ops.bn_acc_for_grad(accs[i], da, y)
+    # (coef[0] is row 0 of the contiguous coefficient block [scale, shift, mean, invstd, ...] of either path)
+    if i > 0 or (not ctx.cfg.first and (need[1] or (ctx.has_x2 and need[2]))):
+        da_f = ops.to_nhwc(da if da.dtype == y.dtype else da.to(y.dtype))
+        if ops.conv3x3_dgrad_bn_ok(da_f, w.shape[1], split):
+            acc = acc if acc is not None else ops.bn_bwd_acc_new(*y.shape, False, y.device)
+            if not done:
+                ops.bn_bwd_reduce_acc(da_f, y, coef[0], acc)
+            _, wd = packed_weights(w, ctx.dt)
+            return ops.conv3x3_dgrad_bn(da_f, y, coef[0], acc, ctx.batch_flags[i], wd, w.shape[1], split=split, **pgrads)
+    return (None, *ops.bn_relu_bwd_acc(da, y, coef[0], ctx.batch_flags[i], acc=acc, acc_filled=done, **pgrads))
+
+
+def _weight_grad(w: Tensor, sink: Optional[Tensor], src1: Tensor, src2: Optional[Tensor], dy: Tensor, mode: int,
+                 scale: Optional[Tensor], shift: Optional[Tensor], first: bool, pass_id: int) -> Optional[Tensor]:
+    """dw of one 3x3 conv (of the image-reading first layer if `first`): added into the live .grad `sink` -- on the side
+    stream with ASYNC_WGRAD -- and None returned, or returned"""
+    side = sink is not None and ops.ASYNC_WGRAD
+    with ops.on_side_stream(src1, src2, dy, scale, shift) if side else contextlib.nullcontext():
+        if first:
+            dw = ops.conv_first_wgrad(src1, dy, out=sink)
+        elif sink is not None:
+            wgrad_into_sink(w, sink, src1, src2, dy, mode, scale, shift, pass_id)
+        else:
+            dw = ops.conv3x3_wgrad(src1, src2, dy, mode=mode, scale=scale, shift=shift)
+    return None if sink is not None else dw
+
+
+def _data_grad(w: Tensor, wd: Tensor, dy: Tensor, split: Optional[int], tail):
+    """conv3x3 data gradient of dy; with `split`, the two parts of a concatenated input.  tail = (y, coef, acc): the
+    output (its second part when split) is the dA of relu(bn(y)); where the launch plan allows, the epilogue adds that
+    BatchNorm's backward sums into acc while vacant (BnAccBuf's rule)."""
+    Cin, c0 = w.shape[1], split or 0
+    if tail is not None and tail[2].vacant() and ops.conv3x3_dgrad_dz_ok(dy, Cin, split, c0, Cin - c0):
+        dx = ops.conv3x3_dgrad_dz(dy, wd, Cin, *tail, split=split)
+        tail[2].filled(dx[1] if split else dx)
+        return dx
+    return ops.conv3x3_fwd(dy, None, wd, Cin, want_stats=False, split=split)[0]
+
+
+def _upsample_grad(dup: Tensor, tail) -> Tensor:
+    """gradient through the nearest 2x upsample.  tail = (y, coef, acc) of the block that produced the upsampled input:
+    the result is the dA of its relu(bn(y)), and the same launch adds those backward sums into acc while vacant."""
+    if tail is not None and tail[2].vacant():
+        dx = ops.upsample2_bwd_bn_acc(dup, *tail)
+        if dx is not None:
+            tail[2].filled(dx)
+            return dx
+    return ops.upsample2_bwd(dup)
+
+
+def _input_grads(ctx, x1: Tensor, w: Tensor, dy: Tensor, fused_dx):
+    """(dx1, dx2) from dy of the block's first conv, or from the data gradient the fused launch already made: x1's
+    through the 2x2 max-pool or the upsample the conv reads it with, or directly; x2's (a concat input) directly"""
+    cfg, need = ctx.cfg, ctx.needs_input_grad
+    need_x1, need_x2 = need[1], ctx.has_x2 and need[2]
+    if not (need_x1 or need_x2):
+        return None, None
+    if cfg.first:
+        raise RuntimeError("gradient w.r.t. the input image is not implemented (the reference never asks for it)")
+    _, wd = packed_weights(w, ctx.dt)
+    dl = fused_dx if fused_dx is not None else \
+        _data_grad(w, wd, dy, x1.shape[1] if ctx.has_x2 else None, ctx.x2_tail if need_x2 else None)
+    dl1, dl2 = dl if ctx.has_x2 else (dl, None)
+    dx2 = dl2 if need_x2 else None
+    if not need_x1:
+        return None, dx2
+    if cfg.mode == ops.CY_SRC_POOL2:
+        dx1 = ops.maxpool2_bwd(x1, dl1)
+    elif cfg.mode == ops.CY_SRC_UP2:
+        dx1 = _upsample_grad(dl1, ctx.up_tail)
+    else:
+        dx1 = dl1
+    return (dx1 if dx1.dtype == ctx.x_dtype else dx1.to(ctx.x_dtype)), dx2
+
+
 class ConvChainFn(torch.autograd.Function):
     """One reference block: _ConvBlock (2 convs) or _UpConv (upsample + 1 conv)."""
 
@@ -353,7 +475,7 @@ class ConvChainFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout: Optional[Tensor], dpooled: Optional[Tensor] = None):
         ops.ensure_backward_join()
-        cfg, nconv, dt = ctx.cfg, ctx.nconv, ctx.dt
+        cfg, nconv, need = ctx.cfg, ctx.nconv, ctx.needs_input_grad  # (need: cfg, x1, x2, *params)
         t = list(ctx.saved_tensors)
         out = t.pop() if cfg.pool_out else None
         if cfg.pool_out and dout is None and dpooled is None:
@@ -363,176 +485,31 @@ class ConvChainFn(torch.autograd.Function):
         params = [t.pop(0) for _ in range(3 * nconv)]
         ys = [t.pop(0) for _ in range(nconv)]
         coefs = [tuple(t.pop(0) for _ in range(4)) for _ in range(nconv)]
-        pool_partials = None
-        acc_ok = ops.BN_ACC and all(yy.shape[1] <= 1024 for yy in ys)
-        accs = ctx.bwd_accs if acc_ok else None
-        ctx.bwd_accs = None  # (a second backward through the same node gets fresh accumulators)
-        if acc_ok and accs is None:
-            accs = [None] * nconv
-        pool_acc_filled = False
-        if accs is not None and accs[-1] is not None and accs[-1].filled_for is not None and not cfg.pool_out:
-            # the producer of `dout` (an upsample backward) has added this block's last BatchNorm's sums -- valid only if
-            # `dout` IS that producer's tensor (autograd hands a single contribution through; a sum of several consumers'
-            # gradients is another tensor, and the accumulator then holds a partial sum: start a fresh one)
-            made = accs[-1].filled_for  # (the producer's tensor, kept alive: no address reuse, no in-place accumulation)
-            if (dout is not None and dout.data_ptr() == made.data_ptr() and dout._version == made._version
-                    and dout.shape == made.shape and dout.dtype == ys[-1].dtype and ops.is_nhwc(dout)):
-                pool_acc_filled = True
-            else:
-                accs[-1] = None
+        accs = _backward_accs(ctx, ys)
+        da, partials = dout, None
         if cfg.pool_out and dpooled is not None:
-            if dpooled.dtype != out.dtype:
-                dpooled = dpooled.to(out.dtype)
-            add = None
-            if dout is not None:
-                add = ops.to_nhwc(dout if dout.dtype == out.dtype else dout.to(out.dtype))
-            # the pooled branch's gradient through the arg-max, + the skip branch's gradient; the same launch takes
-            # the backward sums of the block's last BatchNorm (whose dA it is writing)
-            if accs is not None:
-                dout, acc_p = ops.maxpool2_bwd_bn_acc(out, ops.to_nhwc(dpooled), add, ys[-1], coefs[-1][0], accs[-1])
-                if acc_p is not None:
-                    accs[-1], pool_acc_filled = acc_p, True
-            else:
-                dout, pool_partials = ops.maxpool2_bwd_bn(out, ops.to_nhwc(dpooled), add, ys[-1], *coefs[-1])
-        need = ctx.needs_input_grad  # (cfg, x1, x2, *params)
+            da, partials = _pooled_grad(out, dout, dpooled, ys[-1], coefs[-1], accs)
         grads_p: List[Optional[Tensor]] = [None] * (3 * nconv)
-        da = dout
-        dx1 = dx2 = None
-        dz_filled = False  # the data gradient that produced `da` has added this iteration's BatchNorm's backward sums
         for i in reversed(range(nconv)):
-            if i == nconv - 1:
-                sums_done = pool_acc_filled
-            else:
-                sums_done, dz_filled = dz_filled, False
-            w, g, b = params[3 * i: 3 * i + 3]
-            scale, shift, mean, invstd = coefs[i]
-            need_w, need_g, need_b = need[3 + 3 * i], need[3 + 3 * i + 1], need[3 + 3 * i + 2]
-            # parameter gradients are accumulated straight into .grad when it is a live f32 buffer
-            # (flat-buffer optimizer); otherwise they are returned to autograd as usual
-            gsink = ops.grad_sink(g) if (need_g and need_b) else None
-            bsink = ops.grad_sink(b) if gsink is not None else None
-            if bsink is None:
-                gsink = None
-            # The data gradient of this conv can take the BatchNorm + ReLU backward into its load path (one launch
-            # instead of two; dy comes back as its second output for the weight gradient) where the layer has such a
-            # launch plan -- the flow kernel's tilings with room for a second halo buffer.
-            Cin_i = w.shape[1]
-            want_dgrad = i > 0 or (not cfg.first and (need[1] or (ctx.has_x2 and need[2])))
-            split_i = x1.shape[1] if (i == 0 and ctx.has_x2) else None
-            fused_dx = None
-            if accs is not None and want_dgrad:
-                da_f = ops.to_nhwc(da if da.dtype == ys[i].dtype else da.to(ys[i].dtype))
-                if ops.conv3x3_dgrad_bn_ok(da_f, Cin_i, split_i):
-                    acc_i = accs[i] if accs[i] is not None else ops.bn_bwd_acc_new(*ys[i].shape[:2], *ys[i].shape[2:], False, da_f.device)
-                    if not sums_done:
-                        ops.bn_bwd_reduce_acc(da_f, ys[i], scale, acc_i)
-                    _, wd = packed_weights(w, dt)
-                    fused_dx, dy, dgamma, dbeta = ops.conv3x3_dgrad_bn(
-                        da_f, ys[i], scale, acc_i, ctx.batch_flags[i], wd, Cin_i, dgamma_out=gsink, dbeta_out=bsink,
-                        want_param_grads=need_g or need_b, split=split_i)
-            if fused_dx is not None:
-                pass
-            elif accs is not None:
-                # (scale is row 0 of the contiguous coefficient block [scale, shift, mean, invstd, ...] of either path)
-                dy, dgamma, dbeta = ops.bn_relu_bwd_acc(da, ys[i], scale, ctx.batch_flags[i], dgamma_out=gsink,
-                                                        dbeta_out=bsink, want_param_grads=need_g or need_b,
-                                                        acc=accs[i], acc_filled=sums_done)
-            else:
-                dy, dgamma, dbeta = ops.bn_relu_bwd(da, ys[i], scale, shift, mean, invstd, ctx.batch_flags[i],
-                                                    dgamma_out=gsink, dbeta_out=bsink,
-                                                    want_param_grads=need_g or need_b,
-                                                    partials=pool_partials if i == nconv - 1 else None)
-            if need_g:
-                grads_p[3 * i + 1] = dgamma
-            if need_b:
-                grads_p[3 * i + 2] = dbeta
-            wsink = ops.grad_sink(w) if need_w else None
+            w = params[3 * i]
+            fused_dx, dy, dgamma, dbeta = _bn_relu_grad(ctx, i, da, params, ys[i], coefs[i], accs,
+                                                        partials if i == nconv - 1 else None,
+                                                        x1.shape[1] if (i == 0 and ctx.has_x2) else None)
+            grads_p[3 * i + 1] = dgamma if need[4 + 3 * i] else None
+            grads_p[3 * i + 2] = dbeta if need[5 + 3 * i] else None
+            if need[3 + 3 * i] and i > 0:
+                grads_p[3 * i] = _weight_grad(w, ops.grad_sink(w), ys[i - 1], None, dy, 0, coefs[i - 1][0],
+                                              coefs[i - 1][1], False, ctx.pass_id)
+            elif need[3 + 3 * i]:
+                grads_p[3 * i] = _weight_grad(w, ops.grad_sink(w), x1, x2, dy, cfg.mode, None, None, cfg.first,
+                                              ctx.pass_id)
             if i > 0:
-                ps, ph = coefs[i - 1][0], coefs[i - 1][1]
-                if need_w:
-                    if wsink is not None and ops.ASYNC_WGRAD:
-                        with ops.on_side_stream(ys[i - 1], dy, ps, ph):
-                            wgrad_into_sink(w, wsink, ys[i - 1], None, dy, 0, ps, ph, ctx.pass_id)
-                    elif wsink is not None:
-                        wgrad_into_sink(w, wsink, ys[i - 1], None, dy, 0, ps, ph, ctx.pass_id)
-                    else:
-                        grads_p[3 * i] = ops.conv3x3_wgrad(ys[i - 1], None, dy, scale=ps, shift=ph)
-                if fused_dx is not None:
-                    da = fused_dx
-                else:
-                    _, wd = packed_weights(w, dt)
-                    # the output is the dA of this block's previous BatchNorm: its backward sums from the epilogue
-                    # where the launch plan allows (then the next iteration skips the reduce launch)
-                    if (accs is not None and accs[i - 1] is not None
-                            and ops.conv3x3_dgrad_dz_ok(dy, w.shape[1], None, 0, w.shape[1])):
-                        da = ops.conv3x3_dgrad_dz(dy, wd, w.shape[1], ys[i - 1], coefs[i - 1][0], accs[i - 1])
-                        dz_filled = True
-                    else:
-                        da, _ = ops.conv3x3_fwd(dy, None, wd, w.shape[1], want_stats=False)
-            else:
-                if need_w:
-                    if wsink is not None and ops.ASYNC_WGRAD:
-                        with ops.on_side_stream(x1, x2, dy):
-                            if cfg.first:
-                                ops.conv_first_wgrad(x1, dy, out=wsink)
-                            else:
-                                wgrad_into_sink(w, wsink, x1, x2, dy, cfg.mode, None, None, ctx.pass_id)
-                    else:
-                        if cfg.first:
-                            dw = ops.conv_first_wgrad(x1, dy, out=wsink)
-                        elif wsink is not None:
-                            wgrad_into_sink(w, wsink, x1, x2, dy, cfg.mode, None, None, ctx.pass_id)
-                            dw = None
-                        else:
-                            dw = ops.conv3x3_wgrad(x1, x2, dy, mode=cfg.mode)
-                        grads_p[0] = None if wsink is not None else dw
-                need_x1 = need[1]
-                need_x2 = ctx.has_x2 and need[2]
-                if need_x1 or need_x2:
-                    if cfg.first:
-                        raise RuntimeError("gradient w.r.t. the input image is not implemented "
-                                           "(the reference never asks for it)")
-                    _, wd = packed_weights(w, dt)
-                    C1 = x1.shape[1]
-                    if fused_dx is not None:
-                        if ctx.has_x2:
-                            dl1, dl2 = fused_dx
-                            dx2 = dl2 if need_x2 else None
-                        else:
-                            dl1 = fused_dx
-                    elif ctx.has_x2:
-                        t2 = ctx.x2_tail
-                        if (t2 is not None and need_x2 and t2[2].filled_for is None
-                                and ops.conv3x3_dgrad_dz_ok(dy, w.shape[1], C1, C1, w.shape[1] - C1)):
-                            # the second part of the output is the dA of the block that produced x2 (an _UpConv): its
-                            # BatchNorm's backward sums from this launch's epilogue
-                            dl1, dl2 = ops.conv3x3_dgrad_dz(dy, wd, w.shape[1], t2[0], t2[1], t2[2], split=C1)
-                            t2[2].filled_for = dl2
-                        else:
-                            (dl1, dl2), _ = ops.conv3x3_fwd(dy, None, wd, w.shape[1], want_stats=False,
-                                                            split=C1)
-                        dx2 = dl2 if need_x2 else None
-                    else:
-                        dl1, _ = ops.conv3x3_fwd(dy, None, wd, w.shape[1], want_stats=False)
-                    if need_x1:
-                        if cfg.mode == ops.CY_SRC_POOL2:
-                            dx1 = ops.maxpool2_bwd(x1, dl1)
-                        elif cfg.mode == ops.CY_SRC_UP2:
-                            dx1 = None
-                            if ctx.up_tail is not None and ctx.up_tail[2].filled_for is None:
-                                y_t, coef_t, acc_t = ctx.up_tail
-                                dx1 = ops.upsample2_bwd_bn_acc(dl1, y_t, coef_t, acc_t)
-                                if dx1 is not None:
-                                    acc_t.filled_for = dx1
-                            if dx1 is None:
-                                dx1 = ops.upsample2_bwd(dl1)
-                        else:
-                            dx1 = dl1
-                        if dx1.dtype != ctx.x_dtype:
-                            dx1 = dx1.to(ctx.x_dtype)
+                tail = (ys[i - 1], coefs[i - 1][0], accs[i - 1]) if accs is not None and accs[i - 1] is not None else None
+                da = fused_dx if fused_dx is not None else _data_grad(w, packed_weights(w, ctx.dt)[1], dy, None, tail)
+        dx1, dx2 = _input_grads(ctx, x1, params[0], dy, fused_dx)
         if cfg.ready_tag is not None and (_step_first_pass is None or ctx.pass_id == _step_first_pass):
             # (the pass evaluated first is differentiated last: nothing of this block is parked or still to come)
-            ops.grad_ready_mark(cfg.ready_tag, da.device)
+            ops.grad_ready_mark(cfg.ready_tag, dy.device)
         return (None, dx1, dx2, *grads_p)
 
 

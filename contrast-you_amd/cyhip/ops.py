@@ -793,14 +793,47 @@ def bn_arena_end(prev: Optional[BnArena]) -> None:
 
 
 class BnAccBuf:
-    """an accumulator [R][4][C] (+ R flags) and its ctypes view"""
-    __slots__ = ("t", "R", "C", "s", "ref", "filled_for")
+    """an accumulator [R][4][C] (+ R flags) and its ctypes view.
+
+    The backward sums of a BatchNorm (sum dz, sum dz*xhat) may be added by whichever kernel writes the gradient dA of
+    relu(bn(y)) while it has the values in registers: the max-pool backward of a block's output, the upsample backward
+    or the data-gradient epilogue of the block that consumes it, the data-gradient epilogue inside the block.  The rule:
+      * a producer adds into the accumulator only while it is `vacant`, and then records the tensor it wrote (`filled`);
+      * the BatchNorm's backward uses the sums only if they were added for exactly the dA it holds (`holds`): autograd
+        hands a single contribution through, but a sum of several consumers' gradients is another tensor, and the
+        accumulator then holds a partial sum;
+      * otherwise it runs the reduce launch into this accumulator if still vacant, else into a fresh one
+        (`bn_acc_for_grad`)."""
+    __slots__ = ("t", "R", "C", "s", "ref", "_filled_for")
 
     def __init__(self, t: Tensor, R: int, Cc: int):
         self.t, self.R, self.C = t, R, Cc
-        self.filled_for = None  # the gradient tensor whose producer has added its sums already
+        self._filled_for = None
         self.s = _lib.BnAcc(t.data_ptr(), R, Cc)
         self.ref = C.byref(self.s)
+
+    def vacant(self) -> bool:
+        return self._filled_for is None
+
+    def filled(self, da: Tensor) -> None:
+        # (the tensor is kept alive: no address reuse, and `holds` also checks it was not written in place since)
+        self._filled_for = da
+
+    def holds(self, da: Optional[Tensor], y: Tensor) -> bool:
+        made = self._filled_for
+        return (made is not None and da is not None and da.data_ptr() == made.data_ptr()
+                and da._version == made._version and da.shape == made.shape and da.dtype == y.dtype and is_nhwc(da))
+
+
+def bn_acc_for_grad(acc: Optional[BnAccBuf], da: Optional[Tensor], y: Tensor) -> Tuple[Optional[BnAccBuf], bool]:
+    """the consumer side of BnAccBuf's rule for the backward of relu(bn(y)) at `da`: (acc, True) if a producer added
+    the sums of exactly `da`; else (accumulator for the reduce launch, False) -- `acc` while vacant, else None (the
+    caller takes a fresh one)"""
+    if acc is None or acc.vacant():
+        return acc, False
+    if acc.holds(da, y):
+        return acc, True
+    return None, False
 
 
 def bn_acc_new(Cc: int, workgroups: int, device) -> BnAccBuf:
@@ -907,6 +940,18 @@ def bn_relu_apply_pool(y: Tensor, scale: Tensor, shift: Tensor) -> Tuple[Tensor,
     return out, pooled
 
 
+def _bn_param_grads(Cc: int, dev, dgamma_out: Optional[Tensor], dbeta_out: Optional[Tensor], want: bool):
+    """(pg, pb, accumulate, guard): where a BatchNorm backward launch writes dgamma / dbeta -- ADDED into dgamma_out /
+    dbeta_out, else into a fresh [2, C] pair if wanted, else nowhere -- and the context its launch runs in (in-place
+    accumulation into the parameters' .grad is ordered across streams)"""
+    if dgamma_out is not None:
+        return dgamma_out, dbeta_out, True, ordered(("bn_grad", dgamma_out.data_ptr()))
+    if want:
+        gb = _f32(2 * Cc, dev).view(2, Cc)
+        return gb[0], gb[1], False, contextlib.nullcontext()
+    return None, None, False, contextlib.nullcontext()
+
+
 def bn_relu_bwd(da: Tensor, y: Tensor, scale: Tensor, shift: Tensor, mean: Tensor, invstd: Tensor,
                 batch_stats: bool, dgamma_out: Optional[Tensor] = None, dbeta_out: Optional[Tensor] = None,
                 want_param_grads: bool = True, partials: Optional[Tensor] = None):
@@ -929,30 +974,15 @@ def bn_relu_bwd(da: Tensor, y: Tensor, scale: Tensor, shift: Tensor, mean: Tenso
                   shift.data_ptr(), mean.data_ptr(), invstd.data_ptr(), part.data_ptr(), npix, Cc, dt,
                   _stream())
     coef = _f32(2 * Cc, dev)
-    acc = dgamma_out is not None
-    dgamma = dbeta = None
-    if acc:
-        pg, pb = dgamma_out, dbeta_out
-    elif want_param_grads:
-        gb = _f32(2 * Cc, dev).view(2, Cc)
-        dgamma, dbeta = gb[0], gb[1]
-        pg, pb = dgamma, dbeta
-    else:
-        pg = pb = None
-    def finalize():
+    pg, pb, accum, guard = _bn_param_grads(Cc, dev, dgamma_out, dbeta_out, want_param_grads)
+    with guard:
         _lib.call("cy_bn_bwd_finalize", part.data_ptr(), npart, Cc, scale.data_ptr(), mean.data_ptr(),
-                  invstd.data_ptr(), float(npix), int(batch_stats), _ptr(pg), _ptr(pb), int(acc), coef.data_ptr(),
+                  invstd.data_ptr(), float(npix), int(batch_stats), _ptr(pg), _ptr(pb), int(accum), coef.data_ptr(),
                   _stream())
-
-    if acc:
-        with ordered(("bn_grad", pg.data_ptr())):  # in-place accumulation into the parameters' .grad
-            finalize()
-    else:
-        finalize()
     dy = empty_nhwc(N, Cc, H, W, y.dtype, dev)
     _lib.call("cy_bn_relu_bwd_apply", da.data_ptr(), Cc, y.data_ptr(), scale.data_ptr(), shift.data_ptr(),
               coef.data_ptr(), dy.data_ptr(), npix, Cc, dt, _stream())
-    return dy, dgamma, dbeta
+    return (dy, None, None) if accum else (dy, pg, pb)
 
 
 POOL_BN_FUSE = os.environ.get("CY_POOL_BN_FUSE", "1") != "0"  # (A/B switch)
@@ -976,28 +1006,12 @@ def bn_relu_bwd_acc(da: Tensor, y: Tensor, coef: Tensor, batch_stats: bool, dgam
     if not acc_filled:
         _lib.call("cy_bn_relu_bwd_reduce_acc", da.data_ptr(), Cc, y.data_ptr(), coef.data_ptr(), acc.ref, npix, Cc, dt,
                   _stream())
-    accum = dgamma_out is not None
-    dgamma = dbeta = None
-    if accum:
-        pg, pb = dgamma_out, dbeta_out
-    elif want_param_grads:
-        gb = _f32(2 * Cc, dev).view(2, Cc)
-        dgamma, dbeta = gb[0], gb[1]
-        pg, pb = dgamma, dbeta
-    else:
-        pg = pb = None
+    pg, pb, accum, guard = _bn_param_grads(Cc, dev, dgamma_out, dbeta_out, want_param_grads)
     dy = empty_nhwc(N, Cc, H, W, y.dtype, dev)
-
-    def apply():
+    with guard:
         _lib.call("cy_bn_relu_bwd_apply_fold", da.data_ptr(), Cc, y.data_ptr(), coef.data_ptr(), acc.ref, float(npix),
                   int(batch_stats), _ptr(pg), _ptr(pb), int(accum), dy.data_ptr(), npix, Cc, dt, _stream())
-
-    if accum:
-        with ordered(("bn_grad", pg.data_ptr())):  # in-place accumulation into the parameters' .grad
-            apply()
-    else:
-        apply()
-    return dy, dgamma, dbeta
+    return (dy, None, None) if accum else (dy, pg, pb)
 
 
 def bn_bwd_reduce_acc(da: Tensor, y: Tensor, coef: Tensor, acc: BnAccBuf) -> None:
@@ -1087,16 +1101,7 @@ def conv3x3_dgrad_bn(da: Tensor, y: Tensor, coef: Tensor, acc: "BnAccBuf", batch
     else:
         out, out2 = empty_nhwc(N, Cin, H, W, y.dtype, dev), None
     dy = empty_nhwc(N, Cc, H, W, y.dtype, dev)
-    accum = dgamma_out is not None
-    dgamma = dbeta = None
-    if accum:
-        pg, pb = dgamma_out, dbeta_out
-    elif want_param_grads:
-        gb = _f32(2 * Cc, dev).view(2, Cc)
-        dgamma, dbeta = gb[0], gb[1]
-        pg, pb = dgamma, dbeta
-    else:
-        pg = pb = None
+    pg, pb, accum, guard = _bn_param_grads(Cc, dev, dgamma_out, dbeta_out, want_param_grads)
     if d.fwd_ws is None:
         d.fwd_ws = _lib.load().cy_conv3x3_fwd_ws_bytes(d.ref)
     nbytes = d.fwd_ws
@@ -1104,21 +1109,15 @@ def conv3x3_dgrad_bn(da: Tensor, y: Tensor, coef: Tensor, acc: "BnAccBuf", batch
     bn = _lib.BnBwdIn(y.data_ptr(), coef.data_ptr(), C.pointer(acc.s), float(N * H * W), int(batch_stats), int(accum),
                       _ptr(pg), _ptr(pb), dy.data_ptr())
     ev = _prof_begin()
-
-    def launch():
+    with guard:
         _lib.call("cy_conv3x3_dgrad_bn", d.ref, da.data_ptr(), C.byref(bn), wd.data_ptr(), out.data_ptr(), _ptr(out2),
                   _ptr(ws), nbytes, _stream())
-
-    if accum:
-        with ordered(("bn_grad", pg.data_ptr())):  # the first workgroup adds into the parameters' .grad
-            launch()
-    else:
-        launch()
     if ev is not None:
         esz = y.element_size()
         nb = esz * (3 * y.numel() + N * H * W * Cin + 9 * Cc * Cin)
         _prof_end(ev, "conv3x3_fwd_dgrad", 2.0 * N * H * W * 9 * Cc * Cin, float(nb))
-    return ((out, out2) if split else out), dy, dgamma, dbeta
+    dx = (out, out2) if split else out
+    return (dx, dy, None, None) if accum else (dx, dy, pg, pb)
 
 
 # A data gradient whose output is the dA of a BatchNorm + ReLU adds that layer's backward sums in its epilogue

@@ -374,6 +374,36 @@ def test_producer_side_sums_are_dropped_when_other_gradients_join():
         assert (res[True][n] - gb).abs().max() <= 1e-4 * gb.abs().max() + 1e-8, n
 
 
+@pytest.mark.parametrize("pooled_in_loss", [True, False], ids=["pooled_used", "pooled_unused"])
+def test_pooled_block_read_by_an_upsample(pooled_in_loss):
+    """a block that also writes its max-pooled output, read by an _UpConv: the upsample backward adds the sums of the
+    block's last BatchNorm, so the block's own backward must neither add them again (pooled output unused) nor add
+    the pool backward's sums on top of them (pooled output used: its dA is another tensor)"""
+    ops = _ops()
+    from contrastyou.arch.unet import _ConvBlock, _UpConv
+    res = {}
+    for mode in (True, False):
+        ops.BN_ACC = mode
+        try:
+            torch.manual_seed(0)
+            block, up = _ConvBlock(16, 64).to(DEV), _UpConv(64, 32).to(DEV)
+            block.compute_dtype = up.compute_dtype = torch.float32
+            g = torch.Generator().manual_seed(5)
+            x = torch.randn(3, 16, 32, 32, generator=g).to(DEV)
+            out = block(x, pool_out=True)
+            pooled = block.take_pooled()
+            loss = up(out).square().mean()
+            if pooled_in_loss:
+                loss = loss + pooled.float().square().mean()
+            loss.backward()
+            torch.cuda.synchronize()
+            res[mode] = {n: p.grad.clone() for m in (block, up) for n, p in m.named_parameters(prefix=type(m).__name__)}
+        finally:
+            ops.BN_ACC = True
+    for n, gb in res[False].items():
+        assert (res[True][n] - gb).abs().max() <= 1e-4 * gb.abs().max() + 1e-8, n
+
+
 # (N, H, W, C of dy, Cin of the data gradient, split, dtype)
 DGRAD_DZ_CASES = [
     (16, 56, 56, 128, 128, None, torch.bfloat16),
