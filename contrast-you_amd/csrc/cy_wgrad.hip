@@ -1027,6 +1027,7 @@ int cy_conv3x3_wgrad_plan(const cy_conv_desc* d, int n_b, cy_wgrad_plan* plan) {
   plan->twelve = p.spec ? 2 : (p.twelve ? 1 : 0);
   plan->wco = p.wco, plan->wci = p.wci, plan->wk = p.wk, plan->th = p.TH, plan->tw = p.TW, plan->splits = p.S;
   plan->workgroups = (p.co_pad / (32 * p.wco)) * (p.ci_pad / (32 * p.wci)) * p.S;
+  plan->dma = p.dma ? 1 : 0, plan->blk_order = p.blk_order ? 1 : 0;
   return CY_OK;
 }
 

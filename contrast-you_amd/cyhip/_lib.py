@@ -11,7 +11,7 @@ from pathlib import Path
 
 CY_F32, CY_BF16, CY_F16 = 0, 1, 2
 CY_SRC_DIRECT, CY_SRC_POOL2, CY_SRC_UP2 = 0, 1, 2
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 _ERRORS = {-1: "CY_ERR_ARG (bad/NULL argument)", -2: "CY_ERR_SHAPE (unsupported shape)",
            -3: "CY_ERR_DTYPE (unsupported dtype)", -4: "CY_ERR_LAUNCH (HIP launch failed)",
@@ -49,7 +49,8 @@ class ConvPlan(C.Structure):
 
 class WgradPlan(C.Structure):
     """mirror of cy_wgrad_plan"""
-    _fields_ = [(n, c_int32) for n in ("twelve", "wco", "wci", "wk", "th", "tw", "splits", "workgroups")]
+    _fields_ = [(n, c_int32) for n in ("twelve", "wco", "wci", "wk", "th", "tw", "splits", "workgroups", "dma",
+                                               "blk_order")]
 
 
 class BnAcc(C.Structure):
@@ -269,6 +270,11 @@ def load():
         raise HipExtensionMissing(
             f"{LIB_PATH} not found: build it with `python contrast-you_amd/build.py` "
             "(there is no CPU fallback for the hot path)")
+    # torch first: its wheel carries a HIP runtime of its own (torch/lib/libamdhip64.so, asked for under the unversioned
+    # name).  Loaded after torch, this library's libamdhip64.so.7 resolves to that copy by soname; loaded before it, the
+    # system's copy comes in and torch then maps its own next to it -- two runtimes in one process, and every launch
+    # here on one of torch's streams fails (CY_ERR_LAUNCH).
+    import torch  # noqa: F401
     lib = C.CDLL(str(LIB_PATH))
     for name, (res, args) in _SIGS.items():
         fn = getattr(lib, name)

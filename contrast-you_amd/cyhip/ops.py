@@ -268,13 +268,19 @@ def _desc(N, H, W, C1, C2, Cout, mode, prologue, dt, ld1, ld2, ldo, split_c=0, l
 KERNEL_NAMES = {0: "conv3x3_igemm_kernel", 1: "conv3x3_plane_kernel", 4: "conv3x3_stream_kernel", 5: "conv3x3_flow_kernel"}
 
 
-def conv3x3_plan(N, H, W, C1, C2, Cout, dtype: torch.dtype, mode: int = 0, prologue: bool = False) -> dict:
-    """the launch plan of cy_conv3x3_fwd for this layer geometry (host-side query, no GPU needed)"""
-    d = _desc(N, H, W, C1, C2, Cout, mode, 1 if prologue else 0, dtype_code(dtype), C1, C2, Cout)
+def conv3x3_plan(N, H, W, C1, C2, Cout, dtype: torch.dtype, mode: int = 0, prologue: bool = False,
+                 split: Optional[int] = None) -> dict:
+    """the launch plan of cy_conv3x3_fwd for this layer geometry (host-side query, no GPU needed); `split`: of the
+    form that writes out[:, :split] and out[:, split:] as two tensors (the data gradient of a concat layer)"""
+    if split:
+        d = _desc(N, H, W, C1, C2, Cout, mode, 1 if prologue else 0, dtype_code(dtype), C1, C2, split, split, Cout - split)
+    else:
+        d = _desc(N, H, W, C1, C2, Cout, mode, 1 if prologue else 0, dtype_code(dtype), C1, C2, Cout)
     p = _lib.ConvPlan()
     _lib.call("cy_conv3x3_plan", d.ref, C.byref(p))
     out = {f: getattr(p, f) for f, _ in p._fields_}
     out["kernel"] = KERNEL_NAMES[out["kernel"]]
+    out["ws_bytes"] = int(_lib.load().cy_conv3x3_fwd_ws_bytes(d.ref))  # (the split-K workspace: 0 when ksplit == 1)
     return out
 
 

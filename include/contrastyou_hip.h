@@ -179,6 +179,8 @@ typedef struct cy_wgrad_plan {
   int32_t th, tw;        /* spatial tile */
   int32_t splits;        /* pixel splits = f32 slabs summed by wgrad_reduce_kernel */
   int32_t workgroups;
+  int32_t dma;           /* wgrad12s_kernel: loader waves on LDS-DMA (32-bit buffer offsets: every tensor below 2 GiB) */
+  int32_t blk_order;     /* wgrad12s_kernel: 4 x 4 pixel patches as k-steps (ABI v13: dma, blk_order appended) */
 } cy_wgrad_plan;
 int cy_conv3x3_wgrad_plan(const cy_conv_desc* d, int n_b, cy_wgrad_plan* plan);
 

@@ -70,3 +70,35 @@ def test_no_oracle_import_in_product():
     for p in (REPO / "contrast-you_amd").rglob("*.py"):
         src = p.read_text()
         assert not re.search(r"^\s*(from|import)\s+oracle\b", src, flags=re.M), p
+
+
+def test_wgrad_plan_layout_matches_header():
+    """cy_wgrad_plan (ABI v13: dma, blk_order appended) and its ctypes mirror name the same int32 fields in order"""
+    from cyhip._lib import WgradPlan
+    text = HEADER.read_text()
+    body = re.search(r"typedef struct cy_wgrad_plan \{(.*?)\} cy_wgrad_plan;", text, flags=re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    fields = []
+    for decl in body.split(";"):
+        decl = decl.strip()
+        if decl:
+            assert decl.startswith("int32_t "), decl
+            fields += [f.strip() for f in decl[len("int32_t "):].split(",")]
+    assert fields == [n for n, _ in WgradPlan._fields_]
+    assert fields[-2:] == ["dma", "blk_order"]
+    assert ctypes.sizeof(WgradPlan) == 4 * len(fields)
+
+
+def test_loading_the_library_first_leaves_one_hip_runtime():
+    """a process that loads the library before it imports torch (__graft_entry__.build() followed by smoke() does) must
+    not end up with two HIP runtimes mapped -- the system's and the copy in torch's wheel: launches on torch's streams
+    then fail"""
+    import subprocess
+    import sys
+    code = ("import sys; sys.path[:0] = %r\n"
+            "from cyhip import _lib; _lib.load(); import torch\n"
+            "print(len({l.split()[-1] for l in open('/proc/self/maps') if 'libamdhip64' in l}))\n"
+            % [str(REPO), str(REPO / "contrast-you_amd")])
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    assert int(r.stdout.strip().splitlines()[-1]) == 1, r.stdout

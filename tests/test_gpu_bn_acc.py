@@ -15,6 +15,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests.bn_acc_checks import acc_sums, assert_acc_equals_partial_rows
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
@@ -29,14 +31,6 @@ def nhwc(t, dtype=None):
     if dtype is not None:
         t = t.to(dtype)
     return t.to(DEV).permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
-
-
-def acc_sums(acc):
-    """(sum, sum of squares) per channel as f64 from an accumulator [R][4][C]"""
-    R, C = acc.R, acc.C
-    w = acc.t[: R * 4 * C].view(R, 4, C).sum(0).double()
-    assert int(acc.t[R * 4 * C:].sum()) == 0
-    return w[0] / 4096.0 + w[1] / 2.0 ** 44, w[2] / 4096.0 + w[3] / 2.0 ** 44
 
 
 # (N, H, W, C1, C2, Cout, mode, prologue, dtype): one case per producer kernel family
@@ -63,13 +57,7 @@ def test_accumulated_sums_equal_the_partial_rows(case):
     y0, part = ops.conv3x3_fwd(x, None, wf, Cout, mode=mode)
     y1, acc = ops.conv3x3_fwd(x, None, wf, Cout, mode=mode, stats_acc=True)
     assert torch.equal(y0, y1)
-    s1, s2 = acc_sums(acc)
-    p = part.double().sum(0)
-    # the partial rows are f32; their exact sum is what the accumulator holds (each split is exact above 2^-21) -- but
-    # for the streaming kernel, which sums its four wave rows in f32 before it adds (one add per workgroup)
-    tol = 1e-6 if (C1 <= 64 and Cout <= 64 and H == 224) else 1e-9
-    assert torch.allclose(s1, p[0], rtol=0, atol=tol * max(1.0, p[0].abs().max().item()))
-    assert torch.allclose(s2, p[1], rtol=tol, atol=1e-9)
+    assert_acc_equals_partial_rows(acc, part, streaming=(C1 <= 64 and Cout <= 64 and H == 224))
     # order independence: a second run gives the same words
     _, acc2 = ops.conv3x3_fwd(x, None, wf, Cout, mode=mode, stats_acc=True)
     assert torch.equal(acc.t, acc2.t)

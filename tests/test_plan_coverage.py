@@ -1,34 +1,92 @@
-"""Every conv / weight-gradient kernel instantiation that the benchmark profile (profiles/) shows is reached
-by a parity case of tests/test_gpu_c2_geometry.py: the launch plan is a pure host-side function of the layer
-geometry (cy_conv3x3_plan / cy_conv3x3_wgrad_plan), so the coverage claim is checked here, on the CPU, and
-the GPU test asserts per case that the plan it ran is the one listed here."""
+"""The conv / weight-gradient launch plans of all three benchmark workloads (tests/c2_layers.py WORKLOADS: c2, c4, c5)
+are reached by parity cases of tests/test_gpu_c2_geometry.py.  The launch plan is a pure host-side function of the layer
+geometry, the batch and the storage type (cy_conv3x3_plan / cy_conv3x3_wgrad_plan), so the coverage claim is checked
+here, on the CPU, twice: against the kernel instantiations the newest benchmark profile of each workload names, and --
+independent of any profile -- against the plans today's planner gives every (layer, N, direction) of the workload table.
+The GPU cases take their plans from the same queries and assert per case what a launch lets them observe of it.
+Also here: the 2 GiB rule of the planners (32-bit buffer offsets below it, the 64-bit-offset kernels above)."""
+import pytest
 import torch
 
 from tests import c2_layers as cl
 
 
-def _tested_kernel_names():
-    from cyhip import ops
-    names = set()
-    for N in (16, 32):
-        for name, H, C1, C2, Cout, mode, pro in cl.unet_layers(224, 512):
-            names.add(cl.conv_kernel_name(ops.conv3x3_plan(N, H, H, C1, C2, Cout, torch.bfloat16, mode, pro),
-                                          cin=C1 + C2, stats=True, pro=bool(pro)))
-            names.add(cl.conv_kernel_name(ops.conv3x3_plan(N, H, H, Cout, 0, C1 + C2, torch.bfloat16, 0, 0), cin=Cout))
-            names.add(cl.wgrad_kernel_name(ops.conv3x3_wgrad_plan(N, H, H, C1, C2, Cout, torch.bfloat16, mode, pro)))
-    for name, H, C1, C2, Cout, mode, pro in cl.unet_layers(224, 512):
-        if name in cl.ENCODER:  # the two passes of the two-stage step in one launch
-            names.add(cl.wgrad_kernel_name(ops.conv3x3_wgrad_plan(16, H, H, C1, C2, Cout, torch.bfloat16, mode, pro,
-                                                                  n_b=32)))
-    return names
+def _gpu_case_lists(workload):
+    """the parameter lists tests/test_gpu_c2_geometry.py hands to pytest.mark.parametrize for a workload:
+    ((layer, N) cases, paired weight-gradient layers)"""
+    from tests import test_gpu_c2_geometry as geo
+    layers, batches, pair_layers = geo.GEOMETRY_CASES[workload]
+    return [(l, n) for l in layers for n in batches], pair_layers
 
 
-def test_every_profiled_conv_instantiation_has_a_parity_case():
-    prof = cl.profiled_conv_kernels(cl.latest_profile())
+@pytest.mark.parametrize("workload", sorted(cl.WORKLOADS))
+def test_every_profiled_conv_instantiation_has_a_parity_case(workload):
+    path = cl.latest_profile(workload)
+    assert path is not None, f"no kernel summary of the {workload} benchmark under profiles/"
+    prof = cl.profiled_conv_kernels(path)
     assert prof, "no conv kernels found in the profile summary"
-    tested = _tested_kernel_names()
+    row = cl.WORKLOADS[workload]
+    cases, pair_layers = _gpu_case_lists(workload)
+    tested = cl.kernel_names(cases, pair_layers, row["pair"], row["dtype"])
     missing = sorted(prof - tested)
-    assert not missing, f"{cl.latest_profile().name} names kernel instantiations no C2-geometry parity case reaches: {missing}"
+    assert not missing, f"{path.name} names kernel instantiations no {workload}-geometry parity case reaches: {missing}"
+
+
+@pytest.mark.parametrize("workload", sorted(cl.WORKLOADS))
+def test_every_plan_of_a_workload_has_a_parity_case(workload):
+    """no workload row, layer, N or direction is filtered out of the GPU parametrisation: the plan tuples of the
+    workload table (left) against those of the lists the GPU cases are parametrised with (right)"""
+    row = cl.WORKLOADS[workload]
+    want = cl.workload_plan_tuples(workload)
+    cases, pair_layers = _gpu_case_lists(workload)
+    have = cl.case_tuples(cases, pair_layers, row["pair"], row["dtype"])
+    assert want, workload
+    missing = {t: want[t] for t in want if t not in have}
+    assert not missing, (f"{len(missing)} launch plans of the {workload} benchmark have no parity case "
+                         f"(plan tuple: launches that get it): {missing}")
+
+
+def _largest_below_2gib(H, C, esz=2):
+    """largest N for which an N x H x H x C tensor of esz-byte elements is addressable with 32-bit byte offsets"""
+    return (2 ** 31 - 1) // (H * H * C * esz)
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "fp16"])
+def test_two_gib_rule_streaming_layer(dtype):
+    """224 x 224, 32 -> 32 channels (Conv1b): the last N below 2 GiB keeps the streaming kernel and the LDS-DMA weight
+    gradient, the next one falls back to the 64-bit-offset plane kernel and wgrad12_kernel"""
+    from cyhip import ops
+    n = _largest_below_2gib(224, 32)
+    assert n * 224 * 224 * 32 * 2 <= 2 ** 31 - 1 < (n + 1) * 224 * 224 * 32 * 2
+    for pro in (0, 1):
+        below = ops.conv3x3_plan(n, 224, 224, 32, 0, 32, dtype, 0, pro)
+        above = ops.conv3x3_plan(n + 1, 224, 224, 32, 0, 32, dtype, 0, pro)
+        assert below["kernel"] == "conv3x3_stream_kernel", below
+        assert above["kernel"] == "conv3x3_plane_kernel", above
+        wb = ops.conv3x3_wgrad_plan(n, 224, 224, 32, 0, 32, dtype, 0, pro)
+        wa = ops.conv3x3_wgrad_plan(n + 1, 224, 224, 32, 0, 32, dtype, 0, pro)
+        assert wb["twelve"] == 2 and wb["dma"] == 1, wb
+        assert wa["twelve"] == 1 and wa["dma"] == 0 and wa["blk_order"] == 0, wa
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "fp16"])
+def test_two_gib_rule_flow_layer(dtype):
+    """56 x 56, 128 -> 128 channels (Conv3b): the limit falls at another N; below it the flow kernel and the LDS-DMA
+    weight gradient, above it the plane kernel and register-staging loaders (64 x 64 blocks keep wgrad12s_kernel)"""
+    from cyhip import ops
+    n = _largest_below_2gib(56, 128)
+    assert n != _largest_below_2gib(224, 32)
+    below = ops.conv3x3_plan(n, 56, 56, 128, 0, 128, dtype, 0, 1)
+    above = ops.conv3x3_plan(n + 1, 56, 56, 128, 0, 128, dtype, 0, 1)
+    assert below["kernel"] == "conv3x3_flow_kernel", below
+    assert above["kernel"] == "conv3x3_plane_kernel", above
+    wb = ops.conv3x3_wgrad_plan(n, 56, 56, 128, 0, 128, dtype, 0, 1)
+    wa = ops.conv3x3_wgrad_plan(n + 1, 56, 56, 128, 0, 128, dtype, 0, 1)
+    assert wb["twelve"] == 2 and wb["dma"] == 1, wb
+    assert wa["dma"] == 0 and wa["blk_order"] == 0, wa
+    # the paired launch is planned from the total batch
+    wp = ops.conv3x3_wgrad_plan(n - 15, 56, 56, 128, 0, 128, dtype, 0, 1, n_b=16)
+    assert wp["dma"] == 0, wp
 
 
 def test_plan_query_matches_partials_and_split():
