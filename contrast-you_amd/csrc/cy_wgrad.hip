@@ -14,7 +14,8 @@
 // pixels, `S` splits); inside the workgroup WK waves split the pixels of a tile.
 // Each split writes its f32 slab ws[s][tap][co][ci]; wgrad_reduce_kernel adds
 // the slabs in split order (bitwise reproducible) into the reference layout
-// dw[Cout][Cin][3][3].
+// dw[Cout][Cin][3][3] -- as a launch of its own, or, for the _deferred entry points, as part of ONE
+// wgrad_batched_reduce_kernel launch over many layers (cy_wgrad_reduce_batched, same summation tree).
 //
 // The input tile is staged by the same halo stager as the forward kernel, so
 // pool / upsample / concat / BN+ReLU-prologue addressing is identical.
@@ -613,18 +614,18 @@ __global__ void __launch_bounds__(768, 1)
   }
 }
 
-__global__ void __launch_bounds__(256)
-    wgrad_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dw, int S, int SG, int Cout,
-                        int Cin, int co_pad, int ci_pad, int accumulate) {
+// One workgroup (256 threads) of the slab sum of a layer: `block` is its index in the layer's grid, sred 256 x 36 floats.
+__device__ __forceinline__ void wgrad_reduce_block(const float* __restrict__ ws, float* __restrict__ dw, int S, int SG,
+                                                   int Cout, int Cin, int co_pad, int ci_pad, int accumulate, int block,
+                                                   float* sred) {
   // thread = four consecutive ci of one co (16-byte slab reads, 36 contiguous output floats) x one
   // of SG slab groups.  Group g sums slabs g, g+SG, ... in increasing order, then the SG group sums
   // are added in group order: the summation tree is a function of (S, SG) only => bitwise reproducible.
-  __shared__ float sred[256 * 36];
   const int opb = 256 / SG;
   const int ol = threadIdx.x % opb, sg = threadIdx.x / opb;
   const int Q = Cin / 4;
   const long total = (long)Cout * Q;
-  const long i = (long)blockIdx.x * opb + ol;
+  const long i = (long)block * opb + ol;
   const size_t slab = (size_t)9 * co_pad * ci_pad;
   const size_t tapstride = (size_t)co_pad * ci_pad;
   f32x4 s[9];
@@ -666,6 +667,13 @@ __global__ void __launch_bounds__(256)
           o[j * 9 + t] = s[t][j];
       }
   }
+}
+
+__global__ void __launch_bounds__(256)
+    wgrad_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dw, int S, int SG, int Cout,
+                        int Cin, int co_pad, int ci_pad, int accumulate) {
+  __shared__ float sred[256 * 36];
+  wgrad_reduce_block(ws, dw, S, SG, Cout, Cin, co_pad, ci_pad, accumulate, blockIdx.x, sred);
 }
 
 struct WgPlan {
@@ -968,12 +976,10 @@ __global__ void __launch_bounds__(256)
 }
 
 // dw[i] (+)= sum over the block partials: 4 outputs per workgroup, 64 slices each, fixed order
-__global__ void __launch_bounds__(256)
-    first_wgrad_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dw, int nblk,
-                              int total, int accumulate) {
-  __shared__ float sr[64][4];
+__device__ __forceinline__ void first_wgrad_reduce_block(const float* __restrict__ ws, float* __restrict__ dw, int nblk,
+                                                         int total, int accumulate, int block, float (*sr)[4]) {
   const int el = threadIdx.x & 3, sl = threadIdx.x >> 2;
-  const int i = blockIdx.x * 4 + el;
+  const int i = block * 4 + el;
   float s = 0.f;
   if (i < total)
     for (int q = sl; q < nblk; q += 64) s += ws[(size_t)q * total + i];
@@ -986,6 +992,35 @@ __global__ void __launch_bounds__(256)
   }
 }
 
+__global__ void __launch_bounds__(256)
+    first_wgrad_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dw, int nblk,
+                              int total, int accumulate) {
+  __shared__ float sr[64][4];
+  first_wgrad_reduce_block(ws, dw, nblk, total, accumulate, blockIdx.x, sr);
+}
+
+// The slab sums of up to CY_WGRAD_REDUCE_MAX layers in ONE launch (the table travels as a kernel argument).  Entry j
+// owns workgroups [first_block, first_block + blocks); each runs exactly the workgroup of wgrad_reduce_kernel (conv) or
+// first_wgrad_reduce_kernel (first layer) it replaces, so every output keeps its summation tree.  The host splits a
+// table so that no two entries of one launch write overlapping dW.
+struct WgRedTable {
+  cy_wgrad_reduce_entry e[CY_WGRAD_REDUCE_MAX];
+  int n;
+};
+__global__ void __launch_bounds__(256) wgrad_batched_reduce_kernel(const WgRedTable t) {
+  __shared__ float sred[256 * 36];
+  const int blk = blockIdx.x;
+  int j = 0;
+  for (int k = 1; k < t.n; ++k)
+    if (blk >= t.e[k].first_block) j = k;
+  const cy_wgrad_reduce_entry& e = t.e[j];
+  const int b = blk - e.first_block;
+  if (e.kind == CY_WGRAD_REDUCE_CONV)
+    wgrad_reduce_block(e.ws, e.dw, e.S, e.SG, e.Cout, e.Cin, e.co_pad, e.ci_pad, e.accumulate, b, sred);
+  else
+    first_wgrad_reduce_block(e.ws, e.dw, e.S, e.Cout * e.Cin * 9, e.accumulate, b, reinterpret_cast<float(*)[4]>(sred));
+}
+
 // workgroups of first_wgrad_mfma_kernel (sub-blocks of eight rows, contiguous ranges of them), or 0 where it does not apply
 int first_wgrad_mfma_blocks(int N, int Cin, int H, int W, int Cout, int dtype) {
   static const bool enabled = [] {
@@ -995,6 +1030,26 @@ int first_wgrad_mfma_blocks(int N, int Cin, int H, int W, int Cout, int dtype) {
   if (!enabled || Cin != 1 || Cout != 32 || (dtype != CY_BF16 && dtype != CY_F16) || H % 8 || W % 16 || W > 2048) return 0;
   const long nsub = (long)N * H / 8;
   return (int)(nsub < 1024 ? nsub : 1024);
+}
+
+// the slab sum of a layer (plan p): wgrad_reduce_kernel's (S, SG) and grid; ws / dw / accumulate left to the caller
+void conv_reduce_entry(const WgPlan& p, int Cout, int Cin, cy_wgrad_reduce_entry* e) {
+  const long total = (long)Cout * (Cin / 4);  // one thread per four consecutive ci
+  int SG = 1;  // slab groups per output: more when there are few outputs and many slabs
+  while (SG < 32 && SG * 2 <= p.S && (total * SG) / 256 < 1024) SG *= 2;
+  const int opb = 256 / SG;
+  *e = cy_wgrad_reduce_entry{};
+  e->kind = CY_WGRAD_REDUCE_CONV;
+  e->S = p.S, e->SG = SG, e->Cout = Cout, e->Cin = Cin, e->co_pad = p.co_pad, e->ci_pad = p.ci_pad;
+  e->blocks = (int)((total + opb - 1) / opb);
+}
+
+// the partial sum of the first layer over `nblk` workgroup partials: first_wgrad_reduce_kernel's 64 slices
+void first_reduce_entry(int nblk, int Cin, int Cout, cy_wgrad_reduce_entry* e) {
+  *e = cy_wgrad_reduce_entry{};
+  e->kind = CY_WGRAD_REDUCE_FIRST;
+  e->S = nblk, e->SG = 64, e->Cout = Cout, e->Cin = Cin;
+  e->blocks = cy_cdiv(Cout * Cin * 9, 4);
 }
 
 int first_wgrad_blocks(long npix, int W) {
@@ -1039,10 +1094,11 @@ size_t cy_conv3x3_wgrad_ws_bytes(const cy_conv_desc* d) {
 
 // one launch over the pixels of `d` (segment a) and, when n_b > 0, of the same layer on a second batch
 // of n_b images (segment b: its own tensors and BN coefficients); plan from the total batch
+// deferred != NULL: the slab sum is not launched; its entry (for cy_wgrad_reduce_batched) is left there instead
 static int wgrad_impl(const cy_conv_desc* d, const void* src1, const void* src2, const float* scale,
                       const float* shift, const void* dy, int n_b, const void* src1_b, const void* src2_b,
                       const float* scale_b, const float* shift_b, const void* dy_b, float* dw,
-                      int accumulate, void* ws, size_t ws_bytes, void* stream) {
+                      int accumulate, void* ws, size_t ws_bytes, cy_wgrad_reduce_entry* deferred, void* stream) {
   if (!d || !src1 || !dy || !dw || !ws) return CY_ERR_ARG;
   if (d->N <= 0 || d->H <= 0 || d->W <= 0 || d->C1 <= 0 || d->C2 < 0 || d->Cout <= 0)
     return CY_ERR_SHAPE;
@@ -1106,13 +1162,15 @@ static int wgrad_impl(const cy_conv_desc* d, const void* src1, const void* src2,
   if (rc != CY_OK) return rc;
   const int Cin = d->C1 + d->C2;
   if (Cin % 4) return CY_ERR_SHAPE;
-  const long total = (long)d->Cout * (Cin / 4);  // one thread per four consecutive ci
-  int SG = 1;  // slab groups per output: more when there are few outputs and many slabs
-  while (SG < 32 && SG * 2 <= p.S && (total * SG) / 256 < 1024) SG *= 2;
-  const int opb = 256 / SG;
-  const int blocks = (int)((total + opb - 1) / opb);
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, st, (const float*)ws, dw,
-                     p.S, SG, d->Cout, Cin, p.co_pad, p.ci_pad, accumulate);
+  cy_wgrad_reduce_entry e;
+  conv_reduce_entry(p, d->Cout, Cin, &e);
+  e.ws = (const float*)ws, e.dw = dw, e.accumulate = accumulate ? 1 : 0;
+  if (deferred) {
+    *deferred = e;
+    return CY_OK;
+  }
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(e.blocks), dim3(256), 0, st, (const float*)ws, dw,
+                     e.S, e.SG, d->Cout, Cin, p.co_pad, p.ci_pad, accumulate);
   CY_CHECK_LAUNCH();
   return CY_OK;
 }
@@ -1121,7 +1179,99 @@ int cy_conv3x3_wgrad(const cy_conv_desc* d, const void* src1, const void* src2, 
                      const float* shift, const void* dy, float* dw, int accumulate, void* ws,
                      size_t ws_bytes, void* stream) {
   return wgrad_impl(d, src1, src2, scale, shift, dy, 0, nullptr, nullptr, nullptr, nullptr, nullptr, dw,
-                    accumulate, ws, ws_bytes, stream);
+                    accumulate, ws, ws_bytes, nullptr, stream);
+}
+
+int cy_conv3x3_wgrad_deferred(const cy_conv_desc* d, const void* src1, const void* src2, const float* scale,
+                              const float* shift, const void* dy, float* dw, int accumulate, void* ws,
+                              size_t ws_bytes, cy_wgrad_reduce_entry* h_entry, void* stream) {
+  if (!h_entry) return CY_ERR_ARG;
+  return wgrad_impl(d, src1, src2, scale, shift, dy, 0, nullptr, nullptr, nullptr, nullptr, nullptr, dw,
+                    accumulate, ws, ws_bytes, h_entry, stream);
+}
+
+int cy_conv3x3_wgrad_reduce_entry(const cy_conv_desc* d, int n_b, cy_wgrad_reduce_entry* h_entry) {
+  if (!d || !h_entry || d->Cout <= 0 || d->C1 <= 0 || d->C2 < 0 || d->H <= 0 || d->W <= 0 || d->N <= 0 || n_b < 0)
+    return CY_ERR_ARG;
+  if ((d->C1 + d->C2) % 4) return CY_ERR_SHAPE;
+  cy_conv_desc dt = *d;
+  dt.N += n_b;
+  conv_reduce_entry(plan_wgrad(&dt), d->Cout, d->C1 + d->C2, h_entry);
+  return CY_OK;
+}
+
+int cy_conv3x3_first_wgrad_reduce_entry(int N, int Cin, int H, int W, int Cout, int dy_dtype,
+                                        cy_wgrad_reduce_entry* h_entry) {
+  if (!h_entry || N <= 0 || H <= 0 || W <= 0 || Cin < 1 || Cin > 4 || Cout % 8 || Cout <= 0 || Cout > 64)
+    return CY_ERR_ARG;
+  int nblk = first_wgrad_mfma_blocks(N, Cin, H, W, Cout, dy_dtype);
+  if (!nblk) nblk = first_wgrad_blocks((long)N * H * W, W);
+  if (nblk < 0) return CY_ERR_SHAPE;
+  first_reduce_entry(nblk, Cin, Cout, h_entry);
+  return CY_OK;
+}
+
+int cy_wgrad_reduce_batched(const cy_wgrad_reduce_entry* h_entries, int n, void* stream) {
+  if (!h_entries || n <= 0) return CY_ERR_ARG;
+  for (int i = 0; i < n; ++i) {
+    const cy_wgrad_reduce_entry& e = h_entries[i];
+    if (!e.ws || !e.dw || e.S < 1 || e.Cout <= 0 || e.Cin <= 0) return CY_ERR_ARG;
+    if (e.kind == CY_WGRAD_REDUCE_CONV) {
+      if (e.SG < 1 || e.SG > 32 || (e.SG & (e.SG - 1)) || e.Cin % 4 || e.co_pad < e.Cout || e.ci_pad < e.Cin)
+        return CY_ERR_ARG;
+      const long total = (long)e.Cout * (e.Cin / 4);
+      if (e.blocks != (int)((total + 256 / e.SG - 1) / (256 / e.SG))) return CY_ERR_ARG;
+    } else if (e.kind == CY_WGRAD_REDUCE_FIRST) {
+      if (e.SG != 64 || e.blocks != cy_cdiv(e.Cout * e.Cin * 9, 4)) return CY_ERR_ARG;
+    } else {
+      return CY_ERR_ARG;
+    }
+  }
+  // launches in table order; a new one begins when the table is full or an entry's dW overlaps one already in it
+  // (updates of one dW then take effect in table order)
+  hipStream_t st = (hipStream_t)stream;
+  WgRedTable t;
+  t.n = 0;
+  int blocks = 0;
+  auto launch = [&]() -> int {
+    if (!t.n) return CY_OK;
+    // (the entries of one launch write disjoint dW, so their order in it is free: the longest workgroups -- many slabs
+    //  per thread, a long serial sum of the slab groups -- are dispatched first instead of forming the tail)
+    auto chain = [](const cy_wgrad_reduce_entry& e) { return (e.S + e.SG - 1) / e.SG + e.SG; };
+    for (int i = 1; i < t.n; ++i)
+      for (int k = i; k > 0 && chain(t.e[k]) > chain(t.e[k - 1]); --k) {
+        const cy_wgrad_reduce_entry tmp = t.e[k];
+        t.e[k] = t.e[k - 1], t.e[k - 1] = tmp;
+      }
+    for (int i = 0, b0 = 0; i < t.n; b0 += t.e[i].blocks, ++i) t.e[i].first_block = b0;
+    hipLaunchKernelGGL(wgrad_batched_reduce_kernel, dim3(blocks), dim3(256), 0, st, t);
+    CY_CHECK_LAUNCH();
+    t.n = 0, blocks = 0;
+    return CY_OK;
+  };
+  auto span = [](const cy_wgrad_reduce_entry& e, const float*& lo, const float*& hi) {
+    lo = e.dw, hi = e.dw + (size_t)e.Cout * e.Cin * 9;
+  };
+  for (int i = 0; i < n; ++i) {
+    const cy_wgrad_reduce_entry& e = h_entries[i];
+    const float *lo, *hi;
+    span(e, lo, hi);
+    bool clash = t.n == CY_WGRAD_REDUCE_MAX;
+    for (int k = 0; k < t.n && !clash; ++k) {
+      const float *lo2, *hi2;
+      span(t.e[k], lo2, hi2);
+      clash = lo < hi2 && lo2 < hi;
+    }
+    if (clash) {
+      const int rc = launch();
+      if (rc != CY_OK) return rc;
+    }
+    t.e[t.n] = e;
+    t.e[t.n].first_block = blocks;
+    blocks += e.blocks;
+    ++t.n;
+  }
+  return launch();
 }
 
 size_t cy_conv3x3_wgrad_pair_ws_bytes(const cy_conv_desc* d, int n_b) {
@@ -1138,7 +1288,17 @@ int cy_conv3x3_wgrad_pair(const cy_conv_desc* d, const void* src1, const void* s
                           void* stream) {
   if (n_b <= 0) return CY_ERR_ARG;
   return wgrad_impl(d, src1, src2, scale, shift, dy, n_b, src1_b, src2_b, scale_b, shift_b, dy_b, dw,
-                    accumulate, ws, ws_bytes, stream);
+                    accumulate, ws, ws_bytes, nullptr, stream);
+}
+
+int cy_conv3x3_wgrad_pair_deferred(const cy_conv_desc* d, const void* src1, const void* src2, const float* scale,
+                                   const float* shift, const void* dy, int n_b, const void* src1_b,
+                                   const void* src2_b, const float* scale_b, const float* shift_b,
+                                   const void* dy_b, float* dw, int accumulate, void* ws, size_t ws_bytes,
+                                   cy_wgrad_reduce_entry* h_entry, void* stream) {
+  if (n_b <= 0 || !h_entry) return CY_ERR_ARG;
+  return wgrad_impl(d, src1, src2, scale, shift, dy, n_b, src1_b, src2_b, scale_b, shift_b, dy_b, dw,
+                    accumulate, ws, ws_bytes, h_entry, stream);
 }
 
 size_t cy_conv3x3_first_wgrad_ws_bytes(int N, int Cin, int H, int W, int Cout) {
@@ -1148,9 +1308,9 @@ size_t cy_conv3x3_first_wgrad_ws_bytes(int N, int Cin, int H, int W, int Cout) {
   return (size_t)nb * Cout * Cin * 9 * sizeof(float);
 }
 
-int cy_conv3x3_first_wgrad(const float* x, const void* dy, float* dw, int accumulate, int N, int Cin,
-                           int H, int W, int Cout, int dy_dtype, void* ws, size_t ws_bytes,
-                           void* stream) {
+static int first_wgrad_impl(const float* x, const void* dy, float* dw, int accumulate, int N, int Cin, int H, int W,
+                            int Cout, int dy_dtype, void* ws, size_t ws_bytes, cy_wgrad_reduce_entry* deferred,
+                            void* stream) {
   if (!x || !dy || !dw || !ws) return CY_ERR_ARG;
   if (Cin < 1 || Cin > 4 || Cout % 8 || Cout > 64 || 256 % (Cout / 8)) return CY_ERR_SHAPE;
   if ((long)N * H * W >= (1L << 31)) return CY_ERR_SHAPE;
@@ -1174,6 +1334,11 @@ int cy_conv3x3_first_wgrad(const float* x, const void* dy, float* dw, int accumu
     else
       hipLaunchKernelGGL(first_wgrad_mfma_kernel<f16>, dim3(nm), dim3(256), smem, st, x, (const f16*)dy, (float*)ws, N, H, W, spb);
     CY_CHECK_LAUNCH();
+    if (deferred) {
+      first_reduce_entry(nm, Cin, Cout, deferred);
+      deferred->ws = (const float*)ws, deferred->dw = dw, deferred->accumulate = accumulate ? 1 : 0;
+      return CY_OK;
+    }
     const int total = Cout * 9;
     hipLaunchKernelGGL(first_wgrad_reduce_kernel, dim3(cy_cdiv(total, 4)), dim3(256), 0, st, (const float*)ws, dw, nm, total,
                        accumulate);
@@ -1204,11 +1369,29 @@ int cy_conv3x3_first_wgrad(const float* x, const void* dy, float* dw, int accumu
   else
     return CY_ERR_DTYPE;
   CY_CHECK_LAUNCH();
+  if (deferred) {
+    first_reduce_entry(nblk, Cin, Cout, deferred);
+    deferred->ws = (const float*)ws, deferred->dw = dw, deferred->accumulate = accumulate ? 1 : 0;
+    return CY_OK;
+  }
   const int total = Cout * Cin * 9;
   hipLaunchKernelGGL(first_wgrad_reduce_kernel, dim3(cy_cdiv(total, 4)), dim3(256), 0, st,
                      (const float*)ws, dw, nblk, total, accumulate);
   CY_CHECK_LAUNCH();
   return CY_OK;
+}
+
+int cy_conv3x3_first_wgrad(const float* x, const void* dy, float* dw, int accumulate, int N, int Cin,
+                           int H, int W, int Cout, int dy_dtype, void* ws, size_t ws_bytes,
+                           void* stream) {
+  return first_wgrad_impl(x, dy, dw, accumulate, N, Cin, H, W, Cout, dy_dtype, ws, ws_bytes, nullptr, stream);
+}
+
+int cy_conv3x3_first_wgrad_deferred(const float* x, const void* dy, float* dw, int accumulate, int N, int Cin,
+                                    int H, int W, int Cout, int dy_dtype, void* ws, size_t ws_bytes,
+                                    cy_wgrad_reduce_entry* h_entry, void* stream) {
+  if (!h_entry) return CY_ERR_ARG;
+  return first_wgrad_impl(x, dy, dw, accumulate, N, Cin, H, W, Cout, dy_dtype, ws, ws_bytes, h_entry, stream);
 }
 
 }  // extern "C"

@@ -11,7 +11,7 @@ from pathlib import Path
 
 CY_F32, CY_BF16, CY_F16 = 0, 1, 2
 CY_SRC_DIRECT, CY_SRC_POOL2, CY_SRC_UP2 = 0, 1, 2
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 _ERRORS = {-1: "CY_ERR_ARG (bad/NULL argument)", -2: "CY_ERR_SHAPE (unsupported shape)",
            -3: "CY_ERR_DTYPE (unsupported dtype)", -4: "CY_ERR_LAUNCH (HIP launch failed)",
@@ -53,6 +53,15 @@ class WgradPlan(C.Structure):
                                                "blk_order")]
 
 
+class WgradReduceEntry(C.Structure):
+    """mirror of cy_wgrad_reduce_entry"""
+    _fields_ = [("ws", c_void_p), ("dw", c_void_p)] + [(n, c_int32) for n in (
+        "kind", "S", "SG", "Cout", "Cin", "co_pad", "ci_pad", "accumulate", "blocks", "first_block")]
+
+
+CY_WGRAD_REDUCE_CONV, CY_WGRAD_REDUCE_FIRST, CY_WGRAD_REDUCE_MAX = 0, 1, 32
+
+
 class BnAcc(C.Structure):
     """mirror of cy_bn_acc"""
     _fields_ = [("acc", c_void_p), ("R", c_int32), ("C", c_int32)]
@@ -92,6 +101,7 @@ _PCD = POINTER(ConvDesc)
 _PML = POINTER(MatLayout)
 _PBA = POINTER(BnAcc)
 _PBF = POINTER(BnFold)
+_PWE = POINTER(WgradReduceEntry)
 
 # name -> (restype, argtypes).  restype c_int functions are status-checked.
 _SIGS = {
@@ -121,6 +131,14 @@ _SIGS = {
     "cy_conv3x3_wgrad_pair_ws_bytes": (c_size_t, [_PCD, c_int]),
     "cy_conv3x3_wgrad_pair": (c_int, [_PCD, _P, _P, _P, _P, _P, c_int, _P, _P, _P, _P, _P, _P, c_int, _P,
                                       c_size_t, _P]),
+    "cy_conv3x3_wgrad_deferred": (c_int, [_PCD, _P, _P, _P, _P, _P, _P, c_int, _P, c_size_t, _PWE, _P]),
+    "cy_conv3x3_wgrad_pair_deferred": (c_int, [_PCD, _P, _P, _P, _P, _P, c_int, _P, _P, _P, _P, _P, _P, c_int, _P,
+                                               c_size_t, _PWE, _P]),
+    "cy_conv3x3_first_wgrad_deferred": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P,
+                                                c_size_t, _PWE, _P]),
+    "cy_conv3x3_wgrad_reduce_entry": (c_int, [_PCD, c_int, _PWE]),
+    "cy_conv3x3_first_wgrad_reduce_entry": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, _PWE]),
+    "cy_wgrad_reduce_batched": (c_int, [_PWE, c_int, _P]),
     "cy_bn_acc_replicas": (c_int, [c_int, c_int]),
     "cy_bn_acc_bytes": (c_size_t, [c_int, c_int]),
     "cy_conv3x3_stat_workgroups": (c_int, [_PCD]),

@@ -164,7 +164,7 @@ def _flush_parked() -> None:
         p = _parked.pop(key)
         p.w.__dict__["_cy_uses"] = 0
         with torch.cuda.stream(p.stream):
-            ops.conv3x3_wgrad(p.src1, p.src2, p.dy, mode=p.mode, scale=p.scale, shift=p.shift, out=p.sink)
+            ops.conv3x3_wgrad(p.src1, p.src2, p.dy, mode=p.mode, scale=p.scale, shift=p.shift, out=p.sink, defer=True)
         ops.note_side_work(p.stream)  # (a no-op for the home stream's join; covers a parked side stream)
 
 
@@ -183,7 +183,7 @@ def wgrad_into_sink(w: Tensor, sink: Tensor, src1: Tensor, src2: Optional[Tensor
         if p.stream != cur and p.capid == ops._capture_id(cur):
             cur.wait_event(p.event)
         ops.conv3x3_wgrad_pair(p.src1, p.src2, p.dy, p.scale, p.shift, src1, src2, dy, scale, shift,
-                               mode=mode, out=sink)
+                               mode=mode, out=sink, defer=True)
         if p.stream != cur:
             if ops.CAPTURING:
                 # inside a capture record_stream is not available: keep the other stream's operands
@@ -208,7 +208,7 @@ def wgrad_into_sink(w: Tensor, sink: Tensor, src1: Tensor, src2: Optional[Tensor
         return
     if _step_first_pass is not None:
         ops.at_backward_end(_flush_parked)  # (also re-arms the pass bookkeeping for the next step)
-    ops.conv3x3_wgrad(src1, src2, dy, mode=mode, scale=scale, shift=shift, out=sink)
+    ops.conv3x3_wgrad(src1, src2, dy, mode=mode, scale=scale, shift=shift, out=sink, defer=True)
 
 
 def compute_dtype_for(x: Tensor, requested: Optional[torch.dtype]) -> torch.dtype:
@@ -306,11 +306,12 @@ def _bn_relu_grad(ctx, i: int, da: Tensor, params, y: Tensor, coef, accs: Option
 def _weight_grad(w: Tensor, sink: Optional[Tensor], src1: Tensor, src2: Optional[Tensor], dy: Tensor, mode: int,
                  scale: Optional[Tensor], shift: Optional[Tensor], first: bool, pass_id: int) -> Optional[Tensor]:
     """dw of one 3x3 conv (of the image-reading first layer if `first`): added into the live .grad `sink` -- on the side
-    stream with ASYNC_WGRAD -- and None returned, or returned"""
+    stream with ASYNC_WGRAD, its slab sum deferred to the batched launch of the backward pass (ops.DEFER_WGRAD_REDUCE)
+    -- and None returned, or returned"""
     side = sink is not None and ops.ASYNC_WGRAD
     with ops.on_side_stream(src1, src2, dy, scale, shift) if side else contextlib.nullcontext():
         if first:
-            dw = ops.conv_first_wgrad(src1, dy, out=sink)
+            dw = ops.conv_first_wgrad(src1, dy, out=sink, defer=sink is not None)
         elif sink is not None:
             wgrad_into_sink(w, sink, src1, src2, dy, mode, scale, shift, pass_id)
         else:

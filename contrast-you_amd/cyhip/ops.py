@@ -433,7 +433,7 @@ def ensure_backward_join() -> None:
     weight-gradient stream) or work has been deferred to the end of the backward pass, make sure the
     deferred work is issued and the streams are joined when the backward pass ends"""
     global _join_queued
-    if (_side_pending or _at_backward_end) and not _join_queued:
+    if (_side_pending or _at_backward_end or _wg_batches) and not _join_queued:
         try:
             torch.autograd.Variable._execution_engine.queue_callback(_join_after_backward)
             _join_queued = True
@@ -457,12 +457,21 @@ def at_backward_end(fn) -> None:
             _join_after_backward()
 
 
+_in_join = False  # _join_after_backward is running (deferred work it issues is flushed by it)
+
+
 def _join_after_backward() -> None:
-    global _join_queued
+    global _join_queued, _in_join
     _join_queued = False
-    while _at_backward_end:
-        _at_backward_end.pop(0)()
-    join_side_streams()
+    _in_join = True
+    try:
+        while _at_backward_end:
+            _at_backward_end.pop(0)()
+        join_side_streams()
+        for idx in list(_wg_batches):  # the deferred slab sums, on the home stream after the join
+            flush_wgrad_reduce(idx, onto=_home_stream.get(idx), final=True)
+    finally:
+        _in_join = False
 
 
 _home_stream = {}  # device index -> the stream the step itself runs on
@@ -557,6 +566,7 @@ def grad_ready_mark(tag: str, device) -> None:
         return
     flag = _mark_flags[(idx, tag)]
     cur = torch.cuda.current_stream(idx)
+    flush_wgrad_reduce(idx, onto=cur)  # (the deferred slab sums are part of the gradients the mark declares final)
     if torch.cuda.is_current_stream_capturing():
         # Inside the captured step the weight gradients stay on their pass's stream, and this stream has already
         # waited for whatever the other pass contributes to the block's parameters (the parked operands' events of the
@@ -661,10 +671,147 @@ def grad_sink(p: Tensor) -> Optional[Tensor]:
     return None
 
 
+def wgrad_reduce_entry(N, H, W, C1, C2, Cout, dtype: torch.dtype, mode: int = 0, prologue: bool = False,
+                       n_b: int = 0) -> dict:
+    """the slab-sum entry cy_conv3x3_wgrad (n_b > 0: _pair) makes for this layer geometry (host-side query)"""
+    d = _desc(N, H, W, C1, C2, Cout, mode, 1 if prologue else 0, dtype_code(dtype), C1, C2, Cout)
+    e = _lib.WgradReduceEntry()
+    _lib.call("cy_conv3x3_wgrad_reduce_entry", d.ref, n_b, C.byref(e))
+    return {f: getattr(e, f) for f, _ in e._fields_ if f not in ("ws", "dw")}
+
+
+def first_wgrad_reduce_entry(N, Cin, H, W, Cout, dtype: torch.dtype) -> dict:
+    """the partial-sum entry of cy_conv3x3_first_wgrad for these sizes (host-side query)"""
+    e = _lib.WgradReduceEntry()
+    _lib.call("cy_conv3x3_first_wgrad_reduce_entry", N, Cin, H, W, Cout, dtype_code(dtype), C.byref(e))
+    return {f: getattr(e, f) for f, _ in e._fields_ if f not in ("ws", "dw")}
+
+
+# ---- deferred slab sums of the weight gradients ---------------------------------------------------------------------
+# A weight gradient is an MFMA launch that writes f32 partial sums (slabs) and a reduce launch that adds them into dW.
+# Only the optimizer (or an early data-parallel bucket) reads a live .grad, so for the gradients that go into one the
+# reduce launches are collected and issued as ONE batched launch (cy_wgrad_reduce_batched): when the backward pass
+# ends (home stream, after the side-stream join), before a "gradients final" mark, and when the table is full.  Every
+# dW keeps the summation tree of its own reduce launch, so the results are bit-identical.  The slabs of a backward
+# pass live in one arena (all at once: the cost of the deferral, DESIGN.md).
+DEFER_WGRAD_REDUCE = True
+# also flush (on the stream of the layer that crosses it) once this many slab bytes are pending: groups that the last
+# level cache holds; None = only at the points above (DESIGN.md: the measured choice)
+WGRAD_FLUSH_BYTES: Optional[int] = None
+
+
+class SlabArena:
+    """device memory for the slabs of one backward pass, sized by what earlier passes used; an allocation that does
+    not fit gets a tensor of its own.  Released when the backward pass ends, after the batched reduce is enqueued."""
+    high_water = 0
+
+    def __init__(self, device):
+        self.used = 0
+        self.device = device
+        self.bufs = []  # (tensor, stream it was allocated on): the arena first, then what did not fit
+        n = SlabArena.high_water
+        self.size = n
+        if n:
+            self.bufs.append((_ws(n, device), torch.cuda.current_stream(device)))
+
+    def alloc(self, nbytes: int) -> int:
+        a = self.used
+        self.used += (int(nbytes) + 255) & ~255
+        SlabArena.high_water = max(SlabArena.high_water, self.used)
+        if self.used <= self.size:
+            return self.bufs[0][0].data_ptr() + a
+        t = _ws(nbytes, self.device)
+        self.bufs.append((t, torch.cuda.current_stream(self.device)))
+        return t.data_ptr()
+
+    def release(self, last: "torch.cuda.Stream") -> None:
+        """the last reader of the slabs is `last`: outside a capture the allocator must not hand the memory out again
+        on the allocating stream before `last` has run (inside one the memory is the graph's)"""
+        if not (CAPTURING or _lib.load().cy_stream_capture_id(last.cuda_stream)):
+            for t, st in self.bufs:
+                if st != last:
+                    t.record_stream(last)
+        self.bufs = []
+
+
+class _WgradBatch:
+    __slots__ = ("entries", "streams", "arena")
+
+    def __init__(self, device):
+        self.entries = []   # WgradReduceEntry, in issue order
+        self.streams = set()  # streams that wrote slabs (or ran an earlier flush) in this backward pass
+        self.arena = SlabArena(device)
+
+
+_wg_batches = {}  # device index -> _WgradBatch of the backward pass that is executing
+
+
+def _wg_batch(device) -> _WgradBatch:
+    idx = _dev_index(device)
+    b = _wg_batches.get(idx)
+    if b is None:
+        b = _wg_batches[idx] = _WgradBatch(torch.device("cuda", idx))
+    return b
+
+
+def _wg_defer(device, entry) -> None:
+    """file a reduce entry whose MFMA launch was just enqueued on the current stream"""
+    b = _wg_batch(device)
+    b.entries.append(entry)
+    b.streams.add(torch.cuda.current_stream(device))
+    global _join_queued
+    if not _join_queued and not _in_join:
+        try:
+            torch.autograd.Variable._execution_engine.queue_callback(_join_after_backward)
+            _join_queued = True
+        except RuntimeError:  # not inside a backward pass: nothing else comes
+            flush_wgrad_reduce(device, final=True)
+            return
+    if len(b.entries) >= _lib.CY_WGRAD_REDUCE_MAX or (
+            WGRAD_FLUSH_BYTES is not None and sum(_slab_bytes(e) for e in b.entries) >= WGRAD_FLUSH_BYTES):
+        flush_wgrad_reduce(device)
+
+
+def _slab_bytes(e) -> int:
+    return 4 * e.S * 9 * (e.co_pad * e.ci_pad if e.kind == _lib.CY_WGRAD_REDUCE_CONV else e.Cout * e.Cin)
+
+
+def flush_wgrad_reduce(device=None, onto: Optional["torch.cuda.Stream"] = None, final: bool = False) -> None:
+    """issue the deferred slab sums of `device` (all devices if None) as one batched launch on `onto` (default: the
+    current stream; the home stream at the end of the backward pass), after every stream that wrote their slabs.
+    `final`: the backward pass ends, the slab arena is released."""
+    idxs = [_dev_index(device)] if device is not None else list(_wg_batches)
+    for idx in idxs:
+        b = _wg_batches.get(idx)
+        if b is None:
+            continue
+        tgt = onto if onto is not None else torch.cuda.current_stream(idx)
+        if b.entries:
+            for st in b.streams:
+                if st != tgt:
+                    tgt.wait_stream(st)
+            n = len(b.entries)
+            arr = (_lib.WgradReduceEntry * n)(*b.entries)
+            with torch.cuda.stream(tgt):
+                ev = _prof_begin()
+                _lib.call("cy_wgrad_reduce_batched", arr, n, _stream())
+                if ev is not None:  # slabs read once, dW read (accumulate) and written
+                    nb = sum(_slab_bytes(e) + 4.0 * (1 + e.accumulate) * 9 * e.Cout * e.Cin for e in b.entries)
+                    _prof_end(ev, "wgrad_reduce", 0.0, nb)
+            b.entries = []
+            b.streams = {tgt}
+            if tgt != _home_stream.get(idx):
+                _side_pending.add(tgt)  # (joined when the backward pass ends)
+        if final:
+            b.arena.release(tgt)
+            del _wg_batches[idx]
+
+
 def conv3x3_wgrad(src1: Tensor, src2: Optional[Tensor], dy: Tensor, *, mode: int = 0,
                   scale: Optional[Tensor] = None, shift: Optional[Tensor] = None,
-                  out: Optional[Tensor] = None) -> Tensor:
-    """dw [Cout,Cin,3,3] f32; with `out` the result is ADDED into out (gradient accumulation)."""
+                  out: Optional[Tensor] = None, defer: bool = False) -> Tensor:
+    """dw [Cout,Cin,3,3] f32; with `out` the result is ADDED into out (gradient accumulation).  `defer` (with `out`,
+    a live .grad): the slab sum joins the batched launch of the backward pass (DEFER_WGRAD_REDUCE)."""
     require_gpu(src1, dy)
     N, C1 = src1.shape[0], src1.shape[1]
     C2 = 0 if src2 is None else src2.shape[1]
@@ -674,6 +821,19 @@ def conv3x3_wgrad(src1: Tensor, src2: Optional[Tensor], dy: Tensor, *, mode: int
     if d.wgrad_ws is None:
         d.wgrad_ws = _lib.load().cy_conv3x3_wgrad_ws_bytes(d.ref)
     nbytes = d.wgrad_ws
+    defer = defer and out is not None and DEFER_WGRAD_REDUCE
+    if defer:
+        ev = _prof_begin()
+        e = _lib.WgradReduceEntry()
+        ws_ptr = _wg_batch(src1.device).arena.alloc(nbytes)
+        _lib.call("cy_conv3x3_wgrad_deferred", d.ref, src1.data_ptr(), _ptr(src2), _ptr(scale), _ptr(shift),
+                  dy.data_ptr(), out.data_ptr(), 1, ws_ptr, nbytes, C.byref(e), _stream())
+        if ev is not None:
+            esz = src1.element_size()
+            nb = esz * (src1.numel() + (0 if src2 is None else src2.numel()) + dy.numel()) + 4 * 9 * (C1 + C2) * Cout
+            _prof_end(ev, "conv3x3_wgrad", 2.0 * N * H * W * 9 * (C1 + C2) * Cout, float(nb))
+        _wg_defer(src1.device, e)
+        return out
     ws = _ws(nbytes, src1.device)
     dw = out if out is not None else torch.empty((Cout, C1 + C2, 3, 3), dtype=torch.float32, device=src1.device)
     ev = _prof_begin()
@@ -691,9 +851,10 @@ def conv3x3_wgrad(src1: Tensor, src2: Optional[Tensor], dy: Tensor, *, mode: int
 
 def conv3x3_wgrad_pair(src1: Tensor, src2: Optional[Tensor], dy: Tensor, scale: Optional[Tensor],
                        shift: Optional[Tensor], src1_b: Tensor, src2_b: Optional[Tensor], dy_b: Tensor,
-                       scale_b: Optional[Tensor], shift_b: Optional[Tensor], *, mode: int, out: Tensor) -> Tensor:
+                       scale_b: Optional[Tensor], shift_b: Optional[Tensor], *, mode: int, out: Tensor,
+                       defer: bool = False) -> Tensor:
     """out += dw(segment a) + dw(segment b): the same layer on two batches (e.g. the two passes of a
-    two-stage step) in ONE launch.  bf16 tensors of equal geometry per image."""
+    two-stage step) in ONE launch.  bf16 tensors of equal geometry per image.  `defer`: see conv3x3_wgrad."""
     require_gpu(src1, dy, src1_b, dy_b)
     N, C1 = src1.shape[0], src1.shape[1]
     C2 = 0 if src2 is None else src2.shape[1]
@@ -706,17 +867,27 @@ def conv3x3_wgrad_pair(src1: Tensor, src2: Optional[Tensor], dy: Tensor, scale: 
     nbytes = d.pair_ws.get(nb)
     if nbytes is None:
         nbytes = d.pair_ws[nb] = _lib.load().cy_conv3x3_wgrad_pair_ws_bytes(d.ref, nb)
-    ws = _ws(nbytes, src1.device)
     ev = _prof_begin()
-    with ordered(("conv_grad", out.data_ptr())):
-        _lib.call("cy_conv3x3_wgrad_pair", d.ref, src1.data_ptr(), _ptr(src2), _ptr(scale), _ptr(shift),
+    if defer and DEFER_WGRAD_REDUCE:
+        e = _lib.WgradReduceEntry()
+        _lib.call("cy_conv3x3_wgrad_pair_deferred", d.ref, src1.data_ptr(), _ptr(src2), _ptr(scale), _ptr(shift),
                   dy.data_ptr(), nb, src1_b.data_ptr(), _ptr(src2_b), _ptr(scale_b), _ptr(shift_b),
-                  dy_b.data_ptr(), out.data_ptr(), 1, ws.data_ptr(), nbytes, _stream())
+                  dy_b.data_ptr(), out.data_ptr(), 1, _wg_batch(src1.device).arena.alloc(nbytes), nbytes, C.byref(e),
+                  _stream())
+    else:
+        e = None
+        ws = _ws(nbytes, src1.device)
+        with ordered(("conv_grad", out.data_ptr())):
+            _lib.call("cy_conv3x3_wgrad_pair", d.ref, src1.data_ptr(), _ptr(src2), _ptr(scale), _ptr(shift),
+                      dy.data_ptr(), nb, src1_b.data_ptr(), _ptr(src2_b), _ptr(scale_b), _ptr(shift_b),
+                      dy_b.data_ptr(), out.data_ptr(), 1, ws.data_ptr(), nbytes, _stream())
     if ev is not None:
         esz = src1.element_size()
         nbts = esz * sum(t.numel() for t in (src1, src2, dy, src1_b, src2_b, dy_b) if t is not None) \
             + 4 * 9 * (C1 + C2) * Cout
         _prof_end(ev, "conv3x3_wgrad", 2.0 * (N + nb) * H * W * 9 * (C1 + C2) * Cout, float(nbts))
+    if e is not None:
+        _wg_defer(src1.device, e)
     return out
 
 
@@ -743,12 +914,19 @@ def conv_first_fwd(x: Tensor, w: Tensor, out_dtype: torch.dtype, want_stats: boo
     return out, stats
 
 
-def conv_first_wgrad(x: Tensor, dy: Tensor, out: Optional[Tensor] = None) -> Tensor:
+def conv_first_wgrad(x: Tensor, dy: Tensor, out: Optional[Tensor] = None, defer: bool = False) -> Tensor:
+    """`defer`: see conv3x3_wgrad"""
     require_gpu(x, dy)
     N, Cin, H, W = x.shape
     Cout = dy.shape[1]
     x = x.contiguous() if x.dtype == torch.float32 else x.float().contiguous()
     nbytes = _lib.load().cy_conv3x3_first_wgrad_ws_bytes(N, Cin, H, W, Cout)
+    if defer and out is not None and DEFER_WGRAD_REDUCE:
+        e = _lib.WgradReduceEntry()
+        _lib.call("cy_conv3x3_first_wgrad_deferred", x.data_ptr(), dy.data_ptr(), out.data_ptr(), 1, N, Cin, H, W,
+                  Cout, dtype_code(dy.dtype), _wg_batch(x.device).arena.alloc(nbytes), nbytes, C.byref(e), _stream())
+        _wg_defer(x.device, e)
+        return out
     ws = _ws(nbytes, x.device)
     dw = out if out is not None else torch.empty((Cout, Cin, 3, 3), dtype=torch.float32, device=x.device)
     with (ordered(("conv_grad", out.data_ptr())) if out is not None else contextlib.nullcontext()):

@@ -197,6 +197,46 @@ int cy_conv3x3_wgrad_pair(const cy_conv_desc* d, const void* src1, const void* s
                           const void* dy_b, float* dw, int accumulate, void* ws, size_t ws_bytes,
                           void* stream);
 
+/* ---- The weight gradient's slab sum as a batched step of its own (ABI v14) ------------------------------------------
+ * cy_conv3x3_wgrad / _pair / cy_conv3x3_first_wgrad are two launches: the MFMA (first layer: VALU) kernel writes f32
+ * partial sums into `ws`, then a reduce launch adds them into dw.  The _deferred forms enqueue the first launch only and
+ * fill *h_entry (host memory) with what the second would have done; cy_wgrad_reduce_batched then runs the reductions of
+ * many such entries in ONE launch, each output with exactly the summation tree of its own reduce launch (bit-identical
+ * results).  `ws` must stay untouched until that launch has run. */
+#define CY_WGRAD_REDUCE_CONV 0  /* 3x3 conv slabs ws[S][9][co_pad][ci_pad] */
+#define CY_WGRAD_REDUCE_FIRST 1 /* first-layer partials ws[S][Cout][Cin][9], summed in SG = 64 slices */
+#define CY_WGRAD_REDUCE_MAX 32  /* entries per launch */
+typedef struct cy_wgrad_reduce_entry {
+  const float* ws;
+  float* dw;               /* [Cout][Cin][3][3] f32 */
+  int32_t kind;            /* CY_WGRAD_REDUCE_* */
+  int32_t S, SG;           /* partial sums, slab groups: group g adds slabs g, g + SG, ... in order, then the groups in order */
+  int32_t Cout, Cin, co_pad, ci_pad;
+  int32_t accumulate;      /* dw = dw + sum (1) or dw = sum (0) */
+  int32_t blocks;          /* workgroups of its reduction */
+  int32_t first_block;     /* set by cy_wgrad_reduce_batched */
+} cy_wgrad_reduce_entry;
+int cy_conv3x3_wgrad_deferred(const cy_conv_desc* d, const void* src1, const void* src2, const float* scale,
+                              const float* shift, const void* dy, float* dw, int accumulate, void* ws,
+                              size_t ws_bytes, cy_wgrad_reduce_entry* h_entry, void* stream);
+int cy_conv3x3_wgrad_pair_deferred(const cy_conv_desc* d, const void* src1, const void* src2, const float* scale,
+                                   const float* shift, const void* dy, int n_b, const void* src1_b,
+                                   const void* src2_b, const float* scale_b, const float* shift_b,
+                                   const void* dy_b, float* dw, int accumulate, void* ws, size_t ws_bytes,
+                                   cy_wgrad_reduce_entry* h_entry, void* stream);
+int cy_conv3x3_first_wgrad_deferred(const float* x, const void* dy, float* dw, int accumulate, int N, int Cin,
+                                    int H, int W, int Cout, int dy_dtype, void* ws, size_t ws_bytes,
+                                    cy_wgrad_reduce_entry* h_entry, void* stream);
+/* host-side queries, nothing launched: the entry (kind, S, SG, Cout, Cin, pads, blocks) the call with `d` (+ n_b images
+ * of a second segment) / with these first-layer sizes would produce; ws, dw, accumulate are left zero */
+int cy_conv3x3_wgrad_reduce_entry(const cy_conv_desc* d, int n_b, cy_wgrad_reduce_entry* h_entry);
+int cy_conv3x3_first_wgrad_reduce_entry(int N, int Cin, int H, int W, int Cout, int dy_dtype,
+                                        cy_wgrad_reduce_entry* h_entry);
+/* the reductions of h_entries[0..n) (a HOST array; the table travels as a kernel argument, capturable) in table order.
+ * A new launch begins after CY_WGRAD_REDUCE_MAX entries or where an entry's dw overlaps one already in the current
+ * launch, so several entries on one dw take effect in table order. */
+int cy_wgrad_reduce_batched(const cy_wgrad_reduce_entry* h_entries, int n, void* stream);
+
 /* ---- BatchNorm sums without finalize launches (ABI v11; csrc/cy_bn_acc.h) -------------------------------------
  * A training-mode nn.BatchNorm2d (arch/unet.py:22,25,40) needs per-channel sums over the whole batch.  Instead of
  * per-workgroup partial rows + a finalize launch per layer (cy_bn_finalize / cy_bn_bwd_finalize below, still there),
