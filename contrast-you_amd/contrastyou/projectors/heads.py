@@ -20,7 +20,7 @@ from cyhip.functions import (AdaptiveAvgPoolFn, AdaptiveMaxPoolFn, ClusterHeadFn
 
 from .nn import Flatten, Identical, Normalize, SoftmaxWithT
 
-__all__ = ["ProjectionHead", "DenseProjectionHead", "ClusterHead", "DenseClusterHead"]
+__all__ = ["ProjectionHead", "DenseProjectionHead", "ClusterHead", "DenseClusterHead", "CrossCorrelationProjector"]
 
 
 def _pair(v) -> Tuple[int, int]:
@@ -245,3 +245,13 @@ class DenseClusterHead(_ClusterBase):
             flat = self._logits(rows, lin1=0, lin2=2)
         probs = GroupSoftmaxFn.apply(flat, self._num_subheads, self._num_clusters, float(self._T))
         return [p.view(n, h, w_, self._num_clusters).permute(0, 3, 1, 2) for p in probs.unbind(0)]
+
+
+class CrossCorrelationProjector(DenseClusterHead):
+    """over-segmentation head of the cross-correlation hooks (projectors/heads.py:176-200): the sub-headers of
+    DenseClusterHead (`_headers.{i}.{0,2}.{weight,bias}`) behind the reference's own argument list"""
+
+    def __init__(self, *, input_dim: int, num_clusters: int, head_type: str, normalize: bool, T: float = 1.0,
+                 num_subheads: int = 1, hidden_dim: int = 128):
+        super().__init__(input_dim=input_dim, num_clusters=num_clusters, hidden_dim=hidden_dim,
+                         num_subheads=num_subheads, T=T, head_type=head_type, normalize=normalize)

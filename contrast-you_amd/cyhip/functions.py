@@ -1031,3 +1031,51 @@ def bilinear_resize(x: Tensor, size) -> Tensor:
     if x.dtype not in (torch.float32, torch.bfloat16, torch.float16):
         x = x.float()
     return ops.bilinear_fwd(x, tuple(size))
+
+
+class EntropyMapFn(torch.autograd.Function):
+    """probabilities [n, K, H, W] -> min/max-normalised entropy map [n, 1, H, W] (Entropy(reduction="none") + norm,
+    semi_seg/hooks/ccblock.py:278-285,303; `slicewise=False`: the batch-wide extrema of semi_seg/hooks/cc.py:136).
+    The extrema are constants of the backward pass (min().detach())."""
+
+    @staticmethod
+    def forward(ctx, prob: Tensor, slicewise: bool):
+        ops.require_gpu(prob)
+        prob = ops.to_nhwc(prob.float())
+        out, mm = ops.entropy_map_fwd(prob, slicewise)
+        ctx.save_for_backward(prob, mm)
+        return out
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        prob, mm = ctx.saved_tensors
+        return ops.entropy_map_bwd(prob, mm, g.float().contiguous()), None
+
+
+class CCLossFn(torch.autograd.Function):
+    """CCLoss(win=(k, k), eps)(y_true, y_pred) on two [n, 1, H, W] maps (contrastyou/losses/cross_correlation.py:22-74);
+    the backward recomputes the window sums from the two maps (csrc/cy_cc.hip)"""
+
+    @staticmethod
+    def forward(ctx, y_true: Tensor, y_pred: Tensor, win: int, eps: float):
+        ops.require_gpu(y_true, y_pred)
+        I, J = y_true.float().contiguous(), y_pred.float().contiguous()
+        ctx.save_for_backward(I, J)
+        ctx.win, ctx.eps = win, eps
+        return ops.ccloss_fwd(I, J, win, eps)
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        I, J = ctx.saved_tensors
+        gs = g.reshape(1).float().contiguous()
+        dI, dJ = ops.ccloss_bwd(I, J, gs, ctx.win, ctx.eps, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return dI, dJ, None, None
+
+
+def edge_map(image: Tensor, power: float, size=None) -> Tensor:
+    """norm(diff(image)) ** power of semi_seg/hooks/ccblock.py:296-302 (no gradient: images carry none), the image
+    first resized to `size` when it differs (F.interpolate(mode="bilinear"), ccblock.py:300)"""
+    with torch.no_grad():
+        if size is not None and tuple(image.shape[-2:]) != tuple(size):
+            image = bilinear_resize(image.detach(), (int(size[0]), int(size[1])))
+        return ops.cc_edge_map(image, power)

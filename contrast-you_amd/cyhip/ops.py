@@ -1985,3 +1985,60 @@ def bilinear_fwd(x: Tensor, size: Tuple[int, int]) -> Tensor:
     _lib.call("cy_bilinear_fwd", x.data_ptr(), out.data_ptr(), N, H, W, Cc, size[0], size[1], dtype_code(x.dtype),
               _stream())
     return out
+
+
+# --------------------------------------------------------------------------- cross-correlation regulariser
+def cc_edge_map(image: Tensor, power: float) -> Tensor:
+    """image f32 [N, C, H, W], C <= 4 -> [N, 1, H, W]: per-image min/max-normalised edge strength ** power
+    (semi_seg/hooks/ccblock.py:287-293,302); two launches"""
+    require_gpu(image)
+    x = to_nhwc(image.detach().float())
+    N, Cc, H, W = x.shape
+    out = _f32(N * H * W, x.device).view(N, 1, H, W)
+    nbytes = _lib.load().cy_cc_edge_map_ws_bytes(N)
+    ws = _ws(nbytes, x.device)
+    _lib.call("cy_cc_edge_map", x.data_ptr(), out.data_ptr(), N, H, W, Cc, float(power), ws.data_ptr(), nbytes,
+              _stream())
+    return out
+
+
+def entropy_map_fwd(prob: Tensor, slicewise: bool):
+    """prob f32 [N, K, H, W] with NHWC memory -> (normalised entropy map [N, 1, H, W], extrema [N, 2]); two launches"""
+    require_gpu(prob)
+    N, K, H, W = prob.shape
+    out = _f32(N * H * W, prob.device).view(N, 1, H, W)
+    mm = _f32(N * 2, prob.device).view(N, 2)
+    nbytes = _lib.load().cy_entropy_map_ws_bytes(N)
+    ws = _ws(nbytes, prob.device)
+    _lib.call("cy_entropy_map_fwd", prob.data_ptr(), out.data_ptr(), mm.data_ptr(), N, H * W, K, int(slicewise),
+              ws.data_ptr(), nbytes, _stream())
+    return out, mm
+
+
+def entropy_map_bwd(prob: Tensor, mm: Tensor, dmap: Tensor) -> Tensor:
+    N, K, H, W = prob.shape
+    dp = empty_nhwc(N, K, H, W, torch.float32, prob.device)
+    _lib.call("cy_entropy_map_bwd", prob.data_ptr(), mm.data_ptr(), dmap.data_ptr(), dp.data_ptr(), N, H * W, K,
+              _stream())
+    return dp
+
+
+def ccloss_fwd(I: Tensor, J: Tensor, win: int, eps: float) -> Tensor:
+    """I, J: f32 contiguous [N, 1, H, W] -> scalar CCLoss (contrastyou/losses/cross_correlation.py:22-74); two launches"""
+    require_gpu(I, J)
+    N, _, H, W = I.shape
+    nbytes = _lib.load().cy_ccloss_ws_bytes(N, H, W)
+    ws = _ws(nbytes, I.device)
+    loss = _f32(1, I.device)
+    _lib.call("cy_ccloss_fwd", I.data_ptr(), J.data_ptr(), loss.data_ptr(), N, H, W, win, float(eps), ws.data_ptr(),
+              nbytes, _stream())
+    return loss.view(())
+
+
+def ccloss_bwd(I: Tensor, J: Tensor, gscale: Tensor, win: int, eps: float, need_i: bool, need_j: bool):
+    N, _, H, W = I.shape
+    dI = torch.empty_like(I) if need_i else None
+    dJ = torch.empty_like(J) if need_j else None
+    _lib.call("cy_ccloss_bwd", I.data_ptr(), J.data_ptr(), gscale.data_ptr(), _ptr(dI), _ptr(dJ), N, H, W, win,
+              float(eps), _stream())
+    return dI, dJ

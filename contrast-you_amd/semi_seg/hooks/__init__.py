@@ -1,5 +1,7 @@
 from .consistency import ConsistencyTrainerHook  # noqa: F401
-from .creator import (create_consistency_hook, create_discrete_mi_consistency_hook,  # noqa: F401
+from .cc import CrossCorrelationOnLogitsHook  # noqa: F401
+from .ccblock import ProjectorGeneralHook  # noqa: F401
+from .creator import (create_consistency_hook, create_cross_correlation_hooks2, create_discrete_mi_consistency_hook,  # noqa: F401
                       create_discrete_mi_hooks, create_iid_segmentation_hook, create_infonce_hooks,
                       create_mt_hook, create_sp_infonce_hooks, create_superpixel_hooks, feature_until_from_hooks)
 from .discretemi import DiscreteMITrainHook  # noqa: F401

@@ -1,7 +1,7 @@
-"""hook factories (semi_seg/hooks/creator.py:31-49,51-52,92-122 of the reference)"""
+"""hook factories (semi_seg/hooks/creator.py:31-49,51-52,92-122,196-239 of the reference)"""
 from __future__ import annotations
 
-from typing import List, Sequence, Union
+from typing import Any, Dict, List, Sequence, Union
 
 from torch import nn
 
@@ -9,6 +9,9 @@ from contrastyou.arch._base import sort_arch
 from contrastyou.hooks.base import CombineTrainerHook, TrainerHook
 from contrastyou.utils.utils import ntuple
 
+from .cc import CrossCorrelationOnLogitsHook
+from .ccblock import (ProjectorGeneralHook, _CenterCompactnessHook, _ConsistencyHook, _CrossCorrelationHook,
+                      _IMSATHook, _MIHook, _RedundancyReduction)
 from .consistency import ConsistencyTrainerHook
 from .discretemi import DiscreteMITrainHook, decoder_names
 from .infonce import INFONCEHook, SelfPacedINFONCEHook, SuperPixelInfoNCEHook
@@ -138,3 +141,26 @@ def create_discrete_mi_consistency_hook(*, model: nn.Module, feature_names: Unio
 def create_iid_segmentation_hook(*, weight: float, mi_lambda: float = 1.0):
     """config/hooks/iid.yaml: IIC between the two views' segmentation outputs"""
     return IIDSegmentationTrainerHook(hook_name="midl_hook", weight=weight, mi_lambda=mi_lambda)
+
+
+def create_cross_correlation_hooks2(*, model: nn.Module, feature_name: str, num_clusters: int, head_type: str,
+                                    num_subheads: int, save: bool = True, hook_params: Dict[str, Any]):
+    """config section CrossCorrelationParameters (creator.py:196-239): on a feature map, a projector with the tiny
+    hooks named by the keys of `hook_params`; on "Deconv_1x1", the on-logits hook"""
+    project_params = {"num_clusters": num_clusters, "head_type": head_type, "normalize": False,
+                      "num_subheads": num_subheads, "hidden_dim": 64}
+    if "Deconv_1x1" != feature_name:
+        hook = ProjectorGeneralHook(name=f"cc_{feature_name}", model=model, feature_name=feature_name,
+                                    projector_params=project_params, save=save)
+        for key, tiny in (("mi", _MIHook), ("cc", _CrossCorrelationHook), ("compact", _CenterCompactnessHook),
+                          ("rr", _RedundancyReduction), ("imsat", _IMSATHook), ("consist", _ConsistencyHook)):
+            if key in hook_params:
+                hook.register_dist_hook(tiny(**hook_params[key]))
+    else:
+        mi_params = {"lamda": hook_params["mi"]["lamda"], "padding": hook_params["mi"]["padding"]}
+        norm_params = {"power": hook_params["cc"]["diff_power"]}
+        hook = CrossCorrelationOnLogitsHook(
+            name=f"cc_{feature_name}", cc_weight=hook_params["cc"]["weight"], feature_name=feature_name,
+            kernel_size=hook_params["cc"]["kernel_size"], projector_params=project_params, model=model,
+            mi_weight=hook_params["mi"]["weight"], save=save, mi_criterion_params=mi_params, norm_params=norm_params)
+    return CombineTrainerHook(hook)

@@ -703,6 +703,35 @@ int cy_bilinear_fwd(const void* x, void* out, int N, int H, int W, int C, int h,
                     void* stream);
 
 /* ------------------------------------------------------------------------
+ * Cross-correlation regulariser (ABI v15; csrc/cy_cc.hip), f32.  Maps are [N][H][W] f32, contiguous.
+ * All sums run in a fixed order: two calls on the same inputs give the same bits.
+ * ------------------------------------------------------------------------ */
+/* Edge strength of an NHWC f32 image [N,H,W,C], C <= 4 (semi_seg/hooks/ccblock.py:287-293,302; cc.py:119-125,134):
+ *   d = mean_c sqrt((x - roll(x,1,H))^2 + (x - roll(x,1,W))^2);  out = ((d - min) / (max - min + 1e-6)) ^ power
+ * with the extrema of each image.  Two launches (raw map + extrema partials; normalise).  ws: _ws_bytes(N). */
+size_t cy_cc_edge_map_ws_bytes(int N);
+int cy_cc_edge_map(const float* img, float* out, int N, int H, int W, int C, float power, void* ws, size_t ws_bytes,
+                   void* stream);
+/* Entropy map of probability rows p [N*HW][K], K <= 128 (Entropy(reduction="none"), contrastyou/losses/kl.py:31-55;
+ * ccblock.py:303, cc.py:136): out = (e - min) / (max - min + 1e-6), e = -sum_c p log(p + 1e-16), with the extrema of
+ * each image (slicewise != 0) or of the whole batch; mm [N][2] receives the {min, max} used per image.  Two launches.
+ * Backward: dp = dloss/dp from dmap = dloss/dout; the extrema carry no gradient (min().detach()).  One launch. */
+size_t cy_entropy_map_ws_bytes(int N);
+int cy_entropy_map_fwd(const float* p, float* out, float* mm, int N, long HW, int K, int slicewise, void* ws,
+                       size_t ws_bytes, void* stream);
+int cy_entropy_map_bwd(const float* p, const float* mm, const float* dmap, float* dp, int N, long HW, int K,
+                       void* stream);
+/* CCLoss(win=(k,k), eps)(y_true = I, y_pred = J) (contrastyou/losses/cross_correlation.py:22-74; ccblock.py:305,
+ * cc.py:138): zero-padded k x k box sums of I, J, I^2, J^2, IJ, the three clamped terms, loss = -mean(cross^2 /
+ * (I_var * J_var)).  k odd, 3..15 (CY_ERR_SHAPE otherwise).  Forward: two launches (per-tile sums; ordered final sum).
+ * Backward: dI and / or dJ (either may be NULL) = gscale[0] * dloss/d{I, J}; one launch, recomputes the sums. */
+size_t cy_ccloss_ws_bytes(int N, int H, int W);
+int cy_ccloss_fwd(const float* I, const float* J, float* loss, int N, int H, int W, int win, float eps, void* ws,
+                  size_t ws_bytes, void* stream);
+int cy_ccloss_bwd(const float* I, const float* J, const float* gscale, float* dI, float* dJ, int N, int H, int W,
+                  int win, float eps, void* stream);
+
+/* ------------------------------------------------------------------------
  * The glue of the reference's second backbone, `UNet2` (contrastyou/arch/unet2.py): everything that is not a
  * 3x3 conv + GroupNorm + SiLU block.  f32, NHWC maps viewed as [pixels][channels] matrices.
  *   7x7 stem (:45), Downsample = Conv2d(4, 2, 1) (:180-181), 1x1 projections      -> cy_im2col + cy_gemm_strided
