@@ -4,7 +4,8 @@
 callers.  The supervised loss of the epochers -- KL_div(softmax(logits), one_hot(labels)) with
 mean reduction and no class weights (epocher.py:317-318) -- goes through
 `KL_div.from_logits(logits, labels)`: one fused HIP pass (softmax + log + mean) forward and one
-backward, with no one-hot tensor and no `unique()` host sync.
+backward, with no one-hot tensor and no `unique()` host sync.  `Entropy.from_logits(logits)` is the
+same for `Entropy()(logits.softmax(1))` (semi_seg/hooks/entmin.py:29-30).
 """
 from __future__ import annotations
 
@@ -13,7 +14,7 @@ from typing import List, Optional, Union
 import torch
 from torch import Tensor, nn
 
-from cyhip.functions import SoftmaxKLFn
+from cyhip.functions import SoftmaxEntropyFn, SoftmaxKLFn
 
 __all__ = ["Entropy", "KL_div"]
 
@@ -30,6 +31,12 @@ class Entropy(nn.Module):
         super().__init__()
         _check_reduction_params(reduction)
         self._eps, self._reduction = eps, reduction
+
+    def from_logits(self, logits: Tensor) -> Tensor:
+        """== self(logits.softmax(1)); one fused HIP pass each way for the mean reduction"""
+        if self._reduction != "mean":
+            return self(logits.softmax(1))
+        return SoftmaxEntropyFn.apply(logits, float(self._eps))
 
     def forward(self, input_: Tensor) -> Tensor:
         assert input_.dim() >= 2

@@ -7,6 +7,7 @@
 //   UniversalDice intersections / unions          contrastyou/meters/general_dice_meter.py:37-110
 // All of it is HBM-streaming work over [pixels][K] f32 logits (K = classes).
 #include "cy_common.h"
+#include "cy_pixel_loss.h"  // KMAX, softmax_k, load_logits, block_sum_d, mean_finalize_kernel, loss_blocks
 
 // the wide head on the matrix-core kernels of cy_cluster_head.hip (same shared object)
 bool cy_head_wide_ok(int C, int K);
@@ -18,7 +19,6 @@ int cy_head_wide_bwd(const void* x, const float* w, const float* dlogits, void* 
 
 namespace {
 
-constexpr int KMAX = 16;    // segmentation classes
 constexpr int KWIDE = 128;  // stacked cluster-head outputs
 
 template <typename T> __device__ __forceinline__ void load8h(const T* p, float* f) {
@@ -246,47 +246,6 @@ inline int head_dw_blocks(long npix) {
   return (int)b;
 }
 
-// ---------------------------------------------------------------- softmax helpers
-__device__ __forceinline__ void softmax_k(const float* z, float* p, int K) {
-  float m = z[0];
-#pragma unroll
-  for (int k = 1; k < KMAX; ++k)
-    if (k < K) m = fmaxf(m, z[k]);
-  float s = 0.f;
-#pragma unroll
-  for (int k = 0; k < KMAX; ++k)
-    if (k < K) {
-      p[k] = expf(z[k] - m);
-      s += p[k];
-    }
-  const float inv = 1.f / s;
-#pragma unroll
-  for (int k = 0; k < KMAX; ++k)
-    if (k < K) p[k] *= inv;
-}
-
-__device__ __forceinline__ void load_logits(const float* l, long p, int K, float* z) {
-  if (K == 4) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(l + p * 4);
-    z[0] = v[0], z[1] = v[1], z[2] = v[2], z[3] = v[3];
-  } else {
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k)
-      if (k < K) z[k] = l[p * K + k];
-  }
-}
-
-__device__ __forceinline__ double block_sum_d(double v, double* sh) {
-  const int tid = threadIdx.x;
-  sh[tid] = v;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) sh[tid] += sh[tid + o];
-    __syncthreads();
-  }
-  return sh[0];
-}
-
 // ---------------------------------------------------------------- softmax + KL(one-hot)
 __global__ void __launch_bounds__(256)
     softmax_kl_fwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target,
@@ -307,16 +266,6 @@ __global__ void __launch_bounds__(256)
   }
   const double tot = block_sum_d(acc, sh);
   if (threadIdx.x == 0) partial[blockIdx.x] = tot;
-}
-
-__global__ void __launch_bounds__(256)
-    mean_finalize_kernel(const double* __restrict__ partial, int nblk, double denom,
-                         float* __restrict__ loss) {
-  __shared__ double sh[256];
-  double acc = 0.0;
-  for (int i = threadIdx.x; i < nblk; i += 256) acc += partial[i];
-  const double tot = block_sum_d(acc, sh);
-  if (threadIdx.x == 0) loss[0] = (float)(tot / denom);
 }
 
 __global__ void __launch_bounds__(256)
@@ -431,13 +380,6 @@ __global__ void __launch_bounds__(256)
   __syncthreads();
   if (threadIdx.x < K * 2 && sc[threadIdx.x])
     atomicAdd(&counts[(size_t)n * K * 2 + threadIdx.x], (unsigned long long)sc[threadIdx.x]);
-}
-
-inline int loss_blocks(long npix) {
-  long b = (npix + 255) / 256;
-  if (b > 1024) b = 1024;
-  if (b < 1) b = 1;
-  return (int)b;
 }
 
 }  // namespace

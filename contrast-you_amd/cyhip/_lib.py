@@ -211,6 +211,15 @@ _SIGS = {
     "cy_softmax_mse_ws_bytes": (c_size_t, [c_long]),
     "cy_softmax_mse_fwd": (c_int, [_P, _P, _P, c_long, c_int, _P, c_size_t, _P]),
     "cy_softmax_mse_bwd": (c_int, [_P, _P, _P, _P, _P, c_long, c_int, _P]),
+    "cy_softmax_entropy_ws_bytes": (c_size_t, [c_long]),
+    "cy_softmax_entropy_fwd": (c_int, [_P, _P, c_long, c_int, c_float, _P, c_size_t, _P]),
+    "cy_softmax_entropy_bwd": (c_int, [_P, _P, _P, c_long, c_int, c_float, _P]),
+    "cy_softmax_selfmse_ws_bytes": (c_size_t, [c_long]),
+    "cy_softmax_selfmse_fwd": (c_int, [_P, _P, c_long, c_int, _P, c_size_t, _P]),
+    "cy_softmax_selfmse_bwd": (c_int, [_P, _P, _P, c_long, c_int, _P]),
+    "cy_uamt_mse_ws_bytes": (c_size_t, [c_long]),
+    "cy_uamt_mse_fwd": (c_int, [_P, _P, _P, c_long, c_int, c_float, c_int, _P, c_size_t, _P]),
+    "cy_uamt_mse_bwd": (c_int, [_P, _P, _P, _P, _P, c_long, c_int, c_float, c_int, _P]),
     "cy_radam_step": (c_int, [_P, _P, _P, _P, c_long, c_float, c_float, c_float, c_float, c_float,
                               c_long, _P]),
     "cy_dense_proj_fwd": (c_int, [_P, _P, _P, _P, c_int, _P] + [c_int] * 8 + [c_float, c_int, _P]),

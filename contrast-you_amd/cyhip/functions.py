@@ -583,6 +583,70 @@ class SoftmaxMSEFn(torch.autograd.Function):
         return da, db
 
 
+class SoftmaxEntropyFn(torch.autograd.Function):
+    """Entropy(eps=eps)(logits.softmax(1)), mean reduction (semi_seg/hooks/entmin.py:29-30,
+    contrastyou/losses/kl.py:48-56)."""
+
+    @staticmethod
+    def forward(ctx, logits: Tensor, eps: float):
+        ops.require_gpu(logits)
+        logits = ops.to_nhwc(logits.float())
+        ctx.save_for_backward(logits)
+        ctx.eps = eps
+        return ops.softmax_entropy_fwd(logits, eps)
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        logits, = ctx.saved_tensors
+        gs = g.reshape(1).float().contiguous()
+        return ops.softmax_entropy_bwd(logits, gs, ctx.eps), None
+
+
+class SoftmaxSelfMSEFn(torch.autograd.Function):
+    """nn.MSELoss()(p, one_hot(p.max(1)[1])) with p = logits.softmax(1); the one-hot carries no gradient and is never
+    materialised (semi_seg/hooks/pseudolabel.py:30-36)."""
+
+    @staticmethod
+    def forward(ctx, logits: Tensor):
+        ops.require_gpu(logits)
+        logits = ops.to_nhwc(logits.float())
+        ctx.save_for_backward(logits)
+        return ops.softmax_selfmse_fwd(logits)
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        logits, = ctx.saved_tensors
+        gs = g.reshape(1).float().contiguous()
+        return ops.softmax_selfmse_bwd(logits, gs)
+
+
+class UAMTLossFn(torch.autograd.Function):
+    """(loss, mask_mean) of the uncertainty-aware mean teacher (semi_seg/hooks/mt.py:242-248,266-267): the MSE of
+    softmax(teacher) [hard: its arg-max one-hot] and softmax(student) over the pixels whose teacher entropy lies below
+    `thr`, over (mask_mean + 1e-2).  Both stay on the device; mask_mean is not differentiable, the teacher gets no
+    gradient."""
+
+    @staticmethod
+    def forward(ctx, teacher_logits: Tensor, student_logits: Tensor, thr: float, hard: bool):
+        ops.require_gpu(teacher_logits, student_logits)
+        if teacher_logits.shape != student_logits.shape:
+            raise ValueError(f"teacher {tuple(teacher_logits.shape)} and student {tuple(student_logits.shape)} differ")
+        t = ops.to_nhwc(teacher_logits.detach().float())
+        s = ops.to_nhwc(student_logits.float())
+        res = ops.uamt_mse_fwd(t, s, thr, hard)
+        ctx.save_for_backward(t, s, res)
+        ctx.thr, ctx.hard = float(thr), bool(hard)
+        loss, mask_mean = res[0], res[1]
+        ctx.mark_non_differentiable(mask_mean)
+        return loss, mask_mean
+
+    @staticmethod
+    def backward(ctx, g: Tensor, _g_mask):
+        t, s, res = ctx.saved_tensors
+        gs = g.reshape(1).float().contiguous()
+        return None, ops.uamt_mse_bwd(t, s, res, gs, ctx.thr, ctx.hard), None, None
+
+
 class AvgPoolFn(torch.autograd.Function):
     """nn.AdaptiveAvgPool2d((1,1)) + Flatten (contrastyou/projectors/heads.py:15-16)."""
 

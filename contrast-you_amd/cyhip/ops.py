@@ -1471,6 +1471,61 @@ def softmax_mse_bwd(a: Tensor, b: Tensor, gscale: Tensor, need_a: bool, need_b: 
     return da, db
 
 
+def _pixel_loss_fwd(name: str, x: Tensor, out: int = 1):
+    """what the forward of a pixel-wise regulariser (csrc/cy_pixel_reg.hip) takes: (npix, K, workspace, its bytes, the
+    `out` device floats of the result)"""
+    N, K, H, W = x.shape
+    npix = N * H * W
+    nbytes = getattr(_lib.load(), f"cy_{name}_ws_bytes")(npix)
+    ws = _ws(nbytes, x.device)
+    res = _f32(out, x.device)
+    return npix, K, ws, nbytes, res
+
+
+def softmax_entropy_fwd(logits: Tensor, eps: float) -> Tensor:
+    npix, K, ws, nbytes, loss = _pixel_loss_fwd("softmax_entropy", logits)
+    _lib.call("cy_softmax_entropy_fwd", logits.data_ptr(), loss.data_ptr(), npix, K, float(eps), ws.data_ptr(), nbytes,
+              _stream())
+    return loss.view(())
+
+
+def softmax_entropy_bwd(logits: Tensor, gscale: Tensor, eps: float) -> Tensor:
+    N, K, H, W = logits.shape
+    d = empty_nhwc(N, K, H, W, torch.float32, logits.device)
+    _lib.call("cy_softmax_entropy_bwd", logits.data_ptr(), gscale.data_ptr(), d.data_ptr(), N * H * W, K, float(eps),
+              _stream())
+    return d
+
+
+def softmax_selfmse_fwd(logits: Tensor) -> Tensor:
+    npix, K, ws, nbytes, loss = _pixel_loss_fwd("softmax_selfmse", logits)
+    _lib.call("cy_softmax_selfmse_fwd", logits.data_ptr(), loss.data_ptr(), npix, K, ws.data_ptr(), nbytes, _stream())
+    return loss.view(())
+
+
+def softmax_selfmse_bwd(logits: Tensor, gscale: Tensor) -> Tensor:
+    N, K, H, W = logits.shape
+    d = empty_nhwc(N, K, H, W, torch.float32, logits.device)
+    _lib.call("cy_softmax_selfmse_bwd", logits.data_ptr(), gscale.data_ptr(), d.data_ptr(), N * H * W, K, _stream())
+    return d
+
+
+def uamt_mse_fwd(teacher: Tensor, student: Tensor, thr: float, hard: bool) -> Tensor:
+    """-> device f32 [2] = (loss, mask_mean)"""
+    npix, K, ws, nbytes, res = _pixel_loss_fwd("uamt_mse", teacher, out=2)
+    _lib.call("cy_uamt_mse_fwd", teacher.data_ptr(), student.data_ptr(), res.data_ptr(), npix, K, float(thr),
+              int(bool(hard)), ws.data_ptr(), nbytes, _stream())
+    return res
+
+
+def uamt_mse_bwd(teacher: Tensor, student: Tensor, result: Tensor, gscale: Tensor, thr: float, hard: bool) -> Tensor:
+    N, K, H, W = student.shape
+    d = empty_nhwc(N, K, H, W, torch.float32, student.device)
+    _lib.call("cy_uamt_mse_bwd", teacher.data_ptr(), student.data_ptr(), result.data_ptr(), gscale.data_ptr(),
+              d.data_ptr(), N * H * W, K, float(thr), int(bool(hard)), _stream())
+    return d
+
+
 def dice_counts(logits: Tensor, target: Tensor) -> Tensor:
     """int64 [N,K,2] = per-sample per-class (intersection, union) of argmax(logits) vs target."""
     N, K, H, W = logits.shape

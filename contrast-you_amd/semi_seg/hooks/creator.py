@@ -1,4 +1,6 @@
-"""hook factories (semi_seg/hooks/creator.py:31-49,51-52,92-122,196-239 of the reference)"""
+"""hook factories (semi_seg/hooks/creator.py:31-281 of the reference).  Every name the reference's `hook_creator.py`
+imports from `semi_seg.hooks` exists here; the methods this project has not built are stubs with the reference's
+signature that raise NotImplementedError when called."""
 from __future__ import annotations
 
 from typing import Any, Dict, List, Sequence, Union
@@ -14,9 +16,11 @@ from .ccblock import (ProjectorGeneralHook, _CenterCompactnessHook, _Consistency
                       _IMSATHook, _MIHook, _RedundancyReduction)
 from .consistency import ConsistencyTrainerHook
 from .discretemi import DiscreteMITrainHook, decoder_names
+from .entmin import EntropyMinTrainerHook
 from .infonce import INFONCEHook, SelfPacedINFONCEHook, SuperPixelInfoNCEHook
 from .midl import IIDSegmentationTrainerHook
-from .mt import MeanTeacherTrainerHook
+from .mt import MeanTeacherTrainerHook, UAMeanTeacherTrainerHook
+from .pseudolabel import PseudoLabelTrainerHook
 
 
 def get_individual_hook(*hooks):
@@ -44,9 +48,27 @@ def create_consistency_hook(weight: float):
 
 
 def create_mt_hook(*, model: nn.Module, weight: float, alpha: float = 0.999, weight_decay: float = 1e-5,
-                   update_bn: bool = False, hard_clip: bool = False):
+                   update_bn: bool = False, num_teachers: int = 1, hard_clip: bool = False):
+    """config/hooks/mt.yaml (creator.py:147-151)"""
     return MeanTeacherTrainerHook(name="mt", model=model, weight=weight, alpha=alpha, weight_decay=weight_decay,
-                                  update_bn=update_bn, hard_clip=hard_clip)
+                                  update_bn=update_bn, num_teachers=num_teachers, hard_clip=hard_clip)
+
+
+def create_uamt_hook(*, model: nn.Module, weight: float, alpha: float = 0.999, weight_decay: float = 1e-5,
+                     update_bn: bool = False, num_teachers: int = 1, hard_clip: bool = False):
+    """config/hooks/uamt.yaml (creator.py:154-158; the reference names this hook "mt" as well)"""
+    return UAMeanTeacherTrainerHook(name="mt", model=model, weight=weight, alpha=alpha, weight_decay=weight_decay,
+                                    update_bn=update_bn, num_teachers=num_teachers, hard_clip=hard_clip)
+
+
+def create_ent_min_hook(*, weight: float = 0.001):
+    """config/hooks/entmin.yaml (creator.py:170-172)"""
+    return EntropyMinTrainerHook(name="entropy", weight=weight)
+
+
+def create_pseudo_label_hook(*, weight: float):
+    """config/hooks/pseudolabel.yaml (creator.py:188-189)"""
+    return PseudoLabelTrainerHook(weight=weight, name="plab")
 
 
 def _infonce_hook(*, model: nn.Module, feature_name: str, weight: float, contrast_on: str, data_name: str,
@@ -141,6 +163,46 @@ def create_discrete_mi_consistency_hook(*, model: nn.Module, feature_names: Unio
 def create_iid_segmentation_hook(*, weight: float, mi_lambda: float = 1.0):
     """config/hooks/iid.yaml: IIC between the two views' segmentation outputs"""
     return IIDSegmentationTrainerHook(hook_name="midl_hook", weight=weight, mi_lambda=mi_lambda)
+
+
+def create_iid_seg_hook(*, weight: float = 0.001, mi_lambda=1.0):
+    """the reference's name and hook name for `create_iid_segmentation_hook` (creator.py:184-185)"""
+    return IIDSegmentationTrainerHook(hook_name="iid", weight=weight, mi_lambda=mi_lambda)
+
+
+def _not_built(method: str, factory: str):
+    raise NotImplementedError(f"{factory}: {method} is not implemented in this project (DESIGN.md, out of scope)")
+
+
+def create_differentiable_mt_hook(*, model: nn.Module, weight: float, alpha: float = 0.999,
+                                  weight_decay: float = 0.000001, meta_weight=0, meta_criterion: str,
+                                  method_name: str):
+    _not_built("the differentiable mean teacher (semi_seg/hooks/dmt.py)", "create_differentiable_mt_hook")
+
+
+def create_orthogonal_hook(*, weight: float = 0.001, model: nn.Module):
+    _not_built("the orthogonal-prototype regulariser (semi_seg/hooks/orthogonal.py)", "create_orthogonal_hook")
+
+
+def create_imsat_hook(*, weight: float = 0.1):
+    _not_built("IMSAT on the segmentation output (semi_seg/hooks/midl.py)", "create_imsat_hook")
+
+
+def create_intermediate_imsat_hook(*, feature_name: str, weight: float, num_clusters: int, cons_weight: float,
+                                   model: nn.Module):
+    _not_built("IMSAT on a feature map (semi_seg/hooks/discretemi.py)", "create_intermediate_imsat_hook")
+
+
+def create_mixup_hook(*, weight: float, enable_bn: bool):
+    _not_built("MixUp (semi_seg/hooks/mixup.py)", "create_mixup_hook")
+
+
+def create_ict_hook(*, weight: float, alpha: float, weight_decay: float, update_bn: bool, model):
+    _not_built("interpolation consistency training (semi_seg/hooks/mt.py)", "create_ict_hook")
+
+
+def create_dae_hook(*, weight: float, num_classes: int):
+    _not_built("the denoising auto-encoder prior (semi_seg/hooks/autoencoder.py)", "create_dae_hook")
 
 
 def create_cross_correlation_hooks2(*, model: nn.Module, feature_name: str, num_clusters: int, head_type: str,

@@ -3,9 +3,16 @@ predicts the unlabeled batch (no grad; train-mode BN, or -- with update_bn, wher
 the running statistics -- every teacher BatchNorm in eval mode, mt.py:162-166), its logits go through
 the same affine map, and weight * MSE(softmax(teacher_tf) [hard_clip: its arg-max one-hot, mt.py:190-192],
 softmax(student_tf)) is added; after the step the teacher is updated by `EMAUpdater` = cy_ema_update
-over every parameter."""
+over every parameter.
+
+Uncertainty-aware mean teacher, "UA-MT" (semi_seg/hooks/mt.py:209-276): the teacher's logits are the mean of one
+BN-tracking forward and N forwards of the image plus 0.05 * noise; the MSE against the student counts only where the
+entropy of that mean prediction lies below thr = (3/4 + 1/4 * cur_epoch / max_epoch) * ln C, and is divided by
+(mask.mean() + 1e-2).  Softmax, entropy, mask, [arg-max one-hot,] MSE and both means are one fused pass each way
+(`UAMTLossFn` = cy_uamt_mse_*): no full-size temporary and, unlike the reference's two `.item()`, no host sync."""
 from __future__ import annotations
 
+import math
 from copy import deepcopy
 
 import torch
@@ -14,7 +21,8 @@ from torch import nn
 from contrastyou.hooks.base import EpocherHook, TrainerHook
 from contrastyou.meters import AverageValueMeter, MeterInterface
 from cyhip import ops
-from cyhip.functions import SoftmaxMSEFn, bump_weights_epoch
+from contrastyou.utils.utils import fix_all_seed_within_context
+from cyhip.functions import SoftmaxMSEFn, UAMTLossFn, bump_weights_epoch
 
 
 class EMAUpdater:
@@ -102,3 +110,58 @@ class _MeanTeacherEpocherHook(EpocherHook):
 
     def after_batch_update(self, **kwargs):
         self._updater(ema_model=self._teacher_model, student_model=self._model)
+
+
+def uamt_threshold(num_classes: int, cur_epoch: int, max_epoch: int) -> float:
+    """the entropy bound of the UA-MT mask (mt.py:244), in f64 on the host; the kernel takes it rounded to f32"""
+    log_c = math.log(num_classes)
+    return 3 / 4 * log_c + 1 / 4 * log_c * float(cur_epoch / max_epoch)
+
+
+class UAMeanTeacherTrainerHook(MeanTeacherTrainerHook):
+
+    def __call__(self):
+        return _UAMeanTeacherEpocherHook(name=self._hook_name, weight=self._weight, model=self.trainer._model,
+                                         teacher_model=self._teacher_model, updater=self._updater,
+                                         hard_clip=self._hard_clip)
+
+
+class _UAMeanTeacherEpocherHook(_MeanTeacherEpocherHook):
+
+    def configure_meters_given_epocher(self, meters: MeterInterface):
+        meters = super().configure_meters_given_epocher(meters)
+        meters.register_meter("mask", AverageValueMeter())
+        return meters
+
+    def _call_implementation(self, *, unlabeled_tf_logits, unlabeled_image, seed, affine_transformer, **kwargs):
+        teacher_logits_tf = self._aggregate_predictions(unlabeled_image=unlabeled_image, N=4,
+                                                        affine_transformer=affine_transformer, seed=seed)
+        thr = uamt_threshold(unlabeled_tf_logits.shape[1], self.cur_epoch, self.max_epoch)
+        loss, mask_mean = UAMTLossFn.apply(teacher_logits_tf, unlabeled_tf_logits, thr, self._hard_clip)
+        self.meters["loss"].add(loss.detach())
+        self.meters["mask"].add(mask_mean)
+        return self._weight * loss
+
+    def _noise(self, like: torch.Tensor, i: int) -> torch.Tensor:
+        """the i-th perturbation of the unlabeled batch, before the 0.05 scale (drawn under the step's seed)"""
+        return torch.randn_like(like)
+
+    @torch.no_grad()
+    def _aggregate_predictions(self, *, unlabeled_image: torch.Tensor, N: int = 8, affine_transformer,
+                               seed: int) -> torch.Tensor:
+        """mean of the teacher's logits over the clean image (the one forward that writes the BN statistics) and N
+        noisy copies, warped once (mt.py:250-268); softmax and entropy of it are taken inside the loss kernel"""
+        teacher = self._teacher_model
+        with teacher.switch_bn_track(enable=True):
+            logits = [teacher(unlabeled_image)]
+        with teacher.switch_bn_track(enable=False), fix_all_seed_within_context(seed):
+            logits += [teacher(unlabeled_image + self._noise(unlabeled_image, i) * 0.05) for i in range(N)]
+        return affine_transformer(torch.stack(logits, dim=0).mean(dim=0))
+
+    @property
+    def cur_epoch(self) -> int:
+        return self.epocher.cur_epoch
+
+    @property
+    def max_epoch(self) -> int:
+        return int(self.epocher.trainer._max_epoch)

@@ -573,6 +573,36 @@ int cy_softmax_mse_bwd(const float* a, const float* b, const float* gscale, floa
                        long npix, int K, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Pixel-wise regularisers of the semi-supervised baselines (csrc/cy_pixel_reg.hip; entries added to ABI v15 -- no
+ * existing signature changed, so cy_abi_version() stays 15).  Logits are [npix][K] f32 (NHWC), 2 <= K <= 16.  Every entry checks its arguments before any launch: a NULL pointer,
+ * npix < 1 or K outside 2..16 -> CY_ERR_ARG; a short workspace -> CY_ERR_WORKSPACE.  Forward: two launches (one
+ * f64 partial per block into ws; one-block sum in a fixed order -- two runs give the same bits); backward: one
+ * launch, scaled by the device scalar gscale[0].
+ * ------------------------------------------------------------------------ */
+/* Entropy(reduction="mean", eps)(softmax(logits, 1)) (semi_seg/hooks/entmin.py:29-30, contrastyou/losses/kl.py:48-56):
+ * loss = mean_pix -sum_k p_k log(p_k + eps).  A p_k that underflows to 0 adds 0 to both passes. */
+size_t cy_softmax_entropy_ws_bytes(long npix);
+int cy_softmax_entropy_fwd(const float* logits, float* loss, long npix, int K, float eps, void* ws, size_t ws_bytes,
+                           void* stream);
+int cy_softmax_entropy_bwd(const float* logits, const float* gscale, float* dlogits, long npix, int K, float eps,
+                           void* stream);
+/* MSELoss()(softmax(logits, 1), one_hot(argmax)) (semi_seg/hooks/pseudolabel.py:30-36): the arg-max is taken over the
+ * logits, first maximal index on ties; the one-hot is a constant of the gradient and is never written. */
+size_t cy_softmax_selfmse_ws_bytes(long npix);
+int cy_softmax_selfmse_fwd(const float* logits, float* loss, long npix, int K, void* ws, size_t ws_bytes,
+                           void* stream);
+int cy_softmax_selfmse_bwd(const float* logits, const float* gscale, float* dlogits, long npix, int K, void* stream);
+/* UA-MT (semi_seg/hooks/mt.py:242-248,266-267): t = softmax(teacher), m = [-sum t log(t + 1e-16) < thr],
+ * tau = t or (hard != 0) one_hot(argmax teacher), e = mean_k (tau_k - softmax(student)_k)^2;
+ * result[0] = mean(m e) / (mean(m) + 1e-2), result[1] = mean(m).  The backward writes the student's gradient only
+ * and reads mean(m) from `result`: the denominator is a constant, as through the reference's .item(). */
+size_t cy_uamt_mse_ws_bytes(long npix);
+int cy_uamt_mse_fwd(const float* teacher, const float* student, float* result, long npix, int K, float thr, int hard,
+                    void* ws, size_t ws_bytes, void* stream);
+int cy_uamt_mse_bwd(const float* teacher, const float* student, const float* result, const float* gscale,
+                    float* dstudent, long npix, int K, float thr, int hard, void* stream);
+
+/* ------------------------------------------------------------------------
  * RAdam step over a flat f32 parameter buffer (torch.optim.RAdam semantics,
  * contrastyou/trainer/base.py:66-75, config/base.yaml:10-13).
  * `step` is the 1-based step count AFTER this update.
