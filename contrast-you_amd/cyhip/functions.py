@@ -239,24 +239,175 @@ class ChainCfg:
         self.dtype: Optional[torch.dtype] = None  # forced compute dtype (None = infer)
 
 
-def _bn_flags(bn: nn.BatchNorm2d):
+def _bn_flags(bn: nn.BatchNorm2d, Cout: int):
+    """(use_batch, update, on_acc) of one BatchNorm evaluation: batch statistics or the running ones; whether the
+    running ones are updated; accumulator path (the consumer derives the coefficients) or finalize launch"""
     use_batch = bn.training or bn.running_mean is None
     update = bn.training and bn.track_running_stats and bn.running_mean is not None
-    return use_batch, update
+    return use_batch, update, ops.BN_ACC and use_batch and Cout <= 1024
+
+
+class _BnEval:
+    """the BatchNorm evaluation of one conv of a block: the raw conv output `y`; the contiguous coefficient block `coef`
+    with rows scale, shift, mean, invstd (and the unbiased variance on the accumulator path), which kernels take by its
+    address; `fold`, the ops.BnState whose consumer derives the coefficients (accumulator path), or None when a finalize
+    launch wrote them; `batch`: batch statistics, not the running ones; `acc`: the accumulator of the backward sums."""
+    __slots__ = ("y", "coef", "fold", "batch", "acc")
+
+    def __init__(self, y: Tensor, coef: Tensor, fold: Optional["ops.BnState"], batch: bool):
+        self.y, self.coef, self.fold, self.batch, self.acc = y, coef, fold, batch, None
+
+    @property
+    def scale(self) -> Tensor:
+        return self.coef[0]
+
+    @property
+    def shift(self) -> Tensor:
+        return self.coef[1]
+
+    def prologue(self) -> dict:
+        """how the conv that reads relu(bn(y)) gets the coefficients: conv3x3_fwd's fold= or its scale= / shift="""
+        if self.fold is not None:
+            return {"fold": self.fold}
+        return {"scale": self.scale, "shift": self.shift}
+
+    def apply(self, pool_out: bool):
+        """(relu(bn(y)), its MaxPool2d(2) or None), materialised"""
+        if self.fold is not None and pool_out:
+            return ops.bn_relu_apply_pool_fold(self.y, self.fold)
+        if self.fold is not None:
+            return ops.bn_relu_apply_fold(self.y, self.fold), None
+        if pool_out:
+            return ops.bn_relu_apply_pool(self.y, self.scale, self.shift)
+        return ops.bn_relu_apply(self.y, self.scale, self.shift), None
+
+    def tail(self):
+        """(y, coef, acc): what a kernel that writes the dA of relu(bn(y)) needs to add the backward sums on the way"""
+        return self.y, self.coef, self.acc
+
+
+def _acc_backward(evals: List[_BnEval]) -> bool:
+    """does the block's backward run on accumulators (the finalize-path layers too: they read the first four rows of
+    either coefficient block), or on partial rows (CY_BN_ACC=0, or a layer with more than 1024 channels)?"""
+    return ops.BN_ACC and all(e.y.shape[1] <= 1024 for e in evals)
+
+
+# ---- the steps of ConvChainFn.forward ---------------------------------------------------------------------------
+
+def _cast_inputs(cfg: ChainCfg, x1: Tensor, x2: Optional[Tensor], dt: torch.dtype):
+    """the block's inputs as its first conv reads them: compute dtype, NHWC (the f32 image of the first layer as is)"""
+    if cfg.first:
+        return x1, x2
+    x1 = ops.to_nhwc(x1 if x1.dtype == dt else x1.to(dt))
+    if x2 is not None:
+        x2 = ops.to_nhwc(x2 if x2.dtype == dt else x2.to(dt))
+    return x1, x2
+
+
+def _conv_fwd(cfg: ChainCfg, w: Tensor, dt: torch.dtype, src1: Tensor, src2: Optional[Tensor], prev: Optional[_BnEval],
+              flags, needs_grad: bool):
+    """(y, its statistics) of one conv: the block's first (prev is None) reads the inputs in cfg.mode, a later one
+    relu(bn(prev.y)) through its prologue.  The statistics are an accumulator, partial rows or None, as `flags` say."""
+    use_batch, _, on_acc = flags
+    if prev is None and cfg.first:
+        return ops.conv_first_fwd(src1, w, dt, want_stats=use_batch, stats_acc=on_acc)
+    note_forward_use(w, needs_grad)
+    wf, _ = packed_weights(w, dt)
+    if prev is None:
+        return ops.conv3x3_fwd(src1, src2, wf, w.shape[0], mode=cfg.mode, want_stats=use_batch, stats_acc=on_acc)
+    return ops.conv3x3_fwd(prev.y, None, wf, w.shape[0], want_stats=use_batch, stats_acc=on_acc, **prev.prologue())
+
+
+def _bn_eval(bn: nn.BatchNorm2d, g: Tensor, b: Tensor, y: Tensor, part, flags, run_items: list) -> _BnEval:
+    """the record of bn(y) from the conv's statistics `part`.  Accumulator path: no launch, the consumer of y (the next
+    conv's prologue, or the apply launch) derives the coefficients and leaves them in fold.coef; the running statistics
+    are an item for `run_items`.  Finalize path: one launch writes the coefficients and the running statistics."""
+    use_batch, update, on_acc = flags
+    count = y.shape[0] * y.shape[2] * y.shape[3]
+    mom = bn.momentum if bn.momentum is not None else 0.1
+    if on_acc:
+        fold = ops.BnState(part, g.detach(), b.detach(), count, bn.eps, y.device)
+        coef = fold.coef
+        if update:
+            run_items.append((coef, bn.running_mean, bn.running_var, mom))
+    else:
+        fold = None
+        coef = ops.bn_finalize_block(part, count, g.detach(), b.detach(), bn.running_mean, bn.running_var, mom, bn.eps,
+                                     use_batch, update, y.shape[1], y.device)
+    if update and bn.num_batches_tracked is not None:
+        if _nbt_pending is not None:
+            _nbt_pending.append(bn.num_batches_tracked)
+        else:
+            bn.num_batches_tracked.add_(1)
+    return _BnEval(y, coef, fold, use_batch)
+
+
+def _running_update(run_items: list) -> None:
+    """the running statistics of the block's accumulator-path layers: with the network pass's one launch, or now"""
+    if not run_items:
+        return
+    if _run_pending is not None:
+        _run_pending.extend(run_items)
+    else:
+        ops.bn_running_update(run_items)
+
+
+def _prepare_backward(ctx, x1: Tensor, x2: Optional[Tensor], evals: List[_BnEval], out: Tensor) -> None:
+    """the accumulators of the backward sums, from the same zeroed arena as the forward's (the backward pass allocates
+    nothing to zero), and the hand-offs between blocks"""
+    cfg = ctx.cfg
+    ctx.bwd_accs = None
+    if any(ctx.needs_input_grad) and _acc_backward(evals):
+        for e in evals:
+            e.acc = ops.bn_bwd_acc_new(*e.y.shape, cfg.pool_out and e is evals[-1], e.y.device)
+        ctx.bwd_accs = [e.acc for e in evals]
+        # whoever produces the gradient of `out` may add the sums of this block's last BatchNorm while it has the
+        # values in registers (an _UpConv's upsample backward does): what it needs travels with the tensor
+        out._cy_tail = evals[-1].tail()
+    # ... and this block, if it upsamples on load, is such a producer for the block whose output it reads
+    ctx.up_tail = getattr(x1, "_cy_tail", None) if (cfg.mode == ops.CY_SRC_UP2 and ops.BN_ACC) else None
+    ctx.x2_tail = getattr(x2, "_cy_tail", None) if (x2 is not None and ops.BN_ACC) else None
+
+
+def _save(ctx, x1: Tensor, x2: Optional[Tensor], params, evals: List[_BnEval], out: Optional[Tensor]) -> None:
+    """what backward needs: tensors through save_for_backward (x1, [x2], params, (y, coef) per conv, [out]), the rest
+    of the records by attribute.  `_saved` is the other half: nobody else knows the order."""
+    # (the coefficients of an accumulator-path layer exist once a consumer of y has derived them)
+    assert all(e.fold is None or e.fold.done for e in evals), "BatchNorm coefficients no consumer has written"
+    ctx.has_x2 = x2 is not None
+    ctx.batch_flags = [e.batch for e in evals]
+    tensors = [x1] + ([x2] if x2 is not None else []) + list(params)
+    for e in evals:
+        tensors += (e.y, e.coef)
+    if out is not None:
+        tensors.append(out)
+    ctx.save_for_backward(*tensors)
+
+
+def _saved(ctx):
+    """(x1, x2 or None, params, records, out or None) as `_save` filed them; the records' accumulators come from
+    `_backward_accs`"""
+    t = ctx.saved_tensors
+    n, k = ctx.nconv, 2 if ctx.has_x2 else 1
+    evals = [_BnEval(t[k + 3 * n + 2 * i], t[k + 3 * n + 2 * i + 1], None, ctx.batch_flags[i]) for i in range(n)]
+    return t[0], (t[1] if ctx.has_x2 else None), t[k:k + 3 * n], evals, (t[-1] if ctx.cfg.pool_out else None)
 
 
 # ---- the steps of ConvChainFn.backward --------------------------------------------------------------------------
 
-def _backward_accs(ctx, ys: List[Tensor]) -> Optional[list]:
-    """the accumulators for the backward sums of the block's BatchNorms (a None entry: a fresh one is taken), or None
-    on the partial-row path (CY_BN_ACC=0, or more than 1024 channels)"""
-    accs, ctx.bwd_accs = ctx.bwd_accs, None  # (a second backward through the same node gets fresh accumulators)
-    if not (ops.BN_ACC and all(y.shape[1] <= 1024 for y in ys)):
-        return None
-    return accs if accs is not None else [None] * len(ys)
+def _backward_accs(ctx, evals: List[_BnEval]) -> bool:
+    """is this backward on accumulators (`_acc_backward`)?  If so the records get the ones the forward took (a second
+    backward through the same node: none, fresh ones are taken where needed)."""
+    accs, ctx.bwd_accs = ctx.bwd_accs, None
+    if not _acc_backward(evals):
+        return False
+    if accs is not None:
+        for e, acc in zip(evals, accs):
+            e.acc = acc
+    return True
 
 
-def _pooled_grad(out: Tensor, dout: Optional[Tensor], dpooled: Tensor, y: Tensor, coef, accs: Optional[list]):
+def _pooled_grad(out: Tensor, dout: Optional[Tensor], dpooled: Tensor, ev: _BnEval, on_acc: bool):
     """(dA of the block's last BatchNorm, its partial rows or None) when the block also wrote MaxPool2d(2) of its
     output: the pooled branch's gradient through the arg-max of `out` plus the skip branch's `dout`.  The same launch
     adds that BatchNorm's backward sums: into its accumulator while vacant (BnAccBuf's rule), else into a fresh one;
@@ -264,17 +415,17 @@ def _pooled_grad(out: Tensor, dout: Optional[Tensor], dpooled: Tensor, y: Tensor
     if dpooled.dtype != out.dtype:
         dpooled = dpooled.to(out.dtype)
     add = None if dout is None else ops.to_nhwc(dout if dout.dtype == out.dtype else dout.to(out.dtype))
-    if accs is None:
-        return ops.maxpool2_bwd_bn(out, ops.to_nhwc(dpooled), add, y, *coef)
-    acc = accs[-1] if accs[-1] is not None and accs[-1].vacant() else None
-    da, acc = ops.maxpool2_bwd_bn_acc(out, ops.to_nhwc(dpooled), add, y, coef[0], acc)
+    if not on_acc:
+        return ops.maxpool2_bwd_bn(out, ops.to_nhwc(dpooled), add, ev.y, *ev.coef[:4])
+    acc = ev.acc if ev.acc is not None and ev.acc.vacant() else None
+    da, acc = ops.maxpool2_bwd_bn_acc(out, ops.to_nhwc(dpooled), add, ev.y, ev.coef, acc)
     if acc is not None:
         acc.filled(da)
-        accs[-1] = acc
+        ev.acc = acc
     return da, None
 
 
-def _bn_relu_grad(ctx, i: int, da: Tensor, params, y: Tensor, coef, accs: Optional[list], partials: Optional[Tensor],
+def _bn_relu_grad(ctx, i: int, da: Tensor, params, ev: _BnEval, on_acc: bool, partials: Optional[Tensor],
                   split: Optional[int]):
     """backward of relu(bn(y)) of conv i at `da`: (data gradient of the conv or None, dy, dgamma, dbeta).  The
     BatchNorm's backward sums come from partial rows (legacy path) or an accumulator: a producer's, if it holds the sums
@@ -288,19 +439,19 @@ def _bn_relu_grad(ctx, i: int, da: Tensor, params, y: Tensor, coef, accs: Option
     gsink = ops.grad_sink(g) if (need_g and need_b) else None
     bsink = ops.grad_sink(b) if gsink is not None else None
     pgrads = dict(dgamma_out=gsink if bsink is not None else None, dbeta_out=bsink, want_param_grads=need_g or need_b)
-    if accs is None:
-        return (None, *ops.bn_relu_bwd(da, y, *coef, ctx.batch_flags[i], partials=partials, **pgrads))
-    acc, done = ops.bn_acc_for_grad(accs[i], da, y)
-    # (coef[0] is row 0 of the contiguous coefficient block [scale, shift, mean, invstd, ...] of either path)
+    y = ev.y
+    if not on_acc:
+        return (None, *ops.bn_relu_bwd(da, y, *ev.coef[:4], ev.batch, partials=partials, **pgrads))
+    acc, done = ops.bn_acc_for_grad(ev.acc, da, y)
     if i > 0 or (not ctx.cfg.first and (need[1] or (ctx.has_x2 and need[2]))):
         da_f = ops.to_nhwc(da if da.dtype == y.dtype else da.to(y.dtype))
         if ops.conv3x3_dgrad_bn_ok(da_f, w.shape[1], split):
             acc = acc if acc is not None else ops.bn_bwd_acc_new(*y.shape, False, y.device)
             if not done:
-                ops.bn_bwd_reduce_acc(da_f, y, coef[0], acc)
+                ops.bn_bwd_reduce_acc(da_f, y, ev.coef, acc)
             _, wd = packed_weights(w, ctx.dt)
-            return ops.conv3x3_dgrad_bn(da_f, y, coef[0], acc, ctx.batch_flags[i], wd, w.shape[1], split=split, **pgrads)
-    return (None, *ops.bn_relu_bwd_acc(da, y, coef[0], ctx.batch_flags[i], acc=acc, acc_filled=done, **pgrads))
+            return ops.conv3x3_dgrad_bn(da_f, y, ev.coef, acc, ev.batch, wd, w.shape[1], split=split, **pgrads)
+    return (None, *ops.bn_relu_bwd_acc(da, y, ev.coef, ev.batch, acc=acc, acc_filled=done, **pgrads))
 
 
 def _weight_grad(w: Tensor, sink: Optional[Tensor], src1: Tensor, src2: Optional[Tensor], dy: Tensor, mode: int,
@@ -375,137 +526,59 @@ class ConvChainFn(torch.autograd.Function):
         nconv = len(params) // 3
         ops.require_gpu(x1, x2, *params)
         dt = compute_dtype_for(x1, cfg.dtype)
-        dev = x1.device
-        saved = []
-        batch_flags = []
-        cur, cur2, mode = x1, x2, cfg.mode
-        if not cfg.first:
-            if cur.dtype != dt:
-                cur = cur.to(dt)
-            cur = ops.to_nhwc(cur)
-            if cur2 is not None:
-                cur2 = ops.to_nhwc(cur2.to(dt) if cur2.dtype != dt else cur2)
-        x1s, x2s = cur, cur2
-        scale = shift = None
-        fold = None  # accumulator path: the BatchNorm evaluation whose coefficients the next kernel derives itself
-        ys, coefs, run_items = [], [], []
-        for i in range(nconv):
-            w, g, b = params[3 * i: 3 * i + 3]
-            bn = cfg.bns[i]
-            use_batch, update = _bn_flags(bn)
-            Cout = w.shape[0]
-            acc_i = ops.BN_ACC and use_batch and Cout <= 1024
-            if i == 0 and cfg.first:
-                y, part = ops.conv_first_fwd(cur, w, dt, want_stats=use_batch, stats_acc=acc_i)
-            else:
-                note_forward_use(w, ctx.needs_input_grad[3 + 3 * i])
-                wf, _ = packed_weights(w, dt)
-                y, part = ops.conv3x3_fwd(cur, cur2 if i == 0 else None, wf, Cout,
-                                          mode=mode if i == 0 else 0, scale=scale, shift=shift, fold=fold,
-                                          want_stats=use_batch, stats_acc=acc_i)
-                if fold is not None:
-                    fold.done = True
-            count = y.shape[0] * y.shape[2] * y.shape[3]
-            mom = bn.momentum if bn.momentum is not None else 0.1
-            if acc_i:
-                # no finalize launch: the consumer of y (the next conv's prologue, or the apply launch below) derives
-                # the coefficients from the accumulator and leaves [scale, shift, mean, invstd, var] in fold.coef
-                fold = ops.BnState(part, g.detach(), b.detach(), count, bn.eps, dev)
-                scale = shift = None
-                coefs.append((fold.coef[0], fold.coef[1], fold.coef[2], fold.coef[3]))
-                if update:
-                    run_items.append((fold.coef, bn.running_mean, bn.running_var, mom))
-            else:
-                fold = None
-                scale, shift, mean, invstd = ops.bn_finalize(
-                    part, count, g.detach(), b.detach(), bn.running_mean, bn.running_var, mom, bn.eps, use_batch,
-                    update, Cout, dev)
-                coefs.append((scale, shift, mean, invstd))
-            if update and bn.num_batches_tracked is not None:
-                if _nbt_pending is not None:
-                    _nbt_pending.append(bn.num_batches_tracked)
-                else:
-                    bn.num_batches_tracked.add_(1)
-            ys.append(y)
-            batch_flags.append(use_batch)
-            cur, cur2 = y, None
-        if fold is not None:
-            out, pooled = ops.bn_relu_apply_pool_fold(ys[-1], fold) if cfg.pool_out else (ops.bn_relu_apply_fold(ys[-1], fold), None)
-        elif cfg.pool_out:
-            out, pooled = ops.bn_relu_apply_pool(ys[-1], scale, shift)
-        else:
-            out, pooled = ops.bn_relu_apply(ys[-1], scale, shift), None
-        if run_items:
-            if _run_pending is not None:
-                _run_pending.extend(run_items)
-            else:
-                ops.bn_running_update(run_items)
-        # accumulators of the backward sums, from the same zeroed arena (the backward pass allocates nothing to zero)
-        ctx.bwd_accs = None
-        if ops.BN_ACC and any(ctx.needs_input_grad) and all(yy.shape[1] <= 1024 for yy in ys):
-            ctx.bwd_accs = [ops.bn_bwd_acc_new(yy.shape[0], yy.shape[1], yy.shape[2], yy.shape[3],
-                                               cfg.pool_out and j == nconv - 1, dev) for j, yy in enumerate(ys)]
-            # whoever produces the gradient of `out` may add the sums of this block's last BatchNorm while it has the
-            # values in registers (an _UpConv's upsample backward does): what it needs travels with the tensor
-            out._cy_tail = (ys[-1], coefs[-1][0], ctx.bwd_accs[-1])
-        # ... and this block, if it upsamples on load, is such a producer for the block whose output it reads
-        ctx.up_tail = getattr(x1, "_cy_tail", None) if (cfg.mode == ops.CY_SRC_UP2 and ops.BN_ACC) else None
-        ctx.x2_tail = getattr(x2, "_cy_tail", None) if (x2 is not None and ops.BN_ACC) else None
-        if RAW_TAP is not None:
-            for i in range(nconv):
-                RAW_TAP(cfg.bns[i], ys[i], coefs[i][0], coefs[i][1], out if i == nconv - 1 else None)
         ctx.cfg, ctx.nconv, ctx.dt = cfg, nconv, dt
         ctx.pass_id = _pass_serial
-        ctx.batch_flags = batch_flags
-        ctx.x_shape = tuple(x1.shape)
         ctx.x_dtype = x1.dtype
-        ctx.has_x2 = x2 is not None
-        tensors = [x1s] + ([x2s] if x2 is not None else []) + list(params) + ys
-        for c in coefs:
-            tensors.extend(c)
+        x1s, x2s = _cast_inputs(cfg, x1, x2, dt)
+        evals: List[_BnEval] = []
+        run_items = []
+        for i in range(nconv):
+            w, g, b = params[3 * i: 3 * i + 3]
+            flags = _bn_flags(cfg.bns[i], w.shape[0])
+            y, part = _conv_fwd(cfg, w, dt, x1s, x2s, evals[-1] if evals else None, flags,
+                                ctx.needs_input_grad[3 + 3 * i])
+            evals.append(_bn_eval(cfg.bns[i], g, b, y, part, flags, run_items))
+        out, pooled = evals[-1].apply(cfg.pool_out)
+        _running_update(run_items)
+        _prepare_backward(ctx, x1, x2, evals, out)
         if cfg.pool_out:
             # backward of the pooled output routes through the arg-max of `out`; either output may go unused
             # (a pass whose loss taps only the encoder leaves `out`'s skip branch without a gradient)
-            tensors.append(out)
             ctx.set_materialize_grads(False)
-            ctx.save_for_backward(*tensors)
-            return out, pooled
-        ctx.save_for_backward(*tensors)
-        return out
+        _save(ctx, x1s, x2s, params, evals, out if cfg.pool_out else None)
+        if RAW_TAP is not None:
+            for bn, e in zip(cfg.bns, evals):
+                RAW_TAP(bn, e.y, e.scale, e.shift, out if e is evals[-1] else None)
+        return (out, pooled) if cfg.pool_out else out
 
     @staticmethod
     def backward(ctx, dout: Optional[Tensor], dpooled: Optional[Tensor] = None):
         ops.ensure_backward_join()
         cfg, nconv, need = ctx.cfg, ctx.nconv, ctx.needs_input_grad  # (need: cfg, x1, x2, *params)
-        t = list(ctx.saved_tensors)
-        out = t.pop() if cfg.pool_out else None
+        x1, x2, params, evals, out = _saved(ctx)
         if cfg.pool_out and dout is None and dpooled is None:
             return (None,) * (3 + 3 * nconv)
-        x1 = t.pop(0)
-        x2 = t.pop(0) if ctx.has_x2 else None
-        params = [t.pop(0) for _ in range(3 * nconv)]
-        ys = [t.pop(0) for _ in range(nconv)]
-        coefs = [tuple(t.pop(0) for _ in range(4)) for _ in range(nconv)]
-        accs = _backward_accs(ctx, ys)
+        on_acc = _backward_accs(ctx, evals)
         da, partials = dout, None
         if cfg.pool_out and dpooled is not None:
-            da, partials = _pooled_grad(out, dout, dpooled, ys[-1], coefs[-1], accs)
+            da, partials = _pooled_grad(out, dout, dpooled, evals[-1], on_acc)
         grads_p: List[Optional[Tensor]] = [None] * (3 * nconv)
         for i in reversed(range(nconv)):
             w = params[3 * i]
-            fused_dx, dy, dgamma, dbeta = _bn_relu_grad(ctx, i, da, params, ys[i], coefs[i], accs,
+            prev = evals[i - 1] if i > 0 else None
+            fused_dx, dy, dgamma, dbeta = _bn_relu_grad(ctx, i, da, params, evals[i], on_acc,
                                                         partials if i == nconv - 1 else None,
                                                         x1.shape[1] if (i == 0 and ctx.has_x2) else None)
             grads_p[3 * i + 1] = dgamma if need[4 + 3 * i] else None
             grads_p[3 * i + 2] = dbeta if need[5 + 3 * i] else None
-            if need[3 + 3 * i] and i > 0:
-                grads_p[3 * i] = _weight_grad(w, ops.grad_sink(w), ys[i - 1], None, dy, 0, coefs[i - 1][0],
-                                              coefs[i - 1][1], False, ctx.pass_id)
+            if need[3 + 3 * i] and prev is not None:
+                grads_p[3 * i] = _weight_grad(w, ops.grad_sink(w), prev.y, None, dy, 0, prev.scale, prev.shift, False,
+                                              ctx.pass_id)
             elif need[3 + 3 * i]:
                 grads_p[3 * i] = _weight_grad(w, ops.grad_sink(w), x1, x2, dy, cfg.mode, None, None, cfg.first,
                                               ctx.pass_id)
-            if i > 0:
-                tail = (ys[i - 1], coefs[i - 1][0], accs[i - 1]) if accs is not None and accs[i - 1] is not None else None
+            if prev is not None:
+                tail = prev.tail() if prev.acc is not None else None
                 da = fused_dx if fused_dx is not None else _data_grad(w, packed_weights(w, ctx.dt)[1], dy, None, tail)
         dx1, dx2 = _input_grads(ctx, x1, params[0], dy, fused_dx)
         if cfg.ready_tag is not None and (_step_first_pass is None or ctx.pass_id == _step_first_pass):

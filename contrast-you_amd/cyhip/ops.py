@@ -346,6 +346,8 @@ def conv3x3_fwd(src1: Tensor, src2: Optional[Tensor], wf: Tensor, Cout: int, *, 
                   _ptr(scale), _ptr(shift), wf.data_ptr(), out.data_ptr(), _ptr(out2), None,
                   None if acc is None else acc.ref, _ptr(ws), nbytes, _stream())
         stats = acc
+        if fold is not None:
+            fold.done = True
     else:
         _lib.call("cy_conv3x3_fwd", d.ref, src1.data_ptr(), _ptr(src2), _ptr(scale), _ptr(shift),
                   wf.data_ptr(), out.data_ptr(), _ptr(out2), _ptr(stats), _ptr(ws), nbytes, _stream())
@@ -415,30 +417,34 @@ class on_side_stream:
             for t in self.reads:
                 t.record_stream(self.side)
         _side_pending.add(self.side)
-        global _join_queued
-        if not _join_queued:  # join when this backward pass ends: .grad is then safe to read on the main stream
-            try:
-                torch.autograd.Variable._execution_engine.queue_callback(_join_after_backward)
-                _join_queued = True
-            except RuntimeError:  # not inside a backward pass
-                join_side_streams()
+        # join when this backward pass ends: .grad is then safe to read on the main stream
+        _arm_backward_join(otherwise=join_side_streams)
         return False
 
 
 _join_queued = False
 
 
+def _arm_backward_join(otherwise=None) -> bool:
+    """make sure `_join_after_backward` runs when the backward pass that is executing ends: True if it will.  When no
+    backward pass is executing, `otherwise()` runs now instead (None: nothing does)."""
+    global _join_queued
+    if not _join_queued:
+        try:
+            torch.autograd.Variable._execution_engine.queue_callback(_join_after_backward)
+            _join_queued = True
+        except RuntimeError:  # not inside a backward pass
+            if otherwise is not None:
+                otherwise()
+    return _join_queued
+
+
 def ensure_backward_join() -> None:
     """called by backward nodes: if auxiliary streams carry work of this step (second-pass stream,
     weight-gradient stream) or work has been deferred to the end of the backward pass, make sure the
     deferred work is issued and the streams are joined when the backward pass ends"""
-    global _join_queued
-    if (_side_pending or _at_backward_end or _wg_batches) and not _join_queued:
-        try:
-            torch.autograd.Variable._execution_engine.queue_callback(_join_after_backward)
-            _join_queued = True
-        except RuntimeError:
-            pass
+    if _side_pending or _at_backward_end or _wg_batches:
+        _arm_backward_join()
 
 
 _at_backward_end = []  # callables to run once when the current backward pass ends (before the joins)
@@ -446,15 +452,9 @@ _at_backward_end = []  # callables to run once when the current backward pass en
 
 def at_backward_end(fn) -> None:
     """run `fn()` when the backward pass that is executing ends (immediately if none is)"""
-    global _join_queued
     if fn not in _at_backward_end:
         _at_backward_end.append(fn)
-    if not _join_queued:
-        try:
-            torch.autograd.Variable._execution_engine.queue_callback(_join_after_backward)
-            _join_queued = True
-        except RuntimeError:  # not inside a backward pass
-            _join_after_backward()
+    _arm_backward_join(otherwise=_join_after_backward)
 
 
 _in_join = False  # _join_after_backward is running (deferred work it issues is flushed by it)
@@ -527,6 +527,8 @@ def dp_early_rule(grad_bytes: int, world: int) -> bool:
         return False
     exposed = 2.0 * (world - 1) / world * grad_bytes / 400e9 + 60e-6
     return exposed > 0.3e-3
+
+
 marks_wanted = False   # set by a data-parallel FusedRAdam
 MARK_TAGS = ("decoder", "conv5", "conv4")
 _step_id = {}          # device index -> [int32 device scalar, host value]
@@ -554,11 +556,8 @@ def begin_step_marks(device) -> None:
     _ready_marks.clear()
 
 
-_MARK_AT = MARK_TAGS
-
-
 def grad_ready_mark(tag: str, device) -> None:
-    if not (marks_wanted and DP_EARLY) or tag not in _MARK_AT:
+    if not (marks_wanted and DP_EARLY) or tag not in MARK_TAGS:
         return
     idx = _dev_index(device)
     rec = _step_id.get(idx)
@@ -759,14 +758,9 @@ def _wg_defer(device, entry) -> None:
     b = _wg_batch(device)
     b.entries.append(entry)
     b.streams.add(torch.cuda.current_stream(device))
-    global _join_queued
-    if not _join_queued and not _in_join:
-        try:
-            torch.autograd.Variable._execution_engine.queue_callback(_join_after_backward)
-            _join_queued = True
-        except RuntimeError:  # not inside a backward pass: nothing else comes
-            flush_wgrad_reduce(device, final=True)
-            return
+    # the slab sums run when the backward pass ends; outside a backward pass nothing else comes: this one runs now
+    if not _in_join and not _arm_backward_join(otherwise=lambda: flush_wgrad_reduce(device, final=True)):
+        return
     if len(b.entries) >= _lib.CY_WGRAD_REDUCE_MAX or (
             WGRAD_FLUSH_BYTES is not None and sum(_slab_bytes(e) for e in b.entries) >= WGRAD_FLUSH_BYTES):
         flush_wgrad_reduce(device)
@@ -1082,9 +1076,11 @@ def bn_running_update(items) -> None:
         _lib.call("cy_bn_running_update", arr, len(items), _stream())
 
 
-def bn_finalize(partials: Optional[Tensor], count: int, gamma: Optional[Tensor], beta: Optional[Tensor],
-                running_mean: Optional[Tensor], running_var: Optional[Tensor], momentum: float,
-                eps: float, use_batch_stats: bool, update_running: bool, Cc: int, device):
+def bn_finalize_block(partials: Optional[Tensor], count: int, gamma: Optional[Tensor], beta: Optional[Tensor],
+                      running_mean: Optional[Tensor], running_var: Optional[Tensor], momentum: float,
+                      eps: float, use_batch_stats: bool, update_running: bool, Cc: int, device) -> Tensor:
+    """the coefficients of one BatchNorm evaluation from partial rows (or the running statistics): one contiguous
+    [4, C] block with rows scale, shift, mean, invstd -- the first four rows of BnState.coef"""
     out = _f32(4 * Cc, device).view(4, Cc)
     npart = 0 if partials is None else partials.shape[0]
     def launch():
@@ -1099,7 +1095,13 @@ def bn_finalize(partials: Optional[Tensor], count: int, gamma: Optional[Tensor],
             launch()
     else:
         launch()
-    return out[0], out[1], out[2], out[3]  # scale, shift, mean, invstd
+    return out
+
+
+def bn_finalize(*args, **kwargs):
+    """`bn_finalize_block` as its four rows: (scale, shift, mean, invstd)"""
+    out = bn_finalize_block(*args, **kwargs)
+    return out[0], out[1], out[2], out[3]
 
 
 def bn_relu_apply(y: Tensor, scale: Tensor, shift: Tensor, out_dtype: Optional[torch.dtype] = None) -> Tensor:
@@ -1275,7 +1277,8 @@ def conv3x3_dgrad_bn(da: Tensor, y: Tensor, coef: Tensor, acc: "BnAccBuf", batch
                      dgamma_out: Optional[Tensor] = None, dbeta_out: Optional[Tensor] = None,
                      want_param_grads: bool = True, split: Optional[int] = None):
     """(dx or (dx1, dx2), dy, dgamma, dbeta): dy = the BatchNorm + ReLU backward of da (formed in the conv's load path
-    from da, y and the sums in `acc`), dx = conv3x3(dy, wd).  coef: row 0 of the forward pass's [5, C] block."""
+    from da, y and the sums in `acc`), dx = conv3x3(dy, wd).  coef: the forward pass's coefficient block, taken
+    by its address."""
     N, Cc, H, W = y.shape
     dev = y.device
     d = _dgrad_bn_desc(da, Cin, split)
