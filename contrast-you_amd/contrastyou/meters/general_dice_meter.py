@@ -57,11 +57,18 @@ class UniversalDice(Metric):
                 self._intersections[g], self._unions[g] = i_, u_
 
     @torch.no_grad()
-    def add_logits(self, logits: Tensor, target: Tensor, *, group_name=None):
-        """fused arg-max + counting on the device (HIP); no host sync"""
+    def add_logits(self, logits: Tensor, target: Tensor, *, group_name=None, groups: int = None):
+        """fused arg-max + counting on the device (HIP); no host sync.  `groups=G` (multi-prototype networks): the
+        logits have G * m channels, the prediction is the arg-max over the G per-class sums of the softmax (class g =
+        channels [g*m, (g+1)*m)), and `C` is the true class count G"""
         from cyhip import ops
         tgt = target.squeeze(1) if target.dim() == 4 else target
-        counts = ops.dice_counts(ops.to_nhwc(logits.detach().float()), tgt.contiguous())
+        nhwc = ops.to_nhwc(logits.detach().float())
+        if groups is None:
+            counts = ops.dice_counts(nhwc, tgt.contiguous())
+        else:
+            assert groups == self._C, f"`groups`={groups} must be the meter's class count C={self._C}"
+            counts = ops.group_dice_counts(nhwc, tgt.contiguous(), groups)
         self._pending.append((counts, self._names(group_name, logits.shape[0])))
         self._n += 1
 

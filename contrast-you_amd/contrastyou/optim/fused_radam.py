@@ -34,8 +34,8 @@ class FlatParams:
 
     def __init__(self, params: List[nn.Parameter]):
         params = [p for p in params]
-        assert params, "empty parameter list"
-        dev = params[0].device
+        # an empty group (the parameters of a criterion that has none: semi_seg/trainers/features/multicore.py) is legal
+        dev = params[0].device if params else torch.device("cpu")
         total = sum(p.numel() for p in params)
         self.params = params
         self.data = torch.empty(total, dtype=torch.float32, device=dev)
@@ -134,7 +134,7 @@ class FusedRAdam(torch.optim.Optimizer):
             return
         src_global = dist.get_global_rank(self._pg, src) if self._pg is not None else src
         for i, f in enumerate(self._flat):
-            if f is None:
+            if f is None or not f.params:
                 continue
             st = self._flat_state[i]
             for buf in (f.data, st["exp_avg"], st["exp_avg_sq"]):

@@ -16,10 +16,15 @@ int cy_head_wide_fwd(const void* x, const float* w, const float* b, float* logit
                      void* stream);
 int cy_head_wide_bwd(const void* x, const float* w, const float* dlogits, void* dx, float* dw, float* db, int accumulate,
                      long M, int C, int K, int dtype, void* ws, size_t ws_bytes, void* stream);
+// softmax-MSE at 16 < K <= 64 on the sixteen-lanes-per-pixel kernels of cy_group_loss.hip (same shared object)
+int cy_softmax_mse_row_fwd(const float* a, const float* b, float* loss, long npix, int K, void* ws, void* stream);
+int cy_softmax_mse_row_bwd(const float* a, const float* b, const float* gscale, float* da, float* db, long npix, int K,
+                           void* stream);
 
 namespace {
 
 constexpr int KWIDE = 128;  // stacked cluster-head outputs
+constexpr int KROW = 64;    // multi-prototype outputs the softmax-MSE takes (cy_group_loss.hip)
 
 template <typename T> __device__ __forceinline__ void load8h(const T* p, float* f) {
   if constexpr (sizeof(T) == 2) {
@@ -552,8 +557,9 @@ size_t cy_softmax_mse_ws_bytes(long npix) { return (size_t)loss_blocks(npix) * s
 int cy_softmax_mse_fwd(const float* a, const float* b, float* loss, long npix, int K, void* ws,
                        size_t ws_bytes, void* stream) {
   if (!a || !b || !loss || !ws || npix <= 0) return CY_ERR_ARG;
-  if (K < 1 || K > KMAX) return CY_ERR_SHAPE;
+  if (K < 1 || K > KROW) return CY_ERR_SHAPE;
   if (ws_bytes < cy_softmax_mse_ws_bytes(npix)) return CY_ERR_WORKSPACE;
+  if (K > KMAX) return cy_softmax_mse_row_fwd(a, b, loss, npix, K, ws, stream);
   hipStream_t st = (hipStream_t)stream;
   const int nblk = loss_blocks(npix);
   hipLaunchKernelGGL(softmax_mse_fwd_kernel, dim3(nblk), dim3(256), 0, st, a, b, (double*)ws, npix,
@@ -568,7 +574,8 @@ int cy_softmax_mse_fwd(const float* a, const float* b, float* loss, long npix, i
 int cy_softmax_mse_bwd(const float* a, const float* b, const float* gscale, float* da, float* db,
                        long npix, int K, void* stream) {
   if (!a || !b || !gscale || (!da && !db) || npix <= 0) return CY_ERR_ARG;
-  if (K < 1 || K > KMAX) return CY_ERR_SHAPE;
+  if (K < 1 || K > KROW) return CY_ERR_SHAPE;
+  if (K > KMAX) return cy_softmax_mse_row_bwd(a, b, gscale, da, db, npix, K, stream);
   hipLaunchKernelGGL(softmax_mse_bwd_kernel, dim3(loss_blocks(npix) * 2), dim3(256), 0,
                      (hipStream_t)stream, a, b, gscale, da, db, npix, K);
   CY_CHECK_LAUNCH();

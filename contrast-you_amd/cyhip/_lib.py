@@ -211,6 +211,10 @@ _SIGS = {
     "cy_softmax_mse_ws_bytes": (c_size_t, [c_long]),
     "cy_softmax_mse_fwd": (c_int, [_P, _P, _P, c_long, c_int, _P, c_size_t, _P]),
     "cy_softmax_mse_bwd": (c_int, [_P, _P, _P, _P, _P, c_long, c_int, _P]),
+    "cy_softmax_group_kl_ws_bytes": (c_size_t, [c_long, c_int]),
+    "cy_softmax_group_kl_fwd": (c_int, [_P, _P, _P, c_long, c_int, c_int, c_float, _P, c_size_t, _P]),
+    "cy_softmax_group_kl_bwd": (c_int, [_P, _P, _P, _P, c_long, c_int, c_int, c_float, _P]),
+    "cy_group_dice_counts": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "cy_softmax_entropy_ws_bytes": (c_size_t, [c_long]),
     "cy_softmax_entropy_fwd": (c_int, [_P, _P, c_long, c_int, c_float, _P, c_size_t, _P]),
     "cy_softmax_entropy_bwd": (c_int, [_P, _P, _P, c_long, c_int, c_float, _P]),

@@ -637,6 +637,26 @@ class SoftmaxKLFn(torch.autograd.Function):
         return ops.softmax_kl_bwd(logits, target, gs, ctx.eps), None, None
 
 
+class SoftmaxGroupKLFn(torch.autograd.Function):
+    """MultiCoreKL(grouper(range(K), G))(softmax(logits,1), one_hot(target, G)): KL_div of the per-class sums of the
+    softmax over K/G contiguous channels, mean reduction (contrastyou/losses/multicore_loss.py:41-60)."""
+
+    @staticmethod
+    def forward(ctx, logits: Tensor, target: Tensor, G: int, eps: float):
+        ops.require_gpu(logits, target)
+        logits = ops.to_nhwc(logits.float())
+        target = target.contiguous()
+        ctx.save_for_backward(logits, target)
+        ctx.G, ctx.eps = G, eps
+        return ops.softmax_group_kl_fwd(logits, target, G, eps)
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        logits, target = ctx.saved_tensors
+        gs = g.reshape(1).float().contiguous()
+        return ops.softmax_group_kl_bwd(logits, target, gs, ctx.G, ctx.eps), None, None, None
+
+
 class SoftmaxMSEFn(torch.autograd.Function):
     """nn.MSELoss()(a.softmax(1), b.softmax(1)) (semi_seg/hooks/consistency.py:36, mt.py:186)."""
 

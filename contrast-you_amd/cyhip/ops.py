@@ -1474,6 +1474,26 @@ def softmax_mse_bwd(a: Tensor, b: Tensor, gscale: Tensor, need_a: bool, need_b: 
     return da, db
 
 
+def softmax_group_kl_fwd(logits: Tensor, target: Tensor, G: int, eps: float) -> Tensor:
+    """mean_p -log((P_p + eps) / (1 + eps)), P_p = the softmax mass of the target class's K/G contiguous channels"""
+    N, K, H, W = logits.shape
+    npix = N * H * W
+    nbytes = _lib.load().cy_softmax_group_kl_ws_bytes(npix, K)
+    ws = _ws(nbytes, logits.device)
+    loss = _f32(1, logits.device)
+    _lib.call("cy_softmax_group_kl_fwd", logits.data_ptr(), target.data_ptr(), loss.data_ptr(), npix, K, int(G),
+              float(eps), ws.data_ptr(), nbytes, _stream())
+    return loss.view(())
+
+
+def softmax_group_kl_bwd(logits: Tensor, target: Tensor, gscale: Tensor, G: int, eps: float) -> Tensor:
+    N, K, H, W = logits.shape
+    d = empty_nhwc(N, K, H, W, torch.float32, logits.device)
+    _lib.call("cy_softmax_group_kl_bwd", logits.data_ptr(), target.data_ptr(), gscale.data_ptr(), d.data_ptr(),
+              N * H * W, K, int(G), float(eps), _stream())
+    return d
+
+
 def _pixel_loss_fwd(name: str, x: Tensor, out: int = 1):
     """what the forward of a pixel-wise regulariser (csrc/cy_pixel_reg.hip) takes: (npix, K, workspace, its bytes, the
     `out` device floats of the result)"""
@@ -1534,6 +1554,16 @@ def dice_counts(logits: Tensor, target: Tensor) -> Tensor:
     N, K, H, W = logits.shape
     counts = torch.empty((N, K, 2), dtype=torch.int64, device=logits.device)
     _lib.call("cy_dice_counts", logits.data_ptr(), target.data_ptr(), counts.data_ptr(), N, H * W, K,
+              _stream())
+    return counts
+
+
+def group_dice_counts(logits: Tensor, target: Tensor, G: int) -> Tensor:
+    """int64 [N,G,2] = per-sample per-class (intersection, union) of the arg-max over the G group sums of
+    softmax(logits) (K/G contiguous channels per class) vs target."""
+    N, K, H, W = logits.shape
+    counts = torch.empty((N, int(G), 2), dtype=torch.int64, device=logits.device)
+    _lib.call("cy_group_dice_counts", logits.data_ptr(), target.data_ptr(), counts.data_ptr(), N, H * W, K, int(G),
               _stream())
     return counts
 

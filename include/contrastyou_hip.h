@@ -564,13 +564,38 @@ int cy_dice_counts(const float* logits, const int64_t* target, int64_t* counts, 
  * flat f32 buffer of n elements. */
 int cy_ema_update(float* teacher, const float* student, long n, float alpha, float weight_decay,
                   void* stream);
-/* loss = mean((softmax(a)-softmax(b))^2) over [npix][K] f32 logits */
+/* loss = mean((softmax(a)-softmax(b))^2) over [npix][K] f32 logits, 1 <= K <= 64 (K > 16: the sixteen-lanes-per-pixel
+ * form of csrc/cy_group_loss.hip; CY_ERR_SHAPE above 64) */
 size_t cy_softmax_mse_ws_bytes(long npix);
 int cy_softmax_mse_fwd(const float* a, const float* b, float* loss, long npix, int K, void* ws,
                        size_t ws_bytes, void* stream);
 /* da (and db if not NULL) = gscale[0] * dloss/d{a,b} */
 int cy_softmax_mse_bwd(const float* a, const float* b, const float* gscale, float* da, float* db,
                        long npix, int K, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Multi-prototype ("multicore") supervised loss and metric (csrc/cy_group_loss.hip; entries added to ABI v15 -- no
+ * existing signature changed, so cy_abi_version() stays 15).  The network has K = G * m outputs, class g owns the
+ * contiguous channels [g*m, (g+1)*m) (the reference's `grouper(range(K), G)`).  Logits are [npix][K] f32 (NHWC),
+ * 1 <= K <= 64, labels int64 in [0, G).  Every entry checks its arguments before any launch: a NULL pointer or a
+ * count < 1 -> CY_ERR_ARG; K outside 1..64, G < 1 or K % G != 0 -> CY_ERR_SHAPE; a short workspace ->
+ * CY_ERR_WORKSPACE.  K <= 16 runs one thread per pixel, 16 < K <= 64 sixteen lanes per pixel.
+ * ------------------------------------------------------------------------ */
+/* MultiCoreKL(groups)(softmax(logits), one_hot(target)) (contrastyou/losses/multicore_loss.py:41-60):
+ *   P_p = sum_{k in group(t_p)} softmax(z_p)_k;  loss = mean_p -log((P_p + eps) / (1 + eps))
+ * Workspace: one f64 partial per block = 8 * min(1024, ceil(npix / P)) bytes, P = 256 pixels per block for K <= 16 and
+ * 16 for K > 16; the partials are summed in a fixed order (two runs give the same bits). */
+size_t cy_softmax_group_kl_ws_bytes(long npix, int K);
+int cy_softmax_group_kl_fwd(const float* logits, const int64_t* target, float* loss, long npix, int K, int G,
+                            float eps, void* ws, size_t ws_bytes, void* stream);
+/* dlogits_k = -(gscale[0]/npix) * p_k * ([k in group(t)] - P) / (P + eps)  (gscale: device scalar, upstream grad) */
+int cy_softmax_group_kl_bwd(const float* logits, const int64_t* target, const float* gscale, float* dlogits,
+                            long npix, int K, int G, float eps, void* stream);
+/* UniversalDice counts of `reduced_simplex(softmax(logits)).max(1)[1]` against the target
+ * (semi_seg/epochers/features/multicore_epocher.py:37-39,64-67,84-91): counts is int64 [N][G][2] = {intersection,
+ * union}; the predicted class is the first maximal group sum of exp(z - max z). */
+int cy_group_dice_counts(const float* logits, const int64_t* target, int64_t* counts, int N, int HW, int K, int G,
+                         void* stream);
 
 /* ------------------------------------------------------------------------
  * Pixel-wise regularisers of the semi-supervised baselines (csrc/cy_pixel_reg.hip; entries added to ABI v15 -- no
