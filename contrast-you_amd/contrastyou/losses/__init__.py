@@ -3,3 +3,5 @@ from .redundancy_reduction import RedundancyCriterion  # noqa: F401
 from .discreteMI import IIDLoss, IIDSegmentationLoss  # noqa: F401
 from .kl import KL_div, Entropy  # noqa: F401
 from .multicore_loss import GeneralOverSegmentedLoss, MultiCoreKL  # noqa: F401
+from .multicore_loss import AdaptiveOverSegmentedLoss, GradientReverse, scale_grad  # noqa: F401
+from .multicore_loss import StricterAdaptiveOverSegmentedLoss, StricterAdaptiveOverSegmentedLossWithMI  # noqa: F401

@@ -57,14 +57,20 @@ class UniversalDice(Metric):
                 self._intersections[g], self._unions[g] = i_, u_
 
     @torch.no_grad()
-    def add_logits(self, logits: Tensor, target: Tensor, *, group_name=None, groups: int = None):
+    def add_logits(self, logits: Tensor, target: Tensor, *, group_name=None, groups: int = None, mix: Tensor = None):
         """fused arg-max + counting on the device (HIP); no host sync.  `groups=G` (multi-prototype networks): the
         logits have G * m channels, the prediction is the arg-max over the G per-class sums of the softmax (class g =
-        channels [g*m, (g+1)*m)), and `C` is the true class count G"""
+        channels [g*m, (g+1)*m)), and `C` is the true class count G.  `mix=M` ([K, C], the adaptive criteria): the
+        prediction is the arg-max of softmax(logits) @ M.  `groups` and `mix` exclude each other."""
+        assert groups is None or mix is None, "`groups=` and `mix=` exclude each other"
         from cyhip import ops
         tgt = target.squeeze(1) if target.dim() == 4 else target
         nhwc = ops.to_nhwc(logits.detach().float())
-        if groups is None:
+        if mix is not None:
+            assert mix.dim() == 2 and mix.shape[1] == self._C, \
+                f"`mix` {tuple(mix.shape)} must have the meter's class count C={self._C} columns"
+            counts = ops.mix_dice_counts(nhwc, tgt.contiguous(), mix)
+        elif groups is None:
             counts = ops.dice_counts(nhwc, tgt.contiguous())
         else:
             assert groups == self._C, f"`groups`={groups} must be the meter's class count C={self._C}"

@@ -215,6 +215,11 @@ _SIGS = {
     "cy_softmax_group_kl_fwd": (c_int, [_P, _P, _P, c_long, c_int, c_int, c_float, _P, c_size_t, _P]),
     "cy_softmax_group_kl_bwd": (c_int, [_P, _P, _P, _P, c_long, c_int, c_int, c_float, _P]),
     "cy_group_dice_counts": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    "cy_softmax_mix_kl_ws_bytes": (c_size_t, [c_long, c_int]),
+    "cy_softmax_mix_kl_fwd": (c_int, [_P, _P, _P, _P, c_long, c_int, c_int, c_float, _P, c_size_t, _P]),
+    "cy_softmax_mix_kl_bwd_ws_bytes": (c_size_t, [c_long, c_int, c_int]),
+    "cy_softmax_mix_kl_bwd": (c_int, [_P, _P, _P, _P, _P, _P, c_long, c_int, c_int, c_float, _P, c_size_t, _P]),
+    "cy_mix_dice_counts": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "cy_softmax_entropy_ws_bytes": (c_size_t, [c_long]),
     "cy_softmax_entropy_fwd": (c_int, [_P, _P, c_long, c_int, c_float, _P, c_size_t, _P]),
     "cy_softmax_entropy_bwd": (c_int, [_P, _P, _P, c_long, c_int, c_float, _P]),

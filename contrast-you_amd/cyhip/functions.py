@@ -657,6 +657,29 @@ class SoftmaxGroupKLFn(torch.autograd.Function):
         return ops.softmax_group_kl_bwd(logits, target, gs, ctx.G, ctx.eps), None, None, None
 
 
+class SoftmaxMixKLFn(torch.autograd.Function):
+    """KL_div(softmax(logits,1) mixed by `mix` [K, C], one_hot(target, C)), mean reduction: the KL term of the adaptive
+    over-segmented criteria (contrastyou/losses/multicore_loss.py:63-149).  Gradients go to the logits and, where it
+    asks for one, to `mix` (one more launch)."""
+
+    @staticmethod
+    def forward(ctx, logits: Tensor, target: Tensor, mix: Tensor, eps: float):
+        ops.require_gpu(logits, target, mix)
+        logits = ops.to_nhwc(logits.float())
+        target = target.contiguous()
+        mix = mix.detach().float().contiguous()
+        ctx.save_for_backward(logits, target, mix)
+        ctx.eps = eps
+        return ops.softmax_mix_kl_fwd(logits, target, mix, eps)
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        logits, target, mix = ctx.saved_tensors
+        gs = g.reshape(1).float().contiguous()
+        dlogits, dmix = ops.softmax_mix_kl_bwd(logits, target, mix, gs, ctx.eps, ctx.needs_input_grad[2])
+        return dlogits, None, dmix, None
+
+
 class SoftmaxMSEFn(torch.autograd.Function):
     """nn.MSELoss()(a.softmax(1), b.softmax(1)) (semi_seg/hooks/consistency.py:36, mt.py:186)."""
 

@@ -1494,6 +1494,43 @@ def softmax_group_kl_bwd(logits: Tensor, target: Tensor, gscale: Tensor, G: int,
     return d
 
 
+def _mix_arg(logits: Tensor, mix: Tensor) -> Tensor:
+    """the [K, C] f32 mixing matrix the cy_softmax_mix_* entries read, on the logits' device"""
+    assert mix.dim() == 2 and mix.shape[0] == logits.shape[1], (tuple(mix.shape), tuple(logits.shape))
+    assert mix.device == logits.device, (mix.device, logits.device)
+    return mix.detach().float().contiguous()
+
+
+def softmax_mix_kl_fwd(logits: Tensor, target: Tensor, mix: Tensor, eps: float) -> Tensor:
+    """mean_p -log((R_p + eps) / (1 + eps)), R_p = sum_k softmax(z_p)_k mix[k, t_p]; mix is [K, C]"""
+    N, K, H, W = logits.shape
+    mix = _mix_arg(logits, mix)
+    npix = N * H * W
+    nbytes = _lib.load().cy_softmax_mix_kl_ws_bytes(npix, K)
+    ws = _ws(nbytes, logits.device)
+    loss = _f32(1, logits.device)
+    _lib.call("cy_softmax_mix_kl_fwd", logits.data_ptr(), target.data_ptr(), mix.data_ptr(), loss.data_ptr(), npix, K,
+              mix.shape[1], float(eps), ws.data_ptr(), nbytes, _stream())
+    return loss.view(())
+
+
+def softmax_mix_kl_bwd(logits: Tensor, target: Tensor, mix: Tensor, gscale: Tensor, eps: float, need_mix: bool):
+    """-> (dlogits, dmix or None); dmix [K, C] only where `need_mix` (it costs the per-block partials and a launch)"""
+    N, K, H, W = logits.shape
+    mix = _mix_arg(logits, mix)
+    C = mix.shape[1]
+    npix = N * H * W
+    d = empty_nhwc(N, K, H, W, torch.float32, logits.device)
+    dmix, ws, nbytes = None, None, 0
+    if need_mix:
+        dmix = _f32(K * C, logits.device).view(K, C)
+        nbytes = _lib.load().cy_softmax_mix_kl_bwd_ws_bytes(npix, K, C)
+        ws = _ws(nbytes, logits.device)
+    _lib.call("cy_softmax_mix_kl_bwd", logits.data_ptr(), target.data_ptr(), mix.data_ptr(), gscale.data_ptr(),
+              d.data_ptr(), _ptr(dmix), npix, K, C, float(eps), _ptr(ws), nbytes, _stream())
+    return d, dmix
+
+
 def _pixel_loss_fwd(name: str, x: Tensor, out: int = 1):
     """what the forward of a pixel-wise regulariser (csrc/cy_pixel_reg.hip) takes: (npix, K, workspace, its bytes, the
     `out` device floats of the result)"""
@@ -1565,6 +1602,18 @@ def group_dice_counts(logits: Tensor, target: Tensor, G: int) -> Tensor:
     counts = torch.empty((N, int(G), 2), dtype=torch.int64, device=logits.device)
     _lib.call("cy_group_dice_counts", logits.data_ptr(), target.data_ptr(), counts.data_ptr(), N, H * W, K, int(G),
               _stream())
+    return counts
+
+
+def mix_dice_counts(logits: Tensor, target: Tensor, mix: Tensor) -> Tensor:
+    """int64 [N,C,2] = per-sample per-class (intersection, union) of the arg-max over softmax(logits) @ mix ([K, C])
+    vs target."""
+    N, K, H, W = logits.shape
+    mix = _mix_arg(logits, mix)
+    C = mix.shape[1]
+    counts = torch.empty((N, C, 2), dtype=torch.int64, device=logits.device)
+    _lib.call("cy_mix_dice_counts", logits.data_ptr(), target.data_ptr(), mix.data_ptr(), counts.data_ptr(), N, H * W,
+              K, C, _stream())
     return counts
 
 

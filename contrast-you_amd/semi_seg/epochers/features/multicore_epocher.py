@@ -1,15 +1,17 @@
 """`MultiCoreTrainEpocher`, `MultiCoreEvalEpocher` (semi_seg/epochers/features/multicore_epocher.py:13-91): the
 semi-supervised step and the evaluation of a network with `multiplier x true_num_classes` outputs under an
-over-segmented criterion (`MultiCoreKL`).
+over-segmented criterion (`MultiCoreKL` or one of the adaptive criteria with a translation matrix).
 
 Meters and the order of calls are the reference's.  Execution follows semi_seg/epochers/epocher.py here: the supervised
 loss goes through `criterion.from_logits` (one fused pass over the K-channel logits), the Dice counts of the reduced
-arg-max are taken by `cy_group_dice_counts` on the device, and the two-stage forward (second stream, HIP-graph replay)
-is inherited untouched.  Hooks receive the K-channel logits.
+arg-max are taken by `cy_group_dice_counts` (contiguous groups) or `cy_mix_dice_counts` (a criterion that offers `mix()`)
+on the device, and the two-stage forward (second stream, HIP-graph replay) is inherited untouched.  Hooks receive the
+K-channel logits.  The evaluation's `true_loss` -- the KL term without the criterion's extra terms -- and `loss` come
+from `criterion.kl_and_loss_from_logits` where the criterion has one: no softmax or reduced tensor is formed.
 
 `num_classes` is the TRUE class count.  The reference reads it from its global config manager
-(`Arch.true_num_classes`); here it is `len(criterion.groups)`, and a trainer config that carries
-`Arch.true_num_classes` must agree with it.
+(`Arch.true_num_classes`); here it is `len(criterion.groups)` (adaptive criteria: their `output_num_classes`), and a
+trainer config that carries `Arch.true_num_classes` must agree with it.
 """
 from __future__ import annotations
 
@@ -26,7 +28,8 @@ from semi_seg.epochers.epocher import EvalEpocher, SemiSupervisedEpocher, _scala
 class _MultiCoreMixin:
     @property
     def num_classes(self) -> int:
-        classes = len(self._sup_criterion.groups)
+        groups = getattr(self._sup_criterion, "groups", None)
+        classes = len(groups) if groups is not None else int(self._sup_criterion.output_num_classes)
         config = getattr(self._trainer, "_config", None)  # (no trainer: an epocher run on its own)
         arch = config.get("Arch") if config is not None else None
         if arch is not None and arch.get("true_num_classes") is not None:
@@ -39,7 +42,10 @@ class _MultiCoreMixin:
         return fusable is not None and fusable(logits.shape[1])
 
     def _add_dice(self, meter, logits, target, group_name):
-        if self._contiguous(logits):
+        mix = getattr(self._sup_criterion, "mix", None)
+        if self._contiguous(logits) and mix is not None:
+            meter.add_logits(logits, target, group_name=group_name, mix=mix().detach())
+        elif self._contiguous(logits):
             meter.add_logits(logits, target, group_name=group_name, groups=self.num_classes)
         else:
             reduced = self._sup_criterion.reduced_simplex(logits.softmax(1))
@@ -83,13 +89,17 @@ class MultiCoreEvalEpocher(_MultiCoreMixin, EvalEpocher):
         criterion = self._sup_criterion
         with self.autocast:
             logits = self._model(eval_img)
-            loss = _sup_loss(criterion, logits, eval_target, self.num_classes)
-            # `true_loss` = criterion.kl(reduced_simplex, one_hot): for MultiCoreKL that IS the loss (computed once);
-            # a criterion that adds terms to it pays the second evaluation
-            true_loss = loss
-            if not isinstance(criterion, MultiCoreKL):
-                reduced = criterion.reduced_simplex(logits.softmax(1))
-                true_loss = criterion.kl(reduced, class2one_hot(eval_target.squeeze(1), self.num_classes))
+            # `true_loss` = criterion.kl(reduced_simplex, one_hot): for MultiCoreKL that IS the loss (computed once); the
+            # adaptive criteria give both from one pass over the logits; any other criterion that adds terms pays the
+            # second evaluation
+            both = getattr(criterion, "kl_and_loss_from_logits", None)
+            if both is not None:
+                true_loss, loss = both(logits, eval_target.squeeze(1))
+            else:
+                loss = true_loss = _sup_loss(criterion, logits, eval_target, self.num_classes)
+                if not isinstance(criterion, MultiCoreKL):
+                    reduced = criterion.reduced_simplex(logits.softmax(1))
+                    true_loss = criterion.kl(reduced, class2one_hot(eval_target.squeeze(1), self.num_classes))
         self.meters["loss"].add(loss.detach())
         self.meters["true_loss"].add(true_loss.detach())
         self._add_dice(self.meters["dice"], logits, eval_target, eval_group)

@@ -1,5 +1,10 @@
 """`MulticoreTrainer` (semi_seg/trainers/features/multicore.py:10-35): `SemiTrainer` with the multi-prototype epochers;
-the criterion's own parameters join the optimizer as a further param group (empty for `MultiCoreKL`)."""
+the criterion's own parameters join the optimizer as a further param group (empty for `MultiCoreKL`; the translation
+matrix of the adaptive criteria).  Under `FusedRAdam` that group has flat buffers of its own: the matrix's gradient comes
+out of `SoftmaxMixKLFn.backward`, passes the softmax of the matrix in autograd and is accumulated in place into the
+group's flat gradient buffer, outside the HIP-graph replay of the network passes, which covers the model only.
+As in the reference the criterion is a non-trackable buffer of the trainer: the translation matrix is not part of the
+trainer's checkpoint."""
 from __future__ import annotations
 
 from typing import Type

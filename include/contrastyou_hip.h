@@ -598,6 +598,39 @@ int cy_group_dice_counts(const float* logits, const int64_t* target, int64_t* co
                          void* stream);
 
 /* ------------------------------------------------------------------------
+ * Adaptive over-segmented criteria: the K prototypes are mixed into C true classes by a dense matrix
+ * (csrc/cy_mix_loss.hip; entries added to ABI v15 -- no existing signature changed, so cy_abi_version() stays 15).
+ * Logits are [npix][K] f32 (NHWC), 1 <= K <= 64; labels int64 in [0, C), 1 <= C <= 16; `mix` is a dense [K][C] f32
+ * matrix, row-major, of arbitrary non-negative numbers (the criteria pass softmax(translation matrix, 1); it need not be
+ * row-stochastic).  With p = softmax(z), R_c = sum_k p_k mix[k][c] and P = npix:
+ *   loss       = (1/P) sum_pix -log((R_t + eps) / (1 + eps))
+ *   dlogits_k  = -(gscale[0]/P) * p_k * (mix[k][t] - R_t) / (R_t + eps)
+ *   dmix[k][c] = -(gscale[0]/P) * sum_{pix : t = c} p_k / (R_t + eps)
+ * (AdaptiveOverSegmentedLoss and its stricter variants, contrastyou/losses/multicore_loss.py:63-149.)
+ * Every entry checks its arguments before any launch: a NULL pointer (except `dmix`, and `ws` of the backward pass
+ * when dmix is NULL) or a count < 1 -> CY_ERR_ARG; K outside 1..64 or C outside 1..16 -> CY_ERR_SHAPE; a short
+ * workspace -> CY_ERR_WORKSPACE.  No floating-point atomics: every sum runs in a fixed order, two runs give the same
+ * bits.
+ * ------------------------------------------------------------------------ */
+/* Forward, two launches.  Workspace as cy_softmax_group_kl_ws_bytes: 8 * min(1024, ceil(npix / P)) bytes, P = 256 for
+ * K <= 16 and 16 above. */
+size_t cy_softmax_mix_kl_ws_bytes(long npix, int K);
+int cy_softmax_mix_kl_fwd(const float* logits, const int64_t* target, const float* mix, float* loss, long npix, int K,
+                          int C, float eps, void* ws, size_t ws_bytes, void* stream);
+/* Backward.  dmix == NULL: one launch, dlogits only, ws and ws_bytes are not looked at.  Otherwise two launches: every
+ * block leaves a [K][C] f32 partial in ws and a second launch sums the blocks;
+ * ws_bytes >= 4 * K * C * min(1024, ceil(npix / 16)) = cy_softmax_mix_kl_bwd_ws_bytes (0 for a count < 1).
+ * dlogits has the same bits with and without dmix. */
+size_t cy_softmax_mix_kl_bwd_ws_bytes(long npix, int K, int C);
+int cy_softmax_mix_kl_bwd(const float* logits, const int64_t* target, const float* mix, const float* gscale,
+                          float* dlogits, float* dmix, long npix, int K, int C, float eps, void* ws, size_t ws_bytes,
+                          void* stream);
+/* UniversalDice counts of the reduced arg-max: counts is int64 [N][C][2] = {intersection, union}; the predicted class is
+ * the first maximal c of sum_k exp(z_k - max z) * mix[k][c] (no division). */
+int cy_mix_dice_counts(const float* logits, const int64_t* target, const float* mix, int64_t* counts, int N, int HW,
+                       int K, int C, void* stream);
+
+/* ------------------------------------------------------------------------
  * Pixel-wise regularisers of the semi-supervised baselines (csrc/cy_pixel_reg.hip; entries added to ABI v15 -- no
  * existing signature changed, so cy_abi_version() stays 15).  Logits are [npix][K] f32 (NHWC), 2 <= K <= 16.  Every entry checks its arguments before any launch: a NULL pointer,
  * npix < 1 or K outside 2..16 -> CY_ERR_ARG; a short workspace -> CY_ERR_WORKSPACE.  Forward: two launches (one
