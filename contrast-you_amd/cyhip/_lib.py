@@ -290,6 +290,18 @@ _SIGS = {
     "cy_sinusoidal_emb": (c_int, [_P, _P, c_int, c_int, _P]),
     "cy_act_fwd": (c_int, [_P, _P, c_long, c_int, _P]),
     "cy_act_bwd": (c_int, [_P, _P, _P, c_long, c_int, _P]),
+    "cy_softmax_cat_fwd": (c_int, [_P, _P, _P, c_long, c_int, c_int, _P]),
+    "cy_softmax_cat_bwd": (c_int, [_P, _P, _P, c_long, c_int, c_int, _P]),
+    "cy_bn_rows_ws_bytes": (c_size_t, [c_long, c_int]),
+    "cy_bn_rows_stats": (c_int, [_P, _P, _P, c_long, c_int, _P, _P, _P, c_float, _P, c_size_t, _P]),
+    "cy_bn_lrelu_fwd": (c_int, [_P] * 6 + [c_long, c_int, c_float, c_float, _P]),
+    "cy_bn_lrelu_bwd_reduce": (c_int, [_P] * 8 + [c_long, c_int, c_float, c_float, _P, c_size_t, _P]),
+    "cy_bn_lrelu_bwd_apply": (c_int, [_P] * 9 + [c_long, c_int, c_float, c_float, c_int, _P]),
+    "cy_leaky_relu_fwd": (c_int, [_P, _P, c_long, c_float, _P]),
+    "cy_leaky_relu_bwd": (c_int, [_P, _P, _P, c_long, c_float, _P]),
+    "cy_sigmoid_bce_ws_bytes": (c_size_t, [c_long]),
+    "cy_sigmoid_bce_fwd": (c_int, [_P, c_float, _P, c_long, _P, c_size_t, _P]),
+    "cy_sigmoid_bce_bwd": (c_int, [_P, c_float, _P, _P, c_long, _P]),
 }
 
 # functions whose int return is a count / size, not a status

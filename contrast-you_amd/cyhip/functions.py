@@ -1259,3 +1259,118 @@ def edge_map(image: Tensor, power: float, size=None) -> Tensor:
         if size is not None and tuple(image.shape[-2:]) != tuple(size):
             image = bilinear_resize(image.detach(), (int(size[0]), int(size[1])))
         return ops.cc_edge_map(image, power)
+
+
+# --------------------------------------------------------------------------- adversarial baseline (csrc/cy_disc.hip)
+def _rows(x: Tensor) -> Tensor:
+    """[N, C, H, W] (any memory format) -> f32 [N, H, W, C] contiguous; no copy when the memory is NHWC f32 already"""
+    x = x.detach()
+    return ops.to_nhwc(x if x.dtype == torch.float32 else x.float()).permute(0, 2, 3, 1).contiguous()
+
+
+def _aligned16(t: Tensor) -> Tensor:
+    """f32, contiguous, 16-byte aligned (a parameter that is a view into a flat buffer need not be)"""
+    t = t.detach()
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        t = t.float().contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+class SoftmaxCatFn(torch.autograd.Function):
+    """torch.cat([image, logits.softmax(1)], 1), or logits.softmax(1) alone for image None
+    (semi_seg/epochers/comparable.py:150-153): one pass over the logits each way; the image carries no gradient"""
+
+    @staticmethod
+    def forward(ctx, image: Optional[Tensor], logits: Tensor):
+        ops.require_gpu(image, logits)
+        z = ops.to_nhwc(logits.detach().float())
+        img = None if image is None else ops.to_nhwc(image.detach().float())
+        if img is not None and (img.shape[0], *img.shape[2:]) != (z.shape[0], *z.shape[2:]):
+            raise ValueError(f"image {tuple(img.shape)} and logits {tuple(z.shape)} differ in batch or size")
+        ctx.save_for_backward(z)
+        ctx.ci = 0 if img is None else img.shape[1]
+        return ops.softmax_cat_fwd(img, z).permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, dout: Tensor):
+        z, = ctx.saved_tensors
+        return None, ops.softmax_cat_bwd(z, _rows(dout), ctx.ci)
+
+
+class BNLeakyReLUFn(torch.autograd.Function):
+    """nn.LeakyReLU(slope)(nn.BatchNorm2d(C)(x)) on an NHWC f32 map.  training: batch statistics, and the running
+    statistics / counter (when given) are updated in place by the statistics kernel; otherwise the running statistics
+    normalise.  The backward recomputes the pre-activation from x."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, gamma: Tensor, beta: Tensor, running_mean: Optional[Tensor],
+                running_var: Optional[Tensor], num_batches_tracked: Optional[Tensor], training: bool, momentum: float,
+                eps: float, slope: float):
+        ops.require_gpu(x, gamma, beta)
+        xr = _rows(x)
+        N, H, W, Cc = xr.shape
+        x2d = xr.view(N * H * W, Cc)
+        g, b = _aligned16(gamma), _aligned16(beta)
+        batch = training or running_mean is None
+        if batch:
+            track = training and running_mean is not None
+            mean, var = ops.bn_rows_stats(x2d, running_mean if track else None, running_var if track else None,
+                                          num_batches_tracked if track else None, momentum)
+        else:
+            mean, var = _aligned16(running_mean), _aligned16(running_var)
+        y = ops.bn_lrelu_fwd(x2d, mean, var, g, b, eps, slope)
+        ctx.save_for_backward(x2d, mean, var, g, b)
+        ctx.cfg = (float(eps), float(slope), batch, (N, H, W, Cc))
+        return y.view(N, H, W, Cc).permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, dy: Tensor):
+        x2d, mean, var, g, b = ctx.saved_tensors
+        eps, slope, batch, (N, H, W, Cc) = ctx.cfg
+        dy2d = _rows(dy).view(N * H * W, Cc)
+        need = ctx.needs_input_grad
+        # running statistics and no parameter gradient wanted: dx = gamma * invstd * dz needs no sums
+        dx, dg, db = ops.bn_lrelu_bwd(x2d, dy2d, mean, var, g, b, eps, slope, batch, need[0],
+                                      need_sums=batch or need[1] or need[2])
+        if dx is not None:
+            dx = dx.view(N, H, W, Cc).permute(0, 3, 1, 2)
+        return (dx, dg if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None,
+                None, None, None, None, None, None, None)
+
+
+class LeakyReLUFn(torch.autograd.Function):
+    """nn.LeakyReLU(slope) on an [N, C, H, W] map (kept NHWC f32); the backward works from the input"""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, slope: float):
+        ops.require_gpu(x)
+        xr = _rows(x)  # (the gradient arrives NHWC as well: one layout both ways)
+        ctx.save_for_backward(xr)
+        ctx.slope = float(slope)
+        return ops.leaky_relu_fwd(xr, slope).permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, dy: Tensor):
+        xr, = ctx.saved_tensors
+        return ops.leaky_relu_bwd(xr, _rows(dy), ctx.slope).permute(0, 3, 1, 2), None
+
+
+class SigmoidBCEFn(torch.autograd.Function):
+    """nn.BCELoss()(torch.sigmoid(scores), torch.full_like(scores, label)), label 0 or 1, from the scores: softplus of
+    -s / s, clamped at 100 as torch clamps the logarithm; never forms 1 - sigmoid(s)"""
+
+    @staticmethod
+    def forward(ctx, scores: Tensor, label: float):
+        ops.require_gpu(scores)
+        if label not in (0, 1, 0.0, 1.0):
+            raise ValueError(f"label must be 0 or 1, given {label!r}")
+        s = scores.detach().float().contiguous()
+        ctx.save_for_backward(s)
+        ctx.label, ctx.shape = float(label), scores.shape
+        return ops.sigmoid_bce_fwd(s, label)
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        s, = ctx.saved_tensors
+        gs = g.reshape(1).float().contiguous()
+        return ops.sigmoid_bce_bwd(s, ctx.label, gs).view(ctx.shape), None

@@ -2179,3 +2179,110 @@ def ccloss_bwd(I: Tensor, J: Tensor, gscale: Tensor, win: int, eps: float, need_
     _lib.call("cy_ccloss_bwd", I.data_ptr(), J.data_ptr(), gscale.data_ptr(), _ptr(dI), _ptr(dJ), N, H, W, win,
               float(eps), _stream())
     return dI, dJ
+
+
+# --------------------------------------------------------------------------- adversarial baseline (csrc/cy_disc.hip)
+def softmax_cat_fwd(image: Optional[Tensor], logits: Tensor) -> Tensor:
+    """image f32 [N, Ci, H, W] with NHWC memory (or None), logits f32 [N, K, H, W] with NHWC memory ->
+    rows [N, H, W, Ci + K] = (image, softmax(logits)); one launch"""
+    require_gpu(image, logits)
+    N, K, H, W = logits.shape
+    Ci = 0 if image is None else image.shape[1]
+    out = torch.empty((N, H, W, Ci + K), dtype=torch.float32, device=logits.device)
+    _lib.call("cy_softmax_cat_fwd", _ptr(image), logits.data_ptr(), out.data_ptr(), N * H * W, Ci, K, _stream())
+    return out
+
+
+def softmax_cat_bwd(logits: Tensor, dout: Tensor, Ci: int) -> Tensor:
+    """dout: rows [N, H, W, Ci + K] contiguous -> dlogits [N, K, H, W] with NHWC memory; one launch"""
+    N, K, H, W = logits.shape
+    d = empty_nhwc(N, K, H, W, torch.float32, logits.device)
+    _lib.call("cy_softmax_cat_bwd", logits.data_ptr(), dout.data_ptr(), d.data_ptr(), N * H * W, Ci, K, _stream())
+    return d
+
+
+def _bn_rows_ws(M: int, Cc: int, device):
+    nbytes = _lib.load().cy_bn_rows_ws_bytes(M, Cc)
+    return _ws(nbytes, device), nbytes
+
+
+def bn_rows_stats(x2d: Tensor, running_mean: Optional[Tensor] = None, running_var: Optional[Tensor] = None,
+                  num_batches_tracked: Optional[Tensor] = None, momentum: float = 0.1) -> Tuple[Tensor, Tensor]:
+    """x2d f32 [M, C] contiguous -> (mean [C], biased var [C]); updates the running statistics in place when given
+    (nn.BatchNorm2d's rule: unbiased variance, counter + 1); two launches"""
+    require_gpu(x2d)
+    M, Cc = x2d.shape
+    stats = _f32(2 * Cc + 8, x2d.device)
+    half = (Cc + 3) // 4 * 4  # keeps `var` 16-byte aligned
+    mean, var = stats[:Cc], stats[half:half + Cc]
+    ws, nbytes = _bn_rows_ws(M, Cc, x2d.device)
+    _lib.call("cy_bn_rows_stats", x2d.data_ptr(), mean.data_ptr(), var.data_ptr(), M, Cc, _ptr(running_mean),
+              _ptr(running_var), _ptr(num_batches_tracked), float(momentum), ws.data_ptr(), nbytes, _stream())
+    return mean, var
+
+
+def bn_lrelu_fwd(x2d: Tensor, mean: Tensor, var: Tensor, gamma: Tensor, beta: Tensor, eps: float,
+                 slope: float) -> Tensor:
+    require_gpu(x2d)
+    M, Cc = x2d.shape
+    y = torch.empty_like(x2d)
+    _lib.call("cy_bn_lrelu_fwd", x2d.data_ptr(), mean.data_ptr(), var.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+              y.data_ptr(), M, Cc, float(eps), float(slope), _stream())
+    return y
+
+
+def bn_lrelu_bwd(x2d: Tensor, dy2d: Tensor, mean: Tensor, var: Tensor, gamma: Tensor, beta: Tensor, eps: float,
+                 slope: float, batch_stats: bool, need_dx: bool = True, need_sums: bool = True):
+    """-> (dx [M, C] or None, dgamma [C], dbeta [C]); reduce (two launches) + apply (one launch).  `need_sums=False`
+    (running statistics, no parameter gradient wanted) skips the reduce and returns None for the two sums"""
+    M, Cc = x2d.shape
+    assert need_sums or not batch_stats, "the batch-statistics data gradient needs dgamma and dbeta"
+    dgamma = dbeta = None
+    if need_sums:
+        half = (Cc + 3) // 4 * 4
+        dgb = _f32(2 * Cc + 8, x2d.device)
+        dgamma, dbeta = dgb[:Cc], dgb[half:half + Cc]
+        ws, nbytes = _bn_rows_ws(M, Cc, x2d.device)
+        _lib.call("cy_bn_lrelu_bwd_reduce", x2d.data_ptr(), dy2d.data_ptr(), mean.data_ptr(), var.data_ptr(),
+                  gamma.data_ptr(), beta.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), M, Cc, float(eps),
+                  float(slope), ws.data_ptr(), nbytes, _stream())
+    dx = None
+    if need_dx:
+        dx = torch.empty_like(x2d)
+        _lib.call("cy_bn_lrelu_bwd_apply", x2d.data_ptr(), dy2d.data_ptr(), mean.data_ptr(), var.data_ptr(),
+                  gamma.data_ptr(), beta.data_ptr(), _ptr(dgamma), _ptr(dbeta), dx.data_ptr(), M, Cc,
+                  float(eps), float(slope), int(batch_stats), _stream())
+    return dx, dgamma, dbeta
+
+
+def leaky_relu_fwd(x: Tensor, slope: float) -> Tensor:
+    """x: f32, dense in memory (any dimension order) -> same layout"""
+    require_gpu(x)
+    y = torch.empty_like(x)
+    _lib.call("cy_leaky_relu_fwd", x.data_ptr(), y.data_ptr(), x.numel(), float(slope), _stream())
+    return y
+
+
+def leaky_relu_bwd(x: Tensor, dy: Tensor, slope: float) -> Tensor:
+    dx = torch.empty_like(x)
+    _lib.call("cy_leaky_relu_bwd", x.data_ptr(), dy.data_ptr(), dx.data_ptr(), x.numel(), float(slope), _stream())
+    return dx
+
+
+def sigmoid_bce_fwd(scores: Tensor, label: float) -> Tensor:
+    """scores: f32 contiguous, any shape -> scalar BCELoss()(sigmoid(scores), full(label)); two launches"""
+    require_gpu(scores)
+    n = scores.numel()
+    nbytes = _lib.load().cy_sigmoid_bce_ws_bytes(n)
+    ws = _ws(nbytes, scores.device)
+    loss = _f32(1, scores.device)
+    _lib.call("cy_sigmoid_bce_fwd", scores.data_ptr(), float(label), loss.data_ptr(), n, ws.data_ptr(), nbytes,
+              _stream())
+    return loss.view(())
+
+
+def sigmoid_bce_bwd(scores: Tensor, label: float, gscale: Tensor) -> Tensor:
+    d = torch.empty_like(scores)
+    _lib.call("cy_sigmoid_bce_bwd", scores.data_ptr(), float(label), gscale.data_ptr(), d.data_ptr(), scores.numel(),
+              _stream())
+    return d

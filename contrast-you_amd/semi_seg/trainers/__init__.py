@@ -3,7 +3,7 @@ epochers that are outside this build's hot-path scope and 
 from contrastyou.trainer.base import Trainer as _Trainer
 
 from .pretrain import PretrainDecoderTrainer, PretrainEncoderTrainer  # noqa: F401
-from .trainer import FineTuneTrainer, MTTrainer, SemiTrainer  # noqa: F401
+from .trainer import AdversarialTrainer, FineTuneTrainer, MTTrainer, SemiTrainer  # noqa: F401
 
 
 def _out_of_scope(name):

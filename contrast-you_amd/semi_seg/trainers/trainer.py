@@ -1,5 +1,5 @@
-"""`SemiTrainer`, `FineTuneTrainer`, `MTTrainer` (semi_seg/trainers/trainer.py:27-167, 199-204):
-which epocher runs a training epoch and how evaluation is wired (teacher model for mean teacher).
+"""`SemiTrainer`, `FineTuneTrainer`, `MTTrainer`, `AdversarialTrainer` (semi_seg/trainers/trainer.py:27-167, 199-204,
+215-260): which epocher runs a training epoch and how evaluation is wired (teacher model for mean teacher).
 """
 from __future__ import annotations
 
@@ -8,9 +8,14 @@ import os
 from pathlib import Path
 from typing import Any, Dict, Type
 
+import torch
 from torch import nn
 
-from contrastyou.trainer.base import Trainer
+from contrastyou import optim
+from contrastyou.arch.discriminator import Discriminator
+from contrastyou.trainer.base import _NOT_OPTIMIZER_ARGS, Trainer
+from contrastyou.utils.utils import fix_all_seed_within_context
+from semi_seg.epochers.comparable import AdversarialEpocher
 from semi_seg.epochers.epocher import (EpocherBase, EvalEpocher, FineTuneEpocher, InferenceEpocher,
                                        SemiSupervisedEpocher)
 from semi_seg.hooks import MeanTeacherTrainerHook
@@ -91,3 +96,52 @@ class MTTrainer(SemiTrainer):
         mt_hook = [h for h in self._hooks if isinstance(h, MeanTeacherTrainerHook)]
         assert len(mt_hook) == 1, mt_hook
         return super().eval_epoch(model=mt_hook[0].teacher_model, loader=loader, **kwargs)
+
+
+class AdversarialTrainer(SemiTrainer):
+    """adversarial training without hooks (trainer.py:215-260): a `Discriminator(input_dim, hidden_dim=64)` built under
+    the config's RandomSeed on [image,] softmax(logits), with an optimizer of its own from `config["Optim"]`.  The
+    discriminator (parameters and BatchNorm buffers, `module_state["_discriminator.*"]`) and its optimizer
+    (`other_state["_dis_optimizer"]`) are part of the checkpoint.
+
+    Single process only: two flat-buffer optimizers would both write the process-wide early-bucket switch
+    (`cyhip.ops.DP_EARLY`) from their own gradient volume in a data-parallel run."""
+    activate_hooks = False
+
+    def __init__(self, *, model: nn.Module, labeled_loader, unlabeled_loader, val_loader, test_loader, criterion,
+                 save_dir: str, max_epoch: int = 100, num_batches: int = 100, device="cpu", disable_bn: bool,
+                 two_stage: bool, config: Dict[str, Any], reg_weight: int, dis_consider_image: bool = False,
+                 **kwargs) -> None:
+        dist = torch.distributed
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError(
+                "AdversarialTrainer is single-process: its two FusedRAdam optimizers would both set cyhip.ops.DP_EARLY "
+                f"from their own gradient size (world size {dist.get_world_size()})")
+        super().__init__(model=model, labeled_loader=labeled_loader, unlabeled_loader=unlabeled_loader,
+                         val_loader=val_loader, test_loader=test_loader, criterion=criterion, save_dir=save_dir,
+                         max_epoch=max_epoch, num_batches=num_batches, device=device, disable_bn=disable_bn,
+                         two_stage=two_stage, config=config, **kwargs)
+        input_dim = self._model._input_dim + self._model.num_classes if dis_consider_image else self._model.num_classes
+        self._dis_consider_image = dis_consider_image
+        with fix_all_seed_within_context(self._config.get("RandomSeed", 10)):
+            self._discriminator = Discriminator(input_dim=input_dim, hidden_dim=64)
+        self._discriminator.to(self._device)
+        spec = self._config["Optim"]
+        self._dis_optimizer = getattr(optim, spec["name"])(
+            params=[p for p in self._discriminator.parameters() if p.requires_grad],
+            **{k: v for k, v in spec.items() if k not in _NOT_OPTIMIZER_ARGS})
+        self._reg_weight = float(reg_weight)
+
+    @property
+    def train_epocher(self) -> Type[EpocherBase]:
+        return AdversarialEpocher
+
+    def _create_initialized_tra_epoch(self, **kwargs) -> EpocherBase:
+        epocher = self.train_epocher(
+            model=self._model, optimizer=self._optimizer, labeled_loader=self._labeled_loader,
+            unlabeled_loader=self._unlabeled_loader, sup_criterion=self._criterion, num_batches=self._num_batches,
+            cur_epoch=self._cur_epoch, device=self._device, two_stage=self._two_stage, disable_bn=self._disable_bn,
+            discriminator=self._discriminator, disc_optimizer=self._dis_optimizer, reg_weight=self._reg_weight,
+            dis_consider_image=self._dis_consider_image, scaler=self.scaler)
+        epocher.init(trainer=self)
+        return epocher

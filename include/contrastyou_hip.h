@@ -881,6 +881,59 @@ int cy_sinusoidal_emb(const float* time, float* out, int B, int dim, void* strea
 int cy_act_fwd(const float* x, float* y, long n, int kind, void* stream);
 int cy_act_bwd(const float* x, const float* dy, float* dx, long n, int kind, void* stream);
 
+/* ------------------------------------------------------------------------
+ * The adversarial baseline's discriminator, everything around its convolutions (csrc/cy_disc.hip; 12 entries added to
+ * ABI v15 -- no existing signature changed, so cy_abi_version() stays 15).  f32, NHWC rows.  Every entry checks its
+ * arguments before any launch: a NULL pointer, a count < 1, K outside 2..16, Ci outside 0..4, C outside 1..1024, a
+ * label other than 0 or 1, or a row base that is not 16-byte aligned where rows are read 16 bytes at a time (K == 4,
+ * C % 4 == 0) -> CY_ERR_ARG; a short workspace -> CY_ERR_WORKSPACE.  No floating-point atomics: reductions write f64
+ * partials that a later launch sums in a fixed order, so two runs give the same bits.
+ * ------------------------------------------------------------------------ */
+/* torch.cat([image, logits.softmax(1)], 1) (semi_seg/epochers/comparable.py:150-153,172-182): out[p] =
+ * (image[p][0..Ci), softmax(logits[p][0..K))), rows of Ci + K floats.  Ci == 0 with image == NULL is the
+ * dis_consider_image=False form.  One launch. */
+int cy_softmax_cat_fwd(const float* image, const float* logits, float* out, long npix, int Ci, int K, void* stream);
+/* dlogits = p * (g - sum_k p_k g_k), g = the last K columns of dout's rows of Ci + K floats; the softmax is
+ * recomputed, the image columns carry no gradient.  One launch. */
+int cy_softmax_cat_bwd(const float* logits, const float* dout, float* dlogits, long npix, int Ci, int K,
+                       void* stream);
+/* nn.BatchNorm2d(C) in training mode followed by nn.LeakyReLU(slope) (contrastyou/arch/discriminator.py:26-35) over
+ * rows x[M][C], M = N*H*W.  ws_bytes = 16 * C * chunks, chunks = min(256, ceil(M / (8 * (256 / lpr)))), lpr = the
+ * smallest power of two >= C / V capped at 64, V = 4 when C % 4 == 0, else 1 (0 for M < 1 or a C out of range).
+ * cy_bn_rows_stats (two launches, M >= 2): mean[C] and the biased variance var[C]; the partial sums are f64 sums of
+ * x - x[0][c] and its square (exact differences; no E[x^2] - E[x]^2 cancellation).  With running_mean / running_var
+ * (both or neither) it also does running = (1 - momentum) * running + momentum * {mean, var * M / (M - 1)}, and with
+ * num_batches_tracked (int64) adds 1 to it. */
+size_t cy_bn_rows_ws_bytes(long M, int C);
+int cy_bn_rows_stats(const float* x, float* mean, float* var, long M, int C, float* running_mean, float* running_var,
+                     long long* num_batches_tracked, float momentum, void* ws, size_t ws_bytes, void* stream);
+/* y = lrelu(gamma * (x - mean) / sqrt(var + eps) + beta, slope); handed the running statistics it is the eval-mode
+ * layer.  One launch. */
+int cy_bn_lrelu_fwd(const float* x, const float* mean, const float* var, const float* gamma, const float* beta,
+                    float* y, long M, int C, float eps, float slope, void* stream);
+/* dz = dy * lrelu'(gamma * xhat + beta) with the pre-activation recomputed from x; dgamma = sum dz * xhat,
+ * dbeta = sum dz.  Two launches. */
+int cy_bn_lrelu_bwd_reduce(const float* x, const float* dy, const float* mean, const float* var, const float* gamma,
+                           const float* beta, float* dgamma, float* dbeta, long M, int C, float eps, float slope,
+                           void* ws, size_t ws_bytes, void* stream);
+/* batch_stats != 0: dx = gamma * invstd * (dz - dbeta / M - xhat * dgamma / M) (M >= 2); batch_stats == 0 (running
+ * statistics): dx = gamma * invstd * dz, dgamma / dbeta may be NULL.  One launch. */
+int cy_bn_lrelu_bwd_apply(const float* x, const float* dy, const float* mean, const float* var, const float* gamma,
+                          const float* beta, const float* dgamma, const float* dbeta, float* dx, long M, int C,
+                          float eps, float slope, int batch_stats, void* stream);
+/* nn.LeakyReLU(slope) without a BatchNorm in front (discriminator.py:23): y = x > 0 ? x : x * slope; the backward
+ * works from the input: dx = x > 0 ? dy : dy * slope.  One launch, two when n % 4 != 0. */
+int cy_leaky_relu_fwd(const float* x, float* y, long n, float slope, void* stream);
+int cy_leaky_relu_bwd(const float* x, const float* dy, float* dx, long n, float slope, void* stream);
+/* nn.BCELoss()(sigmoid(scores), full_like(scores, label)) (comparable.py:125,155-156,176-184) without forming
+ * 1 - sigmoid(s): mean over n of min(softplus(-s), 100) for label 1, of min(softplus(s), 100) for label 0 (torch clamps
+ * the logarithm at -100).  ws_bytes = 8 * min(1024, ceil(n / 256)).  Forward: two launches.  Backward (one launch):
+ * dscores = gscale[0] * (sigmoid(s) - label) / n, 0 where the forward was clamped. */
+size_t cy_sigmoid_bce_ws_bytes(long n);
+int cy_sigmoid_bce_fwd(const float* scores, float label, float* loss, long n, void* ws, size_t ws_bytes,
+                       void* stream);
+int cy_sigmoid_bce_bwd(const float* scores, float label, const float* gscale, float* dscores, long n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
