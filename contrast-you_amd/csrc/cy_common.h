@@ -25,6 +25,17 @@ typedef __attribute__((ext_vector_type(4))) short s16x4;
     if (e__ != hipSuccess) return CY_ERR_LAUNCH;            \
   } while (0)
 
+// raise the dynamic-LDS limit of the given kernels to `bytes`, once per process and call form (not per device: ADVICE.md);
+// false = the runtime refused (the caller returns CY_ERR_LAUNCH and the next call tries again)
+template <auto... Kernels>
+inline bool cy_lds_limit_once(int bytes) {
+  static bool done = false;
+  if (!done)
+    done = ((hipFuncSetAttribute(reinterpret_cast<const void*>(Kernels), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 bytes) == hipSuccess) && ...);
+  return done;
+}
+
 // ---- element traits -------------------------------------------------------
 template <typename T> struct ElemTr;
 template <> struct ElemTr<bf16> {

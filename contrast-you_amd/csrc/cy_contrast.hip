@@ -1035,13 +1035,7 @@ int cy_supcon_fused_fwd(const float* P, const int32_t* labels, const uint8_t* po
   hipLaunchKernelGGL(supcon_max_kernel, dim3(1), dim3(256), 0, st, diag, Mv, R);
   CY_CHECK_LAUNCH();
   const size_t smem = (size_t)2 * sc_block_floats(D) * sizeof(float);
-  static bool attr_done = false;
-  if (!attr_done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(supcon_fused_fwd_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 2 * sc_block_floats(256) * 4) != hipSuccess)
-      return CY_ERR_LAUNCH;
-    attr_done = true;
-  }
+  if (!cy_lds_limit_once<supcon_fused_fwd_kernel>(2 * sc_block_floats(256) * 4)) return CY_ERR_LAUNCH;
   hipLaunchKernelGGL(supcon_fused_fwd_kernel, dim3(rb, ns), dim3(256), smem, st, P, labels, pos_mask, Mv, part,
                      n, D, 1.f / t, ns);
   CY_CHECK_LAUNCH();
@@ -1060,14 +1054,7 @@ int cy_supcon_fused_bwd(const float* P, const int32_t* labels, const uint8_t* po
   const int R = 2 * n, ns = sc_nsplit(R), rb = cy_cdiv(R, SC_TM);
   float* dpart = (float*)ws + R + 4;
   const size_t smem = ((size_t)2 * sc_block_floats(D) + SC_TM * (SC_TM + 1) + SC_TM * 2) * sizeof(float);
-  static bool attr_done = false;
-  if (!attr_done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(supcon_fused_bwd_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (2 * sc_block_floats(256) + SC_TM * (SC_TM + 1) + SC_TM * 2) * 4) != hipSuccess)
-      return CY_ERR_LAUNCH;
-    attr_done = true;
-  }
+  if (!cy_lds_limit_once<supcon_fused_bwd_kernel>((2 * sc_block_floats(256) + SC_TM * (SC_TM + 1) + SC_TM * 2) * 4)) return CY_ERR_LAUNCH;
   hipLaunchKernelGGL(supcon_fused_bwd_kernel, dim3(rb, ns), dim3(256), smem, st, P, labels, pos_mask, row_stats,
                      gscale, dpart, n, D, 1.f / t, ns);
   CY_CHECK_LAUNCH();

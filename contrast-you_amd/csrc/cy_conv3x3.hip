@@ -462,14 +462,8 @@ __global__ void __launch_bounds__(256)
 template <typename T, typename TO, int TH, int TW, int BN, int WGM, int WGN, int PITCHB, bool ALLT>
 int launch_conv(ConvArgs a, hipStream_t st) {
   using C = ConvCfg<T, TO, TH, TW, BN, WGM, WGN, PITCHB, ALLT>;
-  auto kern = conv3x3_igemm_kernel<T, TO, TH, TW, BN, WGM, WGN, PITCHB, ALLT>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM) != hipSuccess)
-      return CY_ERR_LAUNCH;
-    attr_done = true;
-  }
+  constexpr auto kern = conv3x3_igemm_kernel<T, TO, TH, TW, BN, WGM, WGN, PITCHB, ALLT>;
+  if (!cy_lds_limit_once<kern>(C::SMEM)) return CY_ERR_LAUNCH;
   const int tiles_h = cy_cdiv(a.NH, TH);
   a.tiles_w = cy_cdiv(a.W, TW);
   a.full_tiles = (a.NH % TH == 0) && (a.W % TW == 0);
@@ -511,20 +505,14 @@ TileChoice choose_tile(long NH, int W, int Cout) {
 
 // The plane kernel (cy_conv_plane.h) tiles the image in 16 x 14 outputs.  CY_CONV_PLANE=0 keeps
 // every layer on conv3x3_igemm_kernel (A/B measurements).
-bool use_plane_kernel(int W) {
-  static const bool enabled = [] {
-    const char* e = getenv("CY_CONV_PLANE");
-    return !(e && e[0] == '0');
-  }();
-  return enabled && W % 14 == 0;
-}
+bool use_plane_kernel(int W) { return cy_switches().conv_plane && W % 14 == 0; }
 constexpr int kPlaneTH = 16, kPlaneTW = 14;
+int plane_tiles(const cy_conv_desc* d) { return cy_cdiv((long)d->N * d->H, kPlaneTH) * (d->W / kPlaneTW); }
 
 struct ConvPlan {
-  bool plane;
-  bool stream;      // plane, 16-bit storage, Cin / Cout in {32, 64}, no load transform: persistent streaming kernel (cy_conv_stream.h)
+  int kernel;       // CY_CONV_KERNEL_*: igemm (this file), plane (cy_conv_plane.h), stream: persistent streaming kernel
+                    // (cy_conv_stream.h), flow: eight-wave LDS-DMA kernel (cy_conv_flow.h), tile.th x tile.tw x tile.bn
   bool one_per_cu;  // plane, 128 couts: at most one workgroup per CU, halo prefetch in registers
-  bool flow;        // eight-wave LDS-DMA kernel (cy_conv_flow.h): one workgroup per CU, tile.th x tile.tw x tile.bn
   TileChoice tile;
   int ksplit;         // >1: split-K over input-channel chunks + finish kernel
   int finish_blocks;  // blocks (= stat partials) of the finish kernel
@@ -532,134 +520,143 @@ struct ConvPlan {
   size_t ws_bytes;
 };
 
-// Deep layers (14x14 / 28x28 at small batch) have too few output tiles to fill 256 CUs: split
-// the reduction over input-channel chunks across blockIdx.z.
-ConvPlan plan_conv(int N, int H, int W, int Cin, int Cout, int elem_bytes, bool stream_ok = false,
-                   bool prologue = false, FlowChoice fc = FlowChoice{false, 0, 0, 0, false}, bool bwd_pro = false) {
+// what every family's plan ends with: `partials` BN partials without split-K, those of the finish kernel with it
+ConvPlan make_plan(const cy_conv_desc* d, int kernel, TileChoice tile, int Z, int partials, bool one_per_cu = false) {
+  const long npix = (long)d->N * d->H * d->W;
   ConvPlan p;
-  p.plane = use_plane_kernel(W);
-  p.stream = false;
-  p.flow = false;
-  static const int stream_mode = [] {
-    const char* e = getenv("CY_STREAM");
-    return e ? atoi(e) : 1;
-  }();
+  p.kernel = kernel, p.tile = tile, p.one_per_cu = one_per_cu;
+  p.ksplit = Z;
+  long fb = (npix + 15) / 16;  // split-K layers are small (<= 12.5k pixels): many short workgroups
+  if (fb > 1024) fb = 1024;
+  p.finish_blocks = (int)fb;
+  p.partials = Z > 1 ? p.finish_blocks : partials;
+  p.ws_bytes = Z > 1 ? (size_t)Z * npix * d->Cout * sizeof(float) : 0;
+  return p;
+}
+
+// ---- streaming kernel: plane tiles, 16-bit storage, Cin / Cout in {32, 64}, no load transform
+bool plan_stream(const cy_conv_desc* d, ConvPlan* p) {
+  const int mode = cy_switches().stream, Cin = d->C1 + d->C2;
+  if (!use_plane_kernel(d->W) || !stream_applicable(d) || !mode) return false;
   // (persistent pipeline: worth it from ~4 tiles per workgroup on -- the 224x224 level at any batch size here)
   // (CY_STREAM=2: no tile-count threshold, for experiments)
   // (32 -> 64 at 112 x 112, N = 32 -- Conv2a reading the pooled tensor: 1792 tiles, 34 us against 43 plane / 38 flow)
-  const long stream_min_tiles = (Cin == 32 && Cout == 64) ? 1700 : 2048;
-  if (p.plane && stream_ok && stream_mode &&
-      (stream_mode == 2 || cy_cdiv((long)N * H, kPlaneTH) * (W / kPlaneTW) >= stream_min_tiles)) {
-    p.stream = true;
-    p.one_per_cu = false;
-    p.tile.th = kPlaneTH, p.tile.tw = kPlaneTW, p.tile.bn = Cout;
-    p.ksplit = 1;
-    p.finish_blocks = 0;
-    p.partials = stream_partials(Cin, Cout, cy_cdiv((long)N * H, kPlaneTH) * (W / kPlaneTW), prologue);
-    p.ws_bytes = 0;
-    return p;
-  }
-  static const int flow_mode = [] {
-    const char* e = getenv("CY_FLOW");
-    return e ? atoi(e) : 1;
-  }();
-  if (fc.ok && flow_mode) {
-    static const int flow_cfg = [] {  // experiments: 1 = always the big tile, 2 = the 16-row tile wherever it exists
-      const char* e = getenv("CY_FLOW_CFG");
-      return e ? atoi(e) : 0;
-    }();
-    const long npixf = (long)N * H * W;
-    const int nccf = Cin / 16;
-    // One workgroup per CU, all of them in step (load the first chunk, compute, store): the kernel pays off where
-    // one or two full rounds of workgroups cover the layer and the K loop is long enough to amortise the two
-    // ends.  Rules from per-layer A/B runs against the plane kernel on one box (tools/flow_sweep.sh,
-    // DESIGN.md section 3 "Flow kernel"); everything else stays on the plane kernel.
-    int th = fc.th, bn = fc.bn, Z = 1;
-    const int tiles_big = cy_cdiv((long)N * H, th) * (W / fc.tw);
-    const int blocks_big = tiles_big * (Cout / bn);
-    auto fills = [](int blocks) {  // share of the CU-rounds a grid occupies
-      const int rounds = (blocks + 255) / 256;
-      return (double)blocks / (256.0 * rounds);
-    };
-    bool use = false;
-    // more than a round of four-wave workgroups of 128 positions x 64 couts per wave (32 rows x 64 couts, two per CU:
-    // the big tile's LDS traffic per MFMA, and each other's load / store phases covered): where a launch is several
-    // rounds of work anyway this beats the one-per-CU tiles (N = 32: 64 -> 64 at 112 x 112 65 (plane) -> 57 us,
-    // 128 -> 256 at 56 x 56 data gradient 66 -> 62) -- below that the one-per-CU tiles stay better (Conv3b 41 vs 45)
-    const long n3264 = cy_cdiv((long)N * H, 32) * (W / fc.tw) * (Cout / 64);
-    constexpr int th3264 = 512;  // (a round of them on 256 CUs at two per CU: swept with tools/flow_sweep.sh)
-    // (not with the backward prologue: its extra halo buffer leaves room for one such workgroup per CU only)
-    if (flow_cfg == 0 && n3264 >= th3264 && !(prologue && Cin > 256) && !bwd_pro) {
-      use = true, th = 32, bn = 64;
-    } else if (flow_cfg == 1) {
-      use = true;
-    } else if (bn == 64) {
-      use = blocks_big >= 160 && (blocks_big <= 256 || (nccf >= 8 && fills(blocks_big) >= 0.75));
-      // too few 64-row tiles for the chip (56 x 56, 128 -> 64: 56 of them at N = 16): four-wave workgroups on
-      // 16 rows x 64 couts, two per CU (Conv3a data gradient 18 -> 14 us)
-      const int n64 = cy_cdiv((long)N * H, 16) * (W / fc.tw) * (Cout / 64);
-      if (!use && blocks_big < 160 && n64 >= 192 && !(prologue && Cin > 256)) use = true, th = 16;
+  const long stream_min_tiles = (Cin == 32 && d->Cout == 64) ? 1700 : 2048;
+  const int tiles = plane_tiles(d);
+  if (mode != 2 && tiles < stream_min_tiles) return false;
+  *p = make_plan(d, CY_CONV_KERNEL_STREAM, {kPlaneTH, kPlaneTW, d->Cout}, 1, stream_partials(Cin, d->Cout, tiles, d->prologue != 0));
+  return true;
+}
+
+// ---- flow kernel
+struct FlowPick {
+  bool use;
+  int th, bn, Z;
+};
+
+// One workgroup per CU, all of them in step (load the first chunk, compute, store): the kernel pays off where
+// one or two full rounds of workgroups cover the layer and the K loop is long enough to amortise the two
+// ends.  Rules from per-layer A/B runs against the plane kernel on one box (tools/flow_sweep.sh,
+// DESIGN.md section 3 "Flow kernel"); everything else stays on the plane kernel.
+// (`rounds_of_3264`: the first branch is on -- off under every CY_FLOW_CFG experiment)
+FlowPick flow_auto_rule(const cy_conv_desc* d, const FlowChoice& fc, bool rounds_of_3264) {
+  const long NH = (long)d->N * d->H;
+  const int Cout = d->Cout, nccf = (d->C1 + d->C2) / 16, tiles_w = d->W / fc.tw;
+  const bool prologue = d->prologue != 0;
+  FlowPick k = {false, fc.th, fc.bn, 1};
+  const int blocks_big = cy_cdiv(NH, k.th) * tiles_w * (Cout / k.bn);
+  auto fills = [](int blocks) {  // share of the CU-rounds a grid occupies
+    const int rounds = (blocks + 255) / 256;
+    return (double)blocks / (256.0 * rounds);
+  };
+  // more than a round of four-wave workgroups of 128 positions x 64 couts per wave (32 rows x 64 couts, two per CU:
+  // the big tile's LDS traffic per MFMA, and each other's load / store phases covered): where a launch is several
+  // rounds of work anyway this beats the one-per-CU tiles (N = 32: 64 -> 64 at 112 x 112 65 (plane) -> 57 us,
+  // 128 -> 256 at 56 x 56 data gradient 66 -> 62) -- below that the one-per-CU tiles stay better (Conv3b 41 vs 45)
+  const long n3264 = cy_cdiv(NH, 32) * tiles_w * (Cout / 64);
+  constexpr int th3264 = 512;  // (a round of them on 256 CUs at two per CU: swept with tools/flow_sweep.sh)
+  // (not with the backward prologue: its extra halo buffer leaves room for one such workgroup per CU only)
+  if (rounds_of_3264 && n3264 >= th3264 && flow_tiling_takes(32, 64, prologue, d->C1) && d->prologue != 2) return {true, 32, 64, 1};
+  if (k.bn == 64) {
+    k.use = blocks_big >= 160 && (blocks_big <= 256 || (nccf >= 8 && fills(blocks_big) >= 0.75));
+    // too few 64-row tiles for the chip (56 x 56, 128 -> 64: 56 of them at N = 16): four-wave workgroups on
+    // 16 rows x 64 couts, two per CU (Conv3a data gradient 18 -> 14 us)
+    const int n64 = cy_cdiv(NH, 16) * tiles_w * (Cout / 64);
+    if (!k.use && blocks_big < 160 && n64 >= 192 && flow_tiling_takes(16, 64, prologue, d->C1)) k.use = true, k.th = 16;
+  } else if (blocks_big >= 192 && (blocks_big <= 256 || (nccf >= 8 && fills(blocks_big) >= 0.85))) {
+    k.use = true;
+  } else if (fc.small_ok && blocks_big < 192) {
+    k.th = 16;
+    const int blocks_small = cy_cdiv(NH, k.th) * tiles_w * (Cout / k.bn);
+    const int n64 = 2 * blocks_small;  // workgroups of the four-wave 16 x 64 tiling (two per CU)
+    if (blocks_small >= 192) {
+      k.use = blocks_small <= 256 || (nccf >= 8 && fills(blocks_small) >= 0.85);
+    } else if (flow_tiling_takes(16, 64, prologue, d->C1) && (n64 >= 192 || (n64 >= 96 && nccf < 32))) {
+      // too few 16 x 128 tiles for the chip: the same wave tile (64 positions x 64 couts) in four-wave
+      // workgroups of 64 couts -- twice the workgroups, two per CU, each other's load / store phases covered
+      // (28 x 28 at N = 16: 256 -> 256 data gradient 28 -> 22 us, 128 -> 256 forward 20 -> 16; 14 x 14, 256 ->
+      // 512 forward 28 (split-K 4) -> 21); with a long K loop and still few workgroups split-K stays better
+      // (14 x 14, 512 -> 512 data gradient: 32 against 36)
+      k.bn = 64;
+      k.use = true;
     } else {
-      if (blocks_big >= 192 && (blocks_big <= 256 || (nccf >= 8 && fills(blocks_big) >= 0.85))) {
-        use = true;
-      } else if (fc.small_ok && blocks_big < 192) {
-        th = 16;
-        const int blocks_small = cy_cdiv((long)N * H, th) * (W / fc.tw) * (Cout / bn);
-        const int n64 = 2 * blocks_small;  // workgroups of the four-wave 16 x 64 tiling (two per CU)
-        if (blocks_small >= 192) {
-          use = blocks_small <= 256 || (nccf >= 8 && fills(blocks_small) >= 0.85);
-        } else if (!(prologue && Cin > 256) && (n64 >= 192 || (n64 >= 96 && nccf < 32))) {
-          // too few 16 x 128 tiles for the chip: the same wave tile (64 positions x 64 couts) in four-wave
-          // workgroups of 64 couts -- twice the workgroups, two per CU, each other's load / store phases covered
-          // (28 x 28 at N = 16: 256 -> 256 data gradient 28 -> 22 us, 128 -> 256 forward 20 -> 16; 14 x 14, 256 ->
-          // 512 forward 28 (split-K 4) -> 21); with a long K loop and still few workgroups split-K stays better
-          // (14 x 14, 512 -> 512 data gradient: 32 against 36)
-          bn = 64;
-          use = true;
-        } else {
-          // too few tiles for the chip: split-K over >= 4 chunks each only where the f32 partial slabs are shared
-          // by many cout blocks and the K loop is long (28x28 at N=16, 256 -> 256: 112 workgroups without a
-          // split take 33 us, 224 with one 36); otherwise the tiles there are run as they are
-          if (Cout >= 256 && (blocks_small < 96 || nccf >= 32)) {
-            Z = (232 + blocks_small / 2) / blocks_small;
-            if (Z > nccf / 4) Z = nccf / 4;
-            if (Z > 8) Z = 8;
-            if (Z < 1) Z = 1;
-          }
-          use = blocks_small * Z >= 48;
-        }
+      // too few tiles for the chip: split-K over >= 4 chunks each only where the f32 partial slabs are shared
+      // by many cout blocks and the K loop is long (28x28 at N=16, 256 -> 256: 112 workgroups without a
+      // split take 33 us, 224 with one 36); otherwise the tiles there are run as they are
+      if (Cout >= 256 && (blocks_small < 96 || nccf >= 32)) {
+        k.Z = (232 + blocks_small / 2) / blocks_small;
+        if (k.Z > nccf / 4) k.Z = nccf / 4;
+        if (k.Z > 8) k.Z = 8;
+        if (k.Z < 1) k.Z = 1;
       }
-    }
-    if (flow_cfg == 2 && fc.small_ok) use = true, th = 16, Z = 1;
-    if (flow_cfg == 3 && !(prologue && Cin > 256)) use = true, th = 16, bn = 64, Z = 1;  // (experiment: 4-wave 16 x 64 tiles)
-    if (flow_cfg == 4 && !(prologue && Cin > 256) && !bwd_pro) use = true, th = 32, bn = 64, Z = 1;  // (experiment: 4-wave 32 x 64 tiles)
-    if (use) {
-    p.flow = true;
-    p.plane = false;
-    p.one_per_cu = false;
-    p.tile.th = th, p.tile.tw = fc.tw, p.tile.bn = bn;
-    p.ksplit = Z;
-    long fb = (npixf + 15) / 16;
-    if (fb > 1024) fb = 1024;
-    p.finish_blocks = (int)fb;
-    p.partials = Z > 1 ? p.finish_blocks : cy_cdiv((long)N * H, th) * (W / fc.tw);
-    p.ws_bytes = Z > 1 ? (size_t)Z * npixf * Cout * sizeof(float) : 0;
-    return p;
+      k.use = blocks_small * k.Z >= 48;
     }
   }
-  p.tile = choose_tile((long)N * H, W, Cout);
-  const long npix = (long)N * H * W;
-  if (p.plane) {
-    p.tile.th = kPlaneTH, p.tile.tw = kPlaneTW;
-    p.tile.bn = Cout >= 128 ? 128 : (Cout > 32 ? 64 : 32);
+  return k;
+}
+
+// the rule, or what CY_FLOW_CFG puts in its place (experiments): 1 = always the big tile, 2 = the 16-row tile wherever it
+// exists, 3 / 4 = the four-wave 16 x 64 / 32 x 64 tiles wherever they apply; 2..4 leave the rule (less its first branch)
+// in charge of the layers their tiling does not take
+FlowPick flow_apply_cfg(const cy_conv_desc* d, const FlowChoice& fc) {
+  const int cfg = cy_switches().flow_cfg;
+  const bool prologue = d->prologue != 0;
+  if (cfg == 1) return {true, fc.th, fc.bn, 1};
+  FlowPick k = flow_auto_rule(d, fc, cfg == 0);
+  if (cfg == 2 && fc.small_ok) k.use = true, k.th = 16, k.Z = 1;
+  if (cfg == 3 && flow_tiling_takes(16, 64, prologue, d->C1)) k = {true, 16, 64, 1};
+  if (cfg == 4 && flow_tiling_takes(32, 64, prologue, d->C1) && d->prologue != 2) k = {true, 32, 64, 1};
+  return k;
+}
+
+bool plan_flow(const cy_conv_desc* d, ConvPlan* p) {
+  const FlowChoice fc = flow_choice(d);
+  if (!fc.ok || !cy_switches().flow) return false;
+  const FlowPick k = flow_apply_cfg(d, fc);
+  if (!k.use) return false;
+  *p = make_plan(d, CY_CONV_KERNEL_FLOW, {k.th, fc.tw, k.bn}, k.Z, cy_cdiv((long)d->N * d->H, k.th) * (d->W / fc.tw));
+  return true;
+}
+
+// ---- plane kernel where the width is a multiple of 14 (and CY_CONV_PLANE allows), the igemm kernel's tiles otherwise.
+// Deep layers (14x14 / 28x28 at small batch) have too few output tiles to fill 256 CUs: split
+// the reduction over input-channel chunks across blockIdx.z.
+ConvPlan plan_tiled(const cy_conv_desc* d) {
+  const long NH = (long)d->N * d->H;
+  const int Cin = d->C1 + d->C2, Cout = d->Cout;
+  const bool plane = use_plane_kernel(d->W);
+  TileChoice tile = choose_tile(NH, d->W, Cout);
+  if (plane) tile.th = kPlaneTH, tile.tw = kPlaneTW;
+  const int tiles = cy_cdiv(NH, tile.th) * cy_cdiv(d->W, tile.tw);
+  if (plane) {
+    tile.bn = Cout >= 128 ? 128 : (Cout > 32 ? 64 : 32);
     // 128-cout layers with fewer tiles than CUs (56x56 at N=16: 224 tiles): two 64-cout workgroups
     // per tile instead of one (10-13 % faster there, 10-50 % slower at 448 tiles)
     constexpr int bn64_below = 300;
-    if (Cout == 128 && cy_cdiv((long)N * H, kPlaneTH) * (W / kPlaneTW) < bn64_below) p.tile.bn = 64;
+    if (Cout == 128 && tiles < bn64_below) tile.bn = 64;
   }
-  const int tiles = cy_cdiv((long)N * H, p.tile.th) * cy_cdiv(W, p.tile.tw);
-  const int blocks = tiles * cy_cdiv(Cout, p.tile.bn);
-  const int kc = (p.tile.bn <= 64 ? 64 : 128) / elem_bytes;  // must match dispatch_conv's PITCHB
+  const int blocks = tiles * cy_cdiv(Cout, tile.bn);
+  const int kc = (tile.bn <= 64 ? 64 : 128) / (d->in_dtype == CY_F32 ? 4 : 2);  // must match dispatch_conv's PITCHB
   const int ncc = cy_cdiv(Cin, kc);
   int Z = 1;
   if (blocks < 192 && ncc >= 2 && Cout % 8 == 0) {
@@ -667,25 +664,21 @@ ConvPlan plan_conv(int N, int H, int W, int Cin, int Cout, int elem_bytes, bool 
     if (Z > ncc) Z = ncc;
     if (Z > 8) Z = 8;
   }
-  p.one_per_cu = false;
-  if (p.plane && p.tile.bn == 128) {
-    if (ncc >= 2) {  // aim at 192..288 workgroups, each with >= 2 chunks to pipeline
-      int z1 = blocks >= 256 ? 1 : 256 / blocks;
-      if (z1 > ncc / 2) z1 = ncc / 2;
-      if (z1 < 1) z1 = 1;
-      if (blocks * z1 >= 192 && blocks * z1 <= 288 && Cout % 8 == 0) {
-        p.one_per_cu = true;
-        Z = z1;
-      }
-    }
+  bool one_per_cu = false;
+  if (plane && tile.bn == 128 && ncc >= 2) {  // aim at 192..288 workgroups, each with >= 2 chunks to pipeline
+    int z1 = blocks >= 256 ? 1 : 256 / blocks;
+    if (z1 > ncc / 2) z1 = ncc / 2;
+    if (z1 < 1) z1 = 1;
+    if (blocks * z1 >= 192 && blocks * z1 <= 288 && Cout % 8 == 0) one_per_cu = true, Z = z1;
   }
-  p.ksplit = Z;
-  long fb = (npix + 15) / 16;  // split-K layers are small (<= 12.5k pixels): many short workgroups
-  if (fb > 1024) fb = 1024;
-  p.finish_blocks = (int)fb;
-  p.partials = Z > 1 ? p.finish_blocks : tiles;
-  p.ws_bytes = Z > 1 ? (size_t)Z * npix * Cout * sizeof(float) : 0;
-  return p;
+  return make_plan(d, plane ? CY_CONV_KERNEL_PLANE : CY_CONV_KERNEL_IGEMM, tile, Z, tiles, one_per_cu);
+}
+
+// the launch plan of a checked descriptor: the first family whose rule takes the layer
+ConvPlan plan_conv(const cy_conv_desc* d) {
+  ConvPlan p;
+  if (plan_stream(d, &p) || plan_flow(d, &p)) return p;
+  return plan_tiled(d);
 }
 
 template <typename TO>
@@ -703,15 +696,15 @@ int launch_finish(const ConvArgs& a, const ConvPlan& p, hipStream_t st) {
 
 template <typename T>
 int dispatch_conv(const ConvArgs& a, const ConvPlan& p, hipStream_t st) {
-  if (p.stream) {
+  if (p.kernel == CY_CONV_KERNEL_STREAM) {
     if constexpr (sizeof(T) == 2) return dispatch_conv_stream<T>(a, st);
     return CY_ERR_DTYPE;
   }
-  if (p.flow) {
+  if (p.kernel == CY_CONV_KERNEL_FLOW) {
     if constexpr (sizeof(T) == 2) return dispatch_conv_flow<T>(a, p.tile.th, p.tile.bn, p.tile.tw, st);
     return CY_ERR_DTYPE;
   }
-  if (p.plane) {
+  if (p.kernel == CY_CONV_KERNEL_PLANE) {
     if (p.tile.bn == 128)
       return p.one_per_cu ? launch_conv_plane<T, kPlaneTH, 128, 2, 2, 128, false, true>(a, st)
                           : launch_conv_plane<T, kPlaneTH, 128, 2, 2, 128, false, false>(a, st);
@@ -1250,22 +1243,17 @@ static int conv_check(const cy_conv_desc* d) {
   return CY_OK;
 }
 
-static ConvPlan plan_of(const cy_conv_desc* d) {
-  return plan_conv(d->N, d->H, d->W, d->C1 + d->C2, d->Cout, d->in_dtype == CY_F32 ? 4 : 2, stream_applicable(d), d->prologue != 0,
-                   flow_choice(d), d->prologue == 2);
-}
-
 int cy_conv3x3_num_partials(const cy_conv_desc* d) {
   if (conv_check(d) != CY_OK) return CY_ERR_ARG;
-  return plan_of(d).partials;
+  return plan_conv(d).partials;
 }
 
 int cy_conv3x3_plan(const cy_conv_desc* d, cy_conv_plan* plan) {
   const int rc = conv_check(d);
   if (rc != CY_OK) return rc;
   if (!plan) return CY_ERR_ARG;
-  const ConvPlan p = plan_of(d);
-  plan->kernel = p.flow ? 5 : (p.stream ? 4 : (p.plane ? 1 : 0));
+  const ConvPlan p = plan_conv(d);
+  plan->kernel = p.kernel;
   plan->th = p.tile.th, plan->tw = p.tile.tw, plan->bn = p.tile.bn;
   plan->ksplit = p.ksplit, plan->one_per_cu = p.one_per_cu ? 1 : 0, plan->partials = p.partials;
   plan->workgroups = cy_cdiv((long)d->N * d->H, p.tile.th) * cy_cdiv(d->W, p.tile.tw) *
@@ -1275,18 +1263,18 @@ int cy_conv3x3_plan(const cy_conv_desc* d, cy_conv_plan* plan) {
 
 size_t cy_conv3x3_fwd_ws_bytes(const cy_conv_desc* d) {
   if (conv_check(d) != CY_OK) return 0;
-  return plan_of(d).ws_bytes;
+  return plan_conv(d).ws_bytes;
 }
 
 // workgroups that add into one channel's sums (the streaming kernel sums its wave rows in LDS first)
 static int stat_workgroups_of(const cy_conv_desc* d, const ConvPlan& p) {
-  if (p.stream) return stream_grid(d->C1 + d->C2, d->Cout, cy_cdiv((long)d->N * d->H, kPlaneTH) * (d->W / kPlaneTW), d->prologue != 0);
+  if (p.kernel == CY_CONV_KERNEL_STREAM) return stream_grid(d->C1 + d->C2, d->Cout, plane_tiles(d), d->prologue != 0);
   return p.partials;
 }
 
 int cy_conv3x3_stat_workgroups(const cy_conv_desc* d) {
   if (conv_check(d) != CY_OK) return CY_ERR_ARG;
-  return stat_workgroups_of(d, plan_of(d));
+  return stat_workgroups_of(d, plan_conv(d));
 }
 
 int cy_bn_acc_replicas(int C, int workgroups) { return (C <= 0 || workgroups <= 0) ? CY_ERR_ARG : bn_acc_replicas(C, workgroups); }
@@ -1313,20 +1301,19 @@ int cy_conv3x3_fwd_bn(const cy_conv_desc* d, const void* src1, const void* src2,
 // the data gradient with the BatchNorm + ReLU backward in its load path: only the flow kernel's tilings that have room
 // for the y buffer take it
 static bool dgrad_bn_plan_ok(const cy_conv_desc* d, const ConvPlan& p) {
-  if (!p.flow || d->in_dtype == CY_F32 || d->C1 > 512) return false;
-  if (p.tile.bn == 64 && p.tile.th <= 32 && d->C1 > 256) return false;  // four-wave tilings: one coefficient set per thread
+  if (p.kernel != CY_CONV_KERNEL_FLOW || d->in_dtype == CY_F32 || d->C1 > 512) return false;
+  if (!flow_tiling_takes(p.tile.th, p.tile.bn, true, d->C1)) return false;
   // Every cout block of a tile (and every tile, for its halo) repeats the in-LDS pass over (dA, y): with 64-cout tiles a
   // 256-channel data gradient does it four times over, and the fused launch is slower than the two it replaces (28 x 28,
   // 256 -> 256 at N = 16: 46.8 against 12.5 + 21.3 us; tools/bench_dgrad_bn.py).  It pays on the 128-cout tilings
   // (56 x 56, 128 -> 128: 32.8 against 17.3 + 20.5).  CY_DGRAD_BN_ALL=1 lifts the rule (measurements).
-  static const int all = [] { const char* e = getenv("CY_DGRAD_BN_ALL"); return e ? atoi(e) : 0; }();
-  if (!all && p.tile.bn != 128) return false;
+  if (!cy_switches().dgrad_bn_all && p.tile.bn != 128) return false;
   return d->in_dtype == CY_BF16 ? flow_bwd_ok<bf16>(p.tile.th, p.tile.bn, p.tile.tw) : flow_bwd_ok<f16>(p.tile.th, p.tile.bn, p.tile.tw);
 }
 
 int cy_conv3x3_dgrad_bn_ok(const cy_conv_desc* d) {
   if (conv_check(d) != CY_OK || d->prologue != 2 || d->C2) return 0;
-  return dgrad_bn_plan_ok(d, plan_of(d)) ? 1 : 0;
+  return dgrad_bn_plan_ok(d, plan_conv(d)) ? 1 : 0;
 }
 
 int cy_conv3x3_dgrad_bn(const cy_conv_desc* d, const void* dA, const cy_bn_bwd_in* bn, const void* w_packed, void* out,
@@ -1339,7 +1326,7 @@ int cy_conv3x3_dgrad_bn(const cy_conv_desc* d, const void* dA, const cy_bn_bwd_i
 // the epilogue can take the backward sums of the BatchNorm behind its output: flow kernel, no split-K, the channel range
 // aligned with the cout blocks (all couts, or the second part of a split output)
 static bool dgrad_dz_plan_ok(const cy_conv_desc* d, const ConvPlan& p, int c0, int Cc) {
-  if (!p.flow || p.ksplit != 1 || d->in_dtype == CY_F32 || d->prologue) return false;
+  if (p.kernel != CY_CONV_KERNEL_FLOW || p.ksplit != 1 || d->in_dtype == CY_F32 || d->prologue) return false;
   // (16-row tiles only: with four fragments per wave and cout block the sums' working set -- 32 partial sums, 16 registers of
   //  y, 16 of coefficients beside 128 accumulators -- does not fit, the compiler spills ~900 registers in the epilogue and
   //  the launch takes 3-4 x as long: tools/bench_dgrad_dz.py)
@@ -1350,7 +1337,7 @@ static bool dgrad_dz_plan_ok(const cy_conv_desc* d, const ConvPlan& p, int c0, i
 
 int cy_conv3x3_dgrad_dz_ok(const cy_conv_desc* d, int c0, int C) {
   if (conv_check(d) != CY_OK) return 0;
-  return dgrad_dz_plan_ok(d, plan_of(d), c0, C) ? 1 : 0;
+  return dgrad_dz_plan_ok(d, plan_conv(d), c0, C) ? 1 : 0;
 }
 
 int cy_conv3x3_dgrad_dz(const cy_conv_desc* d, const void* dy, const void* w_packed, void* out, void* out2,
@@ -1403,7 +1390,7 @@ static int conv_fwd_impl(const cy_conv_desc* d, const void* src1, const void* sr
     a.wflow = fe ? (const unsigned char*)w_packed + 9L * a.w_co_pad * a.w_ci_pad * 2 : nullptr;
     a.bytes_w = fe * 2;
   }
-  const ConvPlan p = plan_of(d);
+  const ConvPlan p = plan_conv(d);
   a.bytes_st = stats ? (long long)p.partials * 2 * d->Cout * 4 : 0;
   a.ksplit = p.ksplit;
   a.ws = (float*)ws;
@@ -1425,11 +1412,8 @@ static int conv_fwd_impl(const cy_conv_desc* d, const void* src1, const void* sr
   if (in_fold) {
     // the flow and streaming kernels derive the coefficients in place; the register-staged kernels (plane, igemm:
     // every thread fetches its channels' pairs per chunk) take them from memory after a fold launch
-    static const int fold_in_kernel = [] {  // (CY_BN_FOLD_IN_KERNEL=0: always the separate launch, A/B runs)
-      const char* e = getenv("CY_BN_FOLD_IN_KERNEL");
-      return e ? atoi(e) : 1;
-    }();
-    if ((p.flow || p.stream) && fold_in_kernel) {
+    // (CY_BN_FOLD_IN_KERNEL=0: always the separate launch, A/B runs)
+    if ((p.kernel == CY_CONV_KERNEL_FLOW || p.kernel == CY_CONV_KERNEL_STREAM) && cy_switches().bn_fold_in_kernel) {
       a.fold = bn_fold_from_abi(in_fold);
     } else {
       rc = cy_bn_fold_coef(in_fold, stream);
@@ -1484,29 +1468,13 @@ static int first_fwd_impl(const float* x, const float* w, void* out, float* stat
   const long per = ((npix + np - 1) / np + ppb - 1) / ppb * ppb;
   const size_t smem = (size_t)Cin * (per / W + 4) * (W + 2) * sizeof(float);
   if (smem > 96 * 1024) return CY_ERR_SHAPE;
-  static bool attr_done = false;
-  if (!attr_done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_first_kernel<bf16>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_first_kernel<f16>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_first_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess)
-      return CY_ERR_LAUNCH;
-    attr_done = true;
-  }
-  static const int first_mfma = [] {  // (CY_FIRST_MFMA=0: the VALU kernel, for A/B runs)
-    const char* e = getenv("CY_FIRST_MFMA");
-    return e ? atoi(e) : 1;
-  }();
-  if (first_mfma && Cin == 1 && Cout <= 32 && (out_dtype == CY_BF16 || out_dtype == CY_F16)) {
+  if (!cy_lds_limit_once<conv3x3_first_kernel<bf16>, conv3x3_first_kernel<f16>, conv3x3_first_kernel<float>>(96 * 1024)) return CY_ERR_LAUNCH;
+  // (CY_FIRST_MFMA=0: the VALU kernel, for A/B runs)
+  if (cy_switches().first_mfma && Cin == 1 && Cout <= 32 && (out_dtype == CY_BF16 || out_dtype == CY_F16)) {
     const long per_m = ((npix + np - 1) / np + 127) / 128 * 128;
     const size_t smem_m = (size_t)(per_m / W + 4) * (W + 2) * sizeof(float);
     if (smem_m <= 96 * 1024) {
-      static bool attr_m = false;
-      if (!attr_m) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_first_mfma_kernel<bf16>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_first_mfma_kernel<f16>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess)
-          return CY_ERR_LAUNCH;
-        attr_m = true;
-      }
+      if (!cy_lds_limit_once<conv3x3_first_mfma_kernel<bf16>, conv3x3_first_mfma_kernel<f16>>(96 * 1024)) return CY_ERR_LAUNCH;
       if (out_dtype == CY_BF16)
         hipLaunchKernelGGL(conv3x3_first_mfma_kernel<bf16>, dim3(np), dim3(256), smem_m, st, x, w, (bf16*)out, stats, N, H, W, Cout, sacc, sR);
       else

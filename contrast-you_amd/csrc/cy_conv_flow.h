@@ -736,15 +736,35 @@ inline FlowChoice flow_choice(const cy_conv_desc* d) {
   if (d->W % 16 == 0) f.tw = 16;
   else if (d->W % 14 == 0) f.tw = 14;
   else return f;
-  const long eb = 2, opx = (long)d->N * d->H * d->W;
-  const long px1 = d->mode1 == CY_SRC_UP2 ? (long)d->N * (d->H / 2) * (d->W / 2) : opx;
-  const long lim = (1L << 31) - 1;
-  if (px1 * d->ld1 * eb > lim || (d->C2 && opx * d->ld2 * eb > lim)) return f;
+  if (!below_2gib(d, kSrc1 | kSrc2)) return f;  // (the sources: DMA through buffer descriptors)
   if (flow_image_elems(d->Cout, Cin) == 0) return f;
   if (d->Cout % 128 == 0) f.th = 32, f.bn = 128, f.small_ok = true;
   else f.th = 64, f.bn = 64;
   f.ok = true;
   return f;
+}
+
+// The tilings of the kernel, in one place: TH rows x BN couts per workgroup on WGM x WGN waves (each 16 or 14 columns
+// wide).  Calls f(FlowTiling<...>{}) for the tiling (th, bn) and returns its result; `none` where there is no such tiling.
+template <int TH_, int BN_, int WGM_, int WGN_> struct FlowTiling {
+  static constexpr int TH = TH_, BN = BN_, WGM = WGM_, WGN = WGN_;
+  template <typename T, bool W16> using Cfg = FlowCfg<T, TH_, BN_, WGM_, WGN_, W16>;
+};
+template <typename R, typename F> R flow_with_tiling(int th, int bn, R none, F f) {
+  // (measured and dropped: four waves of 128 positions x 64 couts on the 16 x 128 tile -- 0.75 KB of LDS fragments per MFMA
+  //  instead of 1.0, but one wave per SIMD: 15-25 % slower on every 56 x 56 / 28 x 28 layer at N = 16)
+  if (th == 16 && bn == 128) return f(FlowTiling<16, 128, 4, 2>{});
+  if (th == 32 && bn == 128) return f(FlowTiling<32, 128, 4, 2>{});
+  if (th == 64 && bn == 64) return f(FlowTiling<64, 64, 8, 1>{});
+  if (th == 32 && bn == 64) return f(FlowTiling<32, 64, 4, 1>{});  // four waves of 128 positions x 64 couts, two workgroups per CU
+  if (th == 16 && bn == 64) return f(FlowTiling<16, 64, 4, 1>{});  // four waves of 64 positions x 64 couts, two workgroups per CU
+  return none;
+}
+
+// does the tiling take this layer?  A prologue keeps one coefficient set per thread: at most 256 input channels on the
+// four-wave tilings (flow_choice stops at the eight-wave tilings' 512)
+inline bool flow_tiling_takes(int th, int bn, bool prologue, int C1) {
+  return flow_with_tiling(th, bn, false, [&](auto t) { return !(prologue && C1 > decltype(t)::template Cfg<bf16, true>::COEF_MAX); });
 }
 
 template <typename T, int TH, int BN, int WGM, int WGN, bool W16, int MODE = 0>
@@ -758,22 +778,12 @@ int launch_conv_flow(ConvArgs a, hipStream_t st) {
     }
     if (a.dz_y != nullptr) return launch_conv_flow<T, TH, BN, WGM, WGN, W16, 2>(a, st);
   }
-  auto kern = conv3x3_flow_kernel<T, TH, BN, WGM, WGN, W16, MODE>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            BWD ? C::SMEM_BWD : C::SMEM) != hipSuccess)
-      return CY_ERR_LAUNCH;
-    attr_done = true;
-  }
+  constexpr auto kern = conv3x3_flow_kernel<T, TH, BN, WGM, WGN, W16, MODE>;
+  if (!cy_lds_limit_once<kern>(BWD ? C::SMEM_BWD : C::SMEM)) return CY_ERR_LAUNCH;
   if (a.W % C::TW != 0 || a.Cout % BN != 0) return CY_ERR_SHAPE;
   a.tiles_w = a.W / C::TW;
   a.stamps = g_conv_stamp_buf;
-  static const int xcd = [] {
-    const char* e = getenv("CY_PLANE_XCD");
-    return e ? atoi(e) : 1;
-  }();
-  a.xcd_remap = xcd;
+  a.xcd_remap = cy_switches().plane_xcd;
   dim3 grid(cy_cdiv(a.NH, TH) * a.tiles_w * (a.Cout / BN), 1, a.ksplit);
   hipLaunchKernelGGL(kern, grid, dim3(C::NTHR), BWD ? C::SMEM_BWD : C::SMEM, st, a);
   CY_CHECK_LAUNCH();
@@ -782,41 +792,20 @@ int launch_conv_flow(ConvArgs a, hipStream_t st) {
 
 // can this tiling take the backward prologue (one more halo buffer in LDS; the four-wave tilings must still fit twice)?
 template <typename T> bool flow_bwd_ok(int th, int bn, int tw) {
-  if (th == 16 && bn == 128) return tw == 16 ? FlowCfg<T, 16, 128, 4, 2, true>::BWD_OK : FlowCfg<T, 16, 128, 4, 2, false>::BWD_OK;
-  if (th == 32 && bn == 128) return tw == 16 ? FlowCfg<T, 32, 128, 4, 2, true>::BWD_OK : FlowCfg<T, 32, 128, 4, 2, false>::BWD_OK;
-  if (th == 64 && bn == 64) return tw == 16 ? FlowCfg<T, 64, 64, 8, 1, true>::BWD_OK : FlowCfg<T, 64, 64, 8, 1, false>::BWD_OK;
-  if (th == 32 && bn == 64) return tw == 16 ? FlowCfg<T, 32, 64, 4, 1, true>::BWD_OK : FlowCfg<T, 32, 64, 4, 1, false>::BWD_OK;
-  if (th == 16 && bn == 64) return tw == 16 ? FlowCfg<T, 16, 64, 4, 1, true>::BWD_OK : FlowCfg<T, 16, 64, 4, 1, false>::BWD_OK;
-  return false;
+  return flow_with_tiling(th, bn, false, [&](auto t) {
+    using X = decltype(t);
+    return tw == 16 ? X::template Cfg<T, true>::BWD_OK : X::template Cfg<T, false>::BWD_OK;
+  });
 }
 
 template <typename T>
 int dispatch_conv_flow(const ConvArgs& a, int th, int bn, int tw, hipStream_t st) {
-  if (th == 16 && bn == 128) {
-    // (measured and dropped: four waves of 128 positions x 64 couts on this tile -- 0.75 KB of LDS fragments per MFMA
-    //  instead of 1.0, but one wave per SIMD: 15-25 % slower on every 56 x 56 / 28 x 28 layer at N = 16)
-    if (tw == 16) return launch_conv_flow<T, 16, 128, 4, 2, true>(a, st);
-    return launch_conv_flow<T, 16, 128, 4, 2, false>(a, st);
-  }
-  if (th == 32 && bn == 128) {
-    if (tw == 16) return launch_conv_flow<T, 32, 128, 4, 2, true>(a, st);
-    return launch_conv_flow<T, 32, 128, 4, 2, false>(a, st);
-  }
-  if (th == 64 && bn == 64) {
-    if (tw == 16) return launch_conv_flow<T, 64, 64, 8, 1, true>(a, st);
-    return launch_conv_flow<T, 64, 64, 8, 1, false>(a, st);
-  }
-  if (th == 32 && bn == 64) {  // four waves of 128 positions x 64 couts, two workgroups per CU
-    if (a.prologue && a.C1 > 256) return CY_ERR_SHAPE;
-    if (tw == 16) return launch_conv_flow<T, 32, 64, 4, 1, true>(a, st);
-    return launch_conv_flow<T, 32, 64, 4, 1, false>(a, st);
-  }
-  if (th == 16 && bn == 64) {  // four waves of 64 positions x 64 couts, two workgroups per CU
-    if (a.prologue && a.C1 > 256) return CY_ERR_SHAPE;
-    if (tw == 16) return launch_conv_flow<T, 16, 64, 4, 1, true>(a, st);
-    return launch_conv_flow<T, 16, 64, 4, 1, false>(a, st);
-  }
-  return CY_ERR_SHAPE;
+  if (!flow_tiling_takes(th, bn, a.prologue != 0, a.C1)) return CY_ERR_SHAPE;
+  return flow_with_tiling(th, bn, (int)CY_ERR_SHAPE, [&](auto t) {
+    using X = decltype(t);
+    if (tw == 16) return launch_conv_flow<T, X::TH, X::BN, X::WGM, X::WGN, true>(a, st);
+    return launch_conv_flow<T, X::TH, X::BN, X::WGM, X::WGN, false>(a, st);
+  });
 }
 
 }  // namespace

@@ -559,22 +559,12 @@ __global__ void __launch_bounds__(256, PREFA ? 1 : 2)
 template <typename T, int TH, int BN, int WGM, int WGN, int PITCHB, bool ALLT, bool PREFA = false>
 int launch_conv_plane(ConvArgs a, hipStream_t st) {
   using C = PlaneCfg<T, TH, BN, WGM, WGN, PITCHB, ALLT>;
-  auto kern = conv3x3_plane_kernel<T, TH, BN, WGM, WGN, PITCHB, ALLT, PREFA>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM) != hipSuccess)
-      return CY_ERR_LAUNCH;
-    attr_done = true;
-  }
+  constexpr auto kern = conv3x3_plane_kernel<T, TH, BN, WGM, WGN, PITCHB, ALLT, PREFA>;
+  if (!cy_lds_limit_once<kern>(C::SMEM)) return CY_ERR_LAUNCH;
   if (a.W % C::TW != 0) return CY_ERR_SHAPE;
   a.tiles_w = a.W / C::TW;
   a.full_tiles = 0;
-  static const int xcd = [] {
-    const char* e = getenv("CY_PLANE_XCD");
-    return e ? atoi(e) : 1;
-  }();
-  a.xcd_remap = xcd;
+  a.xcd_remap = cy_switches().plane_xcd;
   dim3 grid(cy_cdiv(a.NH, TH) * a.tiles_w, cy_cdiv(a.Cout, BN), a.ksplit);
   hipLaunchKernelGGL(kern, grid, dim3(256), C::SMEM, st, a);
   CY_CHECK_LAUNCH();

@@ -557,12 +557,7 @@ inline bool stream_applicable(const cy_conv_desc* d) {
   if (d->C2 != 0 && (d->C1 != 32 || d->C2 != 32)) return false;  // concat: one chunk per source
   if (d->split_c > 0 && d->split_c % 32) return false;
   if (d->W % 14) return false;
-  // buffer descriptors and 32-bit byte offsets: every tensor below 2 GiB
-  const long eb = 2, opx = (long)d->N * d->H * d->W;
-  const long px1 = d->mode1 == CY_SRC_UP2 ? (long)d->N * (d->H / 2) * (d->W / 2) : opx;
-  const long lim = (1L << 31) - 1;
-  if (px1 * d->ld1 * eb > lim || (d->C2 && opx * d->ld2 * eb > lim)) return false;
-  if (opx * d->ldo * eb > lim || (d->split_c > 0 && opx * d->ldo2 * eb > lim)) return false;
+  if (!below_2gib(d, kSrc1 | kSrc2 | kOut | kOut2)) return false;  // buffer descriptors on every tensor
   return true;
 }
 
@@ -572,26 +567,23 @@ int launch_conv_stream(ConvArgs a, hipStream_t st) {
   a.tiles_w = a.W / C::TW;
   const int ntiles = cy_cdiv(a.NH, C::TH) * a.tiles_w;
   const int grid = stream_grid(a.C1 + a.C2, a.Cout, ntiles, a.prologue != 0);
-  auto go = [&](auto kern) {
-    static bool attr_done = false;
-    if (!attr_done) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM) != hipSuccess)
-        return (int)CY_ERR_LAUNCH;
-      attr_done = true;
-    }
-    a.stamps = g_conv_stamp_buf;
+  a.stamps = g_conv_stamp_buf;
+  auto go = [&](auto kern, bool lds_ok) {
+    if (!lds_ok) return (int)CY_ERR_LAUNCH;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(C::NTHR), C::SMEM, st, a);
     return (int)CY_OK;
   };
+#define CY_STREAM_GO(...) go(conv3x3_stream_kernel<__VA_ARGS__>, cy_lds_limit_once<conv3x3_stream_kernel<__VA_ARGS__>>(C::SMEM))
   int rc;
   if (a.prologue) {
     if constexpr (KCH == 1 && NB == 1)
-      rc = (a.stats || a.sacc) ? go(conv3x3_stream_kernel<T, 1, 1, true, true>) : go(conv3x3_stream_kernel<T, 1, 1, false, true>);
+      rc = (a.stats || a.sacc) ? CY_STREAM_GO(T, 1, 1, true, true) : CY_STREAM_GO(T, 1, 1, false, true);
     else
       return CY_ERR_SHAPE;
   } else {
-    rc = (a.stats || a.sacc) ? go(conv3x3_stream_kernel<T, KCH, NB, true>) : go(conv3x3_stream_kernel<T, KCH, NB, false>);
+    rc = (a.stats || a.sacc) ? CY_STREAM_GO(T, KCH, NB, true) : CY_STREAM_GO(T, KCH, NB, false);
   }
+#undef CY_STREAM_GO
   if (rc != CY_OK) return rc;
   CY_CHECK_LAUNCH();
   return CY_OK;

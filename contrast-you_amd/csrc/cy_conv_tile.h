@@ -14,6 +14,21 @@
 //   different 16-byte slots of the 256-byte bank row.
 #pragma once
 #include "cy_bn_acc.h"
+#include "cy_switches.h"
+
+// The kernels that address a tensor through a buffer descriptor use 32-bit byte offsets: every such tensor must stay
+// below 2 GiB (16-bit storage).  `which` names the tensors the kernel in question addresses that way.
+enum : unsigned { kSrc1 = 1, kSrc2 = 2, kOut = 4, kOut2 = 8 };
+static inline bool below_2gib(const cy_conv_desc* d, unsigned which) {
+  const long lim = (1L << 31) - 1, eb = 2;
+  const long opx = (long)d->N * d->H * d->W;
+  const long px1 = d->mode1 == CY_SRC_UP2 ? opx / 4 : opx;  // (H and W are even there)
+  if ((which & kSrc1) && px1 * d->ld1 * eb > lim) return false;
+  if ((which & kSrc2) && d->C2 && opx * d->ld2 * eb > lim) return false;
+  if ((which & kOut) && opx * d->ldo * eb > lim) return false;
+  if ((which & kOut2) && d->split_c > 0 && opx * d->ldo2 * eb > lim) return false;
+  return true;
+}
 
 struct ConvArgs {
   const void* src1;

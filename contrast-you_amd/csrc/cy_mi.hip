@@ -609,13 +609,7 @@ int cy_joint_fwd(const float* x1, const float* x2, float* J, int N, int H, int W
   size_t smem_multi = ((size_t)(R + 2 * pad) * (W + 2 * pad) * kp + (size_t)R * W * kp) * sizeof(float);
   if (smem_multi < (size_t)nsl * kp * kp * sizeof(float)) smem_multi = (size_t)nsl * kp * kp * sizeof(float);
   if (pad > 0 && smem_multi <= 150 * 1024) {
-    static bool attr_set = false;
-    if (!attr_set) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(joint_fwd_multi_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess)
-        return CY_ERR_LAUNCH;
-      attr_set = true;
-    }
+    if (!cy_lds_limit_once<joint_fwd_multi_kernel>(150 * 1024)) return CY_ERR_LAUNCH;
     hipLaunchKernelGGL(joint_fwd_multi_kernel, dim3(nblk, cy_cdiv(T * T, JM_D)), dim3(256), smem_multi, st, x1, x2,
                        (float*)ws, N, H, W, k, pad, R);
   } else {

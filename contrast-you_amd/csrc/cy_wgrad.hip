@@ -711,18 +711,6 @@ WgPlan plan_wgrad(const cy_conv_desc* d) {
   p.TH = best;
   p.tiles_h = (d->N * d->H) / p.TH;
   p.tiles_w = cy_cdiv(d->W, p.TW);
-  static const bool spec_enabled = [] {
-    const char* e = getenv("CY_WGRAD_SPEC");
-    return !(e && e[0] == '0');
-  }();
-  static const bool dma_enabled = [] {
-    const char* e = getenv("CY_WGRAD_DMA");
-    return !(e && e[0] == '0');
-  }();
-  static const bool blk_enabled = [] {
-    const char* e = getenv("CY_WGRAD_BLK");
-    return !(e && e[0] == '0');
-  }();
   {
     // the wave-specialised kernel (cy_wgrad_spec.h).  With register-staging loaders it pays on the 64 x 64 blocks
     // only (measured per layer at N = 32: the pooled-on-load layers -- four synchronous loads per halo item -- and the
@@ -732,14 +720,12 @@ WgPlan plan_wgrad(const cy_conv_desc* d) {
     // layers (Conv5a / Conv5b, both passes paired: 74 -> 58 and 131 -> 116 us).
     // DMA: 32-bit buffer offsets (every tensor below 2 GiB; the caller's total batch is in d->N), a ci block reads
     // one source.
-    const long lim = (1L << 31) - 1, eb = 2;
-    const long opx = (long)d->N * d->H * d->W;
-    const long px1 = d->mode1 == CY_SRC_UP2 ? opx / 4 : opx;
-    const bool small = px1 * d->ld1 * eb <= lim && (!d->C2 || opx * d->ld2 * eb <= lim) && opx * d->ldo * eb <= lim;
+    const CySwitches& sw = cy_switches();
+    const bool small = below_2gib(d, kSrc1 | kSrc2 | kOut);  // (the output of the descriptor is dy here)
     constexpr int min_w = 14;
-    const bool base = p.twelve && spec_enabled && d->mode1 != CY_SRC_POOL2 && d->W >= min_w;
-    const bool dma_ok = dma_enabled && small && (d->C2 == 0 || d->C1 % (32 * p.wci) == 0);
-    const bool patches = dma_ok && blk_enabled && p.TH % 4 == 0 && p.TW % 4 == 0;
+    const bool base = p.twelve && sw.wgrad_spec && d->mode1 != CY_SRC_POOL2 && d->W >= min_w;
+    const bool dma_ok = sw.wgrad_dma && small && (d->C2 == 0 || d->C1 % (32 * p.wci) == 0);
+    const bool patches = dma_ok && sw.wgrad_blk && p.TH % 4 == 0 && p.TW % 4 == 0;
     p.spec = base && ((p.wco == 2 && p.wci == 2) || (p.wco == 1 && patches));
     p.dma = p.spec && dma_ok;
     p.blk_order = p.dma && patches;
@@ -761,14 +747,8 @@ WgPlan plan_wgrad(const cy_conv_desc* d) {
 template <typename T, int WCO, int WCI, int WK>
 int launch_wgrad(const WgradArgs& g, const WgPlan& p, hipStream_t st) {
   using C = WgCfg<T, WCO, WCI, WK>;
-  auto kern = wgrad_kernel<T, WCO, WCI, WK>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM) != hipSuccess)
-      return CY_ERR_LAUNCH;
-    attr_done = true;
-  }
+  constexpr auto kern = wgrad_kernel<T, WCO, WCI, WK>;
+  if (!cy_lds_limit_once<kern>(C::SMEM)) return CY_ERR_LAUNCH;
   dim3 grid((p.co_pad / C::BCO) * (p.ci_pad / C::BCI), p.S);
   hipLaunchKernelGGL(kern, grid, dim3(256), C::SMEM, st, g);
   CY_CHECK_LAUNCH();
@@ -778,14 +758,8 @@ int launch_wgrad(const WgradArgs& g, const WgPlan& p, hipStream_t st) {
 template <int WCO, int WCI, int WK, typename T = bf16>
 int launch_wgrad12(const WgradArgs& g, const WgPlan& p, hipStream_t st) {
   using C = Wg12Cfg<WCO, WCI, WK>;
-  auto kern = wgrad12_kernel<WCO, WCI, WK, T>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM) != hipSuccess)
-      return CY_ERR_LAUNCH;
-    attr_done = true;
-  }
+  constexpr auto kern = wgrad12_kernel<WCO, WCI, WK, T>;
+  if (!cy_lds_limit_once<kern>(C::SMEM)) return CY_ERR_LAUNCH;
   dim3 grid((p.co_pad / C::BCO) * (p.ci_pad / C::BCI), p.S);
   WgradArgs ga = g;
   ga.c.stamps = g_w12_stamp_buf;
@@ -1023,11 +997,7 @@ __global__ void __launch_bounds__(256) wgrad_batched_reduce_kernel(const WgRedTa
 
 // workgroups of first_wgrad_mfma_kernel (sub-blocks of eight rows, contiguous ranges of them), or 0 where it does not apply
 int first_wgrad_mfma_blocks(int N, int Cin, int H, int W, int Cout, int dtype) {
-  static const bool enabled = [] {
-    const char* e = getenv("CY_FIRST_WGRAD_MFMA");
-    return !(e && e[0] == '0');
-  }();
-  if (!enabled || Cin != 1 || Cout != 32 || (dtype != CY_BF16 && dtype != CY_F16) || H % 8 || W % 16 || W > 2048) return 0;
+  if (!cy_switches().first_wgrad_mfma || Cin != 1 || Cout != 32 || (dtype != CY_BF16 && dtype != CY_F16) || H % 8 || W % 16 || W > 2048) return 0;
   const long nsub = (long)N * H / 8;
   return (int)(nsub < 1024 ? nsub : 1024);
 }
@@ -1320,15 +1290,8 @@ static int first_wgrad_impl(const float* x, const void* dy, float* dw, int accum
     const int nsub = N * H / 8, spb = (nsub + nm - 1) / nm;
     size_t smem = 4096 + (size_t)3 * 10 * W * 2;
     if (smem < 16384) smem = 16384;  // (the four waves' accumulators pass through it at the end)
-    if (smem > 48 * 1024) {          // (wide images: W > 730)
-      static bool big_done = false;
-      if (!big_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(first_wgrad_mfma_kernel<bf16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(first_wgrad_mfma_kernel<f16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-          return CY_ERR_LAUNCH;
-        big_done = true;
-      }
-    }
+    // (wide images: W > 730)
+    if (smem > 48 * 1024 && !cy_lds_limit_once<first_wgrad_mfma_kernel<bf16>, first_wgrad_mfma_kernel<f16>>(160 * 1024)) return CY_ERR_LAUNCH;
     if (dy_dtype == CY_BF16)
       hipLaunchKernelGGL(first_wgrad_mfma_kernel<bf16>, dim3(nm), dim3(256), smem, st, x, (const bf16*)dy, (float*)ws, N, H, W, spb);
     else
@@ -1349,14 +1312,7 @@ static int first_wgrad_impl(const float* x, const void* dy, float* dw, int accum
   const long per = ((long)N * H * W + nblk - 1) / nblk;
   const size_t smem = (size_t)(per / W + 4) * (W + 2) * sizeof(float);
   if (nblk < 0 || smem > 96 * 1024) return CY_ERR_SHAPE;
-  static bool attr_done = false;
-  if (!attr_done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(first_wgrad_kernel<bf16>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(first_wgrad_kernel<f16>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(first_wgrad_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess)
-      return CY_ERR_LAUNCH;
-    attr_done = true;
-  }
+  if (!cy_lds_limit_once<first_wgrad_kernel<bf16>, first_wgrad_kernel<f16>, first_wgrad_kernel<float>>(96 * 1024)) return CY_ERR_LAUNCH;
   if (dy_dtype == CY_BF16)
     hipLaunchKernelGGL(first_wgrad_kernel<bf16>, dim3(nblk), dim3(256), smem, st, x, (const bf16*)dy,
                        (float*)ws, N, Cin, H, W, Cout);

@@ -629,14 +629,8 @@ __global__ void __launch_bounds__(768, 1)
 template <typename T, int WCO, int WCI, bool DMA = false, bool BLK = false>
 int launch_wgrad12s(const WgradArgs& g, const WgPlan& p, hipStream_t st) {
   using C = Wg12sCfg<WCO, WCI>;
-  auto kern = wgrad12s_kernel<T, WCO, WCI, DMA, BLK>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            C::SMEM) != hipSuccess)
-      return CY_ERR_LAUNCH;
-    attr_done = true;
-  }
+  constexpr auto kern = wgrad12s_kernel<T, WCO, WCI, DMA, BLK>;
+  if (!cy_lds_limit_once<kern>(C::SMEM)) return CY_ERR_LAUNCH;
   dim3 grid((p.co_pad / C::BCO) * (p.ci_pad / C::BCI), p.S);
   WgradArgs ga = g;
   ga.c.stamps = g_w12_stamp_buf;

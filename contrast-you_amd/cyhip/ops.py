@@ -265,6 +265,7 @@ def _desc(N, H, W, C1, C2, Cout, mode, prologue, dt, ld1, ld2, ldo, split_c=0, l
     return p
 
 
+# cy_conv_plan.kernel: CY_CONV_KERNEL_IGEMM / _PLANE / _STREAM / _FLOW of include/contrastyou_hip.h
 KERNEL_NAMES = {0: "conv3x3_igemm_kernel", 1: "conv3x3_plane_kernel", 4: "conv3x3_stream_kernel", 5: "conv3x3_flow_kernel"}
 
 

@@ -137,8 +137,12 @@ int cy_conv3x3_num_partials(const cy_conv_desc* d);
 /* The launch plan the library derives for `d`: which kernel instantiation cy_conv3x3_fwd will run.
  * Parity tests assert on it, so that every instantiation that appears in profiles/ is known to be
  * covered by a test that provably took it (the plan depends on N, H, W, channel counts and dtype). */
+#define CY_CONV_KERNEL_IGEMM 0  /* conv3x3_igemm_kernel */
+#define CY_CONV_KERNEL_PLANE 1  /* conv3x3_plane_kernel */
+#define CY_CONV_KERNEL_STREAM 4 /* conv3x3_stream_kernel */
+#define CY_CONV_KERNEL_FLOW 5   /* conv3x3_flow_kernel */
 typedef struct cy_conv_plan {
-  int32_t kernel;     /* 0: conv3x3_igemm_kernel, 1: conv3x3_plane_kernel, 4: conv3x3_stream_kernel, 5: conv3x3_flow_kernel */
+  int32_t kernel;     /* CY_CONV_KERNEL_* */
   int32_t th, tw, bn; /* output tile (rows x columns) and output channels per workgroup */
   int32_t ksplit;     /* >1: split-K over input-channel chunks + conv_splitk_finish_kernel */
   int32_t one_per_cu; /* plane kernel, 128 couts: the one-workgroup-per-CU build with halo prefetch */

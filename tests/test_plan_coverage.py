@@ -102,3 +102,69 @@ def test_plan_query_matches_partials_and_split():
     assert q["kernel"] == "conv3x3_plane_kernel" and q["bn"] == 128
     w = ops.conv3x3_wgrad_plan(16, 14, 14, 512, 0, 512, torch.bfloat16, 0, 1)
     assert w["splits"] >= 1 and w["workgroups"] >= 64
+
+
+FLOW_TILINGS = {(16, 128), (32, 128), (64, 64), (32, 64), (16, 64)}  # (th, bn): the list in csrc/cy_conv_flow.h
+IGEMM_TILES = {(8, 32), (16, 16), (32, 8)}
+
+
+def _plan_violations(d, p, q):
+    """the invariants (a) .. (i) that tie a plan to what the dispatcher can launch and the other queries report;
+    d: descriptor, p: cy_conv_plan, q: the other queries' answers.  Returns the letters of the broken ones."""
+    IGEMM, PLANE, STREAM, FLOW = 0, 1, 4, 5  # CY_CONV_KERNEL_*
+    Cin, bits16, tile = d.C1 + d.C2, d.in_dtype != 0, (p.th, p.tw, p.bn)
+    bad = []
+    if q["ws_bytes"] != (p.ksplit * d.N * d.H * d.W * d.Cout * 4 if p.ksplit > 1 else 0):
+        bad.append("a")
+    if q["num_partials"] != p.partials:
+        bad.append("b")
+    if p.kernel == STREAM:
+        if not (bits16 and tile == (16, 14, d.Cout) and p.ksplit == 1 and Cin in (32, 64) and d.Cout in (32, 64)
+                and p.partials == 4 * q["stat_workgroups"]):
+            bad.append("c")
+    elif q["stat_workgroups"] != p.partials:
+        bad.append("c")
+    if p.kernel == FLOW and not (bits16 and (p.th, p.bn) in FLOW_TILINGS and p.tw in (14, 16) and d.W % p.tw == 0
+                                 and d.Cout % p.bn == 0 and d.mode1 != 1):
+        bad.append("d")
+    if p.kernel == PLANE and not ((p.th, p.tw) == (16, 14) and d.W % 14 == 0 and p.bn in (32, 64, 128)):
+        bad.append("e")
+    if p.kernel == IGEMM and not (((p.th, p.tw) in IGEMM_TILES and p.bn in (32, 64, 128))
+                                  or tile in ((8, 28, 128), (16, 14, 128))):
+        bad.append("f")
+    if p.kernel not in (IGEMM, PLANE, STREAM, FLOW):
+        bad.append("kernel")
+    if p.one_per_cu and not (p.kernel == PLANE and p.bn == 128):
+        bad.append("g")
+    if q["dgrad_bn_ok"] and not (p.kernel == FLOW and d.prologue == 2):
+        bad.append("h")
+    if q["dgrad_dz_ok"] and not (p.kernel == FLOW and p.ksplit == 1 and p.th == 16):
+        bad.append("i")
+    return bad
+
+
+def test_every_plan_is_one_the_dispatcher_can_launch():
+    """Every valid descriptor of the reduced grid of tools/plan_dump.py (unit leading dimensions, N in 1, 3, 16, 32,
+    512; invalid combinations are those cy_conv3x3_plan itself refuses) gets a plan that dispatch_conv has a kernel
+    instantiation for, and the partial / workspace / fused-data-gradient queries agree with it.  A tiling added to the
+    planner and not to the dispatcher shows up here instead of as CY_ERR_SHAPE on some layer at run time."""
+    from cyhip import _lib
+    from tools import plan_dump
+    lib = plan_dump.load(_lib.LIB_PATH)
+    d, p = _lib.ConvDesc(), _lib.ConvPlan()
+    names = [n for n, _ in _lib.ConvDesc._fields_]
+    valid, broken = 0, []
+    for fields in plan_dump.descriptors(reduced=True):
+        for n, v in zip(names, fields):
+            setattr(d, n, v)
+        if lib.cy_conv3x3_plan(d, p) != 0:
+            continue
+        valid += 1
+        q = {"ws_bytes": lib.cy_conv3x3_fwd_ws_bytes(d), "num_partials": lib.cy_conv3x3_num_partials(d),
+             "stat_workgroups": lib.cy_conv3x3_stat_workgroups(d), "dgrad_bn_ok": lib.cy_conv3x3_dgrad_bn_ok(d),
+             "dgrad_dz_ok": lib.cy_conv3x3_dgrad_dz_ok(d, 0, d.Cout)}
+        bad = _plan_violations(d, p, q)
+        if bad:
+            broken.append((bad, fields, {f: getattr(p, f) for f, _ in p._fields_}, q))
+    assert valid > 150000, valid  # (270 480 of the 518 400 combinations pass cy_conv3x3_plan's own checks today)
+    assert not broken, f"{len(broken)} of {valid} plans break an invariant; the first: {broken[:3]}"
