@@ -399,19 +399,34 @@ __global__ void __launch_bounds__(256)
   }
 }
 
-inline int ch_blocks(long M) {
-  long nb = ((M + 31) / 32 + 3) / 4;
-  if (nb > 512) nb = 512;
-  if (nb < 1) nb = 1;
-  return (int)nb;
-}
 inline size_t ch_fwd_smem_w(int C, int K, int nw) {
   return ((size_t)CH_KP * (C + 1) + nw * (32 * (C + 1) + 32 * ch_ldl(K)) + CH_KP) * sizeof(float);
 }
-// eight waves where their tiles fit the 160 KB next to the weights (C = 32 up to K = 108), four otherwise
-inline int ch_fwd_waves(int C, int K) { return ch_fwd_smem_w(C, K, 8) <= 160 * 1024 ? 8 : 4; }
-inline size_t ch_fwd_smem(int C, int K) { return ch_fwd_smem_w(C, K, ch_fwd_waves(C, K)); }
+// The launch shape of both kernels, the one place it is decided (cy_cluster_head_plan and, through cy_head_wide_plan,
+// cy_head1x1_plan report it; the launches below take it from here).
+// forward: eight waves where their tiles fit the 160 KB next to the weights (C = 32 up to K = 108), four otherwise; one
+// block per CU (LDS), grid-stride over the 32-pixel tiles.  backward: four waves, at most 512 blocks.
+struct ChLaunch {
+  int fwd_waves, fwd_grid, fwd_trips, bwd_grid, bwd_trips;
+};
+inline ChLaunch ch_launch(long M, int C, int K) {
+  ChLaunch l;
+  const long ntile = (M + 31) / 32;
+  l.fwd_waves = ch_fwd_smem_w(C, K, 8) <= 160 * 1024 ? 8 : 4;
+  const long gb = (ntile + l.fwd_waves - 1) / l.fwd_waves;
+  l.fwd_grid = (int)(gb > 256 ? 256 : gb < 1 ? 1 : gb);
+  l.fwd_trips = (int)((ntile + (long)l.fwd_grid * l.fwd_waves - 1) / ((long)l.fwd_grid * l.fwd_waves));
+  const long nb = (ntile + 3) / 4;
+  l.bwd_grid = (int)(nb > 512 ? 512 : nb < 1 ? 1 : nb);
+  l.bwd_trips = (int)((ntile + (long)l.bwd_grid * 4 - 1) / ((long)l.bwd_grid * 4));
+  return l;
+}
 inline size_t ch_smem(int C) { return ((size_t)CH_KP * (C + 1) + 4 * (32 * (C + 1) + 32 * CH_LDL) + CH_KP) * sizeof(float); }
+
+// per-wave slabs of the backward's blocks + the CH_RG staged group sums
+inline size_t ch_bwd_ws_bytes(int grid, int C) {
+  return ((size_t)grid * 4 + CH_RG) * ((size_t)CH_KP * C + CH_KP) * sizeof(float);
+}
 
 template <typename K_>
 int ch_set_smem(K_ kern, int C) {
@@ -436,12 +451,9 @@ static int ch_check(long M, int C, int K, int S, int k) {
 
 template <bool LINEAR>
 static int ch_fwd_impl(const void* x, const float* w, const float* b, float* out, long M, int C, int K, int S, int k,
-                       float invT, int dtype, void* stream) {
+                       float invT, int dtype, int nw, int grid, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  const int nw = ch_fwd_waves(C, K);
-  long gb = ((M + 31) / 32 + nw - 1) / nw;
-  const int grid = (int)(gb > 256 ? 256 : gb);  // one block per CU (LDS): grid-stride over the pixel tiles
-  const size_t smem = ch_fwd_smem(C, K);
+  const size_t smem = ch_fwd_smem_w(C, K, nw);
 #define CY_CH_FWD(TT)                                                                                         \
   do {                                                                                                        \
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(cluster_head_fwd_kernel<TT, LINEAR>),               \
@@ -466,25 +478,33 @@ int cy_cluster_head_fwd(const void* x, const float* w, const float* b, float* pr
   if (!x || !w || !probs) return CY_ERR_ARG;
   int rc = ch_check(M, C, K, S, k);
   if (rc != CY_OK) return rc;
-  return ch_fwd_impl<false>(x, w, b, probs, M, C, K, S, k, invT, dtype, stream);
+  const ChLaunch l = ch_launch(M, C, K);
+  return ch_fwd_impl<false>(x, w, b, probs, M, C, K, S, k, invT, dtype, l.fwd_waves, l.fwd_grid, stream);
 }
 
-size_t cy_cluster_head_bwd_ws_bytes(long M, int C) {
-  return ((size_t)ch_blocks(M) * 4 + CH_RG) * ((size_t)CH_KP * C + CH_KP) * sizeof(float);
+size_t cy_cluster_head_bwd_ws_bytes(long M, int C) { return ch_bwd_ws_bytes(ch_launch(M, C, CH_KP).bwd_grid, C); }
+
+int cy_cluster_head_plan(long M, int C, int S, int k, cy_cluster_plan* out) {
+  if (!out) return CY_ERR_ARG;
+  int rc = ch_check(M, C, S * k, S, k);
+  if (rc != CY_OK) return rc;
+  const ChLaunch l = ch_launch(M, C, S * k);
+  out->fwd_waves = l.fwd_waves, out->fwd_grid = l.fwd_grid, out->fwd_trips = l.fwd_trips;
+  out->bwd_grid = l.bwd_grid, out->bwd_trips = l.bwd_trips, out->slabs = l.bwd_grid * 4;
+  return CY_OK;
 }
 
 }  // extern "C"
 
 template <bool LINEAR>
 static int ch_bwd_impl(const void* x, const float* w, const float* probs, const float* dprobs, void* dx, float* dw,
-                       float* db, int accumulate, long M, int C, int K, int S, int k, float invT, int dtype, void* ws,
-                       size_t ws_bytes, void* stream) {
+                       float* db, int accumulate, long M, int C, int K, int S, int k, float invT, int dtype, int grid,
+                       void* ws, size_t ws_bytes, void* stream) {
   int rc;
   const int need_dx = dx != nullptr, need_dw = dw != nullptr || db != nullptr;
-  if (need_dw && (!ws || ws_bytes < cy_cluster_head_bwd_ws_bytes(M, C))) return CY_ERR_WORKSPACE;
+  if (need_dw && (!ws || ws_bytes < ch_bwd_ws_bytes(grid, C))) return CY_ERR_WORKSPACE;
   if (!need_dx && !need_dw) return CY_OK;
   hipStream_t st = (hipStream_t)stream;
-  const int grid = ch_blocks(M);
   const size_t smem = ch_smem(C);
 #define CY_CH_BWD(TT)                                                                                          \
   do {                                                                                                         \
@@ -520,20 +540,29 @@ int cy_cluster_head_bwd(const void* x, const float* w, const float* probs, const
   int rc = ch_check(M, C, K, S, k);
   if (rc != CY_OK) return rc;
   if (dw && !db) return CY_ERR_WORKSPACE;
-  return ch_bwd_impl<false>(x, w, probs, dprobs, dx, dw, db, 0, M, C, K, S, k, invT, dtype, ws, ws_bytes, stream);
+  return ch_bwd_impl<false>(x, w, probs, dprobs, dx, dw, db, 0, M, C, K, S, k, invT, dtype, ch_launch(M, C, K).bwd_grid,
+                            ws, ws_bytes, stream);
 }
 
 }  // extern "C"
 
 // ---- the wide 1x1 head (cy_head1x1_fwd / _bwd with 16 < K <= 128 outputs over 32 or 64 channels) on the kernels above:
-// called from cy_head_loss.hip, same shared object
+// called from cy_head_loss.hip, same shared object.  cy_head1x1_plan asks cy_head_wide_plan for the launch shape and hands
+// wave count and grids back to the two launches.
 bool cy_head_wide_ok(int C, int K) { return (C == 32 || C == 64) && K > 16 && K <= CH_KP; }
-size_t cy_head_wide_bwd_ws_bytes(long M, int C) { return cy_cluster_head_bwd_ws_bytes(M, C); }
+void cy_head_wide_plan(long M, int C, int K, int* fwd_waves, int* fwd_grid, int* fwd_trips, int* bwd_grid,
+                       int* bwd_trips) {
+  const ChLaunch l = ch_launch(M, C, K);
+  *fwd_waves = l.fwd_waves, *fwd_grid = l.fwd_grid, *fwd_trips = l.fwd_trips;
+  *bwd_grid = l.bwd_grid, *bwd_trips = l.bwd_trips;
+}
+size_t cy_head_wide_bwd_ws_bytes(int bwd_grid, int C) { return ch_bwd_ws_bytes(bwd_grid, C); }
 int cy_head_wide_fwd(const void* x, const float* w, const float* b, float* logits, long M, int C, int K, int dtype,
-                     void* stream) {
-  return ch_fwd_impl<true>(x, w, b, logits, M, C, K, 1, K, 1.f, dtype, stream);
+                     int fwd_waves, int fwd_grid, void* stream) {
+  return ch_fwd_impl<true>(x, w, b, logits, M, C, K, 1, K, 1.f, dtype, fwd_waves, fwd_grid, stream);
 }
 int cy_head_wide_bwd(const void* x, const float* w, const float* dlogits, void* dx, float* dw, float* db, int accumulate,
-                     long M, int C, int K, int dtype, void* ws, size_t ws_bytes, void* stream) {
-  return ch_bwd_impl<true>(x, w, nullptr, dlogits, dx, dw, db, accumulate, M, C, K, 1, K, 1.f, dtype, ws, ws_bytes, stream);
+                     long M, int C, int K, int dtype, int bwd_grid, void* ws, size_t ws_bytes, void* stream) {
+  return ch_bwd_impl<true>(x, w, nullptr, dlogits, dx, dw, db, accumulate, M, C, K, 1, K, 1.f, dtype, bwd_grid, ws,
+                           ws_bytes, stream);
 }

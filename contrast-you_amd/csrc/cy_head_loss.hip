@@ -9,13 +9,16 @@
 #include "cy_common.h"
 #include "cy_pixel_loss.h"  // KMAX, softmax_k, load_logits, block_sum_d, mean_finalize_kernel, loss_blocks
 
-// the wide head on the matrix-core kernels of cy_cluster_head.hip (same shared object)
+// the wide head on the matrix-core kernels of cy_cluster_head.hip (same shared object); wave count and grids come from
+// cy_head_wide_plan through cy_head1x1_plan
 bool cy_head_wide_ok(int C, int K);
-size_t cy_head_wide_bwd_ws_bytes(long M, int C);
+void cy_head_wide_plan(long M, int C, int K, int* fwd_waves, int* fwd_grid, int* fwd_trips, int* bwd_grid,
+                       int* bwd_trips);
+size_t cy_head_wide_bwd_ws_bytes(int bwd_grid, int C);
 int cy_head_wide_fwd(const void* x, const float* w, const float* b, float* logits, long M, int C, int K, int dtype,
-                     void* stream);
+                     int fwd_waves, int fwd_grid, void* stream);
 int cy_head_wide_bwd(const void* x, const float* w, const float* dlogits, void* dx, float* dw, float* db, int accumulate,
-                     long M, int C, int K, int dtype, void* ws, size_t ws_bytes, void* stream);
+                     long M, int C, int K, int dtype, int bwd_grid, void* ws, size_t ws_bytes, void* stream);
 // softmax-MSE at 16 < K <= 64 on the sixteen-lanes-per-pixel kernels of cy_group_loss.hip (same shared object)
 int cy_softmax_mse_row_fwd(const float* a, const float* b, float* loss, long npix, int K, void* ws, void* stream);
 int cy_softmax_mse_row_bwd(const float* a, const float* b, const float* gscale, float* da, float* db, long npix, int K,
@@ -244,12 +247,14 @@ __global__ void __launch_bounds__(256)
   }
 }
 
-inline int head_dw_blocks(long npix) {
-  long b = (npix + 255) / 256;
-  if (b > 512) b = 512;
+// blocks of 256 threads over `work` items, at most `cap`; and the trips of the grid-stride loop that gives
+inline int capped_blocks(long work, long cap) {
+  long b = (work + 255) / 256;
+  if (b > cap) b = cap;
   if (b < 1) b = 1;
   return (int)b;
 }
+inline int stride_trips(long work, int blocks) { return (int)((work + blocks * 256L - 1) / (blocks * 256L)); }
 
 // ---------------------------------------------------------------- softmax + KL(one-hot)
 __global__ void __launch_bounds__(256)
@@ -391,19 +396,63 @@ __global__ void __launch_bounds__(256)
 
 extern "C" {
 
+// The one dispatch rule of the 1x1 head: kernel family, instantiation, grids and workspace rows from (npix, C, K).
+int cy_head1x1_plan(long npix, int C, int K, int need_dx, int need_dw, cy_head_plan* out) {
+  if (!out || npix <= 0) return CY_ERR_ARG;
+  if (C <= 0 || C % 8 || K < 1 || K > KWIDE || (size_t)(K * C + K) * 4 > 60000) return CY_ERR_SHAPE;
+  cy_head_plan p = {};
+  p.dx_kernel = -1;
+  // stacked cluster sub-heads over 32 / 64 channels: f32 matrix cores, the logits tile written in contiguous runs
+  // (the VALU kernel stores one float per lane at a 4 K-byte stride: 0.8 TB/s at K = 100)
+  if (cy_head_wide_ok(C, K)) {
+    int bwd_grid, bwd_trips;
+    cy_head_wide_plan(npix, C, K, &p.fwd_waves, &p.fwd_grid, &p.fwd_trips, &bwd_grid, &bwd_trips);
+    p.fwd_kernel = 2;
+    p.fwd_quads = K % 4 == 0;
+    if (need_dx) p.dx_kernel = 2, p.dx_grid = bwd_grid, p.dx_trips = bwd_trips;
+    if (need_dw) p.dw_blocks = bwd_grid, p.dw_per = bwd_trips * 128;
+    *out = p;
+    return CY_OK;
+  }
+  p.fwd_kernel = K <= KMAX ? 0 : 1;  // segmentation classes : stacked cluster sub-heads (DenseClusterHead: 5 x 20 outputs)
+  p.fwd_grid = loss_blocks(npix) * 2;
+  p.fwd_trips = stride_trips(npix, p.fwd_grid);
+  if (need_dx) {
+    const bool wide = K > KMAX && K % 4 == 0 && C % 32 == 0;  // dl rows as 16-byte vectors, 32 channels per thread
+    const long work = npix * (wide ? C / 32 : C / 8);
+    p.dx_kernel = wide ? 1 : 0;
+    p.dx_grid = capped_blocks(work, wide ? 8192 : 4096);
+    p.dx_trips = stride_trips(work, p.dx_grid);
+  }
+  if (need_dw) {
+    const int G = C / 8;
+    if (G > 256) return CY_ERR_SHAPE;
+    p.dw_group = K <= KMAX ? 4 : 16;
+    const int groups = (K + p.dw_group - 1) / p.dw_group;
+    p.dw_vec_groups = K % 4 == 0 ? K / p.dw_group : 0;  // whole groups of a K that keeps the dl rows 16-byte aligned
+    p.dw_scalar_groups = groups - p.dw_vec_groups;
+    p.dw_blocks = capped_blocks(npix, 512);
+    p.dw_rows = 256 / G;
+    p.dw_per = (int)((npix + p.dw_blocks - 1) / p.dw_blocks);
+  }
+  *out = p;
+  return CY_OK;
+}
+
 int cy_head1x1_fwd(const void* x, const float* w, const float* b, float* logits, long npix, int C,
                    int K, int x_dtype, void* stream) {
   if (!x || !w || !logits || npix <= 0) return CY_ERR_ARG;
-  if (C % 8 || K < 1 || K > KWIDE || (size_t)(K * C + K) * 4 > 60000) return CY_ERR_SHAPE;
+  cy_head_plan p;
+  const int rc = cy_head1x1_plan(npix, C, K, 0, 0, &p);
+  if (rc != CY_OK) return rc;
   if (x_dtype != CY_BF16 && x_dtype != CY_F32 && x_dtype != CY_F16) return CY_ERR_DTYPE;
-  // stacked cluster sub-heads over 32 / 64 channels: f32 matrix cores, the logits tile written in contiguous runs
-  // (the VALU kernel below stores one float per lane at a 4 K-byte stride: 0.8 TB/s at K = 100)
-  if (cy_head_wide_ok(C, K)) return cy_head_wide_fwd(x, w, b, logits, npix, C, K, x_dtype, stream);
+  if (p.fwd_kernel == 2)
+    return cy_head_wide_fwd(x, w, b, logits, npix, C, K, x_dtype, p.fwd_waves, p.fwd_grid, stream);
   hipStream_t st = (hipStream_t)stream;
-  const int grid = loss_blocks(npix) * 2;
+  const int grid = p.fwd_grid;
   const size_t smem = (size_t)(K * C + K) * sizeof(float);
   const bool h = x_dtype == CY_BF16;
-  if (K <= KMAX) {  // segmentation classes
+  if (p.fwd_kernel == 0) {
     if (h)
       hipLaunchKernelGGL((head_fwd_kernel<bf16, KMAX>), dim3(grid), dim3(256), smem, st,
                          (const bf16*)x, w, b, logits, npix, C, K);
@@ -413,7 +462,7 @@ int cy_head1x1_fwd(const void* x, const float* w, const float* b, float* logits,
     else
       hipLaunchKernelGGL((head_fwd_kernel<float, KMAX>), dim3(grid), dim3(256), smem, st,
                          (const float*)x, w, b, logits, npix, C, K);
-  } else {  // stacked cluster sub-heads (DenseClusterHead: 5 x 20 outputs)
+  } else {
     if (h)
       hipLaunchKernelGGL((head_fwd_kernel<bf16, KWIDE>), dim3(grid), dim3(256), smem, st,
                          (const bf16*)x, w, b, logits, npix, C, K);
@@ -428,9 +477,15 @@ int cy_head1x1_fwd(const void* x, const float* w, const float* b, float* logits,
   return CY_OK;
 }
 
+static size_t head_ws_bytes(const cy_head_plan& p, int C, int K) {
+  if (p.fwd_kernel == 2) return cy_head_wide_bwd_ws_bytes(p.dw_blocks, C);
+  return (size_t)p.dw_blocks * (K * C + K) * sizeof(float);
+}
+
 size_t cy_head1x1_bwd_ws_bytes(long npix, int C, int K) {
-  if (cy_head_wide_ok(C, K)) return cy_head_wide_bwd_ws_bytes(npix, C);
-  return (size_t)head_dw_blocks(npix) * (K * C + K) * sizeof(float);
+  cy_head_plan p;
+  if (cy_head1x1_plan(npix, C, K, 0, 1, &p) != CY_OK) return 0;
+  return head_ws_bytes(p, C, K);
 }
 
 static int head1x1_bwd_impl(const void* x, const float* w, const float* dlogits, void* dx, float* dw,
@@ -453,49 +508,45 @@ static int head1x1_bwd_impl(const void* x, const float* w, const float* dlogits,
                             float* db, int accumulate, long npix, int C, int K, int x_dtype, void* ws, size_t ws_bytes,
                             void* stream) {
   if (!x || !w || !dlogits || npix <= 0) return CY_ERR_ARG;
-  if (C % 8 || K < 1 || K > KWIDE || (size_t)(K * C + K) * 4 > 60000) return CY_ERR_SHAPE;
+  cy_head_plan p;
+  const int rc = cy_head1x1_plan(npix, C, K, dx != nullptr, dw || db, &p);
+  if (rc != CY_OK) return rc;
   if (x_dtype != CY_BF16 && x_dtype != CY_F32 && x_dtype != CY_F16) return CY_ERR_DTYPE;
-  if (cy_head_wide_ok(C, K))
-    return cy_head_wide_bwd(x, w, dlogits, dx, dw, db, accumulate, npix, C, K, x_dtype, ws, ws_bytes, stream);
+  if (p.fwd_kernel == 2)
+    return cy_head_wide_bwd(x, w, dlogits, dx, dw, db, accumulate, npix, C, K, x_dtype, dx ? p.dx_grid : p.dw_blocks, ws,
+                            ws_bytes, stream);
   hipStream_t st = (hipStream_t)stream;
   if (dx) {
-    const long total = npix * (C / 8);
-    long b = (total + 255) / 256;
-    if (b > 4096) b = 4096;
+    const int grid = p.dx_grid;
     const size_t smem = (size_t)K * C * sizeof(float);
-    if (K > KMAX && K % 4 == 0 && C % 32 == 0) {
-      long bw = (npix * (C / 32) + 255) / 256;
-      if (bw > 8192) bw = 8192;
+    if (p.dx_kernel == 1) {
       if (x_dtype == CY_BF16)
-        hipLaunchKernelGGL(head_bwd_dx_wide_kernel<bf16>, dim3((int)bw), dim3(256), smem, st, dlogits,
+        hipLaunchKernelGGL(head_bwd_dx_wide_kernel<bf16>, dim3(grid), dim3(256), smem, st, dlogits,
                            w, (bf16*)dx, npix, C, K);
       else if (x_dtype == CY_F16)
-        hipLaunchKernelGGL(head_bwd_dx_wide_kernel<f16>, dim3((int)bw), dim3(256), smem, st, dlogits,
+        hipLaunchKernelGGL(head_bwd_dx_wide_kernel<f16>, dim3(grid), dim3(256), smem, st, dlogits,
                            w, (f16*)dx, npix, C, K);
       else
-        hipLaunchKernelGGL(head_bwd_dx_wide_kernel<float>, dim3((int)bw), dim3(256), smem, st, dlogits,
+        hipLaunchKernelGGL(head_bwd_dx_wide_kernel<float>, dim3(grid), dim3(256), smem, st, dlogits,
                            w, (float*)dx, npix, C, K);
     } else if (x_dtype == CY_BF16)
-      hipLaunchKernelGGL(head_bwd_dx_kernel<bf16>, dim3((int)b), dim3(256), smem, st, dlogits, w,
+      hipLaunchKernelGGL(head_bwd_dx_kernel<bf16>, dim3(grid), dim3(256), smem, st, dlogits, w,
                          (bf16*)dx, npix, C, K);
     else if (x_dtype == CY_F16)
-      hipLaunchKernelGGL(head_bwd_dx_kernel<f16>, dim3((int)b), dim3(256), smem, st, dlogits, w,
+      hipLaunchKernelGGL(head_bwd_dx_kernel<f16>, dim3(grid), dim3(256), smem, st, dlogits, w,
                          (f16*)dx, npix, C, K);
     else
-      hipLaunchKernelGGL(head_bwd_dx_kernel<float>, dim3((int)b), dim3(256), smem, st, dlogits, w,
+      hipLaunchKernelGGL(head_bwd_dx_kernel<float>, dim3(grid), dim3(256), smem, st, dlogits, w,
                          (float*)dx, npix, C, K);
     CY_CHECK_LAUNCH();
   }
   if (dw || db) {
-    if (!ws || ws_bytes < cy_head1x1_bwd_ws_bytes(npix, C, K)) return CY_ERR_WORKSPACE;
-    const int nblk = head_dw_blocks(npix);
-    const int G = C / 8;
-    const int gpp = G < 256 ? G : 256;
-    if (G > 256) return CY_ERR_SHAPE;
-    const int rows = 256 / gpp;
+    if (!ws || ws_bytes < head_ws_bytes(p, C, K)) return CY_ERR_WORKSPACE;
+    const int nblk = p.dw_blocks;
+    const int gpp = C / 8, rows = p.dw_rows;
     const size_t smem = (size_t)(rows * gpp * 32 + rows * 4) * sizeof(float);
     const bool h = x_dtype == CY_BF16;
-    if (K <= KMAX) {
+    if (p.dw_group == 4) {
       if (h)
         hipLaunchKernelGGL((head_bwd_dw_kernel<bf16, 4>), dim3(nblk), dim3(256), smem, st,
                            (const bf16*)x, dlogits, (float*)ws, npix, C, K);

@@ -11,7 +11,7 @@ from pathlib import Path
 
 CY_F32, CY_BF16, CY_F16 = 0, 1, 2
 CY_SRC_DIRECT, CY_SRC_POOL2, CY_SRC_UP2 = 0, 1, 2
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 _ERRORS = {-1: "CY_ERR_ARG (bad/NULL argument)", -2: "CY_ERR_SHAPE (unsupported shape)",
            -3: "CY_ERR_DTYPE (unsupported dtype)", -4: "CY_ERR_LAUNCH (HIP launch failed)",
@@ -51,6 +51,18 @@ class WgradPlan(C.Structure):
     """mirror of cy_wgrad_plan"""
     _fields_ = [(n, c_int32) for n in ("twelve", "wco", "wci", "wk", "th", "tw", "splits", "workgroups", "dma",
                                                "blk_order")]
+
+
+class HeadPlan(C.Structure):
+    """mirror of cy_head_plan"""
+    _fields_ = [(n, c_int32) for n in ("fwd_kernel", "fwd_waves", "fwd_quads", "fwd_grid", "dx_kernel", "dx_grid",
+                                       "dw_group", "dw_vec_groups", "dw_scalar_groups", "dw_blocks", "dw_rows",
+                                       "fwd_trips", "dx_trips", "dw_per")]
+
+
+class ClusterPlan(C.Structure):
+    """mirror of cy_cluster_plan"""
+    _fields_ = [(n, c_int32) for n in ("fwd_waves", "fwd_grid", "fwd_trips", "bwd_grid", "bwd_trips", "slabs")]
 
 
 class WgradReduceEntry(C.Structure):
@@ -178,6 +190,7 @@ _SIGS = {
     "cy_upsample2_bwd": (c_int, [_P, c_int, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "cy_head1x1_fwd": (c_int, [_P, _P, _P, _P, c_long, c_int, c_int, c_int, _P]),
     "cy_head1x1_bwd_ws_bytes": (c_size_t, [c_long, c_int, c_int]),
+    "cy_head1x1_plan": (c_int, [c_long, c_int, c_int, c_int, c_int, POINTER(HeadPlan)]),
     "cy_head1x1_bwd": (c_int, [_P, _P, _P, _P, _P, _P, c_long, c_int, c_int, c_int, _P, c_size_t,
                                _P]),
     "cy_head1x1_bwd_into": (c_int, [_P, _P, _P, _P, _P, _P, c_long, c_int, c_int, c_int, _P, c_size_t,
@@ -243,6 +256,7 @@ _SIGS = {
     "cy_gather_rows_bwd": (c_int, [_P, _P, _P, c_int, c_int, _P]),
     "cy_cluster_head_fwd": (c_int, [_P, _P, _P, _P, c_long, c_int, c_int, c_int, c_int, c_float, c_int, _P]),
     "cy_cluster_head_bwd_ws_bytes": (c_size_t, [c_long, c_int]),
+    "cy_cluster_head_plan": (c_int, [c_long, c_int, c_int, c_int, POINTER(ClusterPlan)]),
     "cy_cluster_head_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_long, c_int, c_int, c_int, c_int, c_float, c_int, _P,
                                     c_size_t, _P]),
     "cy_group_softmax_fwd": (c_int, [_P, _P, c_long, c_int, c_int, c_float, _P]),

@@ -1406,6 +1406,17 @@ def head_fwd(x: Tensor, w: Tensor, b: Optional[Tensor]) -> Tensor:
     return logits
 
 
+def head_plan(npix: int, C_in: int, K: int, need_dx: bool = True, need_dw: bool = True) -> dict:
+    """the launch plan of cy_head1x1_fwd / _bwd for npix pixels, C_in channels, K outputs (host-side query, no GPU
+    needed): the fields of cy_head_plan, and "ws_bytes", the backward's workspace (0 without need_dw).  Shapes the
+    kernels refuse raise HipKernelError (CY_ERR_SHAPE)."""
+    p = _lib.HeadPlan()
+    _lib.call("cy_head1x1_plan", int(npix), int(C_in), int(K), int(bool(need_dx)), int(bool(need_dw)), C.byref(p))
+    out = {f: getattr(p, f) for f, _ in p._fields_}
+    out["ws_bytes"] = int(_lib.load().cy_head1x1_bwd_ws_bytes(int(npix), int(C_in), int(K))) if need_dw else 0
+    return out
+
+
 def head_bwd(x: Tensor, w: Tensor, dlogits: Tensor, need_dx: bool, need_dw: bool,
              dw_into: Optional[Tensor] = None, db_into: Optional[Tensor] = None):
     """(dx, dw, db); with dw_into (and db_into for a head with bias) the parameter gradients are ADDED into those live
@@ -1952,6 +1963,14 @@ def gather_rows_bwd(dout: Tensor, idx: Tensor, rows: int) -> Tensor:
 # --------------------------------------------------------------------------- cluster heads / discrete MI
 def cluster_head_ok(C: int, S: int, k: int) -> bool:
     return C in (32, 64) and S * k <= 128 and k <= 32
+
+
+def cluster_head_plan(M: int, C_in: int, S: int, k: int) -> dict:
+    """the launch shape of cy_cluster_head_fwd / _bwd (host-side query, no GPU needed): fwd_waves, fwd_grid, fwd_trips,
+    bwd_grid, bwd_trips, slabs"""
+    p = _lib.ClusterPlan()
+    _lib.call("cy_cluster_head_plan", int(M), int(C_in), int(S), int(k), C.byref(p))
+    return {f: getattr(p, f) for f, _ in p._fields_}
 
 
 def cluster_head_fwd(x: Tensor, w: Tensor, b: Optional[Tensor], S: int, k: int, T: float = 1.0) -> Tensor:

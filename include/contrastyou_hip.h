@@ -438,6 +438,31 @@ int cy_head1x1_bwd_into(const void* x, const float* w, const float* dlogits, voi
                         float* db, long npix, int C, int K, int x_dtype, void* ws, size_t ws_bytes,
                         void* stream);
 
+/* Launch plan of the 1x1 head (ABI v16): everything cy_head1x1_fwd / _bwd / _bwd_into decide from (npix, C, K) and from
+ * which gradients are asked for.  Host-side only, launches nothing.  The launches and cy_head1x1_bwd_ws_bytes take
+ * their kernel, grid and workspace size from this function.  CY_ERR_SHAPE exactly where the launches refuse: C % 8,
+ * K outside 1 .. 128, (K*C + K) * 4 > 60000 bytes of LDS weights, C > 2048 with a parameter gradient on the VALU path.
+ * Without need_dx: dx_kernel -1, dx_grid and dx_trips 0; without need_dw: every dw_* field 0. */
+typedef struct cy_head_plan {
+  int32_t fwd_kernel;       /* 0: head_fwd_kernel<T,16> (K <= 16), 1: head_fwd_kernel<T,128>, 2: matrix cores (LINEAR mode of
+                               cluster_head_fwd_kernel; 16 < K <= 128 over 32 / 64 channels) */
+  int32_t fwd_waves;        /* matrix cores: 8 or 4 waves per block; 0 on the VALU kernels */
+  int32_t fwd_quads;        /* matrix cores: 1 when K % 4 == 0 (16-byte stores of the logits tile), else 0 */
+  int32_t fwd_grid;         /* blocks */
+  int32_t dx_kernel;        /* 0: head_bwd_dx_kernel (8 channels per thread), 1: head_bwd_dx_wide_kernel (32 channels per
+                               thread), 2: matrix cores (cluster_head_bwd_kernel, LINEAR), -1: none */
+  int32_t dx_grid;          /* blocks (matrix cores: of the one backward launch, which also gives dW) */
+  int32_t dw_group;         /* head_bwd_dw_kernel<T,4> or <T,16>: outputs per pass over the pixels; 0 on the matrix cores */
+  int32_t dw_vec_groups;    /* how many of the ceil(K / dw_group) passes load their dlogits as 16-byte vectors ... */
+  int32_t dw_scalar_groups; /* ... and how many one float at a time (K % 4 != 0, or the partial last group) */
+  int32_t dw_blocks;        /* blocks = rows of partial sums in the workspace (matrix cores: four slabs per block) */
+  int32_t dw_rows;          /* VALU: pixel rows per block, 256 / min(C/8, 256); 0 on the matrix cores */
+  int32_t fwd_trips;        /* the most trips any thread (VALU) or wave (matrix cores) makes round its grid-stride loop */
+  int32_t dx_trips;         /* the same for the data gradient */
+  int32_t dw_per;           /* pixels per dW block: ceil(npix / dw_blocks); matrix cores: 128 per trip of a block */
+} cy_head_plan;
+int cy_head1x1_plan(long npix, int C, int K, int need_dx, int need_dw, cy_head_plan* out);
+
 /* ------------------------------------------------------------------------
  * Supervised loss  KL_div(softmax(logits), one_hot(target))
  * (semi_seg/epochers/epocher.py:317-318, contrastyou/losses/kl.py:112-125,
@@ -735,6 +760,16 @@ size_t cy_cluster_head_bwd_ws_bytes(long M, int C);
 int cy_cluster_head_bwd(const void* x, const float* w, const float* probs, const float* dprobs, void* dx, float* dw,
                         float* db, long M, int C, int K, int S, int k, float invT, int dtype, void* ws,
                         size_t ws_bytes, void* stream);
+/* Launch shape of the two kernels above (ABI v16; host-side only, launches nothing; CY_ERR_SHAPE as the launches). */
+typedef struct cy_cluster_plan {
+  int32_t fwd_waves;  /* 8 where eight waves' tiles fit the LDS next to the weights, else 4 */
+  int32_t fwd_grid;   /* blocks, at most 256 */
+  int32_t fwd_trips;  /* the most 32-pixel tiles a wave takes */
+  int32_t bwd_grid;   /* blocks of four waves, at most 512 */
+  int32_t bwd_trips;
+  int32_t slabs;      /* per-wave dW / db slabs in the workspace */
+} cy_cluster_plan;
+int cy_cluster_head_plan(long M, int C, int S, int k, cy_cluster_plan* out);
 
 /* logits [M][S*k] -> probs [S][M][k] = softmax(logits*invT) within each of the
  * S sub-heads (SoftmaxWithT, projectors/nn.py:35-44); S=1 is a row softmax. */

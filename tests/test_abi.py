@@ -89,6 +89,25 @@ def test_wgrad_plan_layout_matches_header():
     assert ctypes.sizeof(WgradPlan) == 4 * len(fields)
 
 
+@pytest.mark.parametrize("struct,mirror", [("cy_head_plan", "HeadPlan"), ("cy_cluster_plan", "ClusterPlan")])
+def test_head_plan_layouts_match_header(struct, mirror):
+    """cy_head_plan / cy_cluster_plan (ABI v16) and their ctypes mirrors name the same int32 fields in order"""
+    from cyhip import _lib
+    cls = getattr(_lib, mirror)
+    text = HEADER.read_text()
+    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), text, flags=re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    fields = []
+    for decl in body.split(";"):
+        decl = decl.strip()
+        if decl:
+            assert decl.startswith("int32_t "), decl
+            fields += [f.strip() for f in decl[len("int32_t "):].split(",")]
+    assert fields == [n for n, _ in cls._fields_]
+    assert ctypes.sizeof(cls) == 4 * len(fields)
+    assert _lib.ABI_VERSION == 16
+
+
 def test_loading_the_library_first_leaves_one_hip_runtime():
     """a process that loads the library before it imports torch (__graft_entry__.build() followed by smoke() does) must
     not end up with two HIP runtimes mapped -- the system's and the copy in torch's wheel: launches on torch's streams
