@@ -615,60 +615,101 @@ __global__ void __launch_bounds__(768, 1)
 }
 
 // One workgroup (256 threads) of the slab sum of a layer: `block` is its index in the layer's grid, sred 256 x 36 floats.
-__device__ __forceinline__ void wgrad_reduce_block(const float* __restrict__ ws, float* __restrict__ dw, int S, int SG,
-                                                   int Cout, int Cin, int co_pad, int ci_pad, int accumulate, int block,
-                                                   float* sred) {
-  // thread = four consecutive ci of one co (16-byte slab reads, 36 contiguous output floats) x one
-  // of SG slab groups.  Group g sums slabs g, g+SG, ... in increasing order, then the SG group sums
-  // are added in group order: the summation tree is a function of (S, SG) only => bitwise reproducible.
-  const int opb = 256 / SG;
-  const int ol = threadIdx.x % opb, sg = threadIdx.x / opb;
+// Summing phase: thread = four consecutive ci of one co (16-byte slab reads) x one of SG slab groups.  Group g sums
+// slabs g, g+SG, ... in increasing order, then the SG group sums are added in group order: the summation tree is a
+// function of (S, SG) only => bitwise reproducible.
+// The workgroup is bound by latency, not by bytes (36 KB of slabs per trip to memory, four workgroups per CU), so the
+// trips are what is kept short:
+//  * the slabs are read once: streaming loads.  (A second slab in flight per thread -- 18 loads before the first add
+//    -- takes 170 vector registers, two workgroups per CU instead of four, and was slower: 4.1 against 4.6 TB/s over
+//    the slabs of a C2 step);
+//  * the old dW of an accumulating entry is requested before the slabs, not after the sum;
+//  * every group sum goes through LDS and ALL threads add the groups -- the workgroup's outputs are one contiguous run
+//    of opb x 36 floats of dW ([co][ci][tap], four ci x nine taps per summing thread), one float per thread and
+//    round: coalesced reads and writes instead of 36 floats per thread at a 144-byte stride, and a group chain of
+//    SG LDS reads per thread instead of 36 x SG on the 256 / SG threads of group 0.
+template <int SG>
+__device__ __forceinline__ void wgrad_reduce_block_sg(const float* __restrict__ ws, float* __restrict__ dw, int S,
+                                                      int Cout, int Cin, int co_pad, int ci_pad, int accumulate,
+                                                      int block, float* sred) {
+  constexpr int opb = 256 / SG;
+  constexpr int NOUT = opb * 36;            // floats of dW per workgroup
+  constexpr int KO = (NOUT + 255) / 256;    // ... per thread
+  const int tid = threadIdx.x;
+  const int ol = tid % opb, sg = tid / opb;
   const int Q = Cin / 4;
   const long total = (long)Cout * Q;
-  const long i = (long)block * opb + ol;
+  const long i0 = (long)block * opb;
+  const long i = i0 + ol;
   const size_t slab = (size_t)9 * co_pad * ci_pad;
   const size_t tapstride = (size_t)co_pad * ci_pad;
+  // output i = (co, four ci) owns dw[36 i .. 36 i + 35]: the workgroup's outputs are dw[36 i0 .. 36 i0 + nout)
+  const int nout = (int)(total - i0 < opb ? total - i0 : opb) * 36;
+  float* o = dw + (size_t)i0 * 36;
+  constexpr int KP = KO <= 9 ? KO : 0;      // old values requested ahead (SG < 4, which no 16-bit layer gets: late)
+  float old[KP > 0 ? KP : 1];
+#pragma unroll
+  for (int k = 0; k < KP; ++k) {
+    const int f = tid + k * 256;
+    old[k] = (accumulate && f < nout) ? o[f] : 0.f;
+  }
   f32x4 s[9];
 #pragma unroll
   for (int t = 0; t < 9; ++t) s[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const int co = i < total ? (int)(i / Q) : 0;
-  const int ci = i < total ? (int)(i % Q) * 4 : 0;
   if (i < total) {
-    const size_t off = (size_t)co * ci_pad + ci;
-    for (int q = sg; q < S; q += SG) {
-      const float* p = ws + q * slab + off;
+    const int co = (int)(i / Q), ci = (int)(i % Q) * 4;
+    // address = wave-uniform base (slab group round, tap) + one 32-bit byte offset per thread (group, output; the host
+    // checks SG slabs < 2 GiB)
+    const unsigned voff = (unsigned)(((size_t)sg * slab + (size_t)co * ci_pad + ci) * sizeof(float));
+    const char* p = reinterpret_cast<const char*>(ws);
+    const size_t step = (size_t)SG * slab * sizeof(float), tapb = tapstride * sizeof(float);
+    // rounds of SG slabs (the count is uniform, so the base stays in scalar registers); only the last round can be
+    // short of slabs for the higher groups
+    const int R = (S + SG - 1) / SG;
+    for (int r = 0; r < R; ++r, p += step) {
+      if (sg + r * SG >= S) break;
+      u32x4 a[9];
 #pragma unroll
-      for (int t = 0; t < 9; ++t) s[t] += *reinterpret_cast<const f32x4*>(p + t * tapstride);
+      for (int t = 0; t < 9; ++t) a[t] = ld16_nt(p + t * tapb + voff);
+#pragma unroll
+      for (int t = 0; t < 9; ++t) s[t] += __builtin_bit_cast(f32x4, a[t]);
     }
   }
-  if (SG > 1) {
+  // sred[group][output of the workgroup][tap][ci]
 #pragma unroll
-    for (int t = 0; t < 9; ++t)
+  for (int t = 0; t < 9; ++t) *reinterpret_cast<f32x4*>(sred + (sg * opb + ol) * 36 + t * 4) = s[t];
+  __syncthreads();
 #pragma unroll
-      for (int j = 0; j < 4; ++j) sred[(sg * opb + ol) * 36 + t * 4 + j] = s[t][j];
-    __syncthreads();
-    if (sg == 0) {
-      for (int g = 1; g < SG; ++g)
+  for (int k = 0; k < KO; ++k) {
+    const int f = tid + k * 256;  // float f of the run: output f / 36, then [ci j][tap t]
+    if (f < nout) {
+      const int oo = f / 36, r = f - oo * 36, j = r / 9, t = r - j * 9;
+      const float* g0 = sred + oo * 36 + t * 4 + j;
+      float part[SG];
 #pragma unroll
-        for (int t = 0; t < 9; ++t)
+      for (int g = 0; g < SG; ++g) part[g] = g0[g * NOUT];
+      float v = part[0];
 #pragma unroll
-          for (int j = 0; j < 4; ++j) s[t][j] += sred[(g * opb + ol) * 36 + t * 4 + j];
+      for (int g = 1; g < SG; ++g) v += part[g];
+      o[f] = accumulate ? (k < KP ? old[k < KP ? k : 0] : o[f]) + v : v;
     }
-  }
-  if (sg == 0 && i < total) {
-    float* o = dw + ((size_t)co * Cin + ci) * 9;  // [co][ci][tap]: 4 ci x 9 taps contiguous
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int t = 0; t < 9; ++t) {
-        if (accumulate)
-          o[j * 9 + t] += s[t][j];
-        else
-          o[j * 9 + t] = s[t][j];
-      }
   }
 }
 
+__device__ __forceinline__ void wgrad_reduce_block(const float* __restrict__ ws, float* __restrict__ dw, int S, int SG,
+                                                   int Cout, int Cin, int co_pad, int ci_pad, int accumulate, int block,
+                                                   float* sred) {
+  switch (SG) {  // (uniform in the workgroup; a power of two <= 32: conv_reduce_entry, cy_wgrad_reduce_batched)
+    case 1: wgrad_reduce_block_sg<1>(ws, dw, S, Cout, Cin, co_pad, ci_pad, accumulate, block, sred); break;
+    case 2: wgrad_reduce_block_sg<2>(ws, dw, S, Cout, Cin, co_pad, ci_pad, accumulate, block, sred); break;
+    case 4: wgrad_reduce_block_sg<4>(ws, dw, S, Cout, Cin, co_pad, ci_pad, accumulate, block, sred); break;
+    case 8: wgrad_reduce_block_sg<8>(ws, dw, S, Cout, Cin, co_pad, ci_pad, accumulate, block, sred); break;
+    case 16: wgrad_reduce_block_sg<16>(ws, dw, S, Cout, Cin, co_pad, ci_pad, accumulate, block, sred); break;
+    default: wgrad_reduce_block_sg<32>(ws, dw, S, Cout, Cin, co_pad, ci_pad, accumulate, block, sred); break;
+  }
+}
+
+// (36 KB of LDS and ~100 vector registers: four workgroups per CU)
 __global__ void __launch_bounds__(256)
     wgrad_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dw, int S, int SG, int Cout,
                         int Cin, int co_pad, int ci_pad, int accumulate) {
@@ -1034,6 +1075,22 @@ int first_wgrad_blocks(long npix, int W) {
   return (int)b;
 }
 
+// raise the dynamic-LDS limit of the given kernels on the CURRENT device, once per device (the attribute belongs to the
+// device's copy of the kernel: a process-wide flag would leave every device but the first at 48 KB)
+template <auto... Kernels>
+bool lds_limit_per_device(int bytes) {
+  constexpr int kDevices = 64;
+  static bool done[kDevices] = {};
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess) return false;
+  const bool known = dev >= 0 && dev < kDevices;
+  if (known && done[dev]) return true;
+  const bool ok = ((hipFuncSetAttribute(reinterpret_cast<const void*>(Kernels), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        bytes) == hipSuccess) && ...);
+  if (known) done[dev] = ok;
+  return ok;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1191,6 +1248,7 @@ int cy_wgrad_reduce_batched(const cy_wgrad_reduce_entry* h_entries, int n, void*
         return CY_ERR_ARG;
       const long total = (long)e.Cout * (e.Cin / 4);
       if (e.blocks != (int)((total + 256 / e.SG - 1) / (256 / e.SG))) return CY_ERR_ARG;
+      if ((size_t)e.SG * 9 * e.co_pad * e.ci_pad * sizeof(float) >= ((size_t)1 << 31)) return CY_ERR_ARG;  // (32-bit thread offsets)
     } else if (e.kind == CY_WGRAD_REDUCE_FIRST) {
       if (e.SG != 64 || e.blocks != cy_cdiv(e.Cout * e.Cin * 9, 4)) return CY_ERR_ARG;
     } else {
@@ -1289,9 +1347,10 @@ static int first_wgrad_impl(const float* x, const void* dy, float* dw, int accum
   if (const int nm = first_wgrad_mfma_blocks(N, Cin, H, W, Cout, dy_dtype)) {
     const int nsub = N * H / 8, spb = (nsub + nm - 1) / nm;
     size_t smem = 4096 + (size_t)3 * 10 * W * 2;
+    if (smem > 160 * 1024) return CY_ERR_SHAPE;  // (four tiles + three shifted copies of ten image rows: 4096 + 60 W bytes of LDS)
     if (smem < 16384) smem = 16384;  // (the four waves' accumulators pass through it at the end)
     // (wide images: W > 730)
-    if (smem > 48 * 1024 && !cy_lds_limit_once<first_wgrad_mfma_kernel<bf16>, first_wgrad_mfma_kernel<f16>>(160 * 1024)) return CY_ERR_LAUNCH;
+    if (smem > 48 * 1024 && !lds_limit_per_device<first_wgrad_mfma_kernel<bf16>, first_wgrad_mfma_kernel<f16>>(160 * 1024)) return CY_ERR_LAUNCH;
     if (dy_dtype == CY_BF16)
       hipLaunchKernelGGL(first_wgrad_mfma_kernel<bf16>, dim3(nm), dim3(256), smem, st, x, (const bf16*)dy, (float*)ws, N, H, W, spb);
     else
