@@ -3,8 +3,10 @@ critic -- four Conv2d(4, 2, 1) and a closing Conv2d(4, 1, 0) to one channel, Bat
 
 `_main` holds the reference's own torch modules, so the state dict (keys, shapes, dtypes), `weights_init` and the
 random draws under a seed are the reference's; they are containers only.  `forward` never calls them: the five
-convolutions go through `cyhip.glue.Conv2dFn` (im2col + the f32 MFMA GEMM), everything else through the kernels of
-csrc/cy_disc.hip, NHWC f32 from the input to the score map.
+convolutions go through `Discriminator.conv` -- by default `cyhip.glue.Conv4x4Fn`, the implicit-GEMM kernels of
+csrc/cy_conv4x4.hip (no patch matrix); `conv_im2col` is the `cyhip.glue.Conv2dFn` form (im2col + strided GEMM + col2im)
+kept to compare against -- everything else through the kernels of csrc/cy_disc.hip, NHWC f32 from the input to the
+score map.
 
     scores(x)                          the pre-sigmoid map [N, 1, h, w]: what the fused sigmoid + BCE loss takes
     scores_from_logits(image, logits)  scores(cat([image, softmax(logits)], 1)) with the softmax + concat fused
@@ -19,9 +21,19 @@ from torch import Tensor, nn
 
 from cyhip import ops
 from cyhip.functions import BNLeakyReLUFn, LeakyReLUFn, SoftmaxCatFn
-from cyhip.glue import Conv2dFn
+from cyhip.glue import Conv2dFn, Conv4x4Fn
 
-__all__ = ["Discriminator", "weights_init"]
+__all__ = ["Discriminator", "weights_init", "conv_implicit", "conv_im2col"]
+
+
+def conv_implicit(x: Tensor, weight: Tensor, stride: int, pad: int) -> Tensor:
+    """the bias-free 4 x 4 convolution on the implicit-GEMM kernels (the default of `Discriminator.conv`)"""
+    return Conv4x4Fn.apply(x, weight, stride, pad)
+
+
+def conv_im2col(x: Tensor, weight: Tensor, stride: int, pad: int) -> Tensor:
+    """the same convolution through im2col + GEMM + col2im: `Discriminator.conv = staticmethod(conv_im2col)`"""
+    return Conv2dFn.apply(x, weight, None, stride, pad)
 
 
 def weights_init(m):
@@ -36,6 +48,7 @@ def weights_init(m):
 
 class Discriminator(nn.Module):
     SLOPE = 0.2
+    conv = staticmethod(conv_implicit)  # (x, weight, stride, pad) -> y; a class attribute, not an environment switch
 
     def __init__(self, input_dim, hidden_dim):
         super().__init__()
@@ -60,12 +73,12 @@ class Discriminator(nn.Module):
     def _trunk(self, x: Tensor, param_grads: bool) -> Tensor:
         m = self._main
         par = (lambda p: p) if param_grads else (lambda p: p.detach())
-        x = LeakyReLUFn.apply(Conv2dFn.apply(x, par(m[0].weight), None, 2, 1), self.SLOPE)
+        x = LeakyReLUFn.apply(self.conv(x, par(m[0].weight), 2, 1), self.SLOPE)
         for conv, bn in ((m[2], m[3]), (m[5], m[6]), (m[8], m[9])):
-            x = Conv2dFn.apply(x, par(conv.weight), None, 2, 1)
+            x = self.conv(x, par(conv.weight), 2, 1)
             x = BNLeakyReLUFn.apply(x, par(bn.weight), par(bn.bias), bn.running_mean, bn.running_var,
                                     bn.num_batches_tracked, self.training, bn.momentum, bn.eps, self.SLOPE)
-        return Conv2dFn.apply(x, par(m[11].weight), None, 1, 0)
+        return self.conv(x, par(m[11].weight), 1, 0)
 
     def scores(self, input_: Tensor, param_grads: bool = True) -> Tensor:
         """the map in front of the sigmoid.  `param_grads=False` runs the same arithmetic on detached parameters: the

@@ -316,6 +316,11 @@ _SIGS = {
     "cy_sigmoid_bce_ws_bytes": (c_size_t, [c_long]),
     "cy_sigmoid_bce_fwd": (c_int, [_P, c_float, _P, c_long, _P, c_size_t, _P]),
     "cy_sigmoid_bce_bwd": (c_int, [_P, c_float, _P, _P, c_long, _P]),
+    "cy_conv4x4_pack_weights": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
+    "cy_conv4x4_fwd": (c_int, [_P, _P, _P] + [c_int] * 8 + [_P]),
+    "cy_conv4x4_dgrad": (c_int, [_P, _P, _P] + [c_int] * 8 + [_P]),
+    "cy_conv4x4_wgrad_ws_bytes": (c_size_t, [c_int] * 8),
+    "cy_conv4x4_wgrad": (c_int, [_P, _P, _P] + [c_int] * 8 + [_P, c_size_t, _P]),
 }
 
 # functions whose int return is a count / size, not a status

@@ -15,7 +15,7 @@ from torch import Tensor
 from . import _lib, ops
 from ._lib import MatLayout
 
-__all__ = ["gemm", "LinearRowsFn", "Conv2dFn", "ConvTranspose2dFn", "ChanLayerNormFn", "LinearAttentionFn",
+__all__ = ["gemm", "LinearRowsFn", "Conv2dFn", "Conv4x4Fn", "ConvTranspose2dFn", "ChanLayerNormFn", "LinearAttentionFn",
            "AttentionFn", "rows_view"]
 
 
@@ -176,6 +176,38 @@ class Conv2dFn(torch.autograd.Function):
             gemm((dyr, 0), _rowmajor(Cout), (w2, 0), _rowmajor(K2), (dcols, 0), _rowmajor(K2), Mo, K2, Cout)
             dx = _as_nchw(dcols.view(N, H, W, Cin) if plain else _col2im(dcols, None, N, H, W, Cin, KH, KW, stride, pad))
         return dx, dweight, db, None, None
+
+
+class Conv4x4Fn(torch.autograd.Function):
+    """nn.Conv2d(Cin, Cout, 4, 2, 1, bias=False) / nn.Conv2d(Cin, Cout, 4, 1, 0, bias=False), NHWC f32, as implicit
+    GEMMs (csrc/cy_conv4x4.hip): no patch matrix forward or backward, no im2col / col2im launch.  Saves the input and
+    the weights; a gradient that is not needed costs no launch."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, weight: Tensor, stride: int, pad: int):
+        ops.require_gpu(x, weight)
+        xr = rows_view(x).contiguous()
+        w = _f32c(weight)
+        Cout, Cin, KH, KW = w.shape
+        if KH != KW or Cin != xr.shape[3]:
+            raise ValueError(f"weight {tuple(w.shape)} does not fit an input of {xr.shape[3]} channels")
+        y = ops.conv4x4_fwd(xr, ops.conv4x4_pack(w, False), Cout, KH, stride, pad)
+        ctx.save_for_backward(xr, w)
+        ctx.geom = (KH, stride, pad)
+        return _as_nchw(y)
+
+    @staticmethod
+    def backward(ctx, dy: Tensor):
+        xr, w = ctx.saved_tensors
+        ksize, stride, pad = ctx.geom
+        need = ctx.needs_input_grad
+        dyr = rows_view(dy).contiguous()
+        dx = dweight = None
+        if need[1]:
+            dweight = ops.conv4x4_wgrad(xr, dyr, ksize, stride, pad)
+        if need[0]:
+            dx = _as_nchw(ops.conv4x4_dgrad(dyr, ops.conv4x4_pack(w, True), tuple(xr.shape), ksize, stride, pad))
+        return dx, dweight, None, None
 
 
 class ConvTranspose2dFn(torch.autograd.Function):

@@ -2306,3 +2306,54 @@ def sigmoid_bce_bwd(scores: Tensor, label: float, gscale: Tensor) -> Tensor:
     _lib.call("cy_sigmoid_bce_bwd", scores.data_ptr(), float(label), gscale.data_ptr(), d.data_ptr(), scores.numel(),
               _stream())
     return d
+
+
+# --------------------------------------------------------------------------- the discriminator's 4 x 4 convolutions
+def conv4x4_out_hw(H: int, W: int, stride: int, pad: int) -> Tuple[int, int]:
+    return (H + 2 * pad - 4) // stride + 1, (W + 2 * pad - 4) // stride + 1
+
+
+def conv4x4_pack(w: Tensor, transposed: bool) -> Tensor:
+    """w: f32 [Cout, Cin, 4, 4] contiguous -> flat [Cout][kh][kw][Cin] (forward) or [Cin][kh][kw][Cout] (transposed:
+    what the data gradient reads); one launch"""
+    require_gpu(w)
+    Cout, Cin = w.shape[0], w.shape[1]
+    out = _f32(w.numel(), w.device)
+    _lib.call("cy_conv4x4_pack_weights", w.data_ptr(), out.data_ptr(), Cin, Cout, int(transposed), _stream())
+    return out
+
+
+def conv4x4_fwd(xr: Tensor, wp: Tensor, Cout: int, ksize: int, stride: int, pad: int) -> Tensor:
+    """xr: f32 [N, H, W, Cin] contiguous, wp from conv4x4_pack(w, False) -> y [N, Ho, Wo, Cout]; one launch"""
+    require_gpu(xr, wp)
+    N, H, W, Cin = xr.shape
+    Ho, Wo = conv4x4_out_hw(H, W, stride, pad)
+    y = torch.empty((N, max(Ho, 0), max(Wo, 0), Cout), dtype=torch.float32, device=xr.device)
+    _lib.call("cy_conv4x4_fwd", xr.data_ptr(), wp.data_ptr(), y.data_ptr(), N, H, W, Cin, Cout, ksize, stride, pad,
+              _stream())
+    return y
+
+
+def conv4x4_dgrad(dyr: Tensor, wpt: Tensor, x_shape, ksize: int, stride: int, pad: int) -> Tensor:
+    """dyr: f32 [N, Ho, Wo, Cout] contiguous, wpt from conv4x4_pack(w, True), x_shape = (N, H, W, Cin) -> dx of that
+    shape, every element written; one launch"""
+    require_gpu(dyr, wpt)
+    N, H, W, Cin = x_shape
+    dx = torch.empty((N, H, W, Cin), dtype=torch.float32, device=dyr.device)
+    _lib.call("cy_conv4x4_dgrad", dyr.data_ptr(), wpt.data_ptr(), dx.data_ptr(), N, H, W, Cin, dyr.shape[3], ksize,
+              stride, pad, _stream())
+    return dx
+
+
+def conv4x4_wgrad(xr: Tensor, dyr: Tensor, ksize: int, stride: int, pad: int) -> Tensor:
+    """xr [N, H, W, Cin], dyr [N, Ho, Wo, Cout], both f32 contiguous -> dw [Cout, Cin, 4, 4]; two launches, the
+    partial sums of the output-position ranges are added in a fixed order"""
+    require_gpu(xr, dyr)
+    N, H, W, Cin = xr.shape
+    Cout = dyr.shape[3]
+    nbytes = _lib.load().cy_conv4x4_wgrad_ws_bytes(N, H, W, Cin, Cout, ksize, stride, pad)
+    ws = _ws(nbytes, xr.device)
+    dw = torch.empty((Cout, Cin, 4, 4), dtype=torch.float32, device=xr.device)
+    _lib.call("cy_conv4x4_wgrad", xr.data_ptr(), dyr.data_ptr(), dw.data_ptr(), N, H, W, Cin, Cout, ksize, stride, pad,
+              ws.data_ptr(), nbytes, _stream())
+    return dw

@@ -973,6 +973,39 @@ int cy_sigmoid_bce_fwd(const float* scores, float label, float* loss, long n, vo
                        void* stream);
 int cy_sigmoid_bce_bwd(const float* scores, float label, const float* gscale, float* dscores, long n, void* stream);
 
+/* ------------------------------------------------------------------------
+ * The discriminator's convolutions (contrastyou/arch/discriminator.py:22-40 of the reference: nn.Conv2d(Cin, Cout, 4,
+ * 2, 1, bias=False) four times and nn.Conv2d(Cin, 1, 4, 1, 0, bias=False)) as implicit GEMMs on the f32 MFMA
+ * (csrc/cy_conv4x4.hip; 5 entries added to ABI v16 -- no existing signature changed, so cy_abi_version() stays 16).
+ * f32, NHWC: x [N][H][W][Cin], y / dy [N][Ho][Wo][Cout], Ho = (H + 2 pad - 4) / stride + 1.  No patch matrix is
+ * written and there is no im2col / col2im launch.  Every entry checks its arguments before any launch: a NULL
+ * pointer, a size < 1, Cin or Cout above 2^20, or N * H * W above 2^31 - 1 (pixel indices are 32-bit, element offsets
+ * 64-bit) -> CY_ERR_ARG; (ksize, stride, pad) other than (4, 2, 1) and (4, 1, 0), or a padded input smaller than the
+ * kernel -> CY_ERR_SHAPE; a short workspace -> CY_ERR_WORKSPACE.  Rows are read 16 bytes at a time where the
+ * contiguous channel count is a multiple of 4 and the base is 16-byte aligned, 4 bytes at a time otherwise (chosen by
+ * that rule per call; a misaligned base is never read 16 bytes at a time).  Cout >= 32 runs the MFMA kernels, Cout <
+ * 32 VALU forms (the data gradient also for Cin < 32).  No floating-point atomics: two runs give the same bits.
+ * ------------------------------------------------------------------------ */
+/* w [Cout][Cin][4][4] (torch's layout) -> packed [Cout][kh][kw][Cin] (transposed == 0: what cy_conv4x4_fwd reads) or
+ * [Cin][kh][kw][Cout] (transposed != 0: what cy_conv4x4_dgrad reads).  One launch. */
+int cy_conv4x4_pack_weights(const float* w, float* packed, int Cin, int Cout, int transposed, void* stream);
+/* y = conv(x, w); wp packed with transposed == 0.  One launch. */
+int cy_conv4x4_fwd(const float* x, const float* wp, float* y, int N, int H, int W, int Cin, int Cout, int ksize,
+                   int stride, int pad, void* stream);
+/* dx [N][H][W][Cin] from dy, every element written (zero where no output reaches it); wpt packed with transposed
+ * != 0.  Stride 2: four gather GEMMs over the 2 x 2 taps of each (h, w) parity class, in one launch. */
+int cy_conv4x4_dgrad(const float* dy, const float* wpt, float* dx, int N, int H, int W, int Cin, int Cout, int ksize,
+                     int stride, int pad, void* stream);
+/* dw [Cout][Cin][4][4] from x and dy.  The M = N * Ho * Wo output positions are split into `splits` ranges whose f32
+ * partial sums go through ws and are added in ascending order by a second launch.
+ *   ws_bytes = 4 * splits * Cout * 16 * Cin,  splits = max(1, min(ceil(256 / tiles), ceil(M / rows_min), 256)),
+ *   Cout >= 32: tiles = ceil(Cout / 128) * ceil(16 * Cin / 128), rows_min = 512;
+ *   Cout <  32: tiles = ceil(Cout * 16 * Cin / 256),             rows_min = 64
+ * (0 where the launch would refuse its arguments).  Two launches. */
+size_t cy_conv4x4_wgrad_ws_bytes(int N, int H, int W, int Cin, int Cout, int ksize, int stride, int pad);
+int cy_conv4x4_wgrad(const float* x, const float* dy, float* dw, int N, int H, int W, int Cin, int Cout, int ksize,
+                     int stride, int pad, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
