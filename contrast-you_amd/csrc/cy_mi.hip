@@ -62,13 +62,14 @@ __global__ void __launch_bounds__(256)
 // dlogits[m][s*k+i] = invT * p_i * (dp_i - sum_j p_j dp_j)
 __global__ void __launch_bounds__(256)
     group_softmax_bwd_kernel(const float* __restrict__ p, const float* __restrict__ dp,
-                             float* __restrict__ dlogits, long M, int S, int k, float invT) {
-  extern __shared__ float tile[];  // p then dp: 2 x [GS_PB][S*k + 1]
+                             float* __restrict__ dlogits, long M, int S, int k, float invT, int PB) {
+  extern __shared__ float tile[];  // p then dp: 2 x [PB][S*k + 1]; PB = GS_PB, or GS_PB / 2 where two such tiles
+                                   // exceed 64 KB (S*k > 127)
   const int SK = S * k, pitch = SK + 1;
   float* tp = tile;
-  float* td = tile + GS_PB * pitch;
-  const long m0 = (long)blockIdx.x * GS_PB;
-  const int rows = (int)min((long)GS_PB, M - m0);
+  float* td = tile + PB * pitch;
+  const long m0 = (long)blockIdx.x * PB;
+  const int rows = (int)min((long)PB, M - m0);
   for (int s = 0; s < S; ++s) {
     const float* sp = p + ((long)s * M + m0) * k;
     const float* sd = dp + ((long)s * M + m0) * k;
@@ -336,36 +337,53 @@ __global__ void __launch_bounds__(256)
 // ---------------------------------------------------------------- joint backward
 // which = 0: dx1[pix][i] = g*scale * sum_{d,j} dJ[d][i][j] * x2[pix - disp(d)][j]
 // which = 1: dx2[pix][j] = g*scale * sum_{d,i} dJ[d][i][j] * x1[pix + disp(d)][i]
+// dJ is staged in LDS dchunk displacements at a time (the launch plan: as many as fit 64 KB).  With one chunk, which is
+// every padding-0 launch and padding 1 up to k = 42, it is staged once per block; otherwise once per chunk and trip of
+// the grid-stride loop, whose trip count is the same for every thread of a block (the barriers are block-uniform).
 __global__ void __launch_bounds__(256)
     joint_bwd_kernel(const float* __restrict__ other, const float* __restrict__ dJ,
                      const float* __restrict__ gscale, float* __restrict__ dx, int N, int H, int W,
-                     int k, int pad, float scale, int which) {
-  extern __shared__ float sdj[];  // [T*T][k][k]
-  const int T = 2 * pad + 1, TT = T * T;
-  for (int e = threadIdx.x; e < TT * k * k; e += 256) sdj[e] = dJ[e];
-  __syncthreads();
+                     int k, int pad, float scale, int which, int dchunk) {
+  extern __shared__ float sdj[];  // [min(dchunk, T*T)][k][k]
+  const int T = 2 * pad + 1, TT = T * T, kk = k * k;
+  const bool once = dchunk >= TT;
+  if (once) {
+    for (int e = threadIdx.x; e < TT * kk; e += 256) sdj[e] = dJ[e];
+    __syncthreads();
+  }
   const float g = gscale[0] * scale;
   const long total = (long)N * H * W * k;
-  for (long e = blockIdx.x * 256L + threadIdx.x; e < total; e += (long)gridDim.x * 256L) {
+  for (long base = blockIdx.x * 256L; base < total; base += (long)gridDim.x * 256L) {
+    const long e = base + threadIdx.x;
+    const bool live = e < total;
     const int c = (int)(e % k);
     const long pix = e / k;
     const int w = (int)(pix % W);
     const int h = (int)((pix / W) % H);
     float s = 0.f;
-    for (int d = 0; d < TT; ++d) {
-      const int du = d / T - pad, dv = d % T - pad;
-      const int hh = which ? h + du : h - du, ww = which ? w + dv : w - dv;
-      if (hh < 0 || hh >= H || ww < 0 || ww >= W) continue;
-      const long q = which ? pix + (long)du * W + dv : pix - (long)du * W - dv;
-      const float* o = other + q * k;
-      const float* m = sdj + d * k * k;
-      if (which) {
-        for (int i = 0; i < k; ++i) s = fmaf(m[i * k + c], o[i], s);
-      } else {
-        for (int j = 0; j < k; ++j) s = fmaf(m[c * k + j], o[j], s);
+    for (int d0 = 0; d0 < TT; d0 += dchunk) {
+      const int d1 = d0 + dchunk < TT ? d0 + dchunk : TT;
+      if (!once) {
+        __syncthreads();
+        for (int q = threadIdx.x; q < (d1 - d0) * kk; q += 256) sdj[q] = dJ[(size_t)d0 * kk + q];
+        __syncthreads();
+      }
+      if (!live) continue;
+      for (int d = d0; d < d1; ++d) {
+        const int du = d / T - pad, dv = d % T - pad;
+        const int hh = which ? h + du : h - du, ww = which ? w + dv : w - dv;
+        if (hh < 0 || hh >= H || ww < 0 || ww >= W) continue;
+        const long q = which ? pix + (long)du * W + dv : pix - (long)du * W - dv;
+        const float* o = other + q * k;
+        const float* m = sdj + (d - d0) * kk;
+        if (which) {
+          for (int i = 0; i < k; ++i) s = fmaf(m[i * k + c], o[i], s);
+        } else {
+          for (int j = 0; j < k; ++j) s = fmaf(m[c * k + j], o[j], s);
+        }
       }
     }
-    dx[e] = g * s;
+    if (live) dx[e] = g * s;
   }
 }
 
@@ -373,47 +391,63 @@ __global__ void __launch_bounds__(256)
 __global__ void __launch_bounds__(256)
     joint_bwd4_kernel(const float* __restrict__ other, const float* __restrict__ dJ,
                       const float* __restrict__ gscale, float* __restrict__ dx, int N, int H, int W,
-                      int k, int pad, float scale, int which) {
-  extern __shared__ __attribute__((aligned(16))) float sdj[];  // [T*T][k][k]
-  const int T = 2 * pad + 1, TT = T * T, k4 = k >> 2;
-  for (int e = threadIdx.x; e < TT * k * k; e += 256) sdj[e] = dJ[e];
-  __syncthreads();
+                      int k, int pad, float scale, int which, int dchunk) {
+  extern __shared__ __attribute__((aligned(16))) float sdj[];  // [min(dchunk, T*T)][k][k]
+  const int T = 2 * pad + 1, TT = T * T, k4 = k >> 2, kk = k * k;
+  const bool once = dchunk >= TT;
+  if (once) {
+    for (int e = threadIdx.x; e < TT * kk; e += 256) sdj[e] = dJ[e];
+    __syncthreads();
+  }
   const float g = gscale[0] * scale;
   const long total = (long)N * H * W * k4;
-  for (long e = blockIdx.x * 256L + threadIdx.x; e < total; e += (long)gridDim.x * 256L) {
+  for (long base = blockIdx.x * 256L; base < total; base += (long)gridDim.x * 256L) {
+    const long e = base + threadIdx.x;
+    const bool live = e < total;
     const int c = (int)(e % k4) * 4;
     const long pix = e / k4;
     const int w = (int)(pix % W);
     const int h = (int)((pix / W) % H);
     f32x4 s = {0.f, 0.f, 0.f, 0.f};
-    for (int d = 0; d < TT; ++d) {
-      const int du = d / T - pad, dv = d % T - pad;
-      const int hh = which ? h + du : h - du, ww = which ? w + dv : w - dv;
-      if (hh < 0 || hh >= H || ww < 0 || ww >= W) continue;
-      const long q = which ? pix + (long)du * W + dv : pix - (long)du * W - dv;
-      const float* o = other + q * k;
-      const float* m = sdj + d * k * k;
-      for (int j4 = 0; j4 < k4; ++j4) {
-        const f32x4 ov = *reinterpret_cast<const f32x4*>(o + 4 * j4);
-        if (which) {  // s[c..c+3] += sum_i M[i][c..c+3] * o[i]
+    for (int d0 = 0; d0 < TT; d0 += dchunk) {
+      const int d1 = d0 + dchunk < TT ? d0 + dchunk : TT;
+      if (!once) {
+        __syncthreads();
+        for (int q = threadIdx.x; q < (d1 - d0) * kk; q += 256) sdj[q] = dJ[(size_t)d0 * kk + q];
+        __syncthreads();
+      }
+      if (!live) continue;
+      for (int d = d0; d < d1; ++d) {
+        const int du = d / T - pad, dv = d % T - pad;
+        const int hh = which ? h + du : h - du, ww = which ? w + dv : w - dv;
+        if (hh < 0 || hh >= H || ww < 0 || ww >= W) continue;
+        const long q = which ? pix + (long)du * W + dv : pix - (long)du * W - dv;
+        const float* o = other + q * k;
+        const float* m = sdj + (d - d0) * kk;
+        for (int j4 = 0; j4 < k4; ++j4) {
+          const f32x4 ov = *reinterpret_cast<const f32x4*>(o + 4 * j4);
+          if (which) {  // s[c..c+3] += sum_i M[i][c..c+3] * o[i]
 #pragma unroll
-          for (int t = 0; t < 4; ++t) {
-            const f32x4 mv = *reinterpret_cast<const f32x4*>(m + (4 * j4 + t) * k + c);
+            for (int t = 0; t < 4; ++t) {
+              const f32x4 mv = *reinterpret_cast<const f32x4*>(m + (4 * j4 + t) * k + c);
 #pragma unroll
-            for (int u = 0; u < 4; ++u) s[u] = fmaf(mv[u], ov[t], s[u]);
-          }
-        } else {  // s[c+u] += sum_j M[c+u][j] * o[j]
+              for (int u = 0; u < 4; ++u) s[u] = fmaf(mv[u], ov[t], s[u]);
+            }
+          } else {  // s[c+u] += sum_j M[c+u][j] * o[j]
 #pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const f32x4 mv = *reinterpret_cast<const f32x4*>(m + (c + u) * k + 4 * j4);
+            for (int u = 0; u < 4; ++u) {
+              const f32x4 mv = *reinterpret_cast<const f32x4*>(m + (c + u) * k + 4 * j4);
 #pragma unroll
-            for (int t = 0; t < 4; ++t) s[u] = fmaf(mv[t], ov[t], s[u]);
+              for (int t = 0; t < 4; ++t) s[u] = fmaf(mv[t], ov[t], s[u]);
+            }
           }
         }
       }
     }
-    f32x4 r = {g * s[0], g * s[1], g * s[2], g * s[3]};
-    *reinterpret_cast<f32x4*>(dx + pix * k + c) = r;
+    if (live) {
+      f32x4 r = {g * s[0], g * s[1], g * s[2], g * s[3]};
+      *reinterpret_cast<f32x4*>(dx + pix * k + c) = r;
+    }
   }
 }
 
@@ -560,16 +594,92 @@ inline int joint_blocks(long npix) {
   return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
 }
 
+constexpr int J_FWD_LDS = 150 * 1024;  // the staged tile of joint_fwd_multi_kernel (raised limit)
+constexpr int J_BWD_LDS = 64 * 1024;   // the dJ chunk of the backward kernels (default limit)
+constexpr int GS_LDS = 64 * 1024;      // the softmax tiles (default limit)
+
 }  // namespace
 
 extern "C" {
 
+// The launch rule of cy_joint_fwd / _bwd / _ws_bytes, once (the kernels recompute kp, nsl, per and nd from the same
+// arguments; everything the host decides is decided here).
+int cy_joint_plan(int N, int H, int W, int k, int pad, cy_joint_plan_t* out) {
+  if (!out || N <= 0 || H <= 0 || W <= 0) return CY_ERR_ARG;
+  if (k < 1 || k > J_KMAX || pad < 0 || pad >= H || pad >= W) return CY_ERR_SHAPE;
+  cy_joint_plan_t p = {};
+  const long npix = (long)N * H * W;
+  const int T = 2 * pad + 1, TT = T * T;
+  const int kp = (k + 3) & ~3, k4 = kp / 4, nsl = 256 / (k4 * k4);
+  p.kp = kp;
+  p.nsl = nsl;
+  p.idle = 256 - nsl * k4 * k4;
+  p.nblk = joint_blocks(npix);
+  p.reduce_trips = cy_cdiv(p.nblk, 64);
+  const size_t red = (size_t)nsl * kp * kp * sizeof(float);
+  // padding > 0: every displacement from one staged tile of R rows, if it fits the LDS
+  int R = 256 / W;
+  R = R < 1 ? 1 : (R > H ? H : R);
+  size_t smem_multi = ((size_t)(R + 2 * pad) * (W + 2 * pad) * kp + (size_t)R * W * kp) * sizeof(float);
+  if (smem_multi < red) smem_multi = red;
+  if (pad > 0 && smem_multi <= (size_t)J_FWD_LDS) {
+    p.fwd_kernel = 1;
+    p.fwd_vec = kp == k;
+    p.R = R;
+    p.tiles_h = cy_cdiv(H, R);
+    p.ntile = N * p.tiles_h;
+    p.grid_y = cy_cdiv(TT, JM_D);
+    p.nd_last = TT - (p.grid_y - 1) * JM_D;
+    p.fwd_lds = (int)smem_multi;
+  } else {
+    p.fwd_kernel = 0;
+    p.fwd_vec = pad == 0 && kp == k;
+    p.per = (int)(((npix + p.nblk - 1) / p.nblk + J_P - 1) / J_P * J_P);
+    p.ntile = cy_cdiv(npix, J_P);
+    p.grid_y = TT;
+    p.nd_last = 1;
+    p.fwd_lds = (int)(2 * J_P * kp * sizeof(float) + red);
+  }
+  p.bwd_kernel = (k & 3) == 0;
+  const long work = p.bwd_kernel ? npix * (k / 4) : npix * k;
+  p.bwd_grid = grid_for(work);
+  p.bwd_trips = cy_cdiv(work, 256L * p.bwd_grid);
+  const int fit = J_BWD_LDS / (k * k * (int)sizeof(float));  // >= 4 because k <= 64
+  p.bwd_dchunk = fit < TT ? fit : TT;
+  p.bwd_nchunk = cy_cdiv(TT, p.bwd_dchunk);
+  p.bwd_lds = p.bwd_dchunk * k * k * (int)sizeof(float);
+  *out = p;
+  return CY_OK;
+}
+
+// Forward: GS_PB rows per block.  Backward: two tiles, so GS_PB rows where they fit 64 KB (S*k <= 127) and GS_PB / 2
+// beyond.  Both directions accept S*k <= 255 and refuse the rest here, before any launch.
+int cy_group_softmax_plan(long M, int S, int k, cy_group_softmax_plan_t* out) {
+  if (!out || M <= 0 || S <= 0 || k <= 0) return CY_ERR_ARG;
+  if ((long)S * k > 255) return CY_ERR_SHAPE;
+  cy_group_softmax_plan_t p = {};
+  const int pitch = S * k + 1;
+  p.fwd_rows = GS_PB;
+  p.fwd_lds = GS_PB * pitch * (int)sizeof(float);
+  p.bwd_rows = 2 * GS_PB * pitch * (int)sizeof(float) <= GS_LDS ? GS_PB : GS_PB / 2;
+  p.bwd_lds = 2 * p.bwd_rows * pitch * (int)sizeof(float);
+  p.fwd_ok = p.fwd_lds <= GS_LDS;
+  p.bwd_ok = p.bwd_lds <= GS_LDS;
+  if (!p.fwd_ok || !p.bwd_ok) return CY_ERR_SHAPE;
+  if ((M + p.bwd_rows - 1) / p.bwd_rows > 0x7fffffffL) return CY_ERR_SHAPE;
+  p.fwd_grid = cy_cdiv(M, p.fwd_rows);
+  p.bwd_grid = cy_cdiv(M, p.bwd_rows);
+  *out = p;
+  return CY_OK;
+}
+
 int cy_group_softmax_fwd(const float* logits, float* probs, long M, int S, int k, float invT,
                          void* stream) {
   if (!logits || !probs || M <= 0 || S <= 0 || k <= 0) return CY_ERR_ARG;
-  const size_t smem = (size_t)GS_PB * (S * k + 1) * sizeof(float);
-  if (smem > 64 * 1024) return CY_ERR_SHAPE;
-  hipLaunchKernelGGL(group_softmax_fwd_kernel, dim3(cy_cdiv(M, GS_PB)), dim3(256), smem,
+  cy_group_softmax_plan_t p;
+  const int rc = cy_group_softmax_plan(M, S, k, &p);
+  if (rc != CY_OK) return rc;
+  hipLaunchKernelGGL(group_softmax_fwd_kernel, dim3(p.fwd_grid), dim3(256), (size_t)p.fwd_lds,
                      (hipStream_t)stream, logits, probs, M, S, k, invT);
   CY_CHECK_LAUNCH();
   return CY_OK;
@@ -578,17 +688,20 @@ int cy_group_softmax_fwd(const float* logits, float* probs, long M, int S, int k
 int cy_group_softmax_bwd(const float* probs, const float* dprobs, float* dlogits, long M, int S,
                          int k, float invT, void* stream) {
   if (!probs || !dprobs || !dlogits || M <= 0 || S <= 0 || k <= 0) return CY_ERR_ARG;
-  const size_t smem = (size_t)2 * GS_PB * (S * k + 1) * sizeof(float);
-  if (smem > 64 * 1024) return CY_ERR_SHAPE;
-  hipLaunchKernelGGL(group_softmax_bwd_kernel, dim3(cy_cdiv(M, GS_PB)), dim3(256), smem,
-                     (hipStream_t)stream, probs, dprobs, dlogits, M, S, k, invT);
+  cy_group_softmax_plan_t p;
+  const int rc = cy_group_softmax_plan(M, S, k, &p);
+  if (rc != CY_OK) return rc;
+  hipLaunchKernelGGL(group_softmax_bwd_kernel, dim3(p.bwd_grid), dim3(256), (size_t)p.bwd_lds,
+                     (hipStream_t)stream, probs, dprobs, dlogits, M, S, k, invT, p.bwd_rows);
   CY_CHECK_LAUNCH();
   return CY_OK;
 }
 
 size_t cy_joint_ws_bytes(int N, int H, int W, int k, int pad) {
+  cy_joint_plan_t p;
+  if (cy_joint_plan(N, H, W, k, pad, &p) != CY_OK) return 0;
   const int T = 2 * pad + 1;
-  return (size_t)T * T * joint_blocks((long)N * H * W) * k * k * sizeof(float);
+  return (size_t)T * T * p.nblk * k * k * sizeof(float);
 }
 
 /* J[T*T][k][k] = scale * sum over pixels of x1[shifted] (x) x2 ; scale = 1/(N*H*W) when
@@ -596,29 +709,24 @@ size_t cy_joint_ws_bytes(int N, int H, int W, int k, int pad) {
 int cy_joint_fwd(const float* x1, const float* x2, float* J, int N, int H, int W, int k, int pad,
                  int normalise, void* ws, size_t ws_bytes, void* stream) {
   if (!x1 || !x2 || !J || N <= 0 || H <= 0 || W <= 0) return CY_ERR_ARG;
-  if (k < 1 || k > J_KMAX || pad < 0 || pad >= H || pad >= W) return CY_ERR_SHAPE;
+  cy_joint_plan_t p;
+  const int rc = cy_joint_plan(N, H, W, k, pad, &p);
+  if (rc != CY_OK) return rc;
   if (!ws || ws_bytes < cy_joint_ws_bytes(N, H, W, k, pad)) return CY_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   const long npix = (long)N * H * W;
-  const int nblk = joint_blocks(npix), T = 2 * pad + 1;
-  const int kp = (k + 3) & ~3, k4 = kp / 4, nsl = 256 / (k4 * k4);
-  const size_t smem = (size_t)(2 * J_P * kp + nsl * kp * kp) * sizeof(float);
-  // padding > 0: every displacement from one staged tile of R rows, if it fits the LDS
-  int R = 256 / W;
-  R = R < 1 ? 1 : (R > H ? H : R);
-  size_t smem_multi = ((size_t)(R + 2 * pad) * (W + 2 * pad) * kp + (size_t)R * W * kp) * sizeof(float);
-  if (smem_multi < (size_t)nsl * kp * kp * sizeof(float)) smem_multi = (size_t)nsl * kp * kp * sizeof(float);
-  if (pad > 0 && smem_multi <= 150 * 1024) {
-    if (!cy_lds_limit_once<joint_fwd_multi_kernel>(150 * 1024)) return CY_ERR_LAUNCH;
-    hipLaunchKernelGGL(joint_fwd_multi_kernel, dim3(nblk, cy_cdiv(T * T, JM_D)), dim3(256), smem_multi, st, x1, x2,
-                       (float*)ws, N, H, W, k, pad, R);
+  const int T = 2 * pad + 1;
+  if (p.fwd_kernel == 1) {
+    if (!cy_lds_limit_once<joint_fwd_multi_kernel>(J_FWD_LDS)) return CY_ERR_LAUNCH;
+    hipLaunchKernelGGL(joint_fwd_multi_kernel, dim3(p.nblk, p.grid_y), dim3(256), (size_t)p.fwd_lds, st, x1, x2,
+                       (float*)ws, N, H, W, k, pad, p.R);
   } else {
-    hipLaunchKernelGGL(joint_fwd_kernel, dim3(nblk, T * T), dim3(256), smem, st, x1, x2, (float*)ws,
-                       N, H, W, k, pad);
+    hipLaunchKernelGGL(joint_fwd_kernel, dim3(p.nblk, p.grid_y), dim3(256), (size_t)p.fwd_lds, st, x1, x2,
+                       (float*)ws, N, H, W, k, pad);
   }
   CY_CHECK_LAUNCH();
   hipLaunchKernelGGL(joint_reduce_kernel, dim3(cy_cdiv((long)T * T * k * k, 4)), dim3(256), 0, st,
-                     (const float*)ws, J, T * T, nblk, k * k,
+                     (const float*)ws, J, T * T, p.nblk, k * k,
                      normalise ? 1.0 / (double)npix : 1.0);
   CY_CHECK_LAUNCH();
   return CY_OK;
@@ -627,25 +735,22 @@ int cy_joint_fwd(const float* x1, const float* x2, float* J, int N, int H, int W
 int cy_joint_bwd(const float* x1, const float* x2, const float* dJ, const float* gscale, float* dx1,
                  float* dx2, int N, int H, int W, int k, int pad, int normalise, void* stream) {
   if (!x1 || !x2 || !dJ || !gscale || N <= 0 || H <= 0 || W <= 0) return CY_ERR_ARG;
-  if (k < 1 || k > J_KMAX || pad < 0) return CY_ERR_SHAPE;
-  const int T = 2 * pad + 1;
-  const size_t smem = (size_t)T * T * k * k * sizeof(float);
-  if (smem > 64 * 1024) return CY_ERR_SHAPE;
+  cy_joint_plan_t p;
+  const int rc = cy_joint_plan(N, H, W, k, pad, &p);
+  if (rc != CY_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
   const long npix = (long)N * H * W;
   const float scale = normalise ? (float)(1.0 / (double)npix) : 1.f;
-  const bool v4 = (k & 3) == 0;
-  const int grid = grid_for(v4 ? npix * (k / 4) : npix * k);
   for (int which = 0; which < 2; ++which) {
     float* dst = which ? dx2 : dx1;
     const float* other = which ? x1 : x2;
     if (!dst) continue;
-    if (v4)
-      hipLaunchKernelGGL(joint_bwd4_kernel, dim3(grid), dim3(256), smem, st, other, dJ, gscale, dst, N,
-                         H, W, k, pad, scale, which);
+    if (p.bwd_kernel)
+      hipLaunchKernelGGL(joint_bwd4_kernel, dim3(p.bwd_grid), dim3(256), (size_t)p.bwd_lds, st, other, dJ, gscale,
+                         dst, N, H, W, k, pad, scale, which, p.bwd_dchunk);
     else
-      hipLaunchKernelGGL(joint_bwd_kernel, dim3(grid), dim3(256), smem, st, other, dJ, gscale, dst, N,
-                         H, W, k, pad, scale, which);
+      hipLaunchKernelGGL(joint_bwd_kernel, dim3(p.bwd_grid), dim3(256), (size_t)p.bwd_lds, st, other, dJ, gscale,
+                         dst, N, H, W, k, pad, scale, which, p.bwd_dchunk);
     CY_CHECK_LAUNCH();
   }
   return CY_OK;

@@ -11,7 +11,7 @@ from pathlib import Path
 
 CY_F32, CY_BF16, CY_F16 = 0, 1, 2
 CY_SRC_DIRECT, CY_SRC_POOL2, CY_SRC_UP2 = 0, 1, 2
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 _ERRORS = {-1: "CY_ERR_ARG (bad/NULL argument)", -2: "CY_ERR_SHAPE (unsupported shape)",
            -3: "CY_ERR_DTYPE (unsupported dtype)", -4: "CY_ERR_LAUNCH (HIP launch failed)",
@@ -63,6 +63,19 @@ class HeadPlan(C.Structure):
 class ClusterPlan(C.Structure):
     """mirror of cy_cluster_plan"""
     _fields_ = [(n, c_int32) for n in ("fwd_waves", "fwd_grid", "fwd_trips", "bwd_grid", "bwd_trips", "slabs")]
+
+
+class JointPlan(C.Structure):
+    """mirror of cy_joint_plan_t"""
+    _fields_ = [(n, c_int32) for n in ("fwd_kernel", "fwd_vec", "kp", "nsl", "idle", "R", "tiles_h", "ntile", "nblk",
+                                       "per", "grid_y", "nd_last", "fwd_lds", "reduce_trips", "bwd_kernel", "bwd_grid",
+                                       "bwd_trips", "bwd_lds", "bwd_dchunk", "bwd_nchunk")]
+
+
+class GroupSoftmaxPlan(C.Structure):
+    """mirror of cy_group_softmax_plan_t"""
+    _fields_ = [(n, c_int32) for n in ("fwd_rows", "fwd_grid", "fwd_lds", "fwd_ok", "bwd_rows", "bwd_grid", "bwd_lds",
+                                       "bwd_ok")]
 
 
 class WgradReduceEntry(C.Structure):
@@ -261,6 +274,8 @@ _SIGS = {
                                     c_size_t, _P]),
     "cy_group_softmax_fwd": (c_int, [_P, _P, c_long, c_int, c_int, c_float, _P]),
     "cy_group_softmax_bwd": (c_int, [_P, _P, _P, c_long, c_int, c_int, c_float, _P]),
+    "cy_group_softmax_plan": (c_int, [c_long, c_int, c_int, POINTER(GroupSoftmaxPlan)]),
+    "cy_joint_plan": (c_int, [c_int] * 5 + [POINTER(JointPlan)]),
     "cy_joint_ws_bytes": (c_size_t, [c_int] * 5),
     "cy_joint_fwd": (c_int, [_P, _P, _P] + [c_int] * 6 + [_P, c_size_t, _P]),
     "cy_joint_bwd": (c_int, [_P, _P, _P, _P, _P, _P] + [c_int] * 6 + [_P]),

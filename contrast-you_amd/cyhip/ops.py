@@ -2007,12 +2007,31 @@ def group_softmax_fwd(logits: Tensor, S: int, k: int, T: float = 1.0) -> Tensor:
     return probs
 
 
+def group_softmax_plan(M: int, S: int, k: int) -> dict:
+    """the launch plan of cy_group_softmax_fwd / _bwd (host-side query, no GPU needed): the fields of
+    cy_group_softmax_plan_t.  S*k > 255 raises HipKernelError (CY_ERR_SHAPE), as both launches do."""
+    p = _lib.GroupSoftmaxPlan()
+    _lib.call("cy_group_softmax_plan", int(M), int(S), int(k), C.byref(p))
+    return {f: getattr(p, f) for f, _ in p._fields_}
+
+
 def group_softmax_bwd(probs: Tensor, dprobs: Tensor, T: float = 1.0) -> Tensor:
     S, M, k = probs.shape
     dl = _f32(M * S * k, probs.device).view(M, S * k)
     _lib.call("cy_group_softmax_bwd", probs.data_ptr(), dprobs.data_ptr(), dl.data_ptr(), M, S, k, 1.0 / T,
               _stream())
     return dl
+
+
+def joint_plan(N: int, H: int, W: int, k: int, pad: int) -> dict:
+    """the launch plan of cy_joint_fwd / _bwd for two [N,H,W,k] maps and padding `pad` (host-side query, no GPU needed):
+    the fields of cy_joint_plan_t, and "ws_bytes", the forward's workspace.  Shapes the kernels refuse raise
+    HipKernelError (CY_ERR_SHAPE)."""
+    p = _lib.JointPlan()
+    _lib.call("cy_joint_plan", int(N), int(H), int(W), int(k), int(pad), C.byref(p))
+    out = {f: getattr(p, f) for f, _ in p._fields_}
+    out["ws_bytes"] = int(_lib.load().cy_joint_ws_bytes(int(N), int(H), int(W), int(k), int(pad)))
+    return out
 
 
 def joint_fwd(x1: Tensor, x2: Tensor, N: int, H: int, W: int, k: int, pad: int, normalise: bool) -> Tensor:

@@ -788,6 +788,50 @@ int cy_joint_fwd(const float* x1, const float* x2, float* J, int N, int H, int W
 /* dx1, dx2 (either may be NULL) = gscale[0] * adjoint of cy_joint_fwd applied to dJ */
 int cy_joint_bwd(const float* x1, const float* x2, const float* dJ, const float* gscale, float* dx1,
                  float* dx2, int N, int H, int W, int k, int pad, int normalise, void* stream);
+/* Launch plans of the information-loss kernels (ABI v17).  Host-side only, they launch nothing and need no GPU.
+ * cy_joint_fwd, cy_joint_bwd, cy_joint_ws_bytes and the two softmax launches take every decision from these two
+ * functions, and refuse exactly what they refuse.
+ * Joints (compute_joint / compute_joint_2D / compute_joint_2D_with_padding_zeros, contrastyou/losses/discreteMI.py:
+ * 201-261): 1 <= k <= 64, 0 <= pad < min(H, W), forward and backward alike (CY_ERR_SHAPE otherwise). */
+typedef struct cy_joint_plan_t {
+  int32_t fwd_kernel;   /* 0: joint_fwd_kernel, 64-pixel tiles, one displacement per blockIdx.y (pad 0, and pad > 0 where
+                           the staged rows exceed 150 KB of LDS); 1: joint_fwd_multi_kernel, R image rows per tile, up to
+                           nine displacements per blockIdx.y */
+  int32_t fwd_vec;      /* 1: the tile is staged with 16-byte copies (k % 4 == 0; kernel 0: and pad 0), 0: scalar */
+  int32_t kp;           /* k rounded up to 4: the row pitch of the staged tiles */
+  int32_t nsl;          /* pixel slices per block: 256 / (kp/4)^2 */
+  int32_t idle;         /* threads that own no slice: 256 - nsl * (kp/4)^2 */
+  int32_t R;            /* kernel 1: image rows per tile, min(H, max(1, 256 / W)); kernel 0: 0 */
+  int32_t tiles_h;      /* kernel 1: ceil(H / R); kernel 0: 0 */
+  int32_t ntile;        /* tiles in all: kernel 1 N * tiles_h (a block walks them with stride nblk), kernel 0
+                           ceil(npix / 64) */
+  int32_t nblk;         /* blocks in x = partial joints per displacement: min(2048, ceil(npix / 1024)) */
+  int32_t per;          /* kernel 0: pixels per block, a multiple of 64 (the last block takes what is left); kernel 1: 0 */
+  int32_t grid_y;       /* kernel 0: T*T; kernel 1: ceil(T*T / 9) */
+  int32_t nd_last;      /* displacements of the last blockIdx.y: T*T - 9 * (grid_y - 1) on kernel 1, 1 on kernel 0 */
+  int32_t fwd_lds;      /* dynamic LDS bytes of the forward launch */
+  int32_t reduce_trips; /* partial blocks each of the 64 slices of joint_reduce_kernel adds per element: ceil(nblk/64) */
+  int32_t bwd_kernel;   /* 1: joint_bwd4_kernel (k % 4 == 0), 0: joint_bwd_kernel */
+  int32_t bwd_grid;     /* blocks, at most 8192 */
+  int32_t bwd_trips;    /* trips of the backward's grid-stride loop */
+  int32_t bwd_lds;      /* dynamic LDS bytes: bwd_dchunk * k * k * 4 <= 64 KB */
+  int32_t bwd_dchunk;   /* displacements of dJ staged at a time: min(T*T, 65536 / (4 k^2)) */
+  int32_t bwd_nchunk;   /* ceil(T*T / bwd_dchunk); 1 = staged once per block */
+} cy_joint_plan_t;
+int cy_joint_plan(int N, int H, int W, int k, int pad, cy_joint_plan_t* out);
+/* Grouped softmax (SoftmaxWithT, contrastyou/projectors/nn.py:35-44): S*k <= 255 in both directions, CY_ERR_SHAPE
+ * beyond (from the plan and from both launches, before anything is launched). */
+typedef struct cy_group_softmax_plan_t {
+  int32_t fwd_rows; /* rows of logits per block: 64 */
+  int32_t fwd_grid;
+  int32_t fwd_lds;  /* fwd_rows * (S*k + 1) * 4 */
+  int32_t fwd_ok;   /* 1: fwd_lds fits 64 KB */
+  int32_t bwd_rows; /* 64 where the two tiles fit 64 KB (S*k <= 127), else 32 */
+  int32_t bwd_grid;
+  int32_t bwd_lds;  /* 2 * bwd_rows * (S*k + 1) * 4 */
+  int32_t bwd_ok;
+} cy_group_softmax_plan_t;
+int cy_group_softmax_plan(long M, int S, int k, cy_group_softmax_plan_t* out);
 /* loss on a joint.  mode 0: IIDSegmentationLoss padding 0; mode 1: padding>0
  * (subtract min, +1e-8, per-displacement and global normalisation, loss/T^2);
  * mode 2: IIDLoss on vectors (symmetrise if `symmetric`, normalise to 1).

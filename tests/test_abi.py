@@ -89,9 +89,7 @@ def test_wgrad_plan_layout_matches_header():
     assert ctypes.sizeof(WgradPlan) == 4 * len(fields)
 
 
-@pytest.mark.parametrize("struct,mirror", [("cy_head_plan", "HeadPlan"), ("cy_cluster_plan", "ClusterPlan")])
-def test_head_plan_layouts_match_header(struct, mirror):
-    """cy_head_plan / cy_cluster_plan (ABI v16) and their ctypes mirrors name the same int32 fields in order"""
+def _check_plan_layout(struct, mirror):
     from cyhip import _lib
     cls = getattr(_lib, mirror)
     text = HEADER.read_text()
@@ -105,7 +103,27 @@ def test_head_plan_layouts_match_header(struct, mirror):
             fields += [f.strip() for f in decl[len("int32_t "):].split(",")]
     assert fields == [n for n, _ in cls._fields_]
     assert ctypes.sizeof(cls) == 4 * len(fields)
-    assert _lib.ABI_VERSION == 16
+    return fields
+
+
+@pytest.mark.parametrize("struct,mirror", [("cy_head_plan", "HeadPlan"), ("cy_cluster_plan", "ClusterPlan")])
+def test_head_plan_layouts_match_header(struct, mirror):
+    """cy_head_plan / cy_cluster_plan (ABI v16) and their ctypes mirrors name the same int32 fields in order"""
+    from cyhip import _lib
+    _check_plan_layout(struct, mirror)
+    assert _lib.ABI_VERSION == 17
+
+
+@pytest.mark.parametrize("struct,mirror", [("cy_joint_plan_t", "JointPlan"),
+                                           ("cy_group_softmax_plan_t", "GroupSoftmaxPlan")])
+def test_mi_plan_layouts_match_header(struct, mirror):
+    """cy_joint_plan_t / cy_group_softmax_plan_t (ABI v17) and their ctypes mirrors name the same int32 fields in
+    order; the plan entry points are exported and typed"""
+    from cyhip import _lib
+    fields = _check_plan_layout(struct, mirror)
+    assert fields[0] in ("fwd_kernel", "fwd_rows")
+    assert _lib.ABI_VERSION == 17 and _lib.load().cy_abi_version() == 17
+    assert {"cy_joint_plan", "cy_group_softmax_plan"} <= set(_lib.exported_names()) & set(header_symbols())
 
 
 def test_loading_the_library_first_leaves_one_hip_runtime():
