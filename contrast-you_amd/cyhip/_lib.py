@@ -336,6 +336,8 @@ _SIGS = {
     "cy_conv4x4_dgrad": (c_int, [_P, _P, _P] + [c_int] * 8 + [_P]),
     "cy_conv4x4_wgrad_ws_bytes": (c_size_t, [c_int] * 8),
     "cy_conv4x4_wgrad": (c_int, [_P, _P, _P] + [c_int] * 8 + [_P, c_size_t, _P]),
+    "cy_surface_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "cy_surface_stats": (c_int, [_P, _P, _P] + [c_int] * 5 + [_P, _P, _P, _P, _P, _P, c_size_t, _P]),
 }
 
 # functions whose int return is a count / size, not a status

@@ -1629,6 +1629,35 @@ def mix_dice_counts(logits: Tensor, target: Tensor, mix: Tensor) -> Tensor:
     return counts
 
 
+def surface_stats(pred: Tensor, target: Tensor, classes, ndim: int = 3, maps: bool = False):
+    """Surface-distance statistics of two class-index volumes (csrc/cy_surface.hip).  pred, target: int64 [D, H, W]
+    (ndim=3) or [H, W] / [1, H, W] (ndim=2); classes: the R reported class indices.  Returns device tensors
+    (count int64 [2, R], sum f64 [2, R], maxd2 int32 [2, R]) -- direction 0 is pred -> target, 1 target -> pred -- and
+    with maps=True also (d2 int32 [2, R, D, H, W], border uint8 [2, R, D, H, W]).  No host sync."""
+    require_gpu(pred, target)
+    assert pred.shape == target.shape, f"incompatible shape of `pred` and `target`, given {pred.shape} and {target.shape}."
+    assert pred.dtype == torch.int64 and target.dtype == torch.int64, "class-index volumes are int64"
+    if pred.dim() == 2:
+        pred, target = pred[None], target[None]
+    assert pred.dim() == 3, f"a volume is [D, H, W] or [H, W], given {tuple(pred.shape)}"
+    pred, target = pred.contiguous(), target.contiguous()
+    D, H, W = pred.shape
+    cls = (C.c_int32 * len(classes))(*[int(c) for c in classes])
+    R, dev = len(classes), pred.device
+    count = torch.empty((2, R), dtype=torch.int64, device=dev)
+    total = torch.empty((2, R), dtype=torch.float64, device=dev)
+    maxd2 = torch.empty((2, R), dtype=torch.int32, device=dev)
+    d2 = torch.empty((2, R, D, H, W), dtype=torch.int32, device=dev) if maps else None
+    border = torch.empty((2, R, D, H, W), dtype=torch.uint8, device=dev) if maps else None
+    nbytes = _lib.load().cy_surface_ws_bytes(D, H, W)
+    ws = _ws(nbytes, dev)
+    _lib.call("cy_surface_stats", pred.data_ptr(), target.data_ptr(), cls, R, D, H, W, int(ndim), count.data_ptr(),
+              total.data_ptr(), maxd2.data_ptr(), _ptr(d2), _ptr(border), ws.data_ptr(), nbytes, _stream())
+    if maps:
+        return count, total, maxd2, d2, border
+    return count, total, maxd2
+
+
 # --------------------------------------------------------------------------- projector pieces
 def avgpool_fwd(x: Tensor) -> Tensor:
     N, Cc, H, W = x.shape

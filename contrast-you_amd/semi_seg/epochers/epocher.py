@@ -27,7 +27,7 @@ import torch
 from torch import Tensor, nn
 
 from contrastyou.epochers.base import EpocherBase as _EpocherBase
-from contrastyou.meters import AverageValueMeter, MeterInterface, UniversalDice
+from contrastyou.meters import AverageValueMeter, MeterInterface, SurfaceMeter, UniversalDice
 from contrastyou.utils.general import class2one_hot
 from contrastyou.utils.utils import (class_name, disable_tracking_bn_stats, get_dataset, get_lrs_from_optimizer,
                                      get_model)
@@ -340,10 +340,14 @@ class EvalEpocher(EpocherBase):
 
 class InferenceEpocher(EvalEpocher):
     """`InferenceEpocher` (semi_seg/epochers/epocher.py:174-204): the evaluation epoch of `Trainer.inference`,
-    with an optional prediction saver.  The reference's saver writes PNGs through its dataset tooling and its
-    extra "ASD" surface meter needs the un-vendored `medpy`; here the predictions (class-index maps) are written
-    as one `.npy` per input file under `<save_dir>/predictions/` and the Dice / loss meters are the ones of
-    `EvalEpocher` (the surface meter is out of scope)."""
+    with an optional prediction saver.  The reference's saver writes PNGs through its dataset tooling; here the
+    predictions (class-index maps) are written as one `.npy` per input file under `<save_dir>/predictions/`.  Next to
+    the Dice / loss meters of `EvalEpocher` it reports "ASD", the average symmetric surface distance per foreground
+    class, each batch taken as one 3-D volume as the reference does (epocher.py:187-204).  The reference's meter goes
+    through the un-vendored `medpy` on the host; `SurfaceMeter` here runs the `cy_surface_stats` kernels and reads
+    its statistics back at summary time.  A batch in which a foreground class is missing from the prediction or from
+    the target adds nothing (the reference ignores the exception its meter raises there); `meters["ASD"].skipped`
+    counts them."""
     meter_focus = "infer"
 
     def __init__(self, *, model: nn.Module, loader, sup_criterion, cur_epoch=0, device="cpu", scaler,
@@ -364,12 +368,20 @@ class InferenceEpocher(EvalEpocher):
         os.makedirs(out, exist_ok=True)
         return out
 
+    def configure_meters(self, meters: MeterInterface) -> MeterInterface:
+        meters = super().configure_meters(meters)
+        classes = self.num_classes
+        meters.register_meter("ASD", SurfaceMeter(C=classes, report_axises=list(range(1, classes)),
+                                                  metername="average_surface"))
+        return meters
+
     def _batch_update(self, *, eval_img, eval_target, eval_group, file_names):
         with self.autocast:
             logits = self._model(eval_img)
             loss = _sup_loss(self._sup_criterion, logits, eval_target, self.num_classes)
         self.meters["loss"].add(loss.detach())
         self.meters["dice"].add_logits(logits, eval_target, group_name=eval_group)
+        self.meters["ASD"].add(logits.argmax(1)[None], eval_target.squeeze(1)[None])
         out_dir = self._prediction_dir() if self.enable_prediction_saver else None
         if out_dir is not None:
             import os

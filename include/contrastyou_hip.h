@@ -1050,6 +1050,35 @@ size_t cy_conv4x4_wgrad_ws_bytes(int N, int H, int W, int Cin, int Cout, int ksi
 int cy_conv4x4_wgrad(const float* x, const float* dy, float* dw, int N, int H, int W, int Cin, int Cout, int ksize,
                      int stride, int pad, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Surface-distance statistics at inference (csrc/cy_surface.hip; 2 entries added to ABI v17 -- no existing signature
+ * changed, so cy_abi_version() stays 17).  Replaces SurfaceMeter._evalue (contrastyou/meters/surface_meter.py:93-112)
+ * and the three functions of contrastyou/meters/surface_distance.py:11-31, which go through medpy's
+ * __surface_distances (binary erosion + exact Euclidean distance transform on the host).
+ * pred and target are class-index volumes, int64 [D][H][W], read as they are; classes is a HOST array of R reported
+ * class indices.  Per reported class r and direction d (0: pred -> target, 1: target -> pred), with a = (volume of d ==
+ * class) and b = (the other volume == class):
+ *   border(a)(v) = a(v) && !(all face neighbours of v in a); a neighbour outside the volume is background; ndim == 3
+ *                  tests the depth neighbours too, ndim == 2 (D must be 1) does not;
+ *   d2(v)        = min over border(b) voxels u of |v - u|^2, exact in int32 (separable min-plus passes along W, H, D,
+ *                  one line staged in LDS per output); 2^30 everywhere when border(b) is empty;
+ *   count[d][r]  = |border(a)|, sum[d][r] = sum over border(a) of sqrt((double)d2), maxd2[d][r] = max over border(a).
+ * Outputs are device arrays [2][R].  d2_maps (int32 [2][R][V]) and border_maps (uint8 [2][R][V]), V = D*H*W, are
+ * optional (NULL: not written): d2_maps[d][r] is the distance map direction d reads, border_maps[d][r] is border(a).
+ * No atomics: f64 partials per block (at most 1024 blocks of 256) and one fixed-order final sum, so two runs give
+ * the same bits.  Six launches per class, classes one after the other through the same workspace:
+ *   ws_bytes = roundup(2 V, 16) + 8 V + 2 * 1024 * 24   (two border masks, two d2 maps, the partials).
+ * Checked before any launch: a NULL pointer (the two map pointers excepted), a size < 1 or V > 2^31 - 1 -> CY_ERR_ARG;
+ * D, H or W > CY_SURFACE_MAX_LINE, R outside 1 .. CY_SURFACE_MAX_CLASSES, ndim not 2 or 3, ndim == 2 with D != 1 ->
+ * CY_ERR_SHAPE; a short workspace -> CY_ERR_WORKSPACE.  cy_surface_ws_bytes is 0 where the sizes are refused.
+ * ------------------------------------------------------------------------ */
+#define CY_SURFACE_MAX_LINE 1024   /* the LDS line buffer: 8 lines * 1024 * 4 bytes */
+#define CY_SURFACE_MAX_CLASSES 64
+size_t cy_surface_ws_bytes(int D, int H, int W);
+int cy_surface_stats(const int64_t* pred, const int64_t* target, const int32_t* classes, int R, int D, int H, int W,
+                     int ndim, int64_t* count, double* sum, int32_t* maxd2, int32_t* d2_maps, uint8_t* border_maps,
+                     void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
