@@ -705,6 +705,159 @@ inline int stream_grid(long total_threads) {
   return (int)b;
 }
 
+// workgroups of the fused pool / upsample backward: one partial row (or one accumulator add per channel) each
+inline int stats_grid(long items) {
+  long b = (items + 255) / 256;
+  if (b > 1024) b = 1024;
+  return (int)(b < 1 ? 1 : b);
+}
+
+// workgroups of the backward reduce: 128 pixels per workgroup; small maps (fewer than 512 such workgroups) get 32 pixels
+// per workgroup and the deep-prefetch form of the kernel
+inline int reduce_grid(long npix) {
+  long b = (npix + 127) / 128;
+  if (b < 512) b = (npix + 31) / 32 < 512 ? (npix + 31) / 32 : 511;
+  if (b > 1024) b = 1024;
+  if (b < 1) b = 1;
+  return (int)b;
+}
+
+// a type code as the plan's `dtype` argument takes it (anything outside the encodable range becomes a code no kernel has)
+inline int na_type(int dtype) { return dtype >= 0 && dtype < 15 ? dtype : 14; }
+inline int na_types(int in_dtype, int out_dtype) { return na_type(in_dtype) | CY_NA_OUT(na_type(out_dtype)); }
+
+inline int32_t sat32(long v) { return v > 2147483647L ? 2147483647 : (int32_t)v; }
+
+// THE host-side decisions of this file (cy_norm_act_plan): n = N * H * W in the unit of the kind (contrastyou_hip.h).
+// `status` holds only what depends on the shape and the types (the entries keep their pointer checks); grids are filled
+// in whatever the status, since the count queries answer for any C.
+void na_plan(int kind, long n, int C, int dtype, int fold, cy_norm_act_plan_t* p) {
+  *p = cy_norm_act_plan_t{};
+  const int ti = dtype & 15, to = (dtype >> 4) ? (dtype >> 4) - 1 : ti;
+  p->type_in = ti, p->type_out = to, p->fold = fold;
+  const bool three = ti == CY_BF16 || ti == CY_F16 || ti == CY_F32;
+  const int G = C / 8;
+  const long items = n * (long)G;
+  const bool ew_fold = fold > 0 && (kind == CY_NA_APPLY || kind == CY_NA_APPLY_POOL || kind == CY_NA_BWD_APPLY);
+  auto gather = [&](bool wide) {
+    p->gather = fold <= 0 ? 0 : fold <= 8 ? 1 : (wide && fold <= 32) ? 2 : 3;
+  };
+  auto loop = [&](long work, int cap_grid) {  // grid-stride loop of `threads` x `grid` over `work` items
+    p->items = sat32(work);
+    const long per_trip = (long)p->grid * p->threads;
+    p->trips = sat32(work > 0 ? (work + per_trip - 1) / per_trip : 0);
+    p->one_trip_items = sat32((long)cap_grid * p->threads);
+  };
+  switch (kind) {
+    case CY_NA_APPLY:
+    case CY_NA_APPLY_POOL: {
+      const bool pool = kind == CY_NA_APPLY_POOL;
+      p->kernel = (pool ? 2 : 0) + (ew_fold ? 1 : 0);
+      p->threads = ew_fold ? 1024 : 256;
+      // (the pooled fold form sizes its grid by pixels, four per item)
+      p->grid = ew_fold ? fold_grid(pool ? items * 4 : items) : stream_grid(items);
+      p->lds_bytes = ew_fold ? (int)((size_t)2 * C * sizeof(float) + ((size_t)4 * C + 2) * 8) : 0;
+      loop(items, ew_fold ? 256 : 2048 * 4);
+      gather(true);
+      const bool same = ti == to && three;
+      const bool mixed = !pool && to == CY_F32 && (ti == CY_BF16 || ti == CY_F16);
+      if (C % 8 || (ew_fold && C > 1024)) p->status = CY_ERR_SHAPE;
+      else if (!same && !mixed) p->status = CY_ERR_DTYPE;
+      break;
+    }
+    case CY_NA_BWD_REDUCE: {
+      const int gpp = G < 1 ? 1 : G < 256 ? G : 256;
+      const int rows = 256 / gpp;
+      p->grid = reduce_grid(n);
+      p->threads = 256;
+      p->deep = p->grid < 512;
+      p->kernel = p->deep ? 4 : 5;
+      p->rows = rows, p->groups_per_page = gpp;
+      p->pages = G < 1 ? 0 : (G + gpp - 1) / gpp;
+      p->last_page_groups = G < 1 ? 0 : G - (p->pages - 1) * gpp;
+      p->lds_bytes = (int)((size_t)2 * rows * gpp * 8 * sizeof(float));
+      const long per = (n + p->grid - 1) / p->grid;
+      p->pixels_per_workgroup = sat32(per);
+      p->empty_workgroups = per > 0 ? p->grid - (int)((n + per - 1) / per) : p->grid;
+      const long full = per < n ? per : n;  // pixels of workgroup 0
+      p->idle_rows = rows > full ? (int)(rows - full) : 0;
+      p->idle_threads = 256 - rows * gpp;
+      // which loops run: row r of a workgroup with m pixels walks ceil((m - r) / rows) of them, four at a time (deep);
+      // over the rows that count takes two values at the most, ceil(m / rows) and (from m >= rows on) floor(m / rows)
+      const long last = per > 0 && n % per ? n % per : full;  // pixels of the last workgroup that has any
+      for (long m : {full, last})
+        if (m > 0)
+          for (long cnt : {(m + rows - 1) / rows, m < rows ? 1L : m / rows}) {
+            if (p->deep && cnt >= 4) p->round4 = 1;
+            if (p->deep ? cnt % 4 != 0 : cnt > 0) p->tail1 = 1;
+          }
+      p->items = sat32(n);
+      p->trips = sat32(full > 0 ? (full + rows - 1) / rows : 0);
+      p->partial_rows = p->grid;
+      p->chain = sat32((long)p->trips + rows - p->idle_rows);  // a thread's pixels, then the rows that had any (zeros add exactly)
+      if (C % 8) p->status = CY_ERR_SHAPE;
+      else if (!three) p->status = CY_ERR_DTYPE;
+      break;
+    }
+    case CY_NA_BWD_APPLY:
+      p->kernel = ew_fold ? 7 : 6;
+      p->threads = ew_fold ? 1024 : 256;
+      p->grid = ew_fold ? fold_grid(items) : stream_grid(items);
+      p->lds_bytes = ew_fold ? (int)((size_t)4 * C * sizeof(float) + ((size_t)4 * C + 2) * 8) : 0;
+      p->pow2 = G > 0 && (G & (G - 1)) == 0;
+      loop(items, ew_fold ? 256 : 2048 * 4);
+      gather(true);
+      if (C % 8 || (ew_fold && C > 1024)) p->status = CY_ERR_SHAPE;
+      else if (!three) p->status = CY_ERR_DTYPE;
+      break;
+    case CY_NA_POOL_BWD:
+    case CY_NA_UP_BWD:
+    case CY_NA_POOL_BWD_BN:
+    case CY_NA_UP_BWD_BN: {
+      const bool pool = kind == CY_NA_POOL_BWD || kind == CY_NA_POOL_BWD_BN;
+      const bool bn = kind == CY_NA_POOL_BWD_BN || kind == CY_NA_UP_BWD_BN;
+      p->fused_ok = bn && C > 0 && C % 8 == 0 && G <= 256 && 256 % G == 0;
+      const bool stats = bn && p->fused_ok;
+      p->kernel = (pool ? 8 : 10) + (stats ? 1 : 0);
+      p->threads = 256;
+      p->grid = stats ? stats_grid(items) : stream_grid(items);
+      p->lds_bytes = stats ? 256 * 16 * (int)sizeof(float) : 0;
+      loop(items, stats ? 1024 : 2048 * 4);
+      if (stats) {
+        p->partial_rows = p->grid;
+        // a thread's values (four pixels per quad), then the 256 / G lanes of its channel group
+        p->chain = sat32((long)p->trips * (pool ? 4 : 1) + 256 / G);
+      }
+      if (C % 8 || (bn && !p->fused_ok)) p->status = CY_ERR_SHAPE;
+      else if (!three) p->status = CY_ERR_DTYPE;
+      break;
+    }
+    case CY_NA_FINALIZE:
+    case CY_NA_BWD_FINALIZE: {
+      const int slices = kind == CY_NA_FINALIZE ? 256 : 64;  // partial rows summed side by side (in f64), 4 channels each
+      p->kernel = kind == CY_NA_FINALIZE ? 12 : 13;
+      p->threads = 4 * slices;
+      p->grid = cy_cdiv(C, 4);
+      p->lds_bytes = 2 * slices * 4 * (int)sizeof(double);
+      p->items = sat32(n);
+      p->trips = sat32((n + slices - 1) / slices);
+      p->idle_threads = (p->grid * 4 - C) * slices;
+      break;
+    }
+    case CY_NA_FOLD_COEF:
+      p->kernel = 14;
+      p->threads = 256, p->grid = 1;
+      p->lds_bytes = (int)(((size_t)4 * C + 2) * 8);
+      p->items = C;
+      p->trips = (C + 255) / 256;
+      gather(false);
+      if (C > 2048) p->status = CY_ERR_SHAPE;
+      break;
+    default:
+      break;
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -717,7 +870,9 @@ int cy_bn_finalize(const float* partials, int num_partials, int C, double count,
   if (C <= 0 || !scale || !shift || !mean || !invstd) return CY_ERR_ARG;
   if (use_batch_stats && (!partials || num_partials <= 0 || count <= 0)) return CY_ERR_ARG;
   if ((!use_batch_stats || update_running) && (!running_mean || !running_var)) return CY_ERR_ARG;
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3(cy_cdiv(C, 4)), dim3(1024), 0, (hipStream_t)stream,
+  cy_norm_act_plan_t pl;
+  na_plan(CY_NA_FINALIZE, num_partials, C, CY_F32, 0, &pl);
+  hipLaunchKernelGGL(bn_finalize_kernel, dim3(pl.grid), dim3(pl.threads), 0, (hipStream_t)stream,
                      partials, num_partials, C, count, gamma, beta, running_mean, running_var,
                      momentum, eps, use_batch_stats, update_running, scale, shift, mean, invstd);
   CY_CHECK_LAUNCH();
@@ -729,17 +884,19 @@ static int bn_relu_apply_impl(const void* y, const float* scale, const float* sh
   if (!y || !out || npix <= 0) return CY_ERR_ARG;
   if (!f && (!scale || !shift)) return CY_ERR_ARG;
   if (f && (!f->acc || !f->coef || f->C != C || f->R < 1 || (f->R & (f->R - 1)) || f->count <= 0)) return CY_ERR_ARG;
-  if (C % 8 || (f && C > 1024)) return CY_ERR_SHAPE;
+  cy_norm_act_plan_t pl;
+  na_plan(CY_NA_APPLY, npix, C, na_types(y_dtype, out_dtype), f ? f->R : 0, &pl);
+  if (pl.status) return pl.status;
   hipStream_t st = (hipStream_t)stream;
   const BnFold bf = f ? bn_fold_from_abi(f) : BnFold{};
-  const int grid = f ? fold_grid(npix * (C / 8)) : stream_grid(npix * (C / 8));
-  const size_t smem = f ? (size_t)2 * C * sizeof(float) + ((size_t)4 * C + 2) * 8 : 0;
+  const int grid = pl.grid;
+  const size_t smem = (size_t)pl.lds_bytes;
 #define CY_APPLY(TI, TO)                                                                                        \
   do {                                                                                                          \
-    if (f) hipLaunchKernelGGL((bn_relu_apply_kernel<TI, TO, true>), dim3(grid), dim3(1024), smem, st, (const TI*)y, \
-                              scale, shift, (TO*)out, npix, C, bf);                                             \
-    else hipLaunchKernelGGL((bn_relu_apply_kernel<TI, TO, false>), dim3(grid), dim3(256), 0, st, (const TI*)y,  \
-                            scale, shift, (TO*)out, npix, C, bf);                                               \
+    if (pl.kernel == 1) hipLaunchKernelGGL((bn_relu_apply_kernel<TI, TO, true>), dim3(grid), dim3(pl.threads), smem, st, \
+                                           (const TI*)y, scale, shift, (TO*)out, npix, C, bf);                  \
+    else hipLaunchKernelGGL((bn_relu_apply_kernel<TI, TO, false>), dim3(grid), dim3(pl.threads), smem, st,      \
+                            (const TI*)y, scale, shift, (TO*)out, npix, C, bf);                                 \
   } while (0)
   if (y_dtype == CY_BF16 && out_dtype == CY_BF16) CY_APPLY(bf16, bf16);
   else if (y_dtype == CY_F32 && out_dtype == CY_F32) CY_APPLY(float, float);
@@ -768,18 +925,19 @@ static int bn_relu_apply_pool_impl(const void* y, const float* scale, const floa
   if (!y || !out || !pooled || N <= 0 || H <= 0 || W <= 0) return CY_ERR_ARG;
   if (!f && (!scale || !shift)) return CY_ERR_ARG;
   if (f && (!f->acc || !f->coef || f->C != C || f->R < 1 || (f->R & (f->R - 1)) || f->count <= 0)) return CY_ERR_ARG;
-  if (C % 8 || (f && C > 1024)) return CY_ERR_SHAPE;
+  cy_norm_act_plan_t pl;
+  na_plan(CY_NA_APPLY_POOL, (long)N * H * W, C, na_types(y_dtype, out_dtype), f ? f->R : 0, &pl);
+  if (pl.status) return pl.status;
   hipStream_t st = (hipStream_t)stream;
   const BnFold bf = f ? bn_fold_from_abi(f) : BnFold{};
-  const long items = (long)N * H * W * (C / 8);
-  const int grid = f ? fold_grid(items * 4) : stream_grid(items);
-  const size_t smem = f ? (size_t)2 * C * sizeof(float) + ((size_t)4 * C + 2) * 8 : 0;
+  const int grid = pl.grid;
+  const size_t smem = (size_t)pl.lds_bytes;
 #define CY_APPLY_POOL(TI, TO)                                                                                      \
   do {                                                                                                             \
-    if (f) hipLaunchKernelGGL((bn_relu_apply_pool_kernel<TI, TO, true>), dim3(grid), dim3(1024), smem, st,          \
-                              (const TI*)y, scale, shift, (TO*)out, (TO*)pooled, N, H, W, C, bf);                  \
-    else hipLaunchKernelGGL((bn_relu_apply_pool_kernel<TI, TO, false>), dim3(grid), dim3(256), 0, st, (const TI*)y, \
-                            scale, shift, (TO*)out, (TO*)pooled, N, H, W, C, bf);                                  \
+    if (pl.kernel == 3) hipLaunchKernelGGL((bn_relu_apply_pool_kernel<TI, TO, true>), dim3(grid), dim3(pl.threads), smem, \
+                                           st, (const TI*)y, scale, shift, (TO*)out, (TO*)pooled, N, H, W, C, bf); \
+    else hipLaunchKernelGGL((bn_relu_apply_pool_kernel<TI, TO, false>), dim3(grid), dim3(pl.threads), smem, st,    \
+                            (const TI*)y, scale, shift, (TO*)out, (TO*)pooled, N, H, W, C, bf);                    \
   } while (0)
   if (y_dtype == CY_BF16 && out_dtype == CY_BF16) CY_APPLY_POOL(bf16, bf16);
   else if (y_dtype == CY_F32 && out_dtype == CY_F32) CY_APPLY_POOL(float, float);
@@ -803,8 +961,11 @@ int cy_bn_relu_apply_pool_fold(const void* y, const cy_bn_fold* f, void* out, vo
 
 int cy_bn_fold_coef(const cy_bn_fold* f, void* stream) {
   if (!f || !f->acc || !f->coef || f->C <= 0 || f->R < 1 || (f->R & (f->R - 1)) || f->count <= 0) return CY_ERR_ARG;
-  if (f->C > 2048) return CY_ERR_SHAPE;
-  hipLaunchKernelGGL(bn_fold_kernel, dim3(1), dim3(256), ((size_t)4 * f->C + 2) * 8, (hipStream_t)stream, bn_fold_from_abi(f));
+  cy_norm_act_plan_t pl;
+  na_plan(CY_NA_FOLD_COEF, 1, f->C, CY_F32, f->R, &pl);
+  if (pl.status) return pl.status;
+  hipLaunchKernelGGL(bn_fold_kernel, dim3(pl.grid), dim3(pl.threads), (size_t)pl.lds_bytes, (hipStream_t)stream,
+                     bn_fold_from_abi(f));
   CY_CHECK_LAUNCH();
   return CY_OK;
 }
@@ -824,14 +985,9 @@ int cy_bn_running_update(const cy_bn_run_item* h_items, int n, void* stream) {
 }
 
 int cy_bn_bwd_num_partials(long npix, int C) {
-  (void)C;
-  // 128 pixels per workgroup; small maps (fewer than 512 such workgroups) get 32 pixels per workgroup and the
-  // deep-prefetch form of the kernel
-  long b = (npix + 127) / 128;
-  if (b < 512) b = (npix + 31) / 32 < 512 ? (npix + 31) / 32 : 511;
-  if (b > 1024) b = 1024;
-  if (b < 1) b = 1;
-  return (int)b;
+  cy_norm_act_plan_t pl;
+  na_plan(CY_NA_BWD_REDUCE, npix, C, CY_F32, 0, &pl);
+  return pl.grid;
 }
 
 static int bn_relu_bwd_reduce_impl(const void* da, int ld_da, const void* y, const float* scale,
@@ -859,15 +1015,15 @@ static int bn_relu_bwd_reduce_impl(const void* da, int ld_da, const void* y, con
                                    float* partials, unsigned long long* sacc, int sR, long npix, int C, int dtype, void* stream) {
   if (!da || !y || !scale || !shift || !mean || !invstd || (!partials && !sacc)) return CY_ERR_ARG;
   if (C % 8 || ld_da % 8 || ld_da < C) return CY_ERR_SHAPE;
-  const int G = C / 8;
-  const int gpp = G < 256 ? G : 256;
-  const int rows = 256 / gpp;
-  const size_t smem = (size_t)2 * rows * gpp * 8 * sizeof(float);
-  const int grid = cy_bn_bwd_num_partials(npix, C);
+  cy_norm_act_plan_t pl;
+  na_plan(CY_NA_BWD_REDUCE, npix, C, na_type(dtype), sacc ? sR : 0, &pl);
+  if (pl.status) return pl.status;
+  const size_t smem = (size_t)pl.lds_bytes;
+  const int grid = pl.grid;
   hipStream_t st = (hipStream_t)stream;
-  const bool deep = grid < 512;
+  const bool deep = pl.deep != 0;
 #define CY_BN_RED(TT, DD)                                                                                          \
-  hipLaunchKernelGGL((bn_relu_bwd_reduce_kernel<TT, DD>), dim3(grid), dim3(256), smem, st, (const TT*)da, ld_da,   \
+  hipLaunchKernelGGL((bn_relu_bwd_reduce_kernel<TT, DD>), dim3(grid), dim3(pl.threads), smem, st, (const TT*)da, ld_da, \
                      (const TT*)y, scale, shift, mean, invstd, partials, npix, C, sacc, sR)
   if (dtype == CY_BF16) {
     if (deep) CY_BN_RED(bf16, true); else CY_BN_RED(bf16, false);
@@ -888,7 +1044,9 @@ int cy_bn_bwd_finalize(const float* partials, int num_partials, int C, const flo
                        float* dgamma, float* dbeta, int accumulate, float* coef, void* stream) {
   if (!partials || !coef || num_partials <= 0 || C <= 0) return CY_ERR_ARG;
   if (batch_stats && (!scale || !mean || !invstd || count <= 0)) return CY_ERR_ARG;
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(cy_cdiv(C, 4)), dim3(256), 0,
+  cy_norm_act_plan_t pl;
+  na_plan(CY_NA_BWD_FINALIZE, num_partials, C, CY_F32, 0, &pl);
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(pl.grid), dim3(pl.threads), 0,
                      (hipStream_t)stream, partials, num_partials, C, scale, mean, invstd, count,
                      batch_stats, dgamma, dbeta, accumulate, coef);
   CY_CHECK_LAUNCH();
@@ -901,10 +1059,13 @@ int cy_bn_relu_bwd_apply(const void* da, int ld_da, const void* y, const float* 
   if (!da || !y || !scale || !shift || !coef || !dy) return CY_ERR_ARG;
   if (C % 8 || ld_da % 8 || ld_da < C) return CY_ERR_SHAPE;
   hipStream_t st = (hipStream_t)stream;
-  const int grid = stream_grid(npix * (C / 8));
+  cy_norm_act_plan_t pl;
+  na_plan(CY_NA_BWD_APPLY, npix, C, na_type(dtype), 0, &pl);
+  if (pl.status) return pl.status;
+  const int grid = pl.grid;
   const BnBwdFold nf = {};
 #define CY_BWD_APPLY(TT)                                                                                          \
-  hipLaunchKernelGGL((bn_relu_bwd_apply_kernel<TT, false>), dim3(grid), dim3(256), 0, st, (const TT*)da, ld_da,    \
+  hipLaunchKernelGGL((bn_relu_bwd_apply_kernel<TT, false>), dim3(grid), dim3(pl.threads), 0, st, (const TT*)da, ld_da, \
                      (const TT*)y, scale, shift, coef, (TT*)dy, npix, C, nf)
   if (dtype == CY_BF16) CY_BWD_APPLY(bf16);
   else if (dtype == CY_F16) CY_BWD_APPLY(f16);
@@ -925,10 +1086,13 @@ int cy_bn_relu_bwd_apply_fold(const void* da, int ld_da, const void* y, const fl
   BnBwdFold f;
   f.acc = (const unsigned long long*)acc->acc, f.R = acc->R, f.C = C, f.coef = coef;
   f.inv_count = 1.0 / count, f.batch_stats = batch_stats, f.accumulate = accumulate, f.dgamma = dgamma, f.dbeta = dbeta;
-  const int grid = fold_grid(npix * (C / 8));
-  const size_t smem = (size_t)4 * C * sizeof(float) + ((size_t)4 * C + 2) * 8;
+  cy_norm_act_plan_t pl;
+  na_plan(CY_NA_BWD_APPLY, npix, C, na_type(dtype), acc->R, &pl);
+  if (pl.status) return pl.status;
+  const int grid = pl.grid;
+  const size_t smem = (size_t)pl.lds_bytes;
 #define CY_BWD_APPLY(TT)                                                                                          \
-  hipLaunchKernelGGL((bn_relu_bwd_apply_kernel<TT, true>), dim3(grid), dim3(1024), smem, st, (const TT*)da, ld_da,  \
+  hipLaunchKernelGGL((bn_relu_bwd_apply_kernel<TT, true>), dim3(grid), dim3(pl.threads), smem, st, (const TT*)da, ld_da, \
                      (const TT*)y, coef, coef + C, (const float*)nullptr, (TT*)dy, npix, C, f)
   if (dtype == CY_BF16) CY_BWD_APPLY(bf16);
   else if (dtype == CY_F16) CY_BWD_APPLY(f16);
@@ -944,9 +1108,12 @@ int cy_maxpool2_bwd(const void* x, const void* dpool, const void* add, int ld_ad
   if (!x || !dpool || !dx || N <= 0 || H <= 0 || W <= 0) return CY_ERR_ARG;
   if (C % 8 || (add && (ld_add % 8 || ld_add < C))) return CY_ERR_SHAPE;
   hipStream_t st = (hipStream_t)stream;
-  const int grid = stream_grid((long)N * H * W * (C / 8));
+  cy_norm_act_plan_t pl;
+  na_plan(CY_NA_POOL_BWD, (long)N * H * W, C, na_type(dtype), 0, &pl);
+  if (pl.status) return pl.status;
+  const int grid = pl.grid;
 #define CY_POOL_BWD(TT)                                                                                          \
-  hipLaunchKernelGGL((maxpool2_bwd_kernel<TT, false>), dim3(grid), dim3(256), 0, st, (const TT*)x,              \
+  hipLaunchKernelGGL((maxpool2_bwd_kernel<TT, false>), dim3(grid), dim3(pl.threads), 0, st, (const TT*)x,       \
                      (const TT*)dpool, (const TT*)add, ld_add, (TT*)dx, N, H, W, C, (const TT*)nullptr, nullptr, \
                      nullptr, nullptr, nullptr, nullptr, nullptr, 0)
   if (dtype == CY_BF16) CY_POOL_BWD(bf16);
@@ -961,10 +1128,10 @@ int cy_maxpool2_bwd(const void* x, const void* dpool, const void* add, int ld_ad
 /* partial rows cy_maxpool2_bwd_bn writes (a function of the geometry only), or CY_ERR_SHAPE when the fused form
  * does not apply (the channel groups must divide a workgroup) */
 int cy_maxpool2_bwd_bn_num_partials(int N, int H, int W, int C) {
-  if (N <= 0 || H <= 0 || W <= 0 || C % 8 || C / 8 > 256 || 256 % (C / 8)) return CY_ERR_SHAPE;
-  long b = ((long)N * H * W * (C / 8) + 255) / 256;
-  if (b > 1024) b = 1024;
-  return (int)(b < 1 ? 1 : b);
+  if (N <= 0 || H <= 0 || W <= 0) return CY_ERR_SHAPE;
+  cy_norm_act_plan_t pl;
+  na_plan(CY_NA_POOL_BWD_BN, (long)N * H * W, C, CY_F32, 0, &pl);
+  return pl.fused_ok ? pl.grid : CY_ERR_SHAPE;
 }
 
 static int maxpool2_bwd_bn_impl(const void* x, const void* dpool, const void* add, int ld_add, void* dx, const void* y,
@@ -994,11 +1161,14 @@ static int maxpool2_bwd_bn_impl(const void* x, const void* dpool, const void* ad
                                 void* stream) {
   if (!x || !dpool || !dx || !y || !scale || !shift || !mean || !invstd || (!partials && !sacc)) return CY_ERR_ARG;
   if (add && (ld_add % 8 || ld_add < C)) return CY_ERR_SHAPE;
-  const int grid = cy_maxpool2_bwd_bn_num_partials(N, H, W, C);
-  if (grid < 0) return grid;
+  if (N <= 0 || H <= 0 || W <= 0) return CY_ERR_SHAPE;
+  cy_norm_act_plan_t pl;
+  na_plan(CY_NA_POOL_BWD_BN, (long)N * H * W, C, na_type(dtype), sacc ? sR : 0, &pl);
+  if (pl.status) return pl.status;
+  const int grid = pl.grid;
   hipStream_t st = (hipStream_t)stream;
 #define CY_POOL_BWD(TT)                                                                                      \
-  hipLaunchKernelGGL((maxpool2_bwd_kernel<TT, true>), dim3(grid), dim3(256), 0, st, (const TT*)x,           \
+  hipLaunchKernelGGL((maxpool2_bwd_kernel<TT, true>), dim3(grid), dim3(pl.threads), 0, st, (const TT*)x,    \
                      (const TT*)dpool, (const TT*)add, ld_add, (TT*)dx, N, H, W, C, (const TT*)y, scale, shift, \
                      mean, invstd, partials, sacc, sR)
   if (dtype == CY_BF16) CY_POOL_BWD(bf16);
@@ -1015,16 +1185,15 @@ static int upsample2_bwd_impl(const void* dup, int ld_dup, void* dx, const void*
   if (!dup || !dx || N <= 0 || H <= 0 || W <= 0) return CY_ERR_ARG;
   if (C % 8 || ld_dup % 8 || ld_dup < C) return CY_ERR_SHAPE;
   hipStream_t st = (hipStream_t)stream;
-  int grid = stream_grid((long)N * H * W * (C / 8));
-  if (sacc) {
-    if (C / 8 > 256 || 256 % (C / 8)) return CY_ERR_SHAPE;
-    grid = cy_upsample2_bwd_bn_workgroups(N, H, W, C);
-  }
+  cy_norm_act_plan_t pl;
+  na_plan(sacc ? CY_NA_UP_BWD_BN : CY_NA_UP_BWD, (long)N * H * W, C, na_type(dtype), sacc ? sR : 0, &pl);
+  if (pl.status) return pl.status;
+  const int grid = pl.grid;
 #define CY_UP_BWD(TT)                                                                                             \
   do {                                                                                                            \
-    if (sacc) hipLaunchKernelGGL((upsample2_bwd_kernel<TT, true>), dim3(grid), dim3(256), 0, st, (const TT*)dup,   \
-                                 ld_dup, (TT*)dx, N, H, W, C, (const TT*)y, coef, sacc, sR);                      \
-    else hipLaunchKernelGGL((upsample2_bwd_kernel<TT, false>), dim3(grid), dim3(256), 0, st, (const TT*)dup,       \
+    if (pl.kernel == 11) hipLaunchKernelGGL((upsample2_bwd_kernel<TT, true>), dim3(grid), dim3(pl.threads), 0, st, \
+                                            (const TT*)dup, ld_dup, (TT*)dx, N, H, W, C, (const TT*)y, coef, sacc, sR); \
+    else hipLaunchKernelGGL((upsample2_bwd_kernel<TT, false>), dim3(grid), dim3(pl.threads), 0, st, (const TT*)dup, \
                             ld_dup, (TT*)dx, N, H, W, C, (const TT*)nullptr, (const float*)nullptr,               \
                             (unsigned long long*)nullptr, 0);                                                     \
   } while (0)
@@ -1043,16 +1212,25 @@ int cy_upsample2_bwd(const void* dup, int ld_dup, void* dx, int N, int H, int W,
 }
 
 int cy_upsample2_bwd_bn_workgroups(int N, int H, int W, int C) {
-  if (N <= 0 || H <= 0 || W <= 0 || C % 8 || C / 8 > 256 || 256 % (C / 8)) return CY_ERR_SHAPE;
-  long b = ((long)N * H * W * (C / 8) + 255) / 256;
-  if (b > 1024) b = 1024;
-  return (int)(b < 1 ? 1 : b);
+  if (N <= 0 || H <= 0 || W <= 0) return CY_ERR_SHAPE;
+  cy_norm_act_plan_t pl;
+  na_plan(CY_NA_UP_BWD_BN, (long)N * H * W, C, CY_F32, 0, &pl);
+  return pl.fused_ok ? pl.grid : CY_ERR_SHAPE;
 }
 
 int cy_upsample2_bwd_bn_acc(const void* dup, int ld_dup, void* dx, const void* y, const float* coef,
                             const cy_bn_acc* acc, int N, int H, int W, int C, int dtype, void* stream) {
   if (!y || !coef || !acc || !acc->acc || acc->C != C || acc->R < 1 || (acc->R & (acc->R - 1))) return CY_ERR_ARG;
   return upsample2_bwd_impl(dup, ld_dup, dx, y, coef, (unsigned long long*)acc->acc, acc->R, N, H, W, C, dtype, stream);
+}
+
+/* every host-side decision of this file for one launch (contrastyou_hip.h) */
+int cy_norm_act_plan(int kind, int N, int H, int W, int C, int dtype, int fold, cy_norm_act_plan_t* out) {
+  if (!out || kind < CY_NA_APPLY || kind > CY_NA_FOLD_COEF) return CY_ERR_ARG;
+  if (N < 1 || H < 1 || W < 1 || C < 1 || dtype < 0 || fold < 0 || (fold & (fold - 1))) return CY_ERR_ARG;
+  if (kind == CY_NA_FOLD_COEF && fold < 1) return CY_ERR_ARG;
+  na_plan(kind, (long)N * H * W, C, dtype, fold, out);
+  return CY_OK;
 }
 
 }  // extern "C"

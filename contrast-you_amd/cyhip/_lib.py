@@ -11,7 +11,7 @@ from pathlib import Path
 
 CY_F32, CY_BF16, CY_F16 = 0, 1, 2
 CY_SRC_DIRECT, CY_SRC_POOL2, CY_SRC_UP2 = 0, 1, 2
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 _ERRORS = {-1: "CY_ERR_ARG (bad/NULL argument)", -2: "CY_ERR_SHAPE (unsupported shape)",
            -3: "CY_ERR_DTYPE (unsupported dtype)", -4: "CY_ERR_LAUNCH (HIP launch failed)",
@@ -76,6 +76,19 @@ class GroupSoftmaxPlan(C.Structure):
     """mirror of cy_group_softmax_plan_t"""
     _fields_ = [(n, c_int32) for n in ("fwd_rows", "fwd_grid", "fwd_lds", "fwd_ok", "bwd_rows", "bwd_grid", "bwd_lds",
                                        "bwd_ok")]
+
+
+class NormActPlan(C.Structure):
+    """mirror of cy_norm_act_plan_t"""
+    _fields_ = [(n, c_int32) for n in ("status", "kernel", "type_in", "type_out", "threads", "grid", "lds_bytes", "items",
+                                       "trips", "one_trip_items", "fold", "gather", "pow2", "deep", "rows",
+                                       "groups_per_page", "pages", "last_page_groups", "pixels_per_workgroup",
+                                       "empty_workgroups", "round4", "tail1", "idle_rows", "idle_threads", "fused_ok",
+                                       "partial_rows", "chain")]
+
+
+NORM_ACT_KINDS = ("apply", "apply_pool", "bwd_reduce", "bwd_apply", "pool_bwd", "pool_bwd_bn", "up_bwd", "up_bwd_bn",
+                  "finalize", "bwd_finalize", "fold_coef")
 
 
 class WgradReduceEntry(C.Structure):
@@ -276,6 +289,7 @@ _SIGS = {
     "cy_group_softmax_bwd": (c_int, [_P, _P, _P, c_long, c_int, c_int, c_float, _P]),
     "cy_group_softmax_plan": (c_int, [c_long, c_int, c_int, POINTER(GroupSoftmaxPlan)]),
     "cy_joint_plan": (c_int, [c_int] * 5 + [POINTER(JointPlan)]),
+    "cy_norm_act_plan": (c_int, [c_int] * 7 + [POINTER(NormActPlan)]),
     "cy_joint_ws_bytes": (c_size_t, [c_int] * 5),
     "cy_joint_fwd": (c_int, [_P, _P, _P] + [c_int] * 6 + [_P, c_size_t, _P]),
     "cy_joint_bwd": (c_int, [_P, _P, _P, _P, _P, _P] + [c_int] * 6 + [_P]),

@@ -1393,6 +1393,22 @@ def upsample2_bwd(dup: Tensor) -> Tensor:
     return dx
 
 
+def norm_act_plan(kind: str, N: int, H: int, W: int, Cc: int, dtype: torch.dtype = torch.float32, fold: int = 0,
+                  out_dtype: Optional[torch.dtype] = None) -> dict:
+    """the launch plan of the BatchNorm, pool and upsample kernels (cy_norm_act_plan; host-side query, no GPU needed).
+    kind: one of _lib.NORM_ACT_KINDS; (H, W) are the pooled / low-resolution dims for the pool and upsample kinds, and
+    N * H * W the number of partial rows for the finalize kinds.  fold: 0, or the replica count R of the accumulator the
+    launch reads or adds into.  Returns the fields of cy_norm_act_plan_t; "status" is what the launch answers for the
+    shape (0, or CY_ERR_SHAPE / CY_ERR_DTYPE), so refused shapes do not raise here."""
+    p = _lib.NormActPlan()
+    dt = dtype_code(dtype)
+    if out_dtype is not None and out_dtype != dtype:
+        dt |= (dtype_code(out_dtype) + 1) << 4
+    _lib.call("cy_norm_act_plan", _lib.NORM_ACT_KINDS.index(kind), int(N), int(H), int(W), int(Cc), dt, int(fold),
+              C.byref(p))
+    return {f: getattr(p, f) for f, _ in p._fields_}
+
+
 # --------------------------------------------------------------------------- head + losses
 def head_fwd(x: Tensor, w: Tensor, b: Optional[Tensor]) -> Tensor:
     """x [N,C,H,W] NHWC -> f32 logits [N,K,H,W] NHWC."""

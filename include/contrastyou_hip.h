@@ -422,6 +422,68 @@ int cy_maxpool2_bwd_bn(const void* x, const void* dpool, const void* add, int ld
 int cy_upsample2_bwd(const void* dup, int ld_dup, void* dx, int N, int H, int W, int C, int dtype,
                      void* stream);
 
+/* Launch plan of the BatchNorm, pool and upsample kernels (ABI v18; csrc/cy_norm_act.hip).  Host-side only, launches
+ * nothing and needs no GPU.  Every launch of that file, and cy_bn_bwd_num_partials, cy_bn_relu_bwd_workgroups,
+ * cy_maxpool2_bwd_bn_num_partials and cy_upsample2_bwd_bn_workgroups, take kernel, grid and LDS from this function.
+ *   kind   what N * H * W counts                                         the launches it describes
+ *   CY_NA_APPLY         pixels                                           cy_bn_relu_apply, _apply_fold
+ *   CY_NA_APPLY_POOL    2x2 quads (H, W: the pooled dims)                cy_bn_relu_apply_pool, _apply_pool_fold
+ *   CY_NA_BWD_REDUCE    pixels                                           cy_bn_relu_bwd_reduce, _reduce_acc
+ *   CY_NA_BWD_APPLY     pixels                                           cy_bn_relu_bwd_apply, _apply_fold
+ *   CY_NA_POOL_BWD(_BN) 2x2 quads (H, W: the pooled dims)                cy_maxpool2_bwd, (_bwd_bn, _bwd_bn_acc)
+ *   CY_NA_UP_BWD(_BN)   source pixels (H, W: the low-resolution dims)    cy_upsample2_bwd, (_bwd_bn_acc)
+ *   CY_NA_FINALIZE, CY_NA_BWD_FINALIZE   partial rows                    cy_bn_finalize, cy_bn_bwd_finalize
+ *   CY_NA_FOLD_COEF     ignored (pass 1, 1, 1)                           cy_bn_fold_coef
+ * dtype: the storage type (CY_F32 / CY_BF16 / CY_F16); the two applies that write another type than they read add
+ * CY_NA_OUT(out_dtype).  fold: 0 for the forms fed coefficients or partial rows; R >= 1 (a power of two) for the forms on
+ * an accumulator of R replicas (the fold applies, cy_bn_fold_coef; for the reduce and the fused forms: the accumulator
+ * they add into).  Returns CY_ERR_ARG for a NULL `out`, an unknown kind, a dimension < 1 or such a `fold`; otherwise
+ * CY_OK with `status` = what the launch itself answers for the shape. */
+enum {
+  CY_NA_APPLY = 0, CY_NA_APPLY_POOL = 1, CY_NA_BWD_REDUCE = 2, CY_NA_BWD_APPLY = 3, CY_NA_POOL_BWD = 4,
+  CY_NA_POOL_BWD_BN = 5, CY_NA_UP_BWD = 6, CY_NA_UP_BWD_BN = 7, CY_NA_FINALIZE = 8, CY_NA_BWD_FINALIZE = 9,
+  CY_NA_FOLD_COEF = 10
+};
+#define CY_NA_OUT(out_dtype) (((out_dtype) + 1) << 4)
+typedef struct cy_norm_act_plan_t {
+  int32_t status;        /* CY_OK, or what the launch returns: CY_ERR_SHAPE (C % 8; C > 1024 on the fold applies, > 2048 on
+                            cy_bn_fold_coef; a fused form that does not apply), CY_ERR_DTYPE */
+  int32_t kernel;        /* 0 bn_relu_apply_kernel<false>, 1 <true> (fold), 2 bn_relu_apply_pool_kernel<false>, 3 <true>,
+                            4 bn_relu_bwd_reduce_kernel<DEEP>, 5 <not DEEP>, 6 bn_relu_bwd_apply_kernel<false>, 7 <true>,
+                            8 maxpool2_bwd_kernel<false>, 9 <STATS>, 10 upsample2_bwd_kernel<false>, 11 <STATS>,
+                            12 bn_finalize_kernel, 13 bn_bwd_finalize_kernel, 14 bn_fold_kernel.  A fused kind that does
+                            not apply reports the unfused kernel (8 / 10) and its grid: what the caller then launches */
+  int32_t type_in;       /* CY_F32 / CY_BF16 / CY_F16 */
+  int32_t type_out;
+  int32_t threads;       /* per workgroup */
+  int32_t grid;          /* workgroups */
+  int32_t lds_bytes;     /* static + dynamic */
+  int32_t items;         /* units of the grid-stride loop (8 channels of a pixel, of a quad, of a source pixel; reduce:
+                            pixels; finalize kinds: partial rows; fold_coef: channels), saturated at 2^31 - 1 */
+  int32_t trips;         /* most trips a thread makes through that loop */
+  int32_t one_trip_items;/* the grid's cap times `threads`: a second trip from one item more (0: the loop has no cap) */
+  int32_t fold;          /* replicas R of the accumulator read (fold forms) or added into; 0 none */
+  int32_t gather;        /* how a fold form sums the replicas: 0 none, 1 direct (R <= 8), 2 direct, wide (R = 16, 32 in the
+                            elementwise kernels), 3 LDS atomics */
+  int32_t pow2;          /* backward apply: C/8 is a power of two (shift and mask instead of the division) */
+  int32_t deep;          /* reduce: the four-pixel form (grid < 512) */
+  int32_t rows;          /* reduce: pixel rows of a workgroup, 256 / groups_per_page */
+  int32_t groups_per_page; /* reduce: min(C/8, 256) */
+  int32_t pages;         /* reduce: ceil((C/8) / 256) */
+  int32_t last_page_groups; /* reduce: channel groups of the last page */
+  int32_t pixels_per_workgroup; /* reduce: ceil(pixels / grid) */
+  int32_t empty_workgroups;     /* reduce: trailing workgroups that get no pixel (they write zero rows) */
+  int32_t round4;        /* reduce: 1 if some thread executes the four-pixel round */
+  int32_t tail1;         /* reduce: 1 if some thread executes the one-pixel loop */
+  int32_t idle_rows;     /* reduce: pixel rows beyond the pixels of a full workgroup */
+  int32_t idle_threads;  /* reduce: 256 - rows * groups_per_page; finalize kinds: threads of the last workgroup past C */
+  int32_t fused_ok;      /* kinds *_BN: 1 if the fused form applies (256 % (C/8) == 0), else 0 (status CY_ERR_SHAPE) */
+  int32_t partial_rows;  /* rows of [2][C] partial sums written = workgroups adding into one channel's sums; 0: none */
+  int32_t chain;         /* longest chain of f32 additions of non-zero terms behind one word of those sums (reduce: trips +
+                            rows - idle_rows); 0: none */
+} cy_norm_act_plan_t;
+int cy_norm_act_plan(int kind, int N, int H, int W, int C, int dtype, int fold, cy_norm_act_plan_t* out);
+
 /* ------------------------------------------------------------------------
  * 1x1 classifier head  nn.Conv2d(C, K, 1) + bias  (arch/unet.py:102)
  * logits are f32 [N,H,W,K].

@@ -11,6 +11,22 @@ def acc_sums(acc):
     return w[0] / 4096.0 + w[1] / 2.0 ** 44, w[2] / 4096.0 + w[3] / 2.0 ** 44
 
 
+def acc_encode(parts):
+    """the inverse of acc_sums: float64 parts [R][2][C] (per replica: its share of the two sums) -> int64 words
+    [R][4][C] as bn_acc_add splits them, hi = rint(s * 2^12), lo = rint((s - hi * 2^-12) * 2^44); no flag words"""
+    parts = parts.double()
+    hi = torch.round(parts * 4096.0)
+    lo = torch.round((parts - hi / 4096.0) * 2.0 ** 44)
+    R, _, C = parts.shape
+    return torch.stack([hi[:, 0], lo[:, 0], hi[:, 1], lo[:, 1]], dim=1).to(torch.int64).reshape(R, 4, C)
+
+
+def words_sums(words):
+    """what a consumer reads from int64 words [R][4][C]: the replicas added as integers, then the two limbs joined"""
+    w = words.sum(0).double()
+    return w[0] / 4096.0 + w[1] / 2.0 ** 44, w[2] / 4096.0 + w[3] / 2.0 ** 44
+
+
 def assert_acc_equals_partial_rows(acc, part, streaming: bool, what=""):
     """the partial rows are f32; their exact sum is what the accumulator holds (each split is exact above 2^-21) -- but
     for the streaming kernel, which sums its four wave rows in f32 before it adds (one add per workgroup).

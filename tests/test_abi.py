@@ -111,7 +111,7 @@ def test_head_plan_layouts_match_header(struct, mirror):
     """cy_head_plan / cy_cluster_plan (ABI v16) and their ctypes mirrors name the same int32 fields in order"""
     from cyhip import _lib
     _check_plan_layout(struct, mirror)
-    assert _lib.ABI_VERSION == 17
+    assert _lib.ABI_VERSION == 18
 
 
 @pytest.mark.parametrize("struct,mirror", [("cy_joint_plan_t", "JointPlan"),
@@ -122,8 +122,21 @@ def test_mi_plan_layouts_match_header(struct, mirror):
     from cyhip import _lib
     fields = _check_plan_layout(struct, mirror)
     assert fields[0] in ("fwd_kernel", "fwd_rows")
-    assert _lib.ABI_VERSION == 17 and _lib.load().cy_abi_version() == 17
+    assert _lib.ABI_VERSION == 18 and _lib.load().cy_abi_version() == 18
     assert {"cy_joint_plan", "cy_group_softmax_plan"} <= set(_lib.exported_names()) & set(header_symbols())
+
+
+def test_norm_act_plan_layout_matches_header():
+    """cy_norm_act_plan_t (ABI v18) and its ctypes mirror name the same int32 fields in order; the kinds of the binding
+    are the header's enum, in order; the plan entry point is exported and typed"""
+    from cyhip import _lib
+    fields = _check_plan_layout("cy_norm_act_plan_t", "NormActPlan")
+    assert fields[0] == "status" and fields[-1] == "chain"
+    assert _lib.ABI_VERSION == 18 and _lib.load().cy_abi_version() == 18
+    assert "cy_norm_act_plan" in set(_lib.exported_names()) & set(header_symbols())
+    enum = re.search(r"enum \{\s*(CY_NA_APPLY = 0.*?)\};", HEADER.read_text(), flags=re.S).group(1)
+    names = [(m.group(1).lower(), int(m.group(2))) for m in re.finditer(r"CY_NA_([A-Z0-9_]+) = (\d+)", enum)]
+    assert names == [(k, i) for i, k in enumerate(_lib.NORM_ACT_KINDS)]
 
 
 def test_loading_the_library_first_leaves_one_hip_runtime():
