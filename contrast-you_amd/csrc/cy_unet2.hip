@@ -408,7 +408,9 @@ __global__ void __launch_bounds__(256) sinusoidal_emb_kernel(const float* __rest
   const int e = blockIdx.x * 256 + threadIdx.x;
   if (e >= B * half) return;
   const int b = e / half, i = e - b * half;
-  const float f = expf((float)i * -(logf(10000.f) / (float)(half - 1)));
+  // the frequency in double, rounded once: three f32 roundings of an exponent of up to 9.2 moved t e_i by several of its
+  // ulp at dim = 128 (one thread per table entry: the cost is nothing)
+  const float f = (float)exp((double)i * -(log(10000.0) / (double)(half - 1)));
   const float a = t[b] * f;
   out[(size_t)b * dim + i] = sinf(a);
   out[(size_t)b * dim + half + i] = cosf(a);
