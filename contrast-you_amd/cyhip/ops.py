@@ -265,8 +265,16 @@ def _desc(N, H, W, C1, C2, Cout, mode, prologue, dt, ld1, ld2, ldo, split_c=0, l
     return p
 
 
-# cy_conv_plan.kernel: CY_CONV_KERNEL_IGEMM / _PLANE / _STREAM / _FLOW of include/contrastyou_hip.h
-KERNEL_NAMES = {0: "conv3x3_igemm_kernel", 1: "conv3x3_plane_kernel", 4: "conv3x3_stream_kernel", 5: "conv3x3_flow_kernel"}
+def _query(struct, name: str, *args, skip=()) -> dict:
+    """a host-side query whose last argument is a `struct` the library fills in: the fields it answers, by name"""
+    s = struct()
+    _lib.call(name, *args, C.byref(s))
+    return {f: getattr(s, f) for f, _ in s._fields_ if f not in skip}
+
+
+# cy_conv_plan.kernel
+KERNEL_NAMES = {_lib.CY_CONV_KERNEL_IGEMM: "conv3x3_igemm_kernel", _lib.CY_CONV_KERNEL_PLANE: "conv3x3_plane_kernel",
+                _lib.CY_CONV_KERNEL_STREAM: "conv3x3_stream_kernel", _lib.CY_CONV_KERNEL_FLOW: "conv3x3_flow_kernel"}
 
 
 def conv3x3_plan(N, H, W, C1, C2, Cout, dtype: torch.dtype, mode: int = 0, prologue: bool = False,
@@ -277,9 +285,7 @@ def conv3x3_plan(N, H, W, C1, C2, Cout, dtype: torch.dtype, mode: int = 0, prolo
         d = _desc(N, H, W, C1, C2, Cout, mode, 1 if prologue else 0, dtype_code(dtype), C1, C2, split, split, Cout - split)
     else:
         d = _desc(N, H, W, C1, C2, Cout, mode, 1 if prologue else 0, dtype_code(dtype), C1, C2, Cout)
-    p = _lib.ConvPlan()
-    _lib.call("cy_conv3x3_plan", d.ref, C.byref(p))
-    out = {f: getattr(p, f) for f, _ in p._fields_}
+    out = _query(_lib.ConvPlan, "cy_conv3x3_plan", d.ref)
     out["kernel"] = KERNEL_NAMES[out["kernel"]]
     out["ws_bytes"] = int(_lib.load().cy_conv3x3_fwd_ws_bytes(d.ref))  # (the split-K workspace: 0 when ksplit == 1)
     return out
@@ -289,9 +295,7 @@ def conv3x3_wgrad_plan(N, H, W, C1, C2, Cout, dtype: torch.dtype, mode: int = 0,
                        n_b: int = 0) -> dict:
     """the launch plan of cy_conv3x3_wgrad (n_b > 0: of cy_conv3x3_wgrad_pair) for this layer geometry"""
     d = _desc(N, H, W, C1, C2, Cout, mode, 1 if prologue else 0, dtype_code(dtype), C1, C2, Cout)
-    p = _lib.WgradPlan()
-    _lib.call("cy_conv3x3_wgrad_plan", d.ref, n_b, C.byref(p))
-    return {f: getattr(p, f) for f, _ in p._fields_}
+    return _query(_lib.WgradPlan, "cy_conv3x3_wgrad_plan", d.ref, n_b)
 
 
 def _out_hw(src1: Tensor, mode: int) -> Tuple[int, int]:
@@ -675,16 +679,13 @@ def wgrad_reduce_entry(N, H, W, C1, C2, Cout, dtype: torch.dtype, mode: int = 0,
                        n_b: int = 0) -> dict:
     """the slab-sum entry cy_conv3x3_wgrad (n_b > 0: _pair) makes for this layer geometry (host-side query)"""
     d = _desc(N, H, W, C1, C2, Cout, mode, 1 if prologue else 0, dtype_code(dtype), C1, C2, Cout)
-    e = _lib.WgradReduceEntry()
-    _lib.call("cy_conv3x3_wgrad_reduce_entry", d.ref, n_b, C.byref(e))
-    return {f: getattr(e, f) for f, _ in e._fields_ if f not in ("ws", "dw")}
+    return _query(_lib.WgradReduceEntry, "cy_conv3x3_wgrad_reduce_entry", d.ref, n_b, skip=("ws", "dw"))
 
 
 def first_wgrad_reduce_entry(N, Cin, H, W, Cout, dtype: torch.dtype) -> dict:
     """the partial-sum entry of cy_conv3x3_first_wgrad for these sizes (host-side query)"""
-    e = _lib.WgradReduceEntry()
-    _lib.call("cy_conv3x3_first_wgrad_reduce_entry", N, Cin, H, W, Cout, dtype_code(dtype), C.byref(e))
-    return {f: getattr(e, f) for f, _ in e._fields_ if f not in ("ws", "dw")}
+    return _query(_lib.WgradReduceEntry, "cy_conv3x3_first_wgrad_reduce_entry", N, Cin, H, W, Cout, dtype_code(dtype),
+                  skip=("ws", "dw"))
 
 
 # ---- deferred slab sums of the weight gradients ---------------------------------------------------------------------
@@ -1400,13 +1401,11 @@ def norm_act_plan(kind: str, N: int, H: int, W: int, Cc: int, dtype: torch.dtype
     N * H * W the number of partial rows for the finalize kinds.  fold: 0, or the replica count R of the accumulator the
     launch reads or adds into.  Returns the fields of cy_norm_act_plan_t; "status" is what the launch answers for the
     shape (0, or CY_ERR_SHAPE / CY_ERR_DTYPE), so refused shapes do not raise here."""
-    p = _lib.NormActPlan()
     dt = dtype_code(dtype)
     if out_dtype is not None and out_dtype != dtype:
         dt |= (dtype_code(out_dtype) + 1) << 4
-    _lib.call("cy_norm_act_plan", _lib.NORM_ACT_KINDS.index(kind), int(N), int(H), int(W), int(Cc), dt, int(fold),
-              C.byref(p))
-    return {f: getattr(p, f) for f, _ in p._fields_}
+    return _query(_lib.NormActPlan, "cy_norm_act_plan", _lib.NORM_ACT_KINDS.index(kind), int(N), int(H), int(W), int(Cc),
+                  dt, int(fold))
 
 
 # --------------------------------------------------------------------------- head + losses
@@ -1426,9 +1425,7 @@ def head_plan(npix: int, C_in: int, K: int, need_dx: bool = True, need_dw: bool 
     """the launch plan of cy_head1x1_fwd / _bwd for npix pixels, C_in channels, K outputs (host-side query, no GPU
     needed): the fields of cy_head_plan, and "ws_bytes", the backward's workspace (0 without need_dw).  Shapes the
     kernels refuse raise HipKernelError (CY_ERR_SHAPE)."""
-    p = _lib.HeadPlan()
-    _lib.call("cy_head1x1_plan", int(npix), int(C_in), int(K), int(bool(need_dx)), int(bool(need_dw)), C.byref(p))
-    out = {f: getattr(p, f) for f, _ in p._fields_}
+    out = _query(_lib.HeadPlan, "cy_head1x1_plan", int(npix), int(C_in), int(K), int(bool(need_dx)), int(bool(need_dw)))
     out["ws_bytes"] = int(_lib.load().cy_head1x1_bwd_ws_bytes(int(npix), int(C_in), int(K))) if need_dw else 0
     return out
 
@@ -2013,9 +2010,7 @@ def cluster_head_ok(C: int, S: int, k: int) -> bool:
 def cluster_head_plan(M: int, C_in: int, S: int, k: int) -> dict:
     """the launch shape of cy_cluster_head_fwd / _bwd (host-side query, no GPU needed): fwd_waves, fwd_grid, fwd_trips,
     bwd_grid, bwd_trips, slabs"""
-    p = _lib.ClusterPlan()
-    _lib.call("cy_cluster_head_plan", int(M), int(C_in), int(S), int(k), C.byref(p))
-    return {f: getattr(p, f) for f, _ in p._fields_}
+    return _query(_lib.ClusterPlan, "cy_cluster_head_plan", int(M), int(C_in), int(S), int(k))
 
 
 def cluster_head_fwd(x: Tensor, w: Tensor, b: Optional[Tensor], S: int, k: int, T: float = 1.0) -> Tensor:
@@ -2055,9 +2050,7 @@ def group_softmax_fwd(logits: Tensor, S: int, k: int, T: float = 1.0) -> Tensor:
 def group_softmax_plan(M: int, S: int, k: int) -> dict:
     """the launch plan of cy_group_softmax_fwd / _bwd (host-side query, no GPU needed): the fields of
     cy_group_softmax_plan_t.  S*k > 255 raises HipKernelError (CY_ERR_SHAPE), as both launches do."""
-    p = _lib.GroupSoftmaxPlan()
-    _lib.call("cy_group_softmax_plan", int(M), int(S), int(k), C.byref(p))
-    return {f: getattr(p, f) for f, _ in p._fields_}
+    return _query(_lib.GroupSoftmaxPlan, "cy_group_softmax_plan", int(M), int(S), int(k))
 
 
 def group_softmax_bwd(probs: Tensor, dprobs: Tensor, T: float = 1.0) -> Tensor:
@@ -2072,9 +2065,7 @@ def joint_plan(N: int, H: int, W: int, k: int, pad: int) -> dict:
     """the launch plan of cy_joint_fwd / _bwd for two [N,H,W,k] maps and padding `pad` (host-side query, no GPU needed):
     the fields of cy_joint_plan_t, and "ws_bytes", the forward's workspace.  Shapes the kernels refuse raise
     HipKernelError (CY_ERR_SHAPE)."""
-    p = _lib.JointPlan()
-    _lib.call("cy_joint_plan", int(N), int(H), int(W), int(k), int(pad), C.byref(p))
-    out = {f: getattr(p, f) for f, _ in p._fields_}
+    out = _query(_lib.JointPlan, "cy_joint_plan", int(N), int(H), int(W), int(k), int(pad))
     out["ws_bytes"] = int(_lib.load().cy_joint_ws_bytes(int(N), int(H), int(W), int(k), int(pad)))
     return out
 

@@ -46,7 +46,9 @@ extern "C" {
 #define CY_SRC_POOL2 1  /* src1 is [N,2H,2W,C1]; 2x2 max taken on load */
 #define CY_SRC_UP2 2    /* src1 is [N,H/2,W/2,C1]; nearest x2 on load */
 
-/* ABI version; bumped whenever a signature changes. */
+/* ABI version; bumped whenever a signature changes.  This line is the only place the number is written: the library
+ * returns it and the Python binding (cyhip/_lib.py, derived from this header) reads it from here. */
+#define CY_ABI_VERSION 18
 int cy_abi_version(void);
 /* name of the offload arch the library was built for ("gfx950"). */
 const char* cy_build_arch(void);

@@ -30,18 +30,27 @@ def test_library_exports_every_declared_symbol():
     assert lib.cy_build_arch() == b"gfx950"
 
 
-def test_conv_desc_layout_matches_header():
-    from cyhip._lib import ConvDesc
+def _check_plan_layout(struct, mirror):
+    """the test's own reading of an all-int32 struct body, independent of the parser that derives the mirror"""
+    from cyhip import _lib
+    cls = getattr(_lib, mirror)
     text = HEADER.read_text()
-    body = re.search(r"typedef struct cy_conv_desc \{(.*?)\} cy_conv_desc;", text, flags=re.S).group(1)
+    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), text, flags=re.S).group(1)
     body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
     fields = []
     for decl in body.split(";"):
         decl = decl.strip()
-        if decl.startswith("int32_t"):
-            fields += [f.strip() for f in decl[len("int32_t"):].split(",")]
-    assert fields == [f[0] for f in ConvDesc._fields_]
-    assert ctypes.sizeof(ConvDesc) == 4 * len(fields)
+        if decl:
+            assert decl.startswith("int32_t "), decl
+            fields += [f.strip() for f in decl[len("int32_t "):].split(",")]
+    assert fields == [n for n, _ in cls._fields_]
+    assert all(t is ctypes.c_int32 for _, t in cls._fields_)
+    assert ctypes.sizeof(cls) == 4 * len(fields)
+    return fields
+
+
+def test_conv_desc_layout_matches_header():
+    _check_plan_layout("cy_conv_desc", "ConvDesc")
 
 
 def test_argument_errors_are_reported_not_launched():
@@ -74,36 +83,8 @@ def test_no_oracle_import_in_product():
 
 def test_wgrad_plan_layout_matches_header():
     """cy_wgrad_plan (ABI v13: dma, blk_order appended) and its ctypes mirror name the same int32 fields in order"""
-    from cyhip._lib import WgradPlan
-    text = HEADER.read_text()
-    body = re.search(r"typedef struct cy_wgrad_plan \{(.*?)\} cy_wgrad_plan;", text, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if decl:
-            assert decl.startswith("int32_t "), decl
-            fields += [f.strip() for f in decl[len("int32_t "):].split(",")]
-    assert fields == [n for n, _ in WgradPlan._fields_]
+    fields = _check_plan_layout("cy_wgrad_plan", "WgradPlan")
     assert fields[-2:] == ["dma", "blk_order"]
-    assert ctypes.sizeof(WgradPlan) == 4 * len(fields)
-
-
-def _check_plan_layout(struct, mirror):
-    from cyhip import _lib
-    cls = getattr(_lib, mirror)
-    text = HEADER.read_text()
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), text, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if decl:
-            assert decl.startswith("int32_t "), decl
-            fields += [f.strip() for f in decl[len("int32_t "):].split(",")]
-    assert fields == [n for n, _ in cls._fields_]
-    assert ctypes.sizeof(cls) == 4 * len(fields)
-    return fields
 
 
 @pytest.mark.parametrize("struct,mirror", [("cy_head_plan", "HeadPlan"), ("cy_cluster_plan", "ClusterPlan")])
@@ -111,7 +92,7 @@ def test_head_plan_layouts_match_header(struct, mirror):
     """cy_head_plan / cy_cluster_plan (ABI v16) and their ctypes mirrors name the same int32 fields in order"""
     from cyhip import _lib
     _check_plan_layout(struct, mirror)
-    assert _lib.ABI_VERSION == 18
+    assert _lib.ABI_VERSION == _lib.load().cy_abi_version()
 
 
 @pytest.mark.parametrize("struct,mirror", [("cy_joint_plan_t", "JointPlan"),
@@ -122,7 +103,7 @@ def test_mi_plan_layouts_match_header(struct, mirror):
     from cyhip import _lib
     fields = _check_plan_layout(struct, mirror)
     assert fields[0] in ("fwd_kernel", "fwd_rows")
-    assert _lib.ABI_VERSION == 18 and _lib.load().cy_abi_version() == 18
+    assert _lib.ABI_VERSION == _lib.load().cy_abi_version()
     assert {"cy_joint_plan", "cy_group_softmax_plan"} <= set(_lib.exported_names()) & set(header_symbols())
 
 
@@ -132,7 +113,7 @@ def test_norm_act_plan_layout_matches_header():
     from cyhip import _lib
     fields = _check_plan_layout("cy_norm_act_plan_t", "NormActPlan")
     assert fields[0] == "status" and fields[-1] == "chain"
-    assert _lib.ABI_VERSION == 18 and _lib.load().cy_abi_version() == 18
+    assert _lib.ABI_VERSION == _lib.load().cy_abi_version()
     assert "cy_norm_act_plan" in set(_lib.exported_names()) & set(header_symbols())
     enum = re.search(r"enum \{\s*(CY_NA_APPLY = 0.*?)\};", HEADER.read_text(), flags=re.S).group(1)
     names = [(m.group(1).lower(), int(m.group(2))) for m in re.finditer(r"CY_NA_([A-Z0-9_]+) = (\d+)", enum)]
@@ -152,3 +133,105 @@ def test_loading_the_library_first_leaves_one_hip_runtime():
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr
     assert int(r.stdout.strip().splitlines()[-1]) == 1, r.stdout
+
+
+# ---- the binding is derived from the header: what the derivation must come to is written out here by hand ----------
+
+def test_abi_version_has_one_source():
+    """the number is written once in the header; the library returns the macro and the binding reads it.  This is the
+    one place a test pins it: an ABI bump edits the header's define and this line"""
+    from cyhip import _lib
+    macro = int(re.search(r"^#define CY_ABI_VERSION (\d+)$", HEADER.read_text(), flags=re.M).group(1))
+    assert macro == 18
+    assert _lib.load().cy_abi_version() == 18
+    assert _lib.ABI_VERSION == 18
+
+
+def test_pinned_signatures():
+    """ten signatures written out by hand; between them they use every row of the binding's type map"""
+    from ctypes import (POINTER, c_char_p, c_double, c_float, c_int, c_long, c_longlong, c_size_t, c_ulonglong,
+                        c_void_p)
+    from cyhip import _lib
+    P, PCD, PML = c_void_p, POINTER(_lib.ConvDesc), POINTER(_lib.MatLayout)
+    pinned = {
+        "cy_abi_version": (c_int, []),
+        "cy_build_arch": (c_char_p, []),
+        "cy_stream_capture_id": (c_ulonglong, [P]),
+        "cy_conv3x3_packed_elems": (c_longlong, [c_int, c_int, c_int]),
+        "cy_conv3x3_fwd": (c_int, [PCD, P, P, P, P, P, P, P, P, P, c_size_t, P]),
+        "cy_bn_finalize": (c_int, [P, c_int, c_int, c_double, P, P, P, P, c_float, c_float, c_int, c_int, P, P, P, P,
+                                   P]),
+        "cy_gemm_strided": (c_int, [P, PML, P, PML, P, PML, P, c_int, c_int, c_int, c_int, c_int, c_float, c_int,
+                                    c_int, P, c_size_t, P]),
+        "cy_conv3x3_dgrad_bn": (c_int, [PCD, P, POINTER(_lib.BnBwdIn), P, P, P, P, c_size_t, P]),
+        "cy_head1x1_plan": (c_int, [c_long, c_int, c_int, c_int, c_int, POINTER(_lib.HeadPlan)]),
+        # the one override: the table of items travels as a tensor's data_ptr(), so argument 0 is not POINTER(PackItem)
+        "cy_conv3x3_pack_weights_batched": (c_int, [P, c_int, c_longlong, P, P, c_int, P]),
+    }
+    lib = _lib.load()
+    for name, (res, args) in pinned.items():
+        assert _lib._SIGS[name][0] is res, name
+        got = _lib._SIGS[name][1]
+        assert len(got) == len(args) and all(a is b for a, b in zip(got, args)), (name, got)
+        assert getattr(lib, name).restype is res and list(getattr(lib, name).argtypes) == args, name
+
+
+def test_pinned_layouts():
+    """four mixed-type structs written out by hand: field names, ctypes and order, and the size the C compiler gives
+    them on x86-64 (LP64)"""
+    from ctypes import POINTER, c_double, c_float, c_int32, c_long, c_longlong, c_void_p
+    from cyhip import _lib
+    P = c_void_p
+    pinned = {
+        "BnFold": (56, [("acc", P), ("R", c_int32), ("C", c_int32), ("gamma", P), ("beta", P), ("count", c_double),
+                        ("eps", c_float), ("reserved", c_int32), ("coef", P)]),
+        "PackItem": (72, [("w", P), ("off_f", c_longlong), ("off_d", c_longlong), ("first", c_longlong),
+                          ("Cout", c_int32), ("Cin", c_int32), ("co_pad", c_int32), ("ci_pad", c_int32),
+                          ("ci_pad2", c_int32), ("co_pad2", c_int32), ("off_ff", c_longlong), ("off_fd", c_longlong)]),
+        "BnBwdIn": (64, [("y", P), ("coef", P), ("acc", POINTER(_lib.BnAcc)), ("count", c_double),
+                         ("batch_stats", c_int32), ("accumulate", c_int32), ("dgamma", P), ("dbeta", P), ("dy", P)]),
+        "MatLayout": (32, [("rs", c_long), ("cs", c_long), ("s1", c_long), ("s2", c_long)]),
+    }
+    for mirror, (size, fields) in pinned.items():
+        cls = getattr(_lib, mirror)
+        got = list(cls._fields_)
+        assert [n for n, _ in got] == [n for n, _ in fields], mirror
+        assert all(a[1] is b[1] for a, b in zip(got, fields)), (mirror, got)
+        assert ctypes.sizeof(cls) == size, mirror
+
+
+MIRRORS = {"cy_conv_desc": "ConvDesc", "cy_pack_item": "PackItem", "cy_conv_plan": "ConvPlan",
+           "cy_wgrad_plan": "WgradPlan", "cy_head_plan": "HeadPlan", "cy_cluster_plan": "ClusterPlan",
+           "cy_joint_plan_t": "JointPlan", "cy_group_softmax_plan_t": "GroupSoftmaxPlan",
+           "cy_norm_act_plan_t": "NormActPlan", "cy_wgrad_reduce_entry": "WgradReduceEntry", "cy_bn_acc": "BnAcc",
+           "cy_bn_fold": "BnFold", "cy_bn_bwd_in": "BnBwdIn", "cy_bn_dz_out": "BnDzOut", "cy_bn_run_item": "BnRunItem",
+           "cy_mat_layout": "MatLayout"}
+
+
+def test_every_struct_has_a_mirror_and_every_struct_pointer_resolves_to_it():
+    from cyhip import _lib
+    text = re.sub(r"/\*.*?\*/", "", HEADER.read_text(), flags=re.S)
+    declared = re.findall(r"typedef struct[^{;]*\{[^}]*\}\s*(\w+)\s*;", text)
+    assert len(declared) == 16 and sorted(declared) == sorted(MIRRORS)
+    for struct, mirror in MIRRORS.items():
+        assert issubclass(getattr(_lib, mirror), ctypes.Structure), mirror
+    seen = set()
+    for name, args in re.findall(r"\b(cy_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text):
+        for i, arg in enumerate(args.split(",")):
+            m = re.match(r"\s*(?:const\s+)?(cy_\w+)\s*\*", arg)
+            if m and (name, i) != ("cy_conv3x3_pack_weights_batched", 0):
+                assert _lib._SIGS[name][1][i] is ctypes.POINTER(getattr(_lib, MIRRORS[m.group(1)])), (name, i)
+                seen.add(m.group(1))
+    # cy_pack_item travels as a device table (the override), cy_bn_acc also inside two structs
+    assert seen == set(MIRRORS) - {"cy_pack_item"}
+
+
+def test_binding_refuses_what_it_does_not_know(tmp_path):
+    from cyhip import _lib
+    with pytest.raises(TypeError, match=r"cy_x.*'short'"):
+        _lib.parse_header("int cy_x(short a);")
+    with pytest.raises(TypeError, match=r"cy_y.*'void\*'"):
+        _lib.parse_header("void* cy_y(int a);")
+    missing = tmp_path / "include" / "contrastyou_hip.h"
+    with pytest.raises(_lib.HipExtensionMissing, match=re.escape(str(missing))):
+        _lib.read_header(missing)

@@ -128,7 +128,7 @@ def test_the_five_entries_exist_in_header_and_binding():
         assert name in declared, name
         assert name in _lib._SIGS, name
         assert hasattr(lib, name), name
-    assert lib.cy_abi_version() == 18
+    assert lib.cy_abi_version() == _lib.ABI_VERSION
 
 
 def _host_buffer():
