@@ -2,6 +2,7 @@ from .contrastive import SelfPacedSupConLoss, SupConLoss1, is_normalized  # noqa
 from .redundancy_reduction import RedundancyCriterion  # noqa: F401
 from .discreteMI import IIDLoss, IIDSegmentationLoss  # noqa: F401
 from .kl import KL_div, Entropy  # noqa: F401
+from .dice_loss import BinaryDiceLoss, DiceLoss, make_one_hot  # noqa: F401
 from .multicore_loss import GeneralOverSegmentedLoss, MultiCoreKL  # noqa: F401
 from .multicore_loss import AdaptiveOverSegmentedLoss, GradientReverse, scale_grad  # noqa: F401
 from .multicore_loss import StricterAdaptiveOverSegmentedLoss, StricterAdaptiveOverSegmentedLossWithMI  # noqa: F401

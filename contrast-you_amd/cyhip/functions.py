@@ -637,6 +637,50 @@ class SoftmaxKLFn(torch.autograd.Function):
         return ops.softmax_kl_bwd(logits, target, gs, ctx.eps), None, None
 
 
+class SoftmaxWeightedKLFn(torch.autograd.Function):
+    """KL_div(weight=w, reduction=reduction)(softmax(logits,1), one_hot(target)) for any class weights (`weight`: the
+    normalised [K] f32 device tensor, or None) and any of the three reductions (contrastyou/losses/kl.py:94-125);
+    "none" returns the [N, H, W] map."""
+
+    @staticmethod
+    def forward(ctx, logits: Tensor, target: Tensor, weight: Optional[Tensor], eps: float, reduction: str):
+        ops.require_gpu(logits, target, weight)
+        logits = ops.to_nhwc(logits.float())
+        target = target.contiguous()
+        ctx.save_for_backward(logits, target)
+        ctx.weight, ctx.eps, ctx.reduction = weight, eps, reduction
+        return ops.softmax_wkl_fwd(logits, target, weight, eps, reduction)
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        logits, target = ctx.saved_tensors
+        up = g.float().contiguous() if ctx.reduction == "none" else g.reshape(1).float().contiguous()
+        return ops.softmax_wkl_bwd(logits, target, ctx.weight, up, ctx.eps, ctx.reduction), None, None, None, None
+
+
+class SoftmaxDiceFn(torch.autograd.Function):
+    """DiceLoss(ignore_index=ignore, smooth=smooth, p=p, reduction=reduction)(softmax(logits,1), one_hot(target)) for
+    p in {1, 2} (contrastyou/losses/dice_loss.py:46-105); "none" returns the [N] vector.  The forward's [N, K] table of
+    numerators and denominators is kept for the backward."""
+
+    @staticmethod
+    def forward(ctx, logits: Tensor, target: Tensor, p: int, smooth: float, ignore: Optional[int], reduction: str):
+        ops.require_gpu(logits, target)
+        logits = ops.to_nhwc(logits.float())
+        target = target.contiguous()
+        res, table = ops.softmax_dice_fwd(logits, target, p, smooth, ignore, reduction)
+        ctx.save_for_backward(logits, target, table)
+        ctx.p, ctx.ignore, ctx.reduction = p, ignore, reduction
+        return res
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        logits, target, table = ctx.saved_tensors
+        up = g.reshape(-1).float().contiguous()
+        return ops.softmax_dice_bwd(logits, target, table, up, ctx.p, ctx.ignore, ctx.reduction), None, None, None, \
+            None, None
+
+
 class SoftmaxGroupKLFn(torch.autograd.Function):
     """MultiCoreKL(grouper(range(K), G))(softmax(logits,1), one_hot(target, G)): KL_div of the per-class sums of the
     softmax over K/G contiguous channels, mean reduction (contrastyou/losses/multicore_loss.py:41-60)."""

@@ -1479,6 +1479,79 @@ def softmax_kl_bwd(logits: Tensor, target: Tensor, gscale: Tensor, eps: float) -
     return d
 
 
+def _class_weight(logits: Tensor, weight: Optional[Tensor]) -> Optional[Tensor]:
+    """the [K] f32 class weights the cy_softmax_wkl_* entries read, on the logits' device; None: all ones"""
+    if weight is None:
+        return None
+    assert weight.dim() == 1 and weight.shape[0] == logits.shape[1], (tuple(weight.shape), tuple(logits.shape))
+    assert weight.device == logits.device, (weight.device, logits.device)
+    return weight.detach().float().contiguous()
+
+
+def softmax_wkl_fwd(logits: Tensor, target: Tensor, weight: Optional[Tensor], eps: float, reduction: str) -> Tensor:
+    """sum_pix -w[y] log((softmax(z)_y + eps) / (1 + eps)) over npix ("mean") or 1 ("sum"): a device scalar; "none":
+    the [N, H, W] map (one launch)"""
+    N, K, H, W = logits.shape
+    npix = N * H * W
+    weight = _class_weight(logits, weight)
+    if reduction == "none":
+        out = _f32(npix, logits.device)
+        _lib.call("cy_softmax_wkl_map_fwd", logits.data_ptr(), target.data_ptr(), _ptr(weight), out.data_ptr(), npix, K,
+                  float(eps), _stream())
+        return out.view(N, H, W)
+    nbytes = _lib.load().cy_softmax_wkl_ws_bytes(npix)
+    ws = _ws(nbytes, logits.device)
+    loss = _f32(1, logits.device)
+    _lib.call("cy_softmax_wkl_fwd", logits.data_ptr(), target.data_ptr(), _ptr(weight), loss.data_ptr(), npix, K,
+              float(eps), float(npix if reduction == "mean" else 1), ws.data_ptr(), nbytes, _stream())
+    return loss.view(())
+
+
+def softmax_wkl_bwd(logits: Tensor, target: Tensor, weight: Optional[Tensor], up: Tensor, eps: float,
+                    reduction: str) -> Tensor:
+    """`up`: the upstream gradient on the device, f32 [1] ("mean", "sum") or the contiguous [N, H, W] map ("none")"""
+    N, K, H, W = logits.shape
+    npix = N * H * W
+    weight = _class_weight(logits, weight)
+    d = empty_nhwc(N, K, H, W, torch.float32, logits.device)
+    if reduction == "none":
+        assert up.numel() == npix and up.is_contiguous() and up.dtype == torch.float32, (tuple(up.shape), up.dtype)
+        _lib.call("cy_softmax_wkl_map_bwd", logits.data_ptr(), target.data_ptr(), _ptr(weight), up.data_ptr(),
+                  d.data_ptr(), npix, K, float(eps), _stream())
+    else:
+        _lib.call("cy_softmax_wkl_bwd", logits.data_ptr(), target.data_ptr(), _ptr(weight), up.data_ptr(),
+                  d.data_ptr(), npix, K, float(eps), float(npix if reduction == "mean" else 1), _stream())
+    return d
+
+
+DICE_REDUCTIONS = ("mean", "sum", "none")  # the `reduction` codes of cy_softmax_dice_*
+
+
+def softmax_dice_fwd(logits: Tensor, target: Tensor, p: int, smooth: float, ignore: Optional[int], reduction: str):
+    """-> (result: a device scalar, or [N] for "none"; table: f64 [N, K, 2] = {num, den}, which the backward reads)"""
+    N, K, H, W = logits.shape
+    nbytes = _lib.load().cy_softmax_dice_ws_bytes(N, H * W, K)
+    ws = _ws(nbytes, logits.device)
+    table = torch.empty((N, K, 2), dtype=torch.float64, device=logits.device)
+    res = _f32(N if reduction == "none" else 1, logits.device)
+    _lib.call("cy_softmax_dice_fwd", logits.data_ptr(), target.data_ptr(), table.data_ptr(), res.data_ptr(), N, H * W,
+              K, int(p), float(smooth), -1 if ignore is None else int(ignore), DICE_REDUCTIONS.index(reduction),
+              ws.data_ptr(), nbytes, _stream())
+    return (res if reduction == "none" else res.view(())), table
+
+
+def softmax_dice_bwd(logits: Tensor, target: Tensor, table: Tensor, up: Tensor, p: int, ignore: Optional[int],
+                     reduction: str) -> Tensor:
+    """`up`: the upstream gradient on the device, f32 [1] ("mean", "sum") or [N] ("none")"""
+    N, K, H, W = logits.shape
+    assert up.numel() == (N if reduction == "none" else 1) and up.is_contiguous() and up.dtype == torch.float32
+    d = empty_nhwc(N, K, H, W, torch.float32, logits.device)
+    _lib.call("cy_softmax_dice_bwd", logits.data_ptr(), target.data_ptr(), table.data_ptr(), up.data_ptr(),
+              d.data_ptr(), N, H * W, K, int(p), -1 if ignore is None else int(ignore),
+              DICE_REDUCTIONS.index(reduction), _stream())
+    return d
+
+
 def softmax_mse_fwd(a: Tensor, b: Tensor) -> Tensor:
     N, K, H, W = a.shape
     npix = N * H * W

@@ -754,6 +754,50 @@ int cy_uamt_mse_bwd(const float* teacher, const float* student, const float* res
                     float* dstudent, long npix, int K, float thr, int hard, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Supervised criteria on the segmentation output (csrc/cy_seg_loss.hip; entries added to ABI v18 -- no existing
+ * signature changed, so cy_abi_version() stays 18): class-weighted KL_div with any reduction
+ * (contrastyou/losses/kl.py:94-125, the criterion of semi_seg/epochers/epocher.py:317-318) and the soft Dice loss
+ * (contrastyou/losses/dice_loss.py:46-105), both of softmax(logits) against integer labels.  Logits are [npix][K] f32
+ * (NHWC), labels int64 in [0, K), 1 <= K <= 16.  Every entry checks its arguments before any launch: a NULL pointer
+ * (`weight` alone may be NULL) or a count < 1 -> CY_ERR_ARG; K outside 1..16 -> CY_ERR_SHAPE; a short workspace ->
+ * CY_ERR_WORKSPACE.  No atomics: two runs give the same bits.  Upstream gradients are device memory, never host scalars.
+ * ------------------------------------------------------------------------ */
+/* l_pix = -w[y] log((softmax(z)_y + eps) / (1 + eps)), w = weight [K] or all ones for NULL (the normalised weights
+ * w / sum(w) * K of kl.py:108); the other classes add exactly 0.
+ * cy_softmax_wkl_fwd: loss[0] = sum_pix l_pix / denom (denom = npix for "mean", 1 for "sum"; denom > 0).  Two launches:
+ * one f64 partial per block into ws, then a one-block sum in block order.
+ * ws_bytes >= 8 * min(1024, ceil(npix / 256)) = cy_softmax_wkl_ws_bytes(npix).
+ * cy_softmax_wkl_map_fwd: map[pix] = l_pix (reduction "none"), one launch, no workspace. */
+size_t cy_softmax_wkl_ws_bytes(long npix);
+int cy_softmax_wkl_fwd(const float* logits, const int64_t* target, const float* weight, float* loss, long npix, int K,
+                       float eps, double denom, void* ws, size_t ws_bytes, void* stream);
+int cy_softmax_wkl_map_fwd(const float* logits, const int64_t* target, const float* weight, float* map, long npix,
+                           int K, float eps, void* stream);
+/* dz_k = G w[y] (-p_y / (p_y + eps)) (delta_ky - p_k); G = gscale[0] / denom, or dmap[pix] for the map form.  One
+ * launch each. */
+int cy_softmax_wkl_bwd(const float* logits, const int64_t* target, const float* weight, const float* gscale,
+                       float* dlogits, long npix, int K, float eps, double denom, void* stream);
+int cy_softmax_wkl_map_bwd(const float* logits, const int64_t* target, const float* weight, const float* dmap,
+                           float* dlogits, long npix, int K, float eps, void* stream);
+/* Soft Dice of p = softmax(z) per image n (npix = N * HW, image n is pixels [n HW, (n+1) HW)) and class c:
+ *   A = sum_pix p_c [y = c], B = sum_pix p_c^P (P = 1 or 2), T = #{pix: y = c};
+ *   num = A + smooth, den = B + T + smooth, L_nc = 1 - num / den (no factor 2, dice_loss.py:57-60).
+ * reduction 0 "mean": result[0] = (1/K) sum_{c != ignore} mean_n L_nc; 1 "sum": sum_n; 2 "none": result[n], n < N.
+ * The divisor K counts the ignored class (dice_loss.py:105); an `ignore` outside [0, K) ignores nothing.
+ * Two launches: N x B blocks, B = min(ceil(HW / 256), max(1, 1024 / N)) per image (integer division; a block never
+ * spans two images), each writing K {A, B} f64 pairs and K int64 counts into ws; then one block adds them in block order
+ * and writes `table`, f64 [N][K][2] = {num, den} (the ignored class included), which the backward reads, and `result`.
+ * ws_bytes >= 24 * N * B * K = cy_softmax_dice_ws_bytes(N, HW, K) (0 for a count < 1 or K outside 1..16).
+ * P outside {1, 2} or reduction outside 0..2 -> CY_ERR_ARG. */
+size_t cy_softmax_dice_ws_bytes(int N, long HW, int K);
+int cy_softmax_dice_fwd(const float* logits, const int64_t* target, void* table, float* result, int N, long HW, int K,
+                        int P, double smooth, int ignore, int reduction, void* ws, size_t ws_bytes, void* stream);
+/* dloss/dp_c = g_c = (G_n r / K) (-[y = c] / den + num P p_c^(P-1) / den^2) for c != ignore, 0 otherwise; r = 1/N for
+ * "mean", 1 otherwise; G_n = gup[0], or gup[n] for "none".  dz_k = p_k (g_k - sum_j p_j g_j).  One launch. */
+int cy_softmax_dice_bwd(const float* logits, const int64_t* target, const void* table, const float* gup,
+                        float* dlogits, int N, long HW, int K, int P, int ignore, int reduction, void* stream);
+
+/* ------------------------------------------------------------------------
  * RAdam step over a flat f32 parameter buffer (torch.optim.RAdam semantics,
  * contrastyou/trainer/base.py:66-75, config/base.yaml:10-13).
  * `step` is the 1-based step count AFTER this update.
