@@ -15,7 +15,9 @@
 // The epilogue rounds to the storage type, emits per-tile per-channel sum /
 // sum-of-squares partials for the following BatchNorm (deterministic: one
 // partial per tile, fixed-order reduction in cy_bn_finalize) and stores
-// 16-byte NHWC chunks after a wave-private LDS transpose.
+// 16-byte NHWC chunks after a wave-private LDS transpose.  The workgroup finish
+// of those sums and the split destination are shared with the plane, flow and
+// streaming forms (cy_conv_epilogue.h), which store straight from registers.
 #include "cy_conv_plane.h"
 #include "cy_conv_stream.h"
 #include "cy_conv_flow.h"
@@ -267,7 +269,7 @@ __global__ void __launch_bounds__(256, 2)
         const int ibase = (wm * M_REP + m) * 32;
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg)
-          scr[((reg & 3) + 8 * (reg >> 2) + 4 * h) * 36 + r] = acc[m][n][reg];
+          scr[frag_channel(reg, h) * 36 + r] = acc[m][n][reg];
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int itx = 0; itx < 4; ++itx) {
@@ -303,7 +305,7 @@ __global__ void __launch_bounds__(256, 2)
       const int ibase = (wm * M_REP + m) * 32;
 #pragma unroll
       for (int reg = 0; reg < 16; ++reg) {
-        const int row = (reg & 3) + 8 * (reg >> 2) + 4 * h;
+        const int row = frag_channel(reg, h);
         const float v = acc[m][n][reg];
         scratch[row * 36 + r] = v;
         if (do_stats) {
@@ -341,11 +343,7 @@ __global__ void __launch_bounds__(256, 2)
         const int co = cobase + cch * EPO;
         if (R < a.NH && w < a.W && co < a.Cout) {
           const size_t gp = (size_t)R * a.W + w;
-          u32x4 pk = Chunk<TO>::pack(f);
-          if (a.split_c > 0 && co >= a.split_c)
-            st16(o2 + gp * a.ldo2 + (co - a.split_c), pk);
-          else
-            st16(o1 + gp * a.ldo + co, pk);
+          st16(conv_out_ptr(a, o1, o2, gp, co), Chunk<TO>::pack(f));
         }
       }
       __builtin_amdgcn_wave_barrier();
@@ -362,21 +360,7 @@ __global__ void __launch_bounds__(256, 2)
   }
   if (do_stats) {
     __syncthreads();
-    if (tid < BN && n0 + tid < a.Cout) {
-      float t1 = 0.f, t2 = 0.f;
-#pragma unroll
-      for (int q = 0; q < WGM; ++q) {
-        t1 += sstat[(q * 2 + 0) * BN + tid];
-        t2 += sstat[(q * 2 + 1) * BN + tid];
-      }
-      if (a.sacc) {
-        bn_acc_add(a.sacc, a.sR, a.Cout, tile & (a.sR - 1), 0, n0 + tid, t1);
-        bn_acc_add(a.sacc, a.sR, a.Cout, tile & (a.sR - 1), 1, n0 + tid, t2);
-      } else {
-        a.stats[((size_t)tile * 2 + 0) * a.Cout + n0 + tid] = t1;
-        a.stats[((size_t)tile * 2 + 1) * a.Cout + n0 + tid] = t2;
-      }
-    }
+    conv_stats_finish<BN, WGM>(a, sstat, tile, n0, tid);
   }
 }
 
@@ -983,9 +967,9 @@ __global__ void __launch_bounds__(256)
 // The VALU kernel above spends ~110 instructions and 18 LDS weight reads per (pixel, 8 couts) -- 36 / 56 us at
 // N = 16 / 32 against the 13 / 25 us the output write takes.  Here a wave computes 32 pixels x 32 couts per MFMA:
 // rows = couts (the weights, in registers for the whole kernel), columns = pixels (the patch, eight LDS reads per
-// lane), so that a lane owns one pixel and 16 couts and stores two 16-byte chunks straight from registers (the plane
-// kernel's epilogue).  Image and weights are rounded to the storage type first -- what the reference's autocast
-// convolution does with its inputs.  Same LDS image, block ranges and one statistics partial per block as above.
+// lane), so that a lane owns one pixel and 16 couts and stores two 16-byte chunks straight from registers (the
+// register epilogue of cy_conv_epilogue.h).  Image and weights are rounded to the storage type first -- what the
+// reference's autocast convolution does with its inputs.  Same LDS image, block ranges and one statistics partial per block as above.
 template <typename T>
 __global__ void __launch_bounds__(256)
     conv3x3_first_mfma_kernel(const float* __restrict__ x, const float* __restrict__ w, T* __restrict__ out,
@@ -1054,7 +1038,7 @@ __global__ void __launch_bounds__(256)
     f32x16 acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-    M::mma(fa, fb, acc);  // rows = couts: lane (r = pixel, h) holds couts (i & 3) + 8 * (i >> 2) + 4 * h
+    M::mma(fa, fb, acc);  // rows = couts: lane (r = pixel, h) holds couts frag_channel(i, h)
     u32x2 packed[4];
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
@@ -1073,12 +1057,7 @@ __global__ void __launch_bounds__(256)
 #pragma unroll
     for (int g = 0; g < 4; g += 2) {
       u32x2 lo = packed[g], hi = packed[g + 1];
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const auto sw = __builtin_amdgcn_permlane32_swap(lo[j], hi[j], false, false);
-        lo[j] = sw[0];
-        hi[j] = sw[1];
-      }
+      frag_pair_swap(lo, hi);
       const int co = 8 * g + 8 * h;
       if (valid && co < Cout) st16(out + (size_t)p * Cout + co, u32x4{lo[0], lo[1], hi[0], hi[1]});
     }
@@ -1088,42 +1067,8 @@ __global__ void __launch_bounds__(256)
     while (hq >= H) hq -= H, ++n;
   }
   if (stats || sacc) {
-    // reduce-scatter over the 32 lanes of each half (the plane kernel's): even lanes end up with one channel each
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const bool up = (lane & 16) != 0;
-      const float snd1 = up ? s1[i] : s1[i + 8], snd2 = up ? s2[i] : s2[i + 8];
-      const float kp1 = up ? s1[i + 8] : s1[i], kp2 = up ? s2[i + 8] : s2[i];
-      s1[i] = kp1 + __shfl_xor(snd1, 16, 64);
-      s2[i] = kp2 + __shfl_xor(snd2, 16, 64);
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const bool up = (lane & 8) != 0;
-      const float snd1 = up ? s1[i] : s1[i + 4], snd2 = up ? s2[i] : s2[i + 4];
-      const float kp1 = up ? s1[i + 4] : s1[i], kp2 = up ? s2[i + 4] : s2[i];
-      s1[i] = kp1 + __shfl_xor(snd1, 8, 64);
-      s2[i] = kp2 + __shfl_xor(snd2, 8, 64);
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const bool up = (lane & 4) != 0;
-      const float snd1 = up ? s1[i] : s1[i + 2], snd2 = up ? s2[i] : s2[i + 2];
-      const float kp1 = up ? s1[i + 2] : s1[i], kp2 = up ? s2[i + 2] : s2[i];
-      s1[i] = kp1 + __shfl_xor(snd1, 4, 64);
-      s2[i] = kp2 + __shfl_xor(snd2, 4, 64);
-    }
-    {
-      const bool up = (lane & 2) != 0;
-      const float snd1 = up ? s1[0] : s1[1], snd2 = up ? s2[0] : s2[1];
-      const float kp1 = up ? s1[1] : s1[0], kp2 = up ? s2[1] : s2[0];
-      s1[0] = kp1 + __shfl_xor(snd1, 2, 64);
-      s2[0] = kp2 + __shfl_xor(snd2, 2, 64);
-    }
-    s1[0] += __shfl_xor(s1[0], 1, 64);
-    s2[0] += __shfl_xor(s2[0], 1, 64);
-    const int reg = ((lane >> 4) & 1) * 8 + ((lane >> 3) & 1) * 4 + ((lane >> 2) & 1) * 2 + ((lane >> 1) & 1);
-    const int col = (reg & 3) + 8 * (reg >> 2) + 4 * h;
+    frag_stats_reduce(s1, s2, lane);  // even lanes end up with one channel each
+    const int col = frag_channel(frag_stats_reg(lane), h);
     if ((lane & 1) == 0) {
       sred[(wave * 2 + 0) * 32 + col] = s1[0];
       sred[(wave * 2 + 1) * 32 + col] = s2[0];

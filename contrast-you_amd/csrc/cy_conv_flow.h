@@ -1,7 +1,7 @@
 // "Flow" form of the plane kernel (cy_conv_plane.h) for the MFMA-bound layers (Cout >= 64, 16-bit storage):
 // the same GEMM view (M = flattened halo grid, a tap = one uniform address shift, LDS planes
-// [16-byte channel group][position]) and the same register epilogue, but NO register staging and NO per-tap
-// barrier.  Where a workgroup's time went in the plane kernel's 128-cout build: nine __syncthreads() per
+// [16-byte channel group][position]) and the same register epilogue (cy_conv_epilogue.h), but NO register staging and
+// NO per-tap barrier.  Where a workgroup's time went in the plane kernel's 128-cout build: nine __syncthreads() per
 // 32-channel chunk, each draining the next tap's weight request (vmcnt(0)) and followed by a ds_write commit,
 // plus a synchronous 41 KB halo staging at every chunk boundary -- 40 cycles per MFMA in the tap loop and two
 // workgroups per CU needed just to cover each other's commits.  Here
@@ -453,7 +453,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN, 2)
   FLOW_STAMP(4, __builtin_amdgcn_s_memtime());
   __syncthreads();  // the statistics scratch aliases the operand buffers
 
-  // ---------------- epilogue (as conv3x3_plane_kernel): accumulators -> NHWC from registers ----------------
+  // ---------------- epilogue (cy_conv_epilogue.h): accumulators -> NHWC from registers ----------------
   auto position = [&](int m, int& R, int& w) -> bool {
     R = R0 + 2 * (wm * M_REP + m) + prow;
     if constexpr (C::W16) {
@@ -602,7 +602,9 @@ __global__ void __launch_bounds__(64 * WGM * WGN, 2)
         for (int g = 0; g < 4; ++g) ycur[g] = ynxt[g];
       }
 #pragma unroll
-      for (int g = 0; g < 4; g += 2) {  // half-wave swaps pair the 8-byte channel runs into 16-byte stores
+      // half-wave swaps pair the 8-byte channel runs into 16-byte stores (frag_pair_swap of cy_conv_epilogue.h, written
+      // out: behind the call the f16 builds of this kernel change their register and spill counts)
+      for (int g = 0; g < 4; g += 2) {
         u32x2 lo = packed[m][g], hi = packed[m][g + 1];
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
@@ -612,8 +614,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN, 2)
         }
         const int co = n0 + (wn * N_REP + n) * 32 + 8 * g + 8 * h;
         if (ok && co < a.Cout) {
-          T* dst = (a.split_c > 0 && co >= a.split_c) ? o2 + gp * a.ldo2 + (co - a.split_c)
-                                                      : o1 + gp * a.ldo + co;
+          T* dst = conv_out_ptr(a, o1, o2, gp, co);
           *reinterpret_cast<u32x4*>(dst) = u32x4{lo[0], lo[1], hi[0], hi[1]};
         }
       }
@@ -628,43 +629,11 @@ __global__ void __launch_bounds__(64 * WGM * WGN, 2)
       s2v[2 * i] = keep ? p2[i][0] : 0.f;
       s2v[2 * i + 1] = keep ? p2[i][1] : 0.f;
     }
-    if constexpr (STATS) {  // reduce-scatter over the 32 lanes of each half (see conv3x3_plane_kernel)
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const bool up = (lane & 16) != 0;
-        const float snd1 = up ? s1v[i] : s1v[i + 8], snd2 = up ? s2v[i] : s2v[i + 8];
-        const float kp1 = up ? s1v[i + 8] : s1v[i], kp2 = up ? s2v[i + 8] : s2v[i];
-        s1v[i] = kp1 + __shfl_xor(snd1, 16, 64);
-        s2v[i] = kp2 + __shfl_xor(snd2, 16, 64);
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const bool up = (lane & 8) != 0;
-        const float snd1 = up ? s1v[i] : s1v[i + 4], snd2 = up ? s2v[i] : s2v[i + 4];
-        const float kp1 = up ? s1v[i + 4] : s1v[i], kp2 = up ? s2v[i + 4] : s2v[i];
-        s1v[i] = kp1 + __shfl_xor(snd1, 8, 64);
-        s2v[i] = kp2 + __shfl_xor(snd2, 8, 64);
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const bool up = (lane & 4) != 0;
-        const float snd1 = up ? s1v[i] : s1v[i + 2], snd2 = up ? s2v[i] : s2v[i + 2];
-        const float kp1 = up ? s1v[i + 2] : s1v[i], kp2 = up ? s2v[i + 2] : s2v[i];
-        s1v[i] = kp1 + __shfl_xor(snd1, 4, 64);
-        s2v[i] = kp2 + __shfl_xor(snd2, 4, 64);
-      }
-      {
-        const bool up = (lane & 2) != 0;
-        const float snd1 = up ? s1v[0] : s1v[1], snd2 = up ? s2v[0] : s2v[1];
-        const float kp1 = up ? s1v[1] : s1v[0], kp2 = up ? s2v[1] : s2v[0];
-        s1v[0] = kp1 + __shfl_xor(snd1, 2, 64);
-        s2v[0] = kp2 + __shfl_xor(snd2, 2, 64);
-      }
-      s1v[0] += __shfl_xor(s1v[0], 1, 64);
-      s2v[0] += __shfl_xor(s2v[0], 1, 64);
+    if constexpr (STATS) {
+      frag_stats_reduce(s1v, s2v, lane);
       if ((lane & 1) == 0) {
-        const int reg = ((lane >> 4) & 1) * 8 + ((lane >> 3) & 1) * 4 + ((lane >> 2) & 1) * 2 + ((lane >> 1) & 1);
-        const int col = (wn * N_REP + n) * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
+        const int reg = frag_stats_reg(lane);
+        const int col = (wn * N_REP + n) * 32 + frag_channel(reg, h);
         sstat[(wm * 2 + 0) * BN + col] = s1v[0];
         sstat[(wm * 2 + 1) * BN + col] = s2v[0];
       }
@@ -689,23 +658,13 @@ __global__ void __launch_bounds__(64 * WGM * WGN, 2)
   else epilogue(TapC<1>{}, TapC<1>{});
   if (do_stats || dz_on) {
     __syncthreads();
-    if (tid < BN && n0 + tid < a.Cout) {
-      float t1 = 0.f, t2 = 0.f;
-#pragma unroll
-      for (int qq = 0; qq < WGM; ++qq) {
-        t1 += sstat[(qq * 2 + 0) * BN + tid];
-        t2 += sstat[(qq * 2 + 1) * BN + tid];
-      }
-      if (dz_on) {
-        bn_acc_add(a.dz_acc, a.dz_R, a.dz_C, tile & (a.dz_R - 1), 0, n0 - a.dz_c0 + tid, t1);
-        bn_acc_add(a.dz_acc, a.dz_R, a.dz_C, tile & (a.dz_R - 1), 1, n0 - a.dz_c0 + tid, t2);
-      } else if (a.sacc) {
-        bn_acc_add(a.sacc, a.sR, a.Cout, tile & (a.sR - 1), 0, n0 + tid, t1);
-        bn_acc_add(a.sacc, a.sR, a.Cout, tile & (a.sR - 1), 1, n0 + tid, t2);
-      } else {
-        a.stats[((size_t)tile * 2 + 0) * a.Cout + n0 + tid] = t1;
-        a.stats[((size_t)tile * 2 + 1) * a.Cout + n0 + tid] = t2;
-      }
+    if (!dz_on) {
+      conv_stats_finish<BN, WGM>(a, sstat, tile, n0, tid);
+    } else if (tid < BN && n0 + tid < a.Cout) {
+      float t1, t2;
+      conv_stats_total<BN, WGM>(sstat, tid, t1, t2);
+      bn_acc_add(a.dz_acc, a.dz_R, a.dz_C, tile & (a.dz_R - 1), 0, n0 - a.dz_c0 + tid, t1);
+      bn_acc_add(a.dz_acc, a.dz_R, a.dz_C, tile & (a.dz_R - 1), 1, n0 - a.dz_c0 + tid, t2);
     }
   }
   FLOW_STAMP(5, __builtin_amdgcn_s_memtime());

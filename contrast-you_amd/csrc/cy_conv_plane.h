@@ -20,6 +20,7 @@
 #pragma once
 #include <cstdlib>
 
+#include "cy_conv_epilogue.h"
 #include "cy_conv_tile.h"
 
 #ifndef CY_PLANE_INTERLEAVE
@@ -401,11 +402,10 @@ __global__ void __launch_bounds__(256, PREFA ? 1 : 2)
   }
   if constexpr (ALLT) __syncthreads();  // the statistics scratch aliases the operand buffers
 
-  // ---------------- epilogue: accumulators -> NHWC, straight from registers ----------------
+  // ---------------- epilogue: accumulators -> NHWC, straight from registers (cy_conv_epilogue.h) ----------------
   // The MFMAs run with the WEIGHTS as the row operand, so a lane holds ONE position (q = frag base
   // + r; q = ty*16 + hx, columns hx = 0 and 15 are the halo columns = garbage) and 16 couts in four
-  // runs of four consecutive channels ((reg&3) + 8*(reg>>2) + 4*h): four 8-byte (bf16) stores per
-  // fragment, no LDS transpose and no per-element index arithmetic.
+  // runs of four consecutive channels (frag_channel): no LDS transpose and no per-element index arithmetic.
   auto position = [&](int m, int& R, int& w) -> bool {
     const int q = (wm * M_REP + m) * 32 + r;
     const int hx = q & 15;
@@ -464,72 +464,30 @@ __global__ void __launch_bounds__(256, PREFA ? 1 : 2)
         if constexpr (sizeof(T) == 2) {
           packed[g] = __builtin_bit_cast(u32x2, *reinterpret_cast<const s16x4*>(pk));
         } else if (ok && co < a.Cout) {
-          T* dst = (a.split_c > 0 && co >= a.split_c) ? o2 + gp * a.ldo2 + (co - a.split_c)
-                                                      : o1 + gp * a.ldo + co;
+          T* dst = conv_out_ptr(a, o1, o2, gp, co);
           *reinterpret_cast<f32x4*>(dst) = f32x4{pk[0], pk[1], pk[2], pk[3]};
         }
       }
       if constexpr (sizeof(T) == 2) {
-        // lane i holds channels 8g+0..3, lane i+32 channels 8g+4..7 of the same position: one half-wave
-        // swap per dword of a run pair (g, g+1) leaves the lower half with channels 8g..8g+7 and the
-        // upper half with 8g+8..8g+15 -- two 16-byte stores per fragment instead of four 8-byte ones
+        // two 16-byte stores per fragment instead of four 8-byte ones (frag_pair_swap)
 #pragma unroll
         for (int g = 0; g < 4; g += 2) {
           u32x2 lo = packed[g], hi = packed[g + 1];
-#pragma unroll
-          for (int j = 0; j < 2; ++j) {
-            const auto sw = __builtin_amdgcn_permlane32_swap(lo[j], hi[j], false, false);
-            lo[j] = sw[0];
-            hi[j] = sw[1];
-          }
+          frag_pair_swap(lo, hi);
           const int co = n0 + (wn * N_REP + n) * 32 + 8 * g + 8 * h;
           if (ok && co < a.Cout) {
-            T* dst = (a.split_c > 0 && co >= a.split_c) ? o2 + gp * a.ldo2 + (co - a.split_c)
-                                                        : o1 + gp * a.ldo + co;
+            T* dst = conv_out_ptr(a, o1, o2, gp, co);
             *reinterpret_cast<u32x4*>(dst) = u32x4{lo[0], lo[1], hi[0], hi[1]};
           }
         }
       }
     }
     if (do_stats) {
-      // reduce-scatter over the 32 lanes of each half (same h): xor 16 / 8 / 4 / 2 halve the value
-      // count while they pair the lanes, xor 1 joins the last pair; a lane ends up with the total
-      // of register index ((lane>>4)&1)*8 + ((lane>>3)&1)*4 + ((lane>>2)&1)*2 + ((lane>>1)&1)
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const bool up = (lane & 16) != 0;
-        const float snd1 = up ? s1[i] : s1[i + 8], snd2 = up ? s2[i] : s2[i + 8];
-        const float kp1 = up ? s1[i + 8] : s1[i], kp2 = up ? s2[i + 8] : s2[i];
-        s1[i] = kp1 + __shfl_xor(snd1, 16, 64);
-        s2[i] = kp2 + __shfl_xor(snd2, 16, 64);
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const bool up = (lane & 8) != 0;
-        const float snd1 = up ? s1[i] : s1[i + 4], snd2 = up ? s2[i] : s2[i + 4];
-        const float kp1 = up ? s1[i + 4] : s1[i], kp2 = up ? s2[i + 4] : s2[i];
-        s1[i] = kp1 + __shfl_xor(snd1, 8, 64);
-        s2[i] = kp2 + __shfl_xor(snd2, 8, 64);
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const bool up = (lane & 4) != 0;
-        const float snd1 = up ? s1[i] : s1[i + 2], snd2 = up ? s2[i] : s2[i + 2];
-        const float kp1 = up ? s1[i + 2] : s1[i], kp2 = up ? s2[i + 2] : s2[i];
-        s1[i] = kp1 + __shfl_xor(snd1, 4, 64);
-        s2[i] = kp2 + __shfl_xor(snd2, 4, 64);
-      }
-      {
-        const bool up = (lane & 2) != 0;
-        const float snd1 = up ? s1[0] : s1[1], snd2 = up ? s2[0] : s2[1];
-        const float kp1 = up ? s1[1] : s1[0], kp2 = up ? s2[1] : s2[0];
-        s1[0] = kp1 + __shfl_xor(snd1, 2, 64);
-        s2[0] = kp2 + __shfl_xor(snd2, 2, 64);
-      }
-      s1[0] += __shfl_xor(s1[0], 1, 64);
-      s2[0] += __shfl_xor(s2[0], 1, 64);
+      frag_stats_reduce(s1, s2, lane);
       if ((lane & 1) == 0) {
-        const int reg = ((lane >> 4) & 1) * 8 + ((lane >> 3) & 1) * 4 + ((lane >> 2) & 1) * 2 + ((lane >> 1) & 1);
+        const int reg = frag_stats_reg(lane);
+        // (frag_channel(reg, h) written out: behind the call the 128-cout builds of this kernel spill one
+        //  register more (f16, two workgroups per CU) or change their register count (f32, one per CU))
         const int col = (wn * N_REP + n) * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
         sstat[(wm * 2 + 0) * BN + col] = s1[0];
         sstat[(wm * 2 + 1) * BN + col] = s2[0];
@@ -538,21 +496,7 @@ __global__ void __launch_bounds__(256, PREFA ? 1 : 2)
   }
   if (do_stats) {
     __syncthreads();
-    if (tid < BN && n0 + tid < a.Cout) {
-      float t1 = 0.f, t2 = 0.f;
-#pragma unroll
-      for (int qq = 0; qq < WGM; ++qq) {
-        t1 += sstat[(qq * 2 + 0) * BN + tid];
-        t2 += sstat[(qq * 2 + 1) * BN + tid];
-      }
-      if (a.sacc) {
-        bn_acc_add(a.sacc, a.sR, a.Cout, tile & (a.sR - 1), 0, n0 + tid, t1);
-        bn_acc_add(a.sacc, a.sR, a.Cout, tile & (a.sR - 1), 1, n0 + tid, t2);
-      } else {
-        a.stats[((size_t)tile * 2 + 0) * a.Cout + n0 + tid] = t1;
-        a.stats[((size_t)tile * 2 + 1) * a.Cout + n0 + tid] = t2;
-      }
-    }
+    conv_stats_finish<BN, WGM>(a, sstat, tile, n0, tid);
   }
 }
 

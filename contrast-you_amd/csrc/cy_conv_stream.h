@@ -14,7 +14,8 @@
 //     LDS fragment per MFMA (the activations) and nothing else;
 //   * one s_barrier per tile; vector-memory operations are issued unconditionally (invalid lanes read /
 //     write out of range) so that every wait is a counted vmcnt;
-//   * BN partial sums per (tile, wave row) straight from registers, no second barrier.
+//   * BN partial sums per (tile, wave row) straight from registers, no second barrier (the register epilogue of
+//     cy_conv_epilogue.h; the stores go through buffer descriptors and the sums to this kernel's own LDS rows).
 // Layers with a load transform (BN+ReLU prologue, 2x2 max) stay on the plane kernel.
 #pragma once
 #include "cy_conv_plane.h"
@@ -426,12 +427,7 @@ __global__ void __launch_bounds__((256 * NB / stream_nbw<KCH, NB>()), (PRO ? 2 :
 #pragma unroll
         for (int g = 0; g < 4; g += 2) {
           u32x2 lo = packed[g], hi = packed[g + 1];
-#pragma unroll
-          for (int j = 0; j < 2; ++j) {
-            const auto sw = __builtin_amdgcn_permlane32_swap(lo[j], hi[j], false, false);
-            lo[j] = sw[0];
-            hi[j] = sw[1];
-          }
+          frag_pair_swap(lo, hi);
           const int co = nb0 + 8 * g + 8 * h;
           const bool cok = ok && co < a.Cout;
           const u32x4 v = u32x4{lo[0], lo[1], hi[0], hi[1]};
@@ -458,43 +454,11 @@ __global__ void __launch_bounds__((256 * NB / stream_nbw<KCH, NB>()), (PRO ? 2 :
       float* S1 = s1[nb];
       float* S2 = s2[nb];
       const int nb0 = (wn * NBW + nb) * 32;
-      {  // reduce-scatter over the 32 lanes of each half (see conv3x3_plane_kernel)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const bool up = (lane & 16) != 0;
-          const float snd1 = up ? S1[i] : S1[i + 8], snd2 = up ? S2[i] : S2[i + 8];
-          const float kp1 = up ? S1[i + 8] : S1[i], kp2 = up ? S2[i + 8] : S2[i];
-          S1[i] = kp1 + __shfl_xor(snd1, 16, 64);
-          S2[i] = kp2 + __shfl_xor(snd2, 16, 64);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const bool up = (lane & 8) != 0;
-          const float snd1 = up ? S1[i] : S1[i + 4], snd2 = up ? S2[i] : S2[i + 4];
-          const float kp1 = up ? S1[i + 4] : S1[i], kp2 = up ? S2[i + 4] : S2[i];
-          S1[i] = kp1 + __shfl_xor(snd1, 8, 64);
-          S2[i] = kp2 + __shfl_xor(snd2, 8, 64);
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          const bool up = (lane & 4) != 0;
-          const float snd1 = up ? S1[i] : S1[i + 2], snd2 = up ? S2[i] : S2[i + 2];
-          const float kp1 = up ? S1[i + 2] : S1[i], kp2 = up ? S2[i + 2] : S2[i];
-          S1[i] = kp1 + __shfl_xor(snd1, 4, 64);
-          S2[i] = kp2 + __shfl_xor(snd2, 4, 64);
-        }
-        {
-          const bool up = (lane & 2) != 0;
-          const float snd1 = up ? S1[0] : S1[1], snd2 = up ? S2[0] : S2[1];
-          const float kp1 = up ? S1[1] : S1[0], kp2 = up ? S2[1] : S2[0];
-          S1[0] = kp1 + __shfl_xor(snd1, 2, 64);
-          S2[0] = kp2 + __shfl_xor(snd2, 2, 64);
-        }
-        S1[0] += __shfl_xor(S1[0], 1, 64);
-        S2[0] += __shfl_xor(S2[0], 1, 64);
+      {
+        frag_stats_reduce(S1, S2, lane);
         // partial row (tile, wm): [2][Cout]; even lanes hold one channel each
-        const int reg = ((lane >> 4) & 1) * 8 + ((lane >> 3) & 1) * 4 + ((lane >> 2) & 1) * 2 + ((lane >> 1) & 1);
-        const int col = nb0 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
+        const int reg = frag_stats_reg(lane);
+        const int col = nb0 + frag_channel(reg, h);
         const bool sok = (lane & 1) == 0 && col < a.Cout;
         if (a.sacc) {  // (accumulator form, cy_bn_acc.h: the four wave rows are summed in LDS below, one add per workgroup)
           if (nb == 0) __syncthreads();  // every wave is done with the tile buffers

@@ -70,6 +70,8 @@ CONV_CASES = [
     (3, 14, 28, 64, 0, 48, 0, 1),     # tile spans images, rows not a multiple of 16, prologue
     (1, 28, 28, 64, 0, 96, 1, 0),     # pool on load (staged synchronously), 96 couts
     (5, 14, 14, 128, 128, 128, 0, 0), # 128 couts, concat, image borders inside every tile
+    # 16-bit: the flow kernel (cy_conv_flow.h) without split-K, last row tile half outside (masked statistics)
+    (15, 56, 56, 64, 0, 64, 0, 0),
 ]
 
 
@@ -127,9 +129,11 @@ def test_conv3x3_fwd_and_stats(case, dtype):
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("shape", [(2, 16, 16, 32, 64, 64), (2, 14, 14, 64, 64, 256), (1, 28, 28, 128, 128, 128)])
+@pytest.mark.parametrize("shape", [(2, 16, 16, 32, 64, 64), (2, 14, 14, 64, 64, 256), (1, 28, 28, 128, 128, 128),
+                                   (5, 56, 56, 32, 64, 32)])
 def test_conv3x3_dgrad_with_split(shape, dtype):
-    """data gradient with the two-destination (concat) epilogue, incl. the split-K path"""
+    """data gradient with the two-destination (concat) epilogue, incl. the split-K path; the last shape is the smallest
+    at which the plane kernel itself (16-bit storage, no split-K, last row tile half outside) writes the two tensors"""
     ops = _ops()
     g = torch.Generator().manual_seed(7)
     N, H, W, Cin1, Cin2, Cout = shape
