@@ -16,7 +16,7 @@ import torch
 
 from cyhip import ops
 from cyhip.functions import (AdaptiveAvgPoolFn, AdaptiveMaxPoolFn, ClusterHeadFn, AvgPoolFn, DenseProjHiddenFn, GroupSoftmaxFn, HeadFn, L2NormFn,
-                             LinearFn, ProjHeadFn)
+                             LinearFn, PixelMLPFn, ProjHeadFn, GatherRowsFn)
 
 from .nn import Flatten, Identical, Normalize, SoftmaxWithT
 
@@ -73,20 +73,26 @@ class DenseProjectionHead(nn.Module):
     [pixels, hidden] intermediate never exists) and applies the second conv to the pooled rows.
     `forward(features)` returns the full [N, out, s, s] map as the reference does;
     `project_points(features, points)` evaluates only the listed (image, row, col) bins -- what the
-    dense hook needs after `region_extractor` -- and returns [len(points), out] rows."""
+    dense hook needs after `region_extractor` -- and returns [len(points), out] rows.
+
+    pool_name "adaptive_max": the projector runs on every pixel and the map is max-pooled (`_rows_max`); points are
+    gathered from the pooled rows.  pool_name "identical" / "none" / None (projectors/nn.py:16-23): no pooling, one
+    vector per pixel of the feature map's own grid, by one launch of the per-row projector (`PixelMLPFn`), which for
+    points computes the listed pixels only."""
 
     def __init__(self, *, input_dim: int, hidden_dim=128, output_dim: int, head_type: str, normalize: bool,
                  pool_name="adaptive_avg", spatial_size=(16, 16)):
         super().__init__()
         assert head_type in ("mlp", "linear"), head_type
-        assert pool_name in ("adaptive_avg", "adaptive_max", "identical", "none"), pool_name
-        if pool_name in ("identical", "none", None):
-            raise NotImplementedError("the HIP dense projector pools (adaptive_avg: the hook's setting, or adaptive_max)")
+        assert pool_name in ("adaptive_avg", "adaptive_max", "identical", "none", None), pool_name
         self._input_dim, self._output_dim = input_dim, output_dim
         self._head_type, self._normalize = head_type, normalize
         self._pool_name, self._spatial_size = pool_name, _pair(spatial_size)
-        self._pooling_module = (nn.AdaptiveAvgPool2d if pool_name == "adaptive_avg" else nn.AdaptiveMaxPool2d)(
-            self._spatial_size)
+        if pool_name in ("identical", "none", None):  # (projectors/nn.py:16-23: no pooling, one vector per pixel)
+            self._pooling_module = Identical()
+        else:
+            self._pooling_module = (nn.AdaptiveAvgPool2d if pool_name == "adaptive_avg" else nn.AdaptiveMaxPool2d)(
+                self._spatial_size)
         if head_type == "mlp":
             self._projector = nn.Sequential(nn.Conv2d(input_dim, hidden_dim, 1, 1, 0),
                                             nn.LeakyReLU(0.01, inplace=True),
@@ -110,37 +116,87 @@ class DenseProjectionHead(nn.Module):
         pooled = AdaptiveMaxPoolFn.apply(fmap, self._spatial_size)
         return L2NormFn.apply(pooled) if self._normalize else pooled
 
-    def _rows(self, features: Tensor, bins: Optional[Tensor]) -> Tensor:
+    @property
+    def _unpooled(self) -> bool:
+        return self._pool_name in ("identical", "none", None)
+
+    def output_size(self, features: Tensor) -> Tuple[int, int]:
+        """(h, w) of the grid `forward(features)` returns and `project_points` indexes: the pooling size, or the
+        feature map's own size without pooling"""
+        if self._unpooled:
+            return int(features.shape[2]), int(features.shape[3])
+        return self._spatial_size
+
+    def _weights(self):
         pr = self._projector
-        if self._pool_name == "adaptive_max":
-            if bins is not None:
-                raise NotImplementedError("point evaluation is implemented for adaptive_avg pooling")
-            return self._rows_max(features)
+        w1, b1 = pr[0].weight.reshape(pr[0].weight.shape[0], -1), pr[0].bias
         if self._head_type == "mlp":
-            hp = DenseProjHiddenFn.apply(features, pr[0].weight, pr[0].bias, self._spatial_size, bins)
+            return w1, b1, pr[2].weight.reshape(pr[2].weight.shape[0], -1), pr[2].bias
+        return w1, b1, None, None
+
+    def _rows_pixels(self, features: Tensor, idx: Optional[Tensor]) -> Tensor:
+        """no pooling: the projector (and the normalisation) on every pixel, or on the pixels `idx` lists, in one
+        launch; the [pixels, hidden] intermediate never exists"""
+        w1, b1, w2, b2 = self._weights()
+        hid, out = (0, w1.shape[0]) if w2 is None else (w1.shape[0], w2.shape[0])
+        if b1 is not None and (w2 is None or b2 is not None) and ops.pixel_mlp_ok(features.shape[1], hid, out):
+            return PixelMLPFn.apply(features, idx, w1, b1, w2, b2, 0.01, self._normalize)
+        # outside the fused range: pixels as rows of the Linear kernels, as _rows_max does
+        x = ops.to_nhwc(features)
+        rows = x.permute(0, 2, 3, 1).reshape(-1, x.shape[1])
+        if idx is not None:
+            rows = GatherRowsFn.apply(rows, idx)
+        if w2 is not None:
+            rows = LinearFn.apply(rows, w1, b1, 1, 0.01)
+            rows = LinearFn.apply(rows, w2, b2, 0, 0.0)
+        else:
+            rows = LinearFn.apply(rows, w1, b1, 0, 0.0)
+        return L2NormFn.apply(rows) if self._normalize else rows
+
+    def _rows(self, features: Tensor, bins: Optional[np.ndarray]) -> Tensor:
+        """bins: host int32 [nb, 3] = (image, row, col) on the output grid, or None (the whole grid)"""
+        pr = self._projector
+        dev = features.device
+        gh, gw = self.output_size(features)
+        flat = None  # the listed cells as rows of the [N * gh * gw, .] grid
+        if bins is not None:
+            assert (bins >= 0).all() and (bins[:, 0] < features.shape[0]).all() and (bins[:, 1] < gh).all() \
+                and (bins[:, 2] < gw).all(), "a sampled point lies outside the output grid"
+            flat = (bins[:, 0].astype(np.int64) * gh + bins[:, 1]) * gw + bins[:, 2]
+            assert features.shape[0] * gh * gw < 2 ** 31
+            flat = ops.pinned.upload(torch.as_tensor(flat.astype(np.int32)), dev)
+        if self._unpooled:
+            return self._rows_pixels(features, flat)
+        if self._pool_name == "adaptive_max":
+            rows = self._rows_max(features)
+            return rows if flat is None else GatherRowsFn.apply(rows, flat)
+        if self._head_type == "mlp":
+            hp = DenseProjHiddenFn.apply(features, pr[0].weight, pr[0].bias, self._spatial_size,
+                                         ops._bins_tensor(bins, dev))
             w2 = pr[2].weight.reshape(pr[2].weight.shape[0], -1)
             rows = LinearFn.apply(hp, w2, pr[2].bias, 0, 0.0)
         else:
-            if bins is not None:
-                raise NotImplementedError("point evaluation is implemented for the mlp head")
             pooled = AdaptiveAvgPoolFn.apply(features, self._spatial_size)
+            if flat is not None:
+                pooled = GatherRowsFn.apply(pooled, flat)
             rows = LinearFn.apply(pooled, pr[0].weight.reshape(pr[0].weight.shape[0], -1), pr[0].bias, 0, 0.0)
         return L2NormFn.apply(rows) if self._normalize else rows
 
     def forward(self, features: Tensor) -> Tensor:
         ops.require_gpu(features)
         n = features.shape[0]
-        sh, sw = self._spatial_size
-        rows = self._rows(features, None)  # [n*sh*sw, out] == NHWC
-        return rows.view(n, sh, sw, -1).permute(0, 3, 1, 2)
+        gh, gw = self.output_size(features)
+        rows = self._rows(features, None)  # [n*gh*gw, out] == NHWC
+        return rows.view(n, gh, gw, -1).permute(0, 3, 1, 2)
 
     def project_points(self, features: Tensor, points: Sequence[Sequence[Tuple[int, int]]]) -> Tensor:
-        """points[i] = [(row, col), ...] on the s x s output grid of image i (distinct per image)
+        """points[i] = [(row, col), ...] on the output grid of image i (`output_size(features)`: the s x s pooling
+        grid, or the feature map's own H x W without pooling; distinct per image)
         -> [sum_i len(points[i]), out], image-major: == region_extractor(self(features))"""
         ops.require_gpu(features)
-        bins = np.asarray([(i, a, b) for i, pts in enumerate(points) for a, b in pts], dtype=np.int32)
+        bins = np.asarray([(i, a, b) for i, pts in enumerate(points) for a, b in pts], dtype=np.int32).reshape(-1, 3)
         assert len(np.unique(bins, axis=0)) == len(bins), "sampled bins must be distinct"
-        return self._rows(features, ops._bins_tensor(bins, features.device))
+        return self._rows(features, bins)
 
 
 def _sub_header(dense: bool, head_type: str, input_dim: int, hidden_dim: int, num_clusters: int, normalize: bool,

@@ -991,6 +991,53 @@ class DenseProjHiddenFn(torch.autograd.Function):
         return dx, dw if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None, None, None
 
 
+class PixelMLPFn(torch.autograd.Function):
+    """DenseProjectionHead without pooling (contrastyou/projectors/heads.py:99-123 with projectors/nn.py:16-23
+    `Identical`): Conv1x1(C, hid) -> LeakyReLU(slope) -> Conv1x1(hid, out) [-> F.normalize over channels] on every
+    pixel, or on the listed pixels only, in one launch (csrc/cy_pixel_mlp.hip; the hidden activations never reach
+    memory).  x: an [N, C, H, W] map (read as NHWC) or rows [R, C]; idx: int32 device tensor of distinct rows
+    (n*H*W + r*W + c) or None; w2 = b2 = None: the linear head.  -> f32 rows [M, out], M = len(idx) or R.
+    The gradient of x is zero outside the listed rows."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, idx: Optional[Tensor], w1: Tensor, b1: Tensor, w2: Optional[Tensor],
+                b2: Optional[Tensor], slope: float, normalize: bool):
+        ops.require_gpu(x, w1, b1, w2, b2)
+        if x.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+            x = x.float()
+        ctx.map_shape = None
+        if x.dim() == 4:
+            x = ops.to_nhwc(x)
+            ctx.map_shape = tuple(x.shape)
+            rows = x.permute(0, 2, 3, 1).reshape(-1, x.shape[1])  # (a view: NHWC memory)
+        else:
+            rows = x if x.stride(1) == 1 else x.contiguous()
+        w1f = w1.detach().reshape(w1.shape[0], -1).float().contiguous()
+        b1f = b1.detach().float().contiguous()
+        w2f = None if w2 is None else w2.detach().reshape(w2.shape[0], -1).float().contiguous()
+        b2f = None if b2 is None else b2.detach().float().contiguous()
+        y, inv = ops.pixel_mlp_fwd(rows, idx, w1f, b1f, w2f, b2f, slope, normalize)
+        ctx.save_for_backward(rows, idx, w1f, b1f, w2f, y, inv)
+        ctx.slope, ctx.normalize = float(slope), bool(normalize)
+        ctx.shapes = (tuple(w1.shape), None if w2 is None else tuple(w2.shape))
+        return y
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        rows, idx, w1f, b1f, w2f, y, inv = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        need_dw = need[2] or need[3] or (w2f is not None and (need[4] or need[5]))
+        dx, dw1, db1, dw2, db2 = ops.pixel_mlp_bwd(rows, idx, w1f, b1f, w2f, y, inv, g.float().contiguous(), ctx.slope,
+                                                   ctx.normalize, need[0], need_dw)
+        if dx is not None and ctx.map_shape is not None:
+            n, c, h, w = ctx.map_shape
+            dx = dx.view(n, h, w, c).permute(0, 3, 1, 2)
+        s1, s2 = ctx.shapes
+        return (dx, None, dw1.view(s1) if need[2] else None, db1 if need[3] else None,
+                dw2.view(s2) if (w2f is not None and need[4]) else None,
+                db2 if (w2f is not None and need[5]) else None, None, None)
+
+
 class AdaptiveAvgPoolFn(torch.autograd.Function):
     """nn.AdaptiveAvgPool2d(size) on an NHWC map -> f32 rows [N*sh*sw, C]"""
 

@@ -2075,6 +2075,67 @@ def gather_rows_bwd(dout: Tensor, idx: Tensor, rows: int) -> Tensor:
     return dsrc
 
 
+# --------------------------------------------------------------------------- per-row projector (csrc/cy_pixel_mlp.hip)
+_PIXEL_MLP_PLAN = ("form", "rows_per_tile", "fwd_grid", "fwd_trips", "bwd_grid", "bwd_trips", "slabs", "lds_bytes")
+
+
+def pixel_mlp_ok(C_in: int, hid: int, out: int) -> bool:
+    """the fused range of cy_pixel_mlp_* (hid == 0: the linear head)"""
+    return 1 <= C_in <= 256 and 0 <= hid <= 256 and 1 <= out <= 256
+
+
+def pixel_mlp_plan(M: int, C_in: int, hid: int, out: int, dtype: torch.dtype = torch.float32) -> dict:
+    """the launch shape of cy_pixel_mlp_fwd / _bwd (host-side query, no GPU needed)"""
+    plan = (C.c_int32 * 8)()
+    _lib.call("cy_pixel_mlp_plan", int(M), int(C_in), int(hid), int(out), dtype_code(dtype), plan)
+    return dict(zip(_PIXEL_MLP_PLAN, (int(v) for v in plan)))
+
+
+def _pixel_rows(x: Tensor) -> Tuple[int, int]:
+    """(channels, pixel pitch in elements) of rows [R, C] whose channels are contiguous"""
+    assert x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= x.shape[1], (x.shape, x.stride())
+    return x.shape[1], x.stride(0)
+
+
+def pixel_mlp_fwd(x: Tensor, idx: Optional[Tensor], w1: Tensor, b1: Tensor, w2: Optional[Tensor],
+                  b2: Optional[Tensor], slope: float, normalize: bool):
+    """x: rows [R, C] (f32 / bf16 / f16, row pitch >= C); idx: int32 [M] distinct rows or None (all rows); w1 f32
+    [hid, C] and w2 f32 [out, hid], or w1 f32 [out, C] alone (linear) -> (y f32 [M, out], inv f32 [M] or None)"""
+    require_gpu(x, w1, b1)
+    Cc, ldx = _pixel_rows(x)
+    M = x.shape[0] if idx is None else idx.shape[0]
+    hid, out = (0, w1.shape[0]) if w2 is None else (w1.shape[0], w2.shape[0])
+    y = _f32(M * out, x.device).view(M, out)
+    inv = _f32(M, x.device) if normalize else None
+    _lib.call("cy_pixel_mlp_fwd", x.data_ptr(), _ptr(idx), w1.data_ptr(), b1.data_ptr(), _ptr(w2), _ptr(b2),
+              y.data_ptr(), _ptr(inv), M, Cc, ldx, hid, out, float(slope), int(bool(normalize)), dtype_code(x.dtype),
+              _stream())
+    return y, inv
+
+
+def pixel_mlp_bwd(x: Tensor, idx: Optional[Tensor], w1: Tensor, b1: Tensor, w2: Optional[Tensor], y: Tensor,
+                  inv: Optional[Tensor], dy: Tensor, slope: float, normalize: bool, need_dx: bool, need_dw: bool):
+    """-> (dx like x: zero outside the listed rows, or None; dw1, db1, dw2, db2 f32 or None)"""
+    Cc, ldx = _pixel_rows(x)
+    M, out = dy.shape
+    hid = 0 if w2 is None else w1.shape[0]
+    dx = None
+    if need_dx:  # (the kernel accumulates into the listed rows)
+        dx = torch.zeros(x.shape[0] * ldx, dtype=x.dtype, device=x.device).as_strided(x.shape, x.stride())
+    dw1 = db1 = dw2 = db2 = ws = None
+    nbytes = 0
+    if need_dw:
+        dw1, db1 = _f32(w1.numel(), x.device).view(w1.shape), _f32(w1.shape[0], x.device)
+        if hid:
+            dw2, db2 = _f32(w2.numel(), x.device).view(w2.shape), _f32(out, x.device)
+        nbytes = _lib.load().cy_pixel_mlp_bwd_ws_bytes(M, Cc, hid, out, dtype_code(x.dtype))
+        ws = _ws(nbytes, x.device)
+    _lib.call("cy_pixel_mlp_bwd", x.data_ptr(), _ptr(idx), w1.data_ptr(), b1.data_ptr(), _ptr(w2), y.data_ptr(),
+              _ptr(inv), dy.data_ptr(), _ptr(dx), _ptr(dw1), _ptr(db1), _ptr(dw2), _ptr(db2), 0, M, Cc, ldx, hid, out,
+              float(slope), int(bool(normalize)), dtype_code(x.dtype), _ptr(ws), nbytes, _stream())
+    return dx, dw1, db1, dw2, db2
+
+
 # --------------------------------------------------------------------------- cluster heads / discrete MI
 def cluster_head_ok(C: int, S: int, k: int) -> bool:
     return C in (32, 64) and S * k <= 128 and k <= 32

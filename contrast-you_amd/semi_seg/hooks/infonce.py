@@ -265,7 +265,7 @@ class _SuperPixelInfoNCEEPochHook(_INFONCEEpochHook):
         feature_ = self._extractor.tail(n_unl * 2)
         unlabeled_features, unlabeled_tf_features = torch.chunk(feature_, 2, dim=0)
         unlabeled_features_tf = affine_transformer(unlabeled_features, seed=seed)
-        sh, sw = self._projector._spatial_size
+        sh, sw = self._projector.output_size(unlabeled_features_tf)
         pts = region_points(n_unl, sh, sw, point_nums=5, seed=seed)
         rows = self._projector.project_points(torch.cat([unlabeled_features_tf, unlabeled_tf_features], dim=0),
                                               pts + pts)
@@ -300,7 +300,7 @@ class _INFONCEDenseHook(_INFONCEEpochHook):
         feature_ = self._extractor.tail(n_unl * 2)
         unlabeled_features, unlabeled_tf_features = torch.chunk(feature_, 2, dim=0)
         unlabeled_features_tf = affine_transformer(unlabeled_features, seed=seed)
-        sh, sw = self._projector._spatial_size
+        sh, sw = self._projector.output_size(unlabeled_features_tf)
         pts = region_points(n_unl, sh, sw, point_nums=5, seed=seed)  # same draw for both views (same seed)
         rows = self._projector.project_points(torch.cat([unlabeled_features_tf, unlabeled_tf_features], dim=0),
                                               pts + pts)

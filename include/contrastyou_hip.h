@@ -1187,6 +1187,45 @@ int cy_surface_stats(const int64_t* pred, const int64_t* target, const int32_t* 
                      int ndim, int64_t* count, double* sum, int32_t* maxd2, int32_t* d2_maps, uint8_t* border_maps,
                      void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Per-row projector: the dense projection head without pooling, and point evaluation of it (csrc/cy_pixel_mlp.hip;
+ * 4 entries added to ABI v18 -- no existing signature changed, so cy_abi_version() stays 18).  Replaces, for
+ * pool_name in ("identical", "none", None), the Conv2d(1x1) -> LeakyReLU -> Conv2d(1x1) -> Identical -> F.normalize of
+ * DenseProjectionHead.forward (contrastyou/projectors/heads.py:99-123, projectors/nn.py:16-23) on every pixel, or on
+ * the pixels the dense InfoNCE hook samples (semi_seg/hooks/infonce.py:31-46).
+ *   y[m] = W2 lrelu(W1 x[r(m)] + b1, slope) + b2   (hid > 0)        x: rows of `dtype`, pixel pitch ldx >= C elements
+ *   y[m] = W1 x[r(m)] + b1                          (hid == 0)       w1 f32 [hid or out][C], w2 f32 [out][hid]
+ *   r(m) = idx ? idx[m] : m                                          idx: int32 [M], distinct rows of x; NULL = all rows
+ *   normalize: y[m] *= inv[m], inv[m] = 1 / max(||y[m]||_2, 1e-12)   y f32 [M][out], inv f32 [M] (may be NULL otherwise)
+ * Fused range 1 <= C <= 256, 0 <= hid <= 256, 1 <= out <= 256; sizes are zero-padded to multiples of 32 inside the
+ * kernels.  16-bit rows: bf16 / f16 MFMA with f32 accumulation, W1 and W2 rounded to the storage type, bias and
+ * LeakyReLU in f32, the hidden tile rounded to the storage type once for the second product; it lives in LDS and is
+ * never written to memory.  f32 rows: f32 MFMA, nothing is rounded.  One launch.
+ * Backward (recomputes the hidden tile; dY is formed from dy, y and inv when `normalize`; dY and dH are rounded to the
+ * storage type for their products): dx (dtype, pitch ldx; may be NULL) is ACCUMULATED into, at the rows r(m) only
+ * (zero it first), as cy_dense_proj_bwd does; dw1, db1, dw2, db2 (f32, each may be NULL) are written, or added to
+ * with `accumulate`.  The parameter gradients go through one partial slab per workgroup in ws and a second launch that
+ * adds the slabs in slab order: no atomics, two runs give the same bits.
+ * cy_pixel_mlp_plan (host side, no GPU needed) is the launch rule both launches and the workspace query follow:
+ *   plan[0] kernel form (CY_PIXEL_MLP_*), [1] rows per tile, [2] forward workgroups (<= 1024), [3] forward loop trips,
+ *   [4] backward workgroups (<= 256), [5] backward loop trips, [6] partial slabs, [7] dynamic LDS bytes (the larger of
+ *   the two kernels').  ws_bytes = 4 * slabs * (J Cp + J + (hid ? Op Hp + Op : 0)) with Cp, Hp, Op the sizes rounded up
+ *   to 32 and J = hid ? Hp : Op: it does not grow with M past the cap (0 where the sizes are refused).
+ * Checked before any launch: a NULL required pointer -> CY_ERR_ARG; M < 1, a size outside the fused range or
+ * ldx < C -> CY_ERR_SHAPE; a short workspace (when a parameter gradient is asked for) -> CY_ERR_WORKSPACE.
+ * ------------------------------------------------------------------------ */
+#define CY_PIXEL_MLP_MFMA16 1 /* bf16 / f16 rows: 64 rows per tile */
+#define CY_PIXEL_MLP_MFMA32 2 /* f32 rows: 32 rows per tile */
+int cy_pixel_mlp_plan(long M, int C, int hid, int out, int dtype, int32_t* plan /* [8] */);
+int cy_pixel_mlp_fwd(const void* x, const int32_t* idx, const float* w1, const float* b1, const float* w2,
+                     const float* b2, float* y, float* inv, long M, int C, int ldx, int hid, int out, float slope,
+                     int normalize, int dtype, void* stream);
+size_t cy_pixel_mlp_bwd_ws_bytes(long M, int C, int hid, int out, int dtype);
+int cy_pixel_mlp_bwd(const void* x, const int32_t* idx, const float* w1, const float* b1, const float* w2,
+                     const float* y, const float* inv, const float* dy, void* dx, float* dw1, float* db1, float* dw2,
+                     float* db2, int accumulate, long M, int C, int ldx, int hid, int out, float slope, int normalize,
+                     int dtype, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
