@@ -6,6 +6,9 @@ f32-MFMA similarity GEMM, row statistics with the reference's global-max shift, 
     criterion(z1, z2, target=list|Tensor|None, mask=None) -> scalar loss
     criterion.sim_exp / .sim_logits / .pos_mask / .neg_mask   (materialised on first access)
 
+`mask` is the reference's: [n, n], 1 = positive, 0 = negative, any other value neither (in no denominator), read as
+given -- it need not be symmetric.
+
 The reference asserts unit-norm inputs (AssertionError) and raises RuntimeError on a NaN loss,
 both through host syncs.  Here the same conditions are evaluated on the device and checked by
 `validate()`; with `defer_checks=False` (default) validate() runs inside forward, exactly like the
@@ -84,7 +87,9 @@ class SupConLoss1(nn.Module):
         labels = pos = None
         if mask is not None:
             assert mask.shape == torch.Size([n, n])
-            pos = (mask == 1).to(device=dev, dtype=torch.uint8).contiguous()
+            # contrastive.py:35-36: pos = mask == 1, neg = mask == 0, any other value is neither; as uint8 codes 1 / 0 / 2
+            code = torch.where(mask == 1, 1, torch.where(mask == 0, 0, 2))
+            pos = code.to(device=dev, dtype=torch.uint8).contiguous()
         elif target is not None:
             labels = _encode_target(target, n, dev)
         else:

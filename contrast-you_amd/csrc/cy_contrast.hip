@@ -74,14 +74,23 @@ int launch_sgemm(const float* A, const float* B, float* C, int M, int N, int K, 
 }
 
 // ---------------------------------------------------------------- SupCon
+// An explicit mask holds one code per ordered pair (contrastive.py:35-36): 1 positive, 0 negative, anything else
+// neither -- such a pair enters no sum at all.  It is read as given, pm[i mod n][j mod n] for the pair (i, j), and
+// need not be symmetric: the transposed term of G + G^T reads pm[j mod n][i mod n].
 __device__ __forceinline__ bool is_pos(const int32_t* labels, const uint8_t* pm, int n, int i,
                                        int j) {
   const int a = i % n, b = j % n;
   if (labels) return labels[a] == labels[b];
-  return pm[(size_t)a * n + b] != 0;
+  return pm[(size_t)a * n + b] == 1;
+}
+// code of the ordered pair (i, j): 1, 0, or > 1 for neither (labels know only 1 and 0)
+__device__ __forceinline__ int pair_code(const int32_t* labels, const uint8_t* pm, int n, int i, int j) {
+  const int a = i % n, b = j % n;
+  if (labels) return labels[a] == labels[b] ? 1 : 0;
+  return pm[(size_t)a * n + b];
 }
 
-// one wave per row: row max (incl. diagonal), sum_{k!=i} exp(s-m), sum over positives, count
+// one wave per row: row max (incl. diagonal), sum_{k!=i, not neither} exp(s-m), sum over positives, count
 __global__ void __launch_bounds__(256)
     supcon_rowstats_kernel(const float* __restrict__ S, const int32_t* __restrict__ labels,
                            const uint8_t* __restrict__ pm, float* __restrict__ tmp, int n) {
@@ -96,9 +105,11 @@ __global__ void __launch_bounds__(256)
   float l = 0.f, ps = 0.f, cnt = 0.f;
   for (int j = lane; j < R; j += 64) {
     if (j == row) continue;
+    const int code = pair_code(labels, pm, n, row, j);
+    if (code > 1) continue;
     const float s = sr[j];
     l += expf(s - m);
-    if (is_pos(labels, pm, n, row, j)) {
+    if (code == 1) {
       ps += s;
       cnt += 1.f;
     }
@@ -150,7 +161,7 @@ __global__ void __launch_bounds__(256)
   if (tid == 0) loss[0] = (float)(-ssum[0] / (double)R);
 }
 
-// G + G^T with G_ij = -(g/R) [pos_ij/cnt_i - e_ij/D_i], zero diagonal
+// G + G^T with G_ij = -(g/R) [pos_ij/cnt_i - in_ij e_ij/D_i], zero diagonal; in_ij: the pair is in row i's denominator
 __global__ void __launch_bounds__(256)
     supcon_gsym_kernel(const float* __restrict__ S, const float* __restrict__ rs,
                        const int32_t* __restrict__ labels, const uint8_t* __restrict__ pm,
@@ -166,8 +177,15 @@ __global__ void __launch_bounds__(256)
       const float eij = expf(S[e] - M);
       const float Di = rs[i * 4 + 0], Dj = rs[j * 4 + 0];
       const float ci = rs[i * 4 + 1], cj = rs[j * 4 + 1];
-      const float pos = is_pos(labels, pm, n, i, j) ? 1.f : 0.f;
-      v = -gs * (pos * (1.f / ci + 1.f / cj) - eij * (1.f / Di + 1.f / Dj));
+      if (labels) {
+        const float pos = is_pos(labels, pm, n, i, j) ? 1.f : 0.f;
+        v = -gs * (pos * (1.f / ci + 1.f / cj) - eij * (1.f / Di + 1.f / Dj));
+      } else {  // explicit mask: the transposed term goes by the code of (j, i)
+        const int cij = pair_code(labels, pm, n, i, j), cji = pair_code(labels, pm, n, j, i);
+        const float p = (cij == 1 ? 1.f / ci : 0.f) + (cji == 1 ? 1.f / cj : 0.f);
+        const float q = (cij <= 1 ? 1.f / Di : 0.f) + (cji <= 1 ? 1.f / Dj : 0.f);
+        v = -gs * (p - eij * q);
+      }
     }
     G[e] = v;
   }
@@ -191,15 +209,17 @@ __global__ void __launch_bounds__(256)
   for (int i = lane; i < R; i += 64) M = fmaxf(M, tmp[i * 4]);  // (every wave: the row maxima are 4 R bytes)
   M = wave_max(M);
   const float* sr = S + (size_t)row * R;
-  float ln = 0.f, cnt = 0.f;
+  float ln = 0.f, cnt = 0.f, nc = 0.f;
   for (int j = lane; j < R; j += 64) {
     if (j == row) continue;
-    if (is_pos(labels, pm, n, row, j)) cnt += 1.f;
-    else ln += expf(sr[j] - M);
+    const int code = pair_code(labels, pm, n, row, j);
+    if (code == 1) cnt += 1.f;
+    else if (code == 0) ln += expf(sr[j] - M), nc += 1.f;
   }
   ln = wave_sum(ln);
   cnt = wave_sum(cnt);
-  const float negc = (float)(R - 1) - cnt;
+  nc = wave_sum(nc);
+  const float negc = labels ? (float)(R - 1) - cnt : nc;  // (a mask's "neither" pairs are in neither count)
   const float kappa = 1.f / (negc / (cnt + negc) + 1e-4f);
   const float ai = ln * kappa + 1e-16f;
   float T = 0.f, ls = 0.f;
@@ -238,7 +258,7 @@ __global__ void __launch_bounds__(256)
   }
 }
 
-// G + G^T with G_ij = -(g/R) d loss_i / d s_ij:  pos: (1/c_i) a_i / (e_ij + a_i);  neg: -e_ij kappa_i T_i / c_i
+// G + G^T with G_ij = -(g/R) d loss_i / d s_ij:  pos: (1/c_i) a_i / (e_ij + a_i);  neg: -e_ij kappa_i T_i / c_i;  neither: 0
 __global__ void __launch_bounds__(256)
     supcon_excl_gsym_kernel(const float* __restrict__ S, const float* __restrict__ rs, const float* __restrict__ Mptr,
                             const int32_t* __restrict__ labels, const uint8_t* __restrict__ pm,
@@ -252,11 +272,17 @@ __global__ void __launch_bounds__(256)
     float v = 0.f;
     if (i != j) {
       const float eij = expf(S[e] - M);
-      if (is_pos(labels, pm, n, i, j)) {
-        const float ai = rs[i * 4 + 0], aj = rs[j * 4 + 0];
+      const int cij = pair_code(labels, pm, n, i, j);
+      const int cji = labels ? cij : pair_code(labels, pm, n, j, i);  // (mask: the transposed term has its own code)
+      const float ai = rs[i * 4 + 0], aj = rs[j * 4 + 0];
+      if (cij == 1 && cji == 1) {
         v = -gs * (ai / ((eij + ai) * rs[i * 4 + 1]) + aj / ((eij + aj) * rs[j * 4 + 1]));
-      } else {
+      } else if (cij == 0 && cji == 0) {
         v = gs * eij * (rs[i * 4 + 2] + rs[j * 4 + 2]);
+      } else {  // the two directions differ, or one is neither (no term)
+        const float vi = cij == 1 ? -ai / ((eij + ai) * rs[i * 4 + 1]) : (cij == 0 ? eij * rs[i * 4 + 2] : 0.f);
+        const float vj = cji == 1 ? -aj / ((eij + aj) * rs[j * 4 + 1]) : (cji == 0 ? eij * rs[j * 4 + 2] : 0.f);
+        v = gs * (vi + vj);
       }
     }
     G[e] = v;
@@ -275,9 +301,9 @@ __global__ void __launch_bounds__(256)
     const float s = S[e] - M;
     if (sl) sl[e] = s;
     if (se) se[e] = expf(s);
-    const bool pos = is_pos(labels, pm, n, i, j);
-    if (po) po[e] = (i != j && pos) ? 1.f : 0.f;
-    if (ne) ne[e] = (i != j && !pos) ? 1.f : 0.f;
+    const int code = pair_code(labels, pm, n, i, j);
+    if (po) po[e] = (i != j && code == 1) ? 1.f : 0.f;
+    if (ne) ne[e] = (i != j && code == 0) ? 1.f : 0.f;
   }
 }
 
@@ -355,10 +381,17 @@ __device__ __forceinline__ ScRow sc_row(const int32_t* labels, int n, int row) {
   return q;
 }
 __device__ __forceinline__ bool sc_pos(const ScRow& r, const ScRow& c, const int32_t* labels, const uint8_t* pm, int n) {
-  return labels ? r.lab == c.lab : pm[(size_t)r.a * n + c.a] != 0;
+  return labels ? r.lab == c.lab : pm[(size_t)r.a * n + c.a] == 1;
+}
+// explicit mask: the code of the ordered pair (r, c) -- 1 positive, 0 negative, anything else neither.  Callers keep
+// `row < R && col < R` in front: beyond R the folded index leaves the n x n mask.
+__device__ __forceinline__ int sc_code(const ScRow& r, const ScRow& c, const uint8_t* pm, int n) {
+  return pm[(size_t)r.a * n + c.a];
 }
 
-// grid (row blocks, column splits).  part[split][R][3] = (l, ps, cnt) of the split's columns
+// grid (row blocks, column splits).  part[split][R][3] = (l, ps, cnt) of the split's columns.  MASK: positives from
+// the explicit mask's codes (labels == NULL); the labels instantiation is the one the training hooks run.
+template <bool MASK>
 __global__ void __launch_bounds__(256)
     supcon_fused_fwd_kernel(const float* __restrict__ P, const int32_t* __restrict__ labels,
                             const uint8_t* __restrict__ pm, const float* __restrict__ Mptr,
@@ -397,10 +430,19 @@ __global__ void __launch_bounds__(256)
       const int row = m0 + wm * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * kk;
       if (row < R && col < R && row != col) {
         const float s = acc[reg] * inv_t;
-        l[reg] += expf(s - M);
-        if (sc_pos(rws[reg], cq, labels, pm, n)) {
-          ps[reg] += s;
-          cnt[reg] += 1.f;
+        if (MASK) {
+          const int code = sc_code(rws[reg], cq, pm, n);
+          if (code <= 1) l[reg] += expf(s - M);  // (neither: in no sum)
+          if (code == 1) {
+            ps[reg] += s;
+            cnt[reg] += 1.f;
+          }
+        } else {
+          l[reg] += expf(s - M);
+          if (sc_pos(rws[reg], cq, labels, pm, n)) {
+            ps[reg] += s;
+            cnt[reg] += 1.f;
+          }
         }
       }
     }
@@ -475,7 +517,9 @@ __global__ void __launch_bounds__(256)
   if (tid == 0) loss[0] = (float)(-ssum[0] / (double)R);
 }
 
-// grid (row blocks, column splits).  dpart[split][R][D] = sum over the split's columns of G_ij P_j
+// grid (row blocks, column splits).  dpart[split][R][D] = sum over the split's columns of G_ij P_j.  MASK as above:
+// G_ij + G_ji = -(g/R) [pos_ij/c_i + pos_ji/c_j - e_ij (in_ij/D_i + in_ji/D_j)], the transposed terms by pm[j][i]
+template <bool MASK>
 __global__ void __launch_bounds__(256)
     supcon_fused_bwd_kernel(const float* __restrict__ P, const int32_t* __restrict__ labels,
                             const uint8_t* __restrict__ pm, const float* __restrict__ rs,
@@ -526,8 +570,16 @@ __global__ void __launch_bounds__(256)
       float v = 0.f;
       if (row < R && col < R && row != col) {
         const float e = expf(acc[reg] * inv_t - M);
-        const float pos = sc_pos(sc_row(labels, n, row), cq, labels, pm, n) ? 1.f : 0.f;
-        v = -gs * (pos * (sRow[rr * 2 + 1] + icj) - e * (sRow[rr * 2 + 0] + iDj));
+        if (MASK) {
+          const ScRow rq = sc_row(labels, n, row);
+          const int cij = sc_code(rq, cq, pm, n), cji = sc_code(cq, rq, pm, n);
+          const float p = (cij == 1 ? sRow[rr * 2 + 1] : 0.f) + (cji == 1 ? icj : 0.f);
+          const float q = (cij <= 1 ? sRow[rr * 2 + 0] : 0.f) + (cji <= 1 ? iDj : 0.f);
+          v = -gs * (p - e * q);
+        } else {
+          const float pos = sc_pos(sc_row(labels, n, row), cq, labels, pm, n) ? 1.f : 0.f;
+          v = -gs * (pos * (sRow[rr * 2 + 1] + icj) - e * (sRow[rr * 2 + 0] + iDj));
+        }
       }
       sG[rr * ldg + wn * 32 + i] = v;
     }
@@ -1035,9 +1087,14 @@ int cy_supcon_fused_fwd(const float* P, const int32_t* labels, const uint8_t* po
   hipLaunchKernelGGL(supcon_max_kernel, dim3(1), dim3(256), 0, st, diag, Mv, R);
   CY_CHECK_LAUNCH();
   const size_t smem = (size_t)2 * sc_block_floats(D) * sizeof(float);
-  if (!cy_lds_limit_once<supcon_fused_fwd_kernel>(2 * sc_block_floats(256) * 4)) return CY_ERR_LAUNCH;
-  hipLaunchKernelGGL(supcon_fused_fwd_kernel, dim3(rb, ns), dim3(256), smem, st, P, labels, pos_mask, Mv, part,
-                     n, D, 1.f / t, ns);
+  if (!cy_lds_limit_once<supcon_fused_fwd_kernel<false>, supcon_fused_fwd_kernel<true>>(2 * sc_block_floats(256) * 4))
+    return CY_ERR_LAUNCH;
+  if (labels)
+    hipLaunchKernelGGL(supcon_fused_fwd_kernel<false>, dim3(rb, ns), dim3(256), smem, st, P, labels, pos_mask, Mv, part,
+                       n, D, 1.f / t, ns);
+  else
+    hipLaunchKernelGGL(supcon_fused_fwd_kernel<true>, dim3(rb, ns), dim3(256), smem, st, P, labels, pos_mask, Mv, part,
+                       n, D, 1.f / t, ns);
   CY_CHECK_LAUNCH();
   hipLaunchKernelGGL(supcon_fused_finalize_kernel, dim3(1), dim3(256), 0, st, part, Mv, row_stats, loss, R, ns);
   CY_CHECK_LAUNCH();
@@ -1054,9 +1111,15 @@ int cy_supcon_fused_bwd(const float* P, const int32_t* labels, const uint8_t* po
   const int R = 2 * n, ns = sc_nsplit(R), rb = cy_cdiv(R, SC_TM);
   float* dpart = (float*)ws + R + 4;
   const size_t smem = ((size_t)2 * sc_block_floats(D) + SC_TM * (SC_TM + 1) + SC_TM * 2) * sizeof(float);
-  if (!cy_lds_limit_once<supcon_fused_bwd_kernel>((2 * sc_block_floats(256) + SC_TM * (SC_TM + 1) + SC_TM * 2) * 4)) return CY_ERR_LAUNCH;
-  hipLaunchKernelGGL(supcon_fused_bwd_kernel, dim3(rb, ns), dim3(256), smem, st, P, labels, pos_mask, row_stats,
-                     gscale, dpart, n, D, 1.f / t, ns);
+  if (!cy_lds_limit_once<supcon_fused_bwd_kernel<false>, supcon_fused_bwd_kernel<true>>(
+          (2 * sc_block_floats(256) + SC_TM * (SC_TM + 1) + SC_TM * 2) * 4))
+    return CY_ERR_LAUNCH;
+  if (labels)
+    hipLaunchKernelGGL(supcon_fused_bwd_kernel<false>, dim3(rb, ns), dim3(256), smem, st, P, labels, pos_mask, row_stats,
+                       gscale, dpart, n, D, 1.f / t, ns);
+  else
+    hipLaunchKernelGGL(supcon_fused_bwd_kernel<true>, dim3(rb, ns), dim3(256), smem, st, P, labels, pos_mask, row_stats,
+                       gscale, dpart, n, D, 1.f / t, ns);
   CY_CHECK_LAUNCH();
   const long total = (long)R * D;
   hipLaunchKernelGGL(supcon_dpart_reduce_kernel, dim3(grid_for(total)), dim3(256), 0, st, dpart, dP, total, ns,

@@ -582,13 +582,20 @@ int cy_l2norm_bwd(const float* x, const float* norms, const float* dz, float* dx
  * P = [z1; z2] is [R=2n][D] f32 (unit rows), labels[n] int32 (row i and
  * i+n share labels[i]); t = temperature.
  *   S = P P^T / t;  M = max(S) (incl. diagonal);  E = exp(S - M)
- *   loss = -mean_i [ sum_{j in pos(i)} ((S_ij - M) - log(sum_{k!=i} E_ik + 1e-16)) / |pos(i)| ]
+ *   loss = -mean_i [ sum_{j in pos(i)} ((S_ij - M) - log(sum_{k!=i, k in pos(i) or neg(i)} E_ik + 1e-16)) / |pos(i)| ]
  * row_stats (f32 [R][4]) keeps {denominator_i, |pos(i)|, sum_pos S_ij, M}
  * for the backward pass.  Rows with |pos(i)| == 0 give NaN exactly like the
  * reference (which then raises RuntimeError, contrastive.py:98).
  * ------------------------------------------------------------------------ */
-/* Either labels (int32 [n]) or pos_mask (uint8 [n][n], 1 = positive pair; the
- * `mask=` argument of SupConLoss1.forward) must be non-NULL.
+/* Either labels (int32 [n]) or pos_mask must be non-NULL; labels win when both are given.
+ * pos_mask (uint8 [n][n]) is the `mask=` argument of SupConLoss1.forward, one code per ORDERED pair, in every
+ * cy_supcon_* entry below (contrastive.py:35-36):
+ *     1 = positive,  0 = negative,  any other value (the criterion writes 2) = neither.
+ * A "neither" pair enters no sum: not the denominator sum_k above, not the negative count of exclude_other_pos, and
+ * cy_supcon_matrices reports it in neither mask.  The pair (i, j) of the 2n x 2n problem reads pos_mask[i mod n][j mod n];
+ * the mask is taken as given and need not be symmetric (the gradient's transposed term reads [j mod n][i mod n]).
+ * The diagonal i == j is left out whatever its code.  No signature changed with this contract (codes 1 and 0 mean what
+ * they meant), so cy_abi_version() stays 18.
  * S: f32 [R][R] buffer that receives P P^T / t (kept for backward). */
 int cy_supcon_fwd(const float* P, const int32_t* labels, const uint8_t* pos_mask, float* S,
                   float* loss, float* row_stats, int n, int D, float t, void* stream);

@@ -64,15 +64,17 @@ def dense_projection_head(sd: Dict[str, Tensor], feat: Tensor, spatial_size: Seq
 # ---------------------------------------------------------------- InfoNCE / SupCon
 def supcon_masks(n: int, target: Optional[Sequence[int]] = None, mask: Optional[Tensor] = None):
     """contrastyou/losses/contrastive.py:31-50,62-71: positive / negative masks, tiled 2x2,
-    diagonal removed."""
+    diagonal removed.  An explicit mask is three-valued (:35-36): 1 positive, 0 negative, anything else neither --
+    such a pair enters no denominator -- and it is read as given, never transposed."""
     if mask is not None:
-        pos = (mask == 1).float()
-    elif target is not None:
-        t = torch.as_tensor(list(target), dtype=torch.float32)
-        pos = torch.eq(t[:, None], t[None, :]).float()
+        pos, neg = (mask == 1).float(), (mask == 0).float()
     else:
-        pos = torch.eye(n)
-    neg = 1 - pos
+        if target is not None:
+            t = torch.as_tensor(list(target), dtype=torch.float32)
+            pos = torch.eq(t[:, None], t[None, :]).float()
+        else:
+            pos = torch.eye(n)
+        neg = 1 - pos
     off = 1 - torch.eye(2 * n)
     return pos.repeat(2, 2) * off, neg.repeat(2, 2) * off
 

@@ -80,6 +80,36 @@ def test_supcon_matches_reference(golden_dir):
     close(z1.grad, g["sc_mask_dz1"], rtol=1e-4)
 
 
+def test_supcon_general_masks_match_reference(golden_dir):
+    """explicit masks as the reference reads them (contrastive.py:35-36): 1 positive, 0 negative, anything else
+    neither, never transposed -- symmetric and asymmetric, two- to four-valued, with and without the diagonal
+    (tests/golden/supcon_masks.npz, written by gen_goldens_supcon.py from the reference's SupConLoss1 in f64)"""
+    g = np.load(golden_dir / "supcon_masks.npz")
+    t = float(g["t"])
+    for c in ("a", "b", "c", "d", "z"):
+        mask = T(g[f"{c}_mask"])
+        for excl, fn in ((0, ol.supcon_loss), (1, ol.supcon_loss_exclude_pos)):
+            z1 = T(g["z1"]).double().requires_grad_(True)
+            z2 = T(g["z2"]).double().requires_grad_(True)
+            loss = fn(z1, z2, mask=mask, t=t)
+            # (1e-7: the reference's masks, counts and neg_ratio + 1e-4 are f32 whatever the embeddings' type)
+            close(loss, g[f"{c}_e{excl}_loss"], rtol=1e-7, atol=0)
+            loss.backward()
+            close(z1.grad, g[f"{c}_e{excl}_dz1"], rtol=1e-6, atol=0)  # (stored rounded to f32)
+            close(z2.grad, g[f"{c}_e{excl}_dz2"], rtol=1e-6, atol=0)
+        pos, neg = ol.supcon_masks(mask.shape[0], mask=mask)
+        assert torch.equal(pos, T(g[f"{c}_pos"]).float()) and torch.equal(neg, T(g[f"{c}_neg"]).float()), c
+    _, S, E, _, _ = ol.supcon_loss(T(g["z1"]).double(), T(g["z2"]).double(), mask=T(g["d_mask"]), t=t, return_all=True)
+    close(S, g["d_sim_logits"], rtol=1e-6, atol=0)
+    close(E, g["d_sim_exp"], rtol=1e-6, atol=0)
+    # the cases say what their names promise: c and d hold pairs that are neither, b, d and z are not symmetric
+    for c, neither, symmetric in (("a", False, True), ("b", False, False), ("c", True, True), ("d", True, False),
+                                  ("z", False, False)):
+        m = T(g[f"{c}_mask"])
+        assert bool(((m != 0) & (m != 1)).any()) == neither and torch.equal(m == 1, (m == 1).t()) == symmetric, c
+        assert int(g[f"{c}_pos"].sum(1).min()) >= 1, c
+
+
 def test_kl_and_dice_match_reference(golden_dir):
     g = np.load(golden_dir / "heads_losses.npz")
     lg = T(g["kl_logits"]).requires_grad_(True)
