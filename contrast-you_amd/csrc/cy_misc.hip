@@ -79,7 +79,10 @@ __global__ void __launch_bounds__(256)
     const float xi = (2.f * ix + 1.f) / (float)W - 1.f;
     const float yi = (2.f * iy + 1.f) / (float)H - 1.f;
     const float det = th[0] * th[4] - th[1] * th[3];
-    int x0 = 0, x1 = -1, y0 = 0, y1 = -1;  // empty window when theta is singular
+    // The window may be any superset of the pre-image (the test below decides).  It is the whole image unless a
+    // finite inverse places it: a singular theta still gathers (every pick on a line or on one pixel), and next to
+    // singular the centre and extents leave the range of int.
+    int x0 = 0, x1 = W - 1, y0 = 0, y1 = H - 1;
     if (fabsf(det) > 1e-12f) {
       const float i00 = th[4] / det, i01 = -th[1] / det, i10 = -th[3] / det, i11 = th[0] / det;
       const float bx = xi - th[2], by = yi - th[5];
@@ -87,14 +90,20 @@ __global__ void __launch_bounds__(256)
       const float cx = ((xo + 1.f) * (float)W - 1.f) * 0.5f;
       const float cy = ((yo + 1.f) * (float)H - 1.f) * 0.5f;
       // half extent (in output pixels) of the pre-image of one input pixel, plus a margin
-      const int rx = (int)ceilf(0.5f * (fabsf(i00) + fabsf(i01) * (float)W / (float)H)) + 1;
-      const int ry = (int)ceilf(0.5f * (fabsf(i10) * (float)H / (float)W + fabsf(i11))) + 1;
-      x0 = (int)floorf(cx) - rx, x1 = (int)ceilf(cx) + rx;
-      y0 = (int)floorf(cy) - ry, y1 = (int)ceilf(cy) + ry;
-      if (x0 < 0) x0 = 0;
-      if (y0 < 0) y0 = 0;
-      if (x1 > W - 1) x1 = W - 1;
-      if (y1 > H - 1) y1 = H - 1;
+      const float frx = ceilf(0.5f * (fabsf(i00) + fabsf(i01) * (float)W / (float)H)) + 1.f;
+      const float fry = ceilf(0.5f * (fabsf(i10) * (float)H / (float)W + fabsf(i11))) + 1.f;
+      const float lim = (float)(W + H);
+      // false for NaN and infinity too.  The augmentation's thetas (scale 0.8-1.3, |cx| < 1.6 W on its square
+      // images) pass and keep their small window; only a degenerate theta pays for the scan of the whole image.
+      if (fabsf(cx) <= lim && fabsf(cy) <= lim && frx <= lim && fry <= lim) {
+        const int rx = (int)frx, ry = (int)fry;
+        x0 = (int)floorf(cx) - rx, x1 = (int)ceilf(cx) + rx;
+        y0 = (int)floorf(cy) - ry, y1 = (int)ceilf(cy) + ry;
+        if (x0 < 0) x0 = 0;
+        if (y0 < 0) y0 = 0;
+        if (x1 > W - 1) x1 = W - 1;
+        if (y1 > H - 1) y1 = H - 1;
+      }
     }
     const int c0 = g * 8;
     float acc[8];
