@@ -1,18 +1,30 @@
-"""Discrete mutual-information (IIC) losses with the interface of
-contrastyou/losses/discreteMI.py:90-170,201-261:
+"""Discrete mutual-information (IIC) and IMSAT losses with the interface of
+contrastyou/losses/discreteMI.py:20-170,201-297:
 
     IIDLoss(lamb)(x_out, x_tf_out)                 -> (loss, loss_no_lamb, p_i_j)   on [n,k] simplexes
     IIDSegmentationLoss(lamda, padding, eps, symmetric)(x_out, x_tf_out, mask=None) -> loss
                                                                                   on [n,k,H,W] maps
     compute_joint / compute_joint_2D / compute_joint_2D_with_padding_zeros
+    imsat_with_entropy(prediction)                 -> (marginal entropy, mean conditional entropy)
+    imsat_loss(prediction, lamda)                  -> conditional - lamda * marginal
+    IMSATLoss(lamda, eps)(x_out, x_tf_out=None)    -> imsat_loss, or the mean of the two views'   on [n,k] simplexes
+    IMSATDynamicWeight(lamda, use_dynamic, eps)(x_out) -> -w * marginal + conditional, w a buffer that follows
+                                                      log k - marginal
 
 The k x k (or (2p+1)^2 x k x k) joint is a contraction over all n*H*W pixels -- HBM-bound, k = 20 --
 done by the HIP joint kernels; the loss on the joint and its gradient come from one single-block
 kernel (csrc/cy_mi.hip).  Inputs must be probability maps; the reference's `simplex()` assertion is a
 host sync and is evaluated on demand by `validate()`.
+
+The IMSAT family is one streaming pass over the [rows][k] probabilities (csrc/cy_imsat.hip): it yields the two
+entropies as device scalars and every combination above is formed from them with ordinary tensor ops.  Its entropies
+use eps = 1e-8, the module-level `entropy_criterion` of semi_seg/hooks/midl.py:13; the `eps` argument of the two
+classes is kept and, as in the reference, never read.  The reference's `assert simplex(...)` calls in `IMSATLoss` and
+`IMSATDynamicWeight` are host syncs and are left out; the dynamic weight is updated on the device.
 """
 from __future__ import annotations
 
+import math
 import sys
 from typing import Tuple
 
@@ -20,10 +32,10 @@ import torch
 from torch import Tensor, nn
 
 from cyhip import ops
-from cyhip.functions import IIDFn
+from cyhip.functions import IIDFn, IMSATFn, IMSATPairFn
 
 __all__ = ["IIDLoss", "IIDSegmentationLoss", "compute_joint", "compute_joint_2D",
-           "compute_joint_2D_with_padding_zeros"]
+           "compute_joint_2D_with_padding_zeros", "IMSATLoss", "IMSATDynamicWeight", "imsat_loss", "imsat_with_entropy"]
 
 
 def _nhwc_f32(x: Tensor) -> Tensor:
@@ -100,3 +112,58 @@ def compute_joint_2D_with_padding_zeros(x_out: Tensor, x_tf_out: Tensor, *, symm
     J = ops.joint_fwd(_nhwc_f32(x_out), _nhwc_f32(x_tf_out), n, H, W, k, 0, True)
     _, P, _ = ops.iid_loss(J, 0, bool(symmetric), 1.0, 1e-5, want_grad=False)
     return P.view(1, 1, k, k)
+
+
+def imsat_with_entropy(prediction: Tensor) -> Tuple[Tensor, Tensor]:
+    """[n,k] simplexes or an [n,k,H,W] map -> (entropy of the mean row, mean entropy of the rows)
+    (discreteMI.py:287-297)"""
+    return IMSATFn.apply(prediction)
+
+
+def imsat_loss(prediction: Tensor, lamda: float = 1.0) -> Tensor:
+    """-(lamda * marginal - conditional) (discreteMI.py:275-284)"""
+    marginal, conditional = IMSATFn.apply(prediction)
+    return conditional - marginal * lamda
+
+
+class IMSATLoss(nn.Module):
+
+    def __init__(self, lamda: float = 1.0, eps: float = sys.float_info.epsilon):
+        super().__init__()
+        self.eps = float(eps)
+        self.lamda = float(lamda)
+
+    def forward(self, x_out: Tensor, x_tf_out: Tensor = None):
+        assert len(x_out.shape) == 2, x_out.shape
+        self.x_out = x_out
+        self.x_tf_out = x_out if x_tf_out is None else x_tf_out
+        if x_tf_out is None:
+            return imsat_loss(x_out, lamda=self.lamda)
+        marg1, cond1, marg2, cond2, _ = IMSATPairFn.apply(x_out, x_tf_out)  # one pass over both; the MSE is not used
+        return 0.5 * ((cond1 - marg1 * self.lamda) + (cond2 - marg2 * self.lamda))
+
+    @torch.no_grad()
+    def get_joint_matrix(self):
+        """x_out^T x_tf_out / n as a numpy [k,k] array: compute_joint_2D_with_padding_zeros(symmetric=False) on [n,k]"""
+        a, b = self.x_out.detach().float().contiguous(), self.x_tf_out.detach().float().contiguous()
+        n, k = a.shape
+        return ops.joint_fwd(a, b, n, 1, 1, k, 0, True).view(k, k).cpu().numpy()
+
+
+class IMSATDynamicWeight(IMSATLoss):
+
+    def __init__(self, lamda: float = 1.0, use_dynamic: bool = True, eps: float = sys.float_info.epsilon):
+        super().__init__(lamda, eps)
+        self.register_buffer("dynamic_weight", torch.tensor(lamda))
+        self.use_dynamic_weight = use_dynamic
+
+    def forward(self, x_out: Tensor, **kwargs):
+        self.dynamic_weight = self.dynamic_weight.to(x_out.device).to(x_out.dtype)
+        assert len(x_out.shape) == 2, x_out.shape
+        self.x_out = self.x_tf_out = x_out
+        marg, cond = imsat_with_entropy(x_out)
+        mi = self.dynamic_weight * marg * -1.0 + cond
+        if self.use_dynamic_weight:
+            with torch.no_grad():  # on the device: the weight is never read on the host
+                self.dynamic_weight = self.dynamic_weight + (math.log(x_out.shape[1]) - marg.detach()) * 0.01
+        return mi

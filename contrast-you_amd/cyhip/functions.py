@@ -1187,6 +1187,104 @@ class JointFn(torch.autograd.Function):
         return d1, d2
 
 
+def _imsat_rows(x: Tensor) -> Tensor:
+    """[R, K] rows or a [b, K, ...] map of any memory format -> its f32 rows [R, K], contiguous (a view where the
+    channels already are innermost in memory)"""
+    ops.require_gpu(x)
+    if x.dim() == 4:
+        return ops.to_nhwc(x.float()).permute(0, 2, 3, 1).reshape(-1, x.shape[1])
+    return x.float().movedim(1, -1).reshape(-1, x.shape[1]).contiguous()
+
+
+def _imsat_grad(d: Tensor, like) -> Tensor:
+    """rows [R, K] -> the (shape, dtype) of the input they are the gradient of"""
+    shape, dtype = list(like[0]), like[1]
+    return d.view(shape[:1] + shape[2:] + shape[1:2]).movedim(-1, 1).to(dtype)
+
+
+def _grad_vector(*gs: Tensor) -> Tensor:
+    """the upstream gradients of a function's scalars as one device vector (no host sync)"""
+    return torch.stack([g.reshape(()).float() for g in gs])
+
+
+class IMSATFn(torch.autograd.Function):
+    """imsat_with_entropy(p) -> (marginal entropy, mean conditional entropy) of the probability rows of p, [R, K] or
+    [b, K, H, W] in any memory format (contrastyou/losses/discreteMI.py:287-297); eps = 1e-8.  One read forward, one
+    read and one write backward (csrc/cy_imsat.hip).
+
+    `tangent`: for a p that is the output of a softmax.  The marginal's gradient c_k is the same in every row, and
+    where the marginals are balanced the c_k are nearly equal; a softmax backward (dp - sum_j p_j dp_j) removes that
+    common part again, by a subtraction that costs it the leading digits in f32.  With `tangent` the coefficients are
+    handed on as c_k - sum_j m_j c_j: the same gradient on the simplex (a row-constant apart, which the softmax
+    backward annihilates exactly), without the common part.  The result is then not dL/dp of an unconstrained p."""
+
+    @staticmethod
+    def forward(ctx, p: Tensor, tangent: bool = False):
+        rows = _imsat_rows(p)
+        out, coef, mean = ops.imsat_fwd(rows)
+        ctx.save_for_backward(rows, coef, mean)
+        ctx.like, ctx.tangent = (p.shape, p.dtype), tangent
+        return out[0], out[1]
+
+    @staticmethod
+    def backward(ctx, g_marg: Tensor, g_cond: Tensor):
+        rows, coef, mean = ctx.saved_tensors
+        if ctx.tangent:
+            coef = coef - (mean * coef).sum()
+        return _imsat_grad(ops.imsat_bwd(rows, coef, _grad_vector(g_marg, g_cond)), ctx.like), None
+
+
+class IMSATPairFn(torch.autograd.Function):
+    """two views of the same shape -> (marg1, cond1, marg2, cond2, mse): the entropies of IMSATFn for each and
+    nn.MSELoss()(x1, x2), each input read once (semi_seg/hooks/discretemi.py:148-167)"""
+
+    @staticmethod
+    def forward(ctx, x1: Tensor, x2: Tensor):
+        assert x1.shape == x2.shape, (x1.shape, x2.shape)
+        r1, r2 = _imsat_rows(x1), _imsat_rows(x2)
+        out, coef, _ = ops.imsat_pair_fwd(r1, r2)
+        ctx.save_for_backward(r1, r2, coef)
+        ctx.like = ((x1.shape, x1.dtype), (x2.shape, x2.dtype))
+        return tuple(out.unbind(0))
+
+    @staticmethod
+    def backward(ctx, *gs: Tensor):
+        r1, r2, coef = ctx.saved_tensors
+        d1, d2 = ops.imsat_pair_bwd(r1, r2, coef, _grad_vector(*gs))
+        return (_imsat_grad(d1, ctx.like[0]) if ctx.needs_input_grad[0] else None,
+                _imsat_grad(d2, ctx.like[1]) if ctx.needs_input_grad[1] else None)
+
+
+class SoftmaxIMSATFn(torch.autograd.Function):
+    """imsat_with_entropy(logits.softmax(1)) of an [N, K, H, W] logit map, K <= 16, without the probabilities in
+    memory (semi_seg/hooks/midl.py:83-90); `softmax_imsat` is the entry for any K"""
+
+    @staticmethod
+    def forward(ctx, logits: Tensor):
+        ops.require_gpu(logits)
+        z = ops.to_nhwc(logits.float())
+        out, coef, _ = ops.softmax_imsat_fwd(z)
+        ctx.save_for_backward(z, coef)
+        ctx.dtype = logits.dtype
+        return out[0], out[1]
+
+    @staticmethod
+    def backward(ctx, g_marg: Tensor, g_cond: Tensor):
+        z, coef = ctx.saved_tensors
+        return ops.softmax_imsat_bwd(z, coef, _grad_vector(g_marg, g_cond)).to(ctx.dtype)
+
+
+def softmax_imsat(logits: Tensor):
+    """(marg, cond) of softmax(logits, 1): the fused kernels up to 16 classes; past them the row-softmax kernel
+    followed by the probability-row kernels (the way KL_div composes past 16)"""
+    n, k, h, w = logits.shape
+    if k <= ops.IMSAT_LOGITS_KMAX:
+        return SoftmaxIMSATFn.apply(logits)
+    ops.require_gpu(logits)
+    flat = ops.to_nhwc(logits.float()).permute(0, 2, 3, 1).reshape(n * h * w, k)
+    return IMSATFn.apply(GroupSoftmaxFn.apply(flat, 1, k, 1.0)[0], True)
+
+
 class SgemmFn(torch.autograd.Function):
     """alpha * A @ B^T on the exact f32 MFMA kernel, differentiable in both operands"""
 

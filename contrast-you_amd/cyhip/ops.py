@@ -1684,6 +1684,101 @@ def uamt_mse_bwd(teacher: Tensor, student: Tensor, result: Tensor, gscale: Tenso
     return d
 
 
+# --------------------------------------------------------------------------- IMSAT (csrc/cy_imsat.hip)
+IMSAT_EPS = 1e-8  # the module-level entropy_criterion of semi_seg/hooks/midl.py:13
+IMSAT_FORMS = {"rows": _lib.CY_IMSAT_ROWS, "pair": _lib.CY_IMSAT_PAIR, "logits": _lib.CY_IMSAT_LOGITS}
+IMSAT_LOGITS_KMAX = 16  # classes of cy_softmax_imsat_*
+
+
+_IMSAT_PLAN = ("vec", "kt", "threads", "tile", "fwd_grid", "fwd_trips", "bwd_grid", "bwd_trips", "slots")
+
+
+def imsat_plan(form: str, R: int, K: int, align: int = 16) -> dict:
+    """the launch rule of the IMSAT kernels (host-side query, no GPU needed): the values of cy_imsat_plan by name, and
+    "ws_bytes", the forward's workspace.  `align`: the bytes every base pointer of the call is aligned to.  What the
+    launches refuse raises HipKernelError with their status."""
+    plan = (C.c_int32 * 9)()
+    _lib.call("cy_imsat_plan", IMSAT_FORMS[form], int(R), int(K), int(align), plan)
+    out = dict(zip(_IMSAT_PLAN, (int(v) for v in plan)))
+    query = {"rows": "cy_imsat_ws_bytes", "pair": "cy_imsat_pair_ws_bytes", "logits": "cy_softmax_imsat_ws_bytes"}
+    out["ws_bytes"] = int(getattr(_lib.load(), query[form])(int(R), int(K)))
+    return out
+
+
+def _imsat_outputs(nin: int, K: int, device, out: Optional[Tensor], coef: Optional[Tensor], mean: Optional[Tensor]):
+    out = _f32(5 if nin == 2 else 2, device) if out is None else out
+    coef = _f32(nin * K, device) if coef is None else coef
+    mean = _f32(nin * K, device) if mean is None else mean
+    return out, coef, mean
+
+
+def imsat_fwd(p: Tensor, out: Optional[Tensor] = None, coef: Optional[Tensor] = None, mean: Optional[Tensor] = None):
+    """p: f32 [R, K] contiguous probability rows (any 4-byte aligned base) -> (out [2] = {marg, cond}, coef [K], mean
+    [K]); the three results may be given as contiguous f32 views to write into"""
+    require_gpu(p)
+    R, K = p.shape
+    out, coef, mean = _imsat_outputs(1, K, p.device, out, coef, mean)
+    nbytes = _lib.load().cy_imsat_ws_bytes(R, K)
+    ws = _ws(nbytes, p.device)
+    _lib.call("cy_imsat_fwd", p.data_ptr(), out.data_ptr(), coef.data_ptr(), mean.data_ptr(), R, K, IMSAT_EPS,
+              ws.data_ptr(), nbytes, _stream())
+    return out, coef, mean
+
+
+def imsat_bwd(p: Tensor, coef: Tensor, g: Tensor, dp: Optional[Tensor] = None) -> Tensor:
+    """g: device f32 [2], the upstream gradients of (marg, cond) -> dp [R, K]"""
+    R, K = p.shape
+    dp = _f32(R * K, p.device).view(R, K) if dp is None else dp
+    _lib.call("cy_imsat_bwd", p.data_ptr(), coef.data_ptr(), g.data_ptr(), dp.data_ptr(), R, K, IMSAT_EPS, _stream())
+    return dp
+
+
+def imsat_pair_fwd(x1: Tensor, x2: Tensor, out: Optional[Tensor] = None, coef: Optional[Tensor] = None,
+                   mean: Optional[Tensor] = None):
+    """x1, x2: f32 [R, K] contiguous -> (out [5] = {marg1, cond1, marg2, cond2, mse}, coef [2, K], mean [2, K])"""
+    require_gpu(x1, x2)
+    R, K = x1.shape
+    assert x2.shape == x1.shape, (x1.shape, x2.shape)
+    out, coef, mean = _imsat_outputs(2, K, x1.device, out, coef, mean)
+    nbytes = _lib.load().cy_imsat_pair_ws_bytes(R, K)
+    ws = _ws(nbytes, x1.device)
+    _lib.call("cy_imsat_pair_fwd", x1.data_ptr(), x2.data_ptr(), out.data_ptr(), coef.data_ptr(), mean.data_ptr(), R, K,
+              IMSAT_EPS, ws.data_ptr(), nbytes, _stream())
+    return out, coef.view(2, K), mean.view(2, K)
+
+
+def imsat_pair_bwd(x1: Tensor, x2: Tensor, coef: Tensor, g: Tensor, d1: Optional[Tensor] = None,
+                   d2: Optional[Tensor] = None):
+    """g: device f32 [5], the upstream gradients in the order of `out` -> (dx1, dx2)"""
+    R, K = x1.shape
+    d1 = _f32(R * K, x1.device).view(R, K) if d1 is None else d1
+    d2 = _f32(R * K, x1.device).view(R, K) if d2 is None else d2
+    _lib.call("cy_imsat_pair_bwd", x1.data_ptr(), x2.data_ptr(), coef.data_ptr(), g.data_ptr(), d1.data_ptr(),
+              d2.data_ptr(), R, K, IMSAT_EPS, _stream())
+    return d1, d2
+
+
+def softmax_imsat_fwd(logits: Tensor, out: Optional[Tensor] = None, coef: Optional[Tensor] = None,
+                      mean: Optional[Tensor] = None):
+    """logits: f32 [N, K, H, W] with NHWC memory, K <= 16 -> as imsat_fwd, of softmax(logits, 1)"""
+    require_gpu(logits)
+    N, K, H, W = logits.shape
+    out, coef, mean = _imsat_outputs(1, K, logits.device, out, coef, mean)
+    nbytes = _lib.load().cy_softmax_imsat_ws_bytes(N * H * W, K)
+    ws = _ws(nbytes, logits.device)
+    _lib.call("cy_softmax_imsat_fwd", logits.data_ptr(), out.data_ptr(), coef.data_ptr(), mean.data_ptr(), N * H * W, K,
+              IMSAT_EPS, ws.data_ptr(), nbytes, _stream())
+    return out, coef, mean
+
+
+def softmax_imsat_bwd(logits: Tensor, coef: Tensor, g: Tensor) -> Tensor:
+    N, K, H, W = logits.shape
+    d = empty_nhwc(N, K, H, W, torch.float32, logits.device)
+    _lib.call("cy_softmax_imsat_bwd", logits.data_ptr(), coef.data_ptr(), g.data_ptr(), d.data_ptr(), N * H * W, K,
+              IMSAT_EPS, _stream())
+    return d
+
+
 def dice_counts(logits: Tensor, target: Tensor) -> Tensor:
     """int64 [N,K,2] = per-sample per-class (intersection, union) of argmax(logits) vs target."""
     N, K, H, W = logits.shape

@@ -10,6 +10,11 @@ maximise, per sub-head, the mutual information between the two cluster assignmen
 
 The loss is the mean over sub-heads times `weight`.  Heads and losses run on the HIP kernels of
 csrc/cy_mi.hip (stacked sub-head projection, grouped softmax, k x k joint, loss on the joint).
+
+`DiscreteIMSATTrainHook` (discretemi.py:119-176) is the same tap, warp and head with another criterion: per sub-head
+`IMSATLoss(lamda=1)` of the two views' pixel rows plus `cons_weight` times their `nn.MSELoss()`, both from one pass
+of the pair kernels of csrc/cy_imsat.hip.  The reference's `flatten_predict` asserts 4-D maps, so with an encoder
+feature (pooled vectors) it dies on the first call; here such a `feature_name` is refused at construction.
 """
 from __future__ import annotations
 
@@ -21,9 +26,10 @@ from torch import nn
 from contrastyou.arch import UNet
 from contrastyou.arch.utils import SingleFeatureExtractor
 from contrastyou.hooks.base import EpocherHook, TrainerHook
-from contrastyou.losses.discreteMI import IIDLoss, IIDSegmentationLoss
+from contrastyou.losses.discreteMI import IIDLoss, IIDSegmentationLoss, IMSATLoss
 from contrastyou.meters import AverageValueMeter
 from contrastyou.projectors.heads import ClusterHead, DenseClusterHead
+from cyhip.functions import IMSATPairFn
 
 decoder_names = UNet.decoder_names
 encoder_names = UNet.encoder_names
@@ -99,3 +105,54 @@ class DiscreteMITrainHook(TrainerHook):
     def __call__(self):
         return _DiscreteMIEpochHook(name=self._hook_name, weight=self._weight, extractor=self._extractor,
                                     projector=self._projector, criterion=self._criterion)
+
+
+class DiscreteIMSATTrainHook(DiscreteMITrainHook):
+
+    def __init__(self, *, name, model: nn.Module, feature_name: str, weight: float = 1.0, num_clusters=20,
+                 num_subheads=5, cons_weight: float) -> None:
+        if feature_name in encoder_names:
+            raise ValueError("DiscreteIMSATTrainHook needs a decoder feature: its loss flattens [n,k,H,W] maps, and "
+                             f"the head of the encoder feature {feature_name!r} gives [n,k] vectors")
+        super().__init__(name=name, model=model, feature_name=feature_name, weight=weight, num_clusters=num_clusters,
+                         num_subheads=num_subheads)
+        self._criterion = IMSATLoss(lamda=1.0)
+        self._consistency_criterion = nn.MSELoss()
+        self._consistency_weight = float(cons_weight)
+
+    def __call__(self):
+        return _DiscreteIMSATEpochHook(name=self._hook_name, weight=self._weight, extractor=self._extractor,
+                                       projector=self._projector, criterion=self._criterion,
+                                       cons_criterion=self._consistency_criterion,
+                                       cons_weight=self._consistency_weight)
+
+
+class _DiscreteIMSATEpochHook(_DiscreteMIEpochHook):
+    """`criterion` (an IMSATLoss: its lamda is read) and `cons_criterion` (nn.MSELoss) name what is computed; both come
+    out of IMSATPairFn, which reads each view once"""
+
+    def __init__(self, *, name: str, weight: float, extractor, projector, criterion, cons_criterion,
+                 cons_weight) -> None:
+        super().__init__(name=name, weight=weight, extractor=extractor, projector=projector, criterion=criterion)
+        self._cons_criterion = cons_criterion
+        self._cons_weight = cons_weight
+
+    def configure_meters_given_epocher(self, meters):
+        super().configure_meters_given_epocher(meters)
+        meters.register_meter("cons", AverageValueMeter())
+
+    def _call_implementation(self, *, unlabeled_image, unlabeled_image_tf, affine_transformer, **kwargs):
+        n_unl = len(unlabeled_image)
+        plain, transformed = torch.chunk(self._extractor.tail(2 * n_unl), 2, dim=0)
+        assert plain.shape == transformed.shape
+        both_views = torch.cat([affine_transformer(plain), transformed], dim=0)
+        lamda = self._criterion.lamda
+        losses, cons = [], []
+        for prob in self._projector(both_views):
+            marg1, cond1, marg2, cond2, mse = IMSATPairFn.apply(*torch.chunk(prob, 2, dim=0))
+            losses.append(0.5 * ((cond1 - marg1 * lamda) + (cond2 - marg2 * lamda)))
+            cons.append(mse)
+        loss, cons_loss = sum(losses) / len(losses), sum(cons) / len(cons)
+        self.meters["mi"].add(loss.detach())
+        self.meters["cons"].add(cons_loss.detach())
+        return loss * self._weight + cons_loss * self._cons_weight

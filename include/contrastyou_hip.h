@@ -1233,6 +1233,73 @@ int cy_pixel_mlp_bwd(const void* x, const int32_t* idx, const float* w1, const f
                      float* db2, int accumulate, long M, int C, int ldx, int hid, int out, float slope, int normalize,
                      int dtype, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------
+ * IMSAT: marginal and conditional entropy of probability rows (csrc/cy_imsat.hip; entries added to ABI v18 -- no
+ * existing signature changed, so cy_abi_version() stays 18).  For p [R][K] f32, every row a probability simplex, and
+ * eps the module-level entropy_criterion's 1e-8 (semi_seg/hooks/midl.py:13; not IMSATLoss.eps, which the reference
+ * never reads):
+ *   cond = (1/R) sum_r -sum_k p_rk log(p_rk + eps)      m_k = (1/R) sum_r p_rk      marg = -sum_k m_k log(m_k + eps)
+ *   dcond/dp_rk = -(log(p_rk + eps) + p_rk/(p_rk + eps)) / R        dmarg/dp_rk = c_k = -(log(m_k + eps) + m_k/(m_k + eps)) / R
+ * p_rk = 0 adds exactly 0 to cond and has the gradient entry -log(eps) / R.  Rows may come in any order (a 4-D
+ * [b,K,H,W] map is its b*H*W rows).  The forward is two launches: every block writes one f64 partial of cond and K f64
+ * column sums into ws, then one block adds the partials of all blocks in an order the grid alone decides (computing
+ * m_k, c_k and marg in f64) and writes
+ *   out [2] = {marg, cond},  coef [K] = c_k,  mean [K] = m_k.
+ * The backward is one launch: dp_rk = g[1] * dcond/dp_rk + g[0] * c_k, with g the two upstream gradients in device
+ * memory.  No atomics: two runs give the same bits.  Every entry checks its arguments before any launch: a NULL
+ * pointer or R < 1 -> CY_ERR_ARG; K outside 2..64 (2..16 from logits) -> CY_ERR_SHAPE; a short workspace ->
+ * CY_ERR_WORKSPACE.  The *_ws_bytes queries return 0 where the sizes are refused.
+ * ------------------------------------------------------------------------ */
+#define CY_IMSAT_ROWS 0   /* cy_imsat_* */
+#define CY_IMSAT_PAIR 1   /* cy_imsat_pair_* */
+#define CY_IMSAT_LOGITS 2 /* cy_softmax_imsat_* */
+/* The launch rule of the three groups (host-side only, launches nothing; the launches and the workspace queries take
+ * every decision from it), in the style of cy_pixel_mlp_plan.  `align`: the bytes every tensor base pointer of the call
+ * is aligned to (the launches work it out from their pointers; 16 and more count as 16).
+ * Rows and pair: the buffer is swept flat, thread t of a block reading `vec` floats at vec * t of each chunk, with
+ * `threads` = the largest T <= 256 with (vec * T) % K == 0 working threads, so that a thread keeps its columns.
+ * vec = 4 where align is a multiple of 16, else 1 -- the only two kernel forms.  Logits: one thread per pixel; kt = K
+ * for the compiled K = 2, 4, 8 where the rows are aligned to their 8 / 16 bytes, else 0 (run-time K, one float at a
+ * time).  K == 4 rows are read 16 bytes at a time in both forms: a misaligned base is CY_ERR_ARG.
+ *   plan[0] vec: floats per memory access (rows / pair 4 or 1; logits 2 (kt 2), 4 (kt 4, 8) or 1)
+ *   plan[1] kt: logits: the compiled K (2, 4, 8) or 0; rows / pair: 0
+ *   plan[2] threads: working threads of the 256 of a block
+ *   plan[3] tile: rows / pair: floats per block and trip = threads * vec * 4; logits: pixels = 256
+ *   plan[4] fwd_grid = min(1024, tiles) blocks = rows of partials, [5] fwd_trips of the busiest block
+ *   plan[6] bwd_grid = min(2048, tiles), [7] bwd_trips
+ *   plan[8] slots: f64 partials per block = 1 + K, pair 3 + 2 K
+ * Returns what the launches answer: CY_ERR_ARG for a NULL `plan`, an unknown form, R < 1, align < 1 or misaligned
+ * K == 4 logits; CY_ERR_SHAPE for K out of range; otherwise CY_OK. */
+int cy_imsat_plan(int form, long R, int K, int align, int32_t* plan /* [9] */);
+/* imsat_with_entropy(p) / imsat_loss(p, lamda) = cond - lamda * marg / IMSATDynamicWeight's -w * marg + cond
+ * (contrastyou/losses/discreteMI.py:20-87,275-297; the combination is left to the caller, on the two device scalars).
+ * ws_bytes >= 8 * (1 + K) * min(1024, ceil(R K / (4 K floor(256 / K)))) = cy_imsat_ws_bytes(R, K): the grid of
+ * the 4-byte form, which is never the smaller one. */
+size_t cy_imsat_ws_bytes(long R, int K);
+int cy_imsat_fwd(const float* p, float* out, float* coef, float* mean, long R, int K, float eps, void* ws,
+                 size_t ws_bytes, void* stream);
+int cy_imsat_bwd(const float* p, const float* coef, const float* g, float* dp, long R, int K, float eps, void* stream);
+/* Two views x1, x2 [R][K] and their consistency, what _DiscreteIMSATEpochHook evaluates per sub-head
+ * (semi_seg/hooks/discretemi.py:148-167: IMSATLoss(x1, x2) and nn.MSELoss()(x1, x2)), each input read once:
+ *   out [5] = {marg1, cond1, marg2, cond2, mse},  mse = sum (x1 - x2)^2 / (R K);  coef, mean [2][K].
+ * Backward, one launch, both gradients from the five upstream scalars g [5] (same order as out).  The inputs are
+ * usually the halves of one [2R][K] tensor, so a base is only known to be 4-byte aligned: see cy_imsat_plan.
+ * ws_bytes >= 8 * (3 + 2 K) * (the blocks of cy_imsat_ws_bytes). */
+size_t cy_imsat_pair_ws_bytes(long R, int K);
+int cy_imsat_pair_fwd(const float* x1, const float* x2, float* out, float* coef, float* mean, long R, int K, float eps,
+                      void* ws, size_t ws_bytes, void* stream);
+int cy_imsat_pair_bwd(const float* x1, const float* x2, const float* coef, const float* g, float* dx1, float* dx2,
+                      long R, int K, float eps, void* stream);
+/* The same of softmax(logits, 1), logits [npix][K] f32 (NHWC), 2 <= K <= 16 (_IMSATEpochHook,
+ * semi_seg/hooks/midl.py:83-90); outputs as cy_imsat_fwd.  The backward recomputes the softmax:
+ *   a_k = g[1] * dcond/dp_k + g[0] * c_k,  dz_k = p_k (a_k - sum_j p_j a_j).
+ * ws_bytes >= 8 * (1 + K) * min(1024, ceil(npix / 256)). */
+size_t cy_softmax_imsat_ws_bytes(long npix, int K);
+int cy_softmax_imsat_fwd(const float* logits, float* out, float* coef, float* mean, long npix, int K, float eps,
+                         void* ws, size_t ws_bytes, void* stream);
+int cy_softmax_imsat_bwd(const float* logits, const float* coef, const float* g, float* dlogits, long npix, int K,
+                         float eps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
