@@ -743,6 +743,52 @@ class SoftmaxMSEFn(torch.autograd.Function):
         return da, db
 
 
+class MixupKLFn(torch.autograd.Function):
+    """KL_div(eps=eps)(logits.softmax(1), w_self * onehot(target) + w_other * onehot(target)[index]), mean reduction
+    (semi_seg/hooks/mixup.py:49-58 with mixup_data of hooks/utils.py:284-297).  target: integer labels [N,H,W] or
+    [N,1,H,W]; index: a CPU integer tensor [N] (or its ops.mix_index copy).  Neither one-hot tensor is formed."""
+
+    @staticmethod
+    def forward(ctx, logits: Tensor, target: Tensor, index: Tensor, w_self: float, w_other: float, eps: float = 1e-16):
+        ops.require_gpu(logits, target)
+        logits = ops.to_nhwc(logits.float())
+        N, _, H, W = logits.shape
+        target = target.reshape(N, H, W).to(torch.int64).contiguous()
+        index = ops.mix_index(index, N, logits.device)
+        ctx.save_for_backward(logits, target, index)
+        ctx.args = (float(w_self), float(w_other), float(eps))
+        return ops.softmax_mixkl_fwd(logits, target, index, *ctx.args)
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        logits, target, index = ctx.saved_tensors
+        w_self, w_other, eps = ctx.args
+        gs = g.reshape(1).float().contiguous()
+        return ops.softmax_mixkl_bwd(logits, target, index, w_self, w_other, gs, eps), None, None, None, None, None
+
+
+class MixSoftmaxMSEFn(torch.autograd.Function):
+    """MSELoss(reduction="none")(student.softmax(1), w_self * teacher.softmax(1) + w_other * teacher.softmax(1)[index])
+    .mean() (semi_seg/hooks/mt.py:301-319).  The gradient goes to the student alone; the mixed target lives in
+    registers."""
+
+    @staticmethod
+    def forward(ctx, student_logits: Tensor, teacher_logits: Tensor, index: Tensor, w_self: float, w_other: float):
+        ops.require_gpu(student_logits, teacher_logits)
+        student = ops.to_nhwc(student_logits.float())
+        teacher = ops.to_nhwc(teacher_logits.detach().float())
+        index = ops.mix_index(index, student.shape[0], student.device)
+        ctx.save_for_backward(student, teacher, index)
+        ctx.args = (float(w_self), float(w_other))
+        return ops.softmax_mixmse_fwd(student, teacher, index, *ctx.args)
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        student, teacher, index = ctx.saved_tensors
+        gs = g.reshape(1).float().contiguous()
+        return ops.softmax_mixmse_bwd(student, teacher, index, *ctx.args, gs), None, None, None, None
+
+
 class SoftmaxEntropyFn(torch.autograd.Function):
     """Entropy(eps=eps)(logits.softmax(1)), mean reduction (semi_seg/hooks/entmin.py:29-30,
     contrastyou/losses/kl.py:48-56)."""

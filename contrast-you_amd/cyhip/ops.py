@@ -1779,6 +1779,108 @@ def softmax_imsat_bwd(logits: Tensor, coef: Tensor, g: Tensor) -> Tensor:
     return d
 
 
+# --------------------------------------------------------------------------- MixUp and ICT (csrc/cy_mixup.hip)
+MIX_FORMS = {"images": _lib.CY_MIX_IMAGES, "mixkl": _lib.CY_MIX_KL, "mixmse": _lib.CY_MIX_MSE}
+_MIX_PLAN = ("vec", "kt", "fwd_grid", "fwd_trips", "bwd_grid", "bwd_trips", "rows")
+
+
+def mix_plan(form: str, N: int, per_image: int, K: int = 0, align: int = 16) -> dict:
+    """the launch rule of the mixing kernels (host-side query, no GPU needed): the values of cy_mix_plan by name.
+    `per_image`: the elements of an image (form "images") or its pixels (the losses).  What the launches refuse raises
+    HipKernelError with their status."""
+    plan = (C.c_int32 * 7)()
+    _lib.call("cy_mix_plan", MIX_FORMS[form], int(N), int(per_image), int(K), int(align), plan)
+    return dict(zip(_MIX_PLAN, (int(v) for v in plan)))
+
+
+def mix_weights(lam: float) -> Tuple[float, float]:
+    """(w_self, w_other) = lam and 1 - lam, formed in f64 as `lam * x + (1 - lam) * x[index]` forms them; ctypes
+    rounds each to f32 at the call, as torch does when it multiplies an f32 tensor by a Python scalar"""
+    lam = float(lam)
+    return lam, 1.0 - lam
+
+
+def mix_index(index: Tensor, N: int, device) -> Tensor:
+    """the int32 [N] device copy of a mixing index the kernels read.  `index` is a CPU integer tensor (what
+    torch.randperm gives); any values in [0, N) are allowed, one outside raises ValueError before anything is uploaded
+    or launched.  A CUDA int32 tensor is taken as the result of an earlier call and returned as it is."""
+    if index.is_cuda and index.dtype == torch.int32 and index.shape == (N,):
+        return index
+    if index.is_cuda or index.is_floating_point() or index.dtype == torch.bool:
+        raise TypeError(f"mixing index: expected a CPU integer tensor, got {index.dtype} on {index.device}")
+    if index.shape != (N,):
+        raise ValueError(f"mixing index: expected shape ({N},), got {tuple(index.shape)}")
+    if N and (int(index.min()) < 0 or int(index.max()) >= N):
+        raise ValueError(f"mixing index: values must lie in [0, {N}), got {index.tolist()}")
+    return pinned.upload(index.to(torch.int32), device)
+
+
+def mix_images(x: Tensor, index: Tensor, w_self: float, w_other: float) -> Tensor:
+    """w_self * x + w_other * x[index] over the leading dimension of an f32 tensor, in x's memory format: bit-equal to
+    torch's CPU f32 evaluation of that expression.  No gradient is recorded (images and targets carry none)."""
+    require_gpu(x)
+    assert x.dtype == torch.float32 and x.dim() >= 1, (x.dtype, tuple(x.shape))
+    N = x.shape[0]
+    idx = mix_index(index, N, x.device)
+    x = x.detach()
+    if not (x.is_contiguous() or (x.dim() == 4 and is_nhwc(x))):
+        x = x.contiguous()
+    out = torch.empty_like(x)
+    if x.numel():
+        _lib.call("cy_mix_images", x.data_ptr(), idx.data_ptr(), float(w_self), float(w_other), out.data_ptr(), N,
+                  x.numel() // N, _stream())
+    return out
+
+
+def softmax_mixkl_fwd(logits: Tensor, target: Tensor, index: Tensor, w_self: float, w_other: float,
+                      eps: float) -> Tensor:
+    """logits f32 [N,K,H,W] with NHWC memory, target int64 [N,H,W] contiguous -> device scalar: KL_div(eps) of
+    softmax(logits) against w_self * onehot(target) + w_other * onehot(target)[index]"""
+    N, K, H, W = logits.shape
+    idx = mix_index(index, N, logits.device)
+    nbytes = _lib.load().cy_softmax_mixkl_ws_bytes(N, H * W)
+    ws = _ws(nbytes, logits.device)
+    loss = _f32(1, logits.device)
+    _lib.call("cy_softmax_mixkl_fwd", logits.data_ptr(), target.data_ptr(), idx.data_ptr(), float(w_self),
+              float(w_other), loss.data_ptr(), N, H * W, K, float(eps), ws.data_ptr(), nbytes, _stream())
+    return loss.view(())
+
+
+def softmax_mixkl_bwd(logits: Tensor, target: Tensor, index: Tensor, w_self: float, w_other: float, gscale: Tensor,
+                      eps: float) -> Tensor:
+    N, K, H, W = logits.shape
+    idx = mix_index(index, N, logits.device)
+    d = empty_nhwc(N, K, H, W, torch.float32, logits.device)
+    _lib.call("cy_softmax_mixkl_bwd", logits.data_ptr(), target.data_ptr(), idx.data_ptr(), float(w_self),
+              float(w_other), gscale.data_ptr(), d.data_ptr(), N, H * W, K, float(eps), _stream())
+    return d
+
+
+def softmax_mixmse_fwd(student: Tensor, teacher: Tensor, index: Tensor, w_self: float, w_other: float) -> Tensor:
+    """student, teacher: f32 logits [N,K,H,W] with NHWC memory -> device scalar: the mean of (softmax(student) -
+    (w_self * softmax(teacher) + w_other * softmax(teacher)[index]))^2"""
+    N, K, H, W = student.shape
+    assert teacher.shape == student.shape, (tuple(teacher.shape), tuple(student.shape))
+    idx = mix_index(index, N, student.device)
+    nbytes = _lib.load().cy_softmax_mixmse_ws_bytes(N, H * W)
+    ws = _ws(nbytes, student.device)
+    loss = _f32(1, student.device)
+    _lib.call("cy_softmax_mixmse_fwd", student.data_ptr(), teacher.data_ptr(), idx.data_ptr(), float(w_self),
+              float(w_other), loss.data_ptr(), N, H * W, K, ws.data_ptr(), nbytes, _stream())
+    return loss.view(())
+
+
+def softmax_mixmse_bwd(student: Tensor, teacher: Tensor, index: Tensor, w_self: float, w_other: float,
+                       gscale: Tensor) -> Tensor:
+    """the student's gradient (the teacher carries none)"""
+    N, K, H, W = student.shape
+    idx = mix_index(index, N, student.device)
+    d = empty_nhwc(N, K, H, W, torch.float32, student.device)
+    _lib.call("cy_softmax_mixmse_bwd", student.data_ptr(), teacher.data_ptr(), idx.data_ptr(), float(w_self),
+              float(w_other), gscale.data_ptr(), d.data_ptr(), N, H * W, K, _stream())
+    return d
+
+
 def dice_counts(logits: Tensor, target: Tensor) -> Tensor:
     """int64 [N,K,2] = per-sample per-class (intersection, union) of argmax(logits) vs target."""
     N, K, H, W = logits.shape

@@ -1,4 +1,5 @@
-"""`AdversarialEpocher` (semi_seg/epochers/comparable.py:93-200 of the reference): the adversarial-training baseline.
+"""`AdversarialEpocher` (semi_seg/epochers/comparable.py:93-200 of the reference): the adversarial-training baseline;
+`MixupEpocher` (comparable.py:14-90): the MixUp baseline, documented at the class.
 
 One step, in the reference's order:
   G  zero the segmentation optimizer; forward the labeled batch, supervised loss; with reg_weight > 0 forward the
@@ -20,15 +21,18 @@ The two U-Net passes run eagerly on the current stream: no graph replay, no seco
 """
 from __future__ import annotations
 
+import random
+from functools import partial
+
 import torch
 from torch import nn
 
 from contrastyou.meters import AverageValueMeter, MeterInterface
 from contrastyou.utils.utils import get_lrs_from_optimizer
 from cyhip.functions import SigmoidBCEFn
-from semi_seg.epochers.epocher import SemiSupervisedEpocher, _sup_loss
+from semi_seg.epochers.epocher import SemiSupervisedEpocher, _scalar, _sup_loss
 
-__all__ = ["AdversarialEpocher"]
+__all__ = ["AdversarialEpocher", "MixupEpocher"]
 
 TRUE_LABEL, FAKE_LABEL = 1.0, 0.0
 
@@ -124,3 +128,56 @@ class AdversarialEpocher(SemiSupervisedEpocher):
         if self.on_master:
             with self.meters.focus_on("adv_reg"):
                 self.meters["dis_loss"].add(disc_loss.detach())
+
+
+class MixupEpocher(SemiSupervisedEpocher):
+    """`MixupEpocher` (semi_seg/epochers/comparable.py:14-90 of the reference): no unlabeled image takes part.  One
+    forward over cat([labeled_image, labeled_image_tf]), the supervised loss on the first half, and the hooks'
+    regularisers on the labeled batch, its transformed view and the transformed target (`MixUpTrainHook`).  The
+    unlabeled loader is still drawn from, as in the reference, so that the data order of a run matches the baselines'.
+    The pass runs eagerly on the current stream: no graph replay, no second stream.  Meters take device scalars."""
+
+    def _forward_pass(self, *, labeled_image, labeled_image_tf, **kwargs):
+        predict_logits = self._model(torch.cat([labeled_image, labeled_image_tf], dim=0))
+        label_logits, labeled_tf_logits = torch.chunk(predict_logits, 2, dim=0)
+        return label_logits, labeled_tf_logits
+
+    def _run_implement(self):
+        if len(self._unlabeled_loader) == 0:  # fully supervised: the labeled stream doubles as unlabeled
+            self._unlabeled_loader = self._labeled_loader
+        batches = zip(self.indicator, self._labeled_loader, self._unlabeled_loader)
+        for self.cur_batch_num, labeled_data, unlabeled_data in batches:
+            seed = random.randint(0, int(1e7))
+            (labeled_image, _), labeled_target, labeled_filename, _, label_group = \
+                self._unzip_data(labeled_data, self._device)
+            (unlabeled_image, _), _, unlabeled_filename, unl_partition, unl_group = \
+                self._unzip_data(unlabeled_data, self._device)
+            labeled_image_tf = self.transform_with_seed(labeled_image, seed=seed, mode="image")
+            labeled_target_tf = self.transform_with_seed(labeled_target.float(), seed=seed, mode="feature")
+            self.batch_update(
+                cur_batch_num=self.cur_batch_num, labeled_image=labeled_image, labeled_image_tf=labeled_image_tf,
+                labeled_target=labeled_target, labeled_target_tf=labeled_target_tf, labeled_filename=labeled_filename,
+                label_group=label_group, unlabeled_image=unlabeled_image, seed=seed, unl_group=unl_group,
+                unl_partition=unl_partition, unlabeled_filename=unlabeled_filename, retain_graph=self.retain_graph)
+            self._report(self.cur_batch_num, self.cur_batch_num == self.num_batches - 1)
+
+    def _batch_update(self, *, cur_batch_num: int, labeled_image, labeled_target, labeled_image_tf, labeled_target_tf,
+                      labeled_filename, label_group, seed, unl_group, unl_partition, unlabeled_filename,
+                      retain_graph=False, **kwargs):
+        self.optimizer_zero(self._optimizer, cur_iter=cur_batch_num)
+        with self.autocast:
+            label_logits, labeled_tf_logits = self.forward_pass(labeled_image=labeled_image,
+                                                                labeled_image_tf=labeled_image_tf)
+            sup_loss = _sup_loss(self._sup_criterion, label_logits, labeled_target, self.num_classes)
+            reg_loss = self.regularization(
+                seed=seed, labeled_image=labeled_image, labeled_target=labeled_target,
+                labeled_image_tf=labeled_image_tf, labeled_target_tf=labeled_target_tf,
+                labeled_filename=labeled_filename,
+                affine_transformer=partial(self.transform_with_seed, seed=seed, mode="feature"))
+        self.scale_loss(sup_loss + reg_loss).backward(retain_graph=retain_graph)
+        self.optimizer_step(self._optimizer, cur_iter=cur_batch_num)
+        if self.on_master:
+            with torch.no_grad():
+                self.meters["sup_loss"].add(sup_loss.detach())
+                self.meters["sup_dice"].add_logits(label_logits, labeled_target, group_name=label_group)
+                self.meters["reg_loss"].add(_scalar(reg_loss))

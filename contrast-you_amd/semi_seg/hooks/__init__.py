@@ -12,5 +12,7 @@ from .entmin import EntropyMinTrainerHook  # noqa: F401
 from .infonce import (INFONCEHook, PScheduler, SelfPacedINFONCEHook, SuperPixelInfoNCEHook,  # noqa: F401
                       region_extractor)
 from .midl import IIDSegmentationTrainerHook, IMSATTrainHook  # noqa: F401
-from .mt import EMAUpdater, MeanTeacherTrainerHook, UAMeanTeacherTrainerHook  # noqa: F401
+from .mixup import MixUpTrainHook  # noqa: F401
+from .mt import (EMAUpdater, ICTMeanTeacherTrainerHook, MeanTeacherTrainerHook,  # noqa: F401
+                 UAMeanTeacherTrainerHook)
 from .pseudolabel import PseudoLabelTrainerHook  # noqa: F401

@@ -9,7 +9,14 @@ Uncertainty-aware mean teacher, "UA-MT" (semi_seg/hooks/mt.py:209-276): the teac
 BN-tracking forward and N forwards of the image plus 0.05 * noise; the MSE against the student counts only where the
 entropy of that mean prediction lies below thr = (3/4 + 1/4 * cur_epoch / max_epoch) * ln C, and is divided by
 (mask.mean() + 1e-2).  Softmax, entropy, mask, [arg-max one-hot,] MSE and both means are one fused pass each way
-(`UAMTLossFn` = cy_uamt_mse_*): no full-size temporary and, unlike the reference's two `.item()`, no host sync."""
+(`UAMTLossFn` = cy_uamt_mse_*): no full-size temporary and, unlike the reference's two `.item()`, no host sync.
+
+Interpolation-consistency training, "ICT" (semi_seg/hooks/mt.py:279-319): the teacher predicts the unlabeled batch and
+its transformed view in two no-grad forwards (it is in train mode: each has its own batch statistics); under the step's
+seed one (lam, index) is drawn for the 2B batch with alpha = 0.2, the student runs on the mixed images
+(`ops.mix_images`), and weight * mean((softmax(student) - (lam * p + (1 - lam) * p[index]))^2), p the teacher's
+softmax, is added.  `MixSoftmaxMSEFn` (cy_softmax_mixmse_*) recomputes both teacher softmaxes and their blend in
+registers: neither probability tensor, nor the gathered copy, nor the mixed target is formed."""
 from __future__ import annotations
 
 import math
@@ -22,7 +29,8 @@ from contrastyou.hooks.base import EpocherHook, TrainerHook
 from contrastyou.meters import AverageValueMeter, MeterInterface
 from cyhip import ops
 from contrastyou.utils.utils import fix_all_seed_within_context
-from cyhip.functions import SoftmaxMSEFn, UAMTLossFn, bump_weights_epoch
+from cyhip.functions import MixSoftmaxMSEFn, SoftmaxMSEFn, UAMTLossFn, bump_weights_epoch
+from semi_seg.hooks.utils import mixup_draw
 
 
 class EMAUpdater:
@@ -165,3 +173,39 @@ class _UAMeanTeacherEpocherHook(_MeanTeacherEpocherHook):
     @property
     def max_epoch(self) -> int:
         return int(self.epocher.trainer._max_epoch)
+
+
+class ICTMeanTeacherTrainerHook(MeanTeacherTrainerHook):
+
+    def __init__(self, *, name: str, model: nn.Module, weight: float, alpha: float = 0.999, weight_decay: float = 1e-5,
+                 update_bn=False):
+        super().__init__(name=name, model=model, weight=weight, alpha=alpha, weight_decay=weight_decay,
+                         update_bn=update_bn, num_teachers=1, hard_clip=False)
+
+    def __call__(self):
+        return _ICTMeanTeacherEpocherHook(name=self._hook_name, weight=self._weight, model=self.trainer._model,
+                                          teacher_model=self._teacher_model, updater=self._updater)
+
+
+class _ICTMeanTeacherEpocherHook(_MeanTeacherEpocherHook):
+    MIX_ALPHA = 0.2  # mt.py:312
+
+    def __init__(self, *, name: str, weight: float, model, teacher_model, updater: EMAUpdater) -> None:
+        super().__init__(name=name, weight=weight, model=model, teacher_model=teacher_model, updater=updater,
+                         hard_clip=False)
+
+    def _call_implementation(self, *, unlabeled_tf_logits, unlabeled_image, unlabeled_image_tf, seed, **kwargs):
+        with torch.no_grad():
+            teacher_logits = torch.cat([self._teacher_model(unlabeled_image),
+                                        self._teacher_model(unlabeled_image_tf)], dim=0)
+            images = torch.cat([unlabeled_image, unlabeled_image_tf], dim=0)
+            n = images.shape[0]
+            with fix_all_seed_within_context(seed):
+                lam, index = mixup_draw(n, alpha=self.MIX_ALPHA)
+            w_self, w_other = ops.mix_weights(lam)
+            index = ops.mix_index(index, n, images.device)
+            mixed_image = ops.mix_images(images.float(), index, w_self, w_other)
+        loss = MixSoftmaxMSEFn.apply(self._model(mixed_image), teacher_logits, index, w_self, w_other)
+        if self.meters:
+            self.meters["loss"].add(loss.detach())
+        return self._weight * loss

@@ -1,9 +1,10 @@
-"""Trainer zoo (semi_seg/trainers/__init__.py:7-15).  `dmt` and `mixup` drive comparison-method
-epochers that are outside this build's hot-path scope and raise on use."""
+"""Trainer zoo (semi_seg/trainers/__init__.py:7-15).  `dmt` drives a comparison-method epocher that is
+outside this build's hot-path scope and raises on use.  The `mixup` entry still raises
+too (existing tests pin it); the trainer itself is built and is reached as the class `MixUpTrainer`."""
 from contrastyou.trainer.base import Trainer as _Trainer
 
 from .pretrain import PretrainDecoderTrainer, PretrainEncoderTrainer  # noqa: F401
-from .trainer import AdversarialTrainer, FineTuneTrainer, MTTrainer, SemiTrainer  # noqa: F401
+from .trainer import AdversarialTrainer, FineTuneTrainer, MixUpTrainer, MTTrainer, SemiTrainer  # noqa: F401
 
 
 def _out_of_scope(name):

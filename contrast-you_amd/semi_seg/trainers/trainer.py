@@ -1,5 +1,5 @@
-"""`SemiTrainer`, `FineTuneTrainer`, `MTTrainer`, `AdversarialTrainer` (semi_seg/trainers/trainer.py:27-167, 199-204,
-215-260): which epocher runs a training epoch and how evaluation is wired (teacher model for mean teacher).
+"""`SemiTrainer`, `FineTuneTrainer`, `MTTrainer`, `MixUpTrainer`, `AdversarialTrainer` (semi_seg/trainers/trainer.py:
+27-167, 199-260): which epocher runs a training epoch and how evaluation is wired (teacher model for mean teacher).
 """
 from __future__ import annotations
 
@@ -15,7 +15,7 @@ from contrastyou import optim
 from contrastyou.arch.discriminator import Discriminator
 from contrastyou.trainer.base import _NOT_OPTIMIZER_ARGS, Trainer
 from contrastyou.utils.utils import fix_all_seed_within_context
-from semi_seg.epochers.comparable import AdversarialEpocher
+from semi_seg.epochers.comparable import AdversarialEpocher, MixupEpocher
 from semi_seg.epochers.epocher import (EpocherBase, EvalEpocher, FineTuneEpocher, InferenceEpocher,
                                        SemiSupervisedEpocher)
 from semi_seg.hooks import MeanTeacherTrainerHook
@@ -96,6 +96,33 @@ class MTTrainer(SemiTrainer):
         mt_hook = [h for h in self._hooks if isinstance(h, MeanTeacherTrainerHook)]
         assert len(mt_hook) == 1, mt_hook
         return super().eval_epoch(model=mt_hook[0].teacher_model, loader=loader, **kwargs)
+
+
+class MixUpTrainer(SemiTrainer):
+    """MixUp baseline (trainer.py:207-212): `MixupEpocher` with hooks, `MixUpTrainHook` the one it is meant for.
+
+    Single process only: the hook runs a second forward of the model inside the regularisation, which the
+    data-parallel step does not wrap."""
+    activate_hooks = True
+
+    def __init__(self, *, model: nn.Module, labeled_loader, unlabeled_loader, val_loader, test_loader, criterion,
+                 save_dir: str, max_epoch: int = 100, num_batches: int = 100, device="cpu", disable_bn: bool,
+                 two_stage: bool, config: Dict[str, Any], enable_scale=True, accumulate_iter: int = 1,
+                 **kwargs) -> None:
+        dist = torch.distributed
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError(
+                "MixUpTrainer is single-process: the mixed pass of its hook is not part of the data-parallel step "
+                f"(world size {dist.get_world_size()})")
+        super().__init__(model=model, labeled_loader=labeled_loader, unlabeled_loader=unlabeled_loader,
+                         val_loader=val_loader, test_loader=test_loader, criterion=criterion, save_dir=save_dir,
+                         max_epoch=max_epoch, num_batches=num_batches, device=device, disable_bn=disable_bn,
+                         two_stage=two_stage, config=config, enable_scale=enable_scale,
+                         accumulate_iter=accumulate_iter, **kwargs)
+
+    @property
+    def train_epocher(self) -> Type[EpocherBase]:
+        return MixupEpocher
 
 
 class AdversarialTrainer(SemiTrainer):

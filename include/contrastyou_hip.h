@@ -1300,6 +1300,63 @@ int cy_softmax_imsat_fwd(const float* logits, float* out, float* coef, float* me
 int cy_softmax_imsat_bwd(const float* logits, const float* coef, const float* g, float* dlogits, long npix, int K,
                          float eps, void* stream);
 
+/* ------------------------------------------------------------------------
+ * MixUp and interpolation-consistency training (csrc/cy_mixup.hip; entries added to ABI v18 -- no existing signature
+ * changed, so cy_abi_version() stays 18).  Image n of a batch of N is mixed with image index[n]; `index` is int32 [N]
+ * in device memory and a gather: any values in [0, N), not only permutations (the caller checks the range; the kernels
+ * trust it).  w_self and w_other are lam and 1 - lam, formed in f64 on the host and rounded to f32 each, which is what
+ * `lam * x + (1 - lam) * x[index]` (semi_seg/hooks/utils.py:284-297) does; no kernel forms 1 - w.  Logits are
+ * [npix][K] f32 rows (NHWC), npix = N * HW, image n owning the pixels [n HW, (n + 1) HW); 2 <= K <= 16.  Every entry
+ * checks its arguments before any launch: a NULL pointer, N < 1, a size < 1 or a base that is not 4-byte aligned ->
+ * CY_ERR_ARG; K out of range -> CY_ERR_SHAPE; a short workspace -> CY_ERR_WORKSPACE.  The losses are one thread per
+ * pixel, grid-stride; the forward writes one f64 partial per block and one block sums them in block order, the
+ * backward is one launch.  No atomics: two runs give the same bits.  Upstream gradients are device memory.
+ * ------------------------------------------------------------------------ */
+#define CY_MIX_IMAGES 0 /* cy_mix_images */
+#define CY_MIX_KL 1     /* cy_softmax_mixkl_* */
+#define CY_MIX_MSE 2    /* cy_softmax_mixmse_* */
+/* The launch rule of the three groups (host-side only, launches nothing; the launches take every decision from it), in
+ * the style of cy_imsat_plan.  `per_image`: E of cy_mix_images, HW of the losses.  `align`: the bytes every tensor base
+ * pointer of the call is aligned to (the launches work it out from their pointers; 16 and more count as 16).
+ *   plan[0] vec: floats per memory access.  Images: 4 where per_image % 4 == 0 and align is a multiple of 16, else 1.
+ *           Losses: 2 (kt 2), 4 (kt 4, 8) or 1
+ *   plan[1] kt: losses: the compiled K (2, 4, 8) where the rows are aligned to their 8 / 16 bytes, else 0 (run-time K,
+ *           one float at a time; K == 4 rows are read 16 bytes at a time in both forms: a misaligned base is
+ *           CY_ERR_ARG).  Images: 0
+ *   plan[2] fwd_grid: losses min(1024, ceil(npix / 256)) blocks = the f64 partials; images rows * columns, with
+ *           columns = min(ceil(per_image / vec / 256), 2048 / rows) blocks striding over one image
+ *   plan[3] fwd_trips: loop trips of the busiest block
+ *   plan[4] bwd_grid = 2 * fwd_grid, plan[5] bwd_trips (images: 0, 0)
+ *   plan[6] rows: images: min(N, 1024) grid rows striding over the images; losses: 0
+ * Returns what the launches answer: CY_ERR_ARG for a NULL `plan`, an unknown form, N < 1, per_image < 1 or such an
+ * align; CY_ERR_SHAPE for K out of range (losses; images ignore K); otherwise CY_OK. */
+int cy_mix_plan(int form, int N, long per_image, int K, int align, int32_t* plan /* [7] */);
+/* out[n][e] = w_self * x[n][e] + w_other * x[index[n]][e], E contiguous f32 elements per image (any memory format, the
+ * same for x and out; out must not be x).  Two correctly rounded products and one correctly rounded sum, never an
+ * FMA: the bits of torch's CPU f32 evaluation of the reference expression. */
+int cy_mix_images(const float* x, const int32_t* index, float w_self, float w_other, float* out, int N, long E,
+                  void* stream);
+/* MixUp (semi_seg/hooks/mixup.py:49-58): KL_div(eps)(softmax(logits), t), t = w_self onehot(target) + w_other
+ * onehot(target)[index], without the one-hot tensors: per pixel a = target[pix], b = target[index[n] HW + hw],
+ *   l = -sum_{k in {a, b}} t_k log((p_k + eps) / (t_k + eps)),  t_a = w_self, t_b = w_other (a == b: the one term with
+ *   t_a = w_self + w_other, summed in f32);  loss[0] = sum l / npix.
+ * A weight of exactly 0 adds exactly 0; a label outside [0, K) selects no class (p = 0) and nothing is read out of
+ * range.  Backward: dz_j = (gscale[0] / npix) sum_{k in {a, b}} t_k p_k / (p_k + eps) (p_j - [k == j]).
+ * ws_bytes >= 8 * min(1024, ceil(npix / 256)). */
+size_t cy_softmax_mixkl_ws_bytes(int N, long HW);
+int cy_softmax_mixkl_fwd(const float* logits, const int64_t* target, const int32_t* index, float w_self, float w_other,
+                         float* loss, int N, long HW, int K, float eps, void* ws, size_t ws_bytes, void* stream);
+int cy_softmax_mixkl_bwd(const float* logits, const int64_t* target, const int32_t* index, float w_self, float w_other,
+                         const float* gscale, float* dlogits, int N, long HW, int K, float eps, void* stream);
+/* ICT (semi_seg/hooks/mt.py:301-319): MSE of softmax(student) against m = w_self softmax(teacher[pix]) + w_other
+ * softmax(teacher[index[n] HW + hw]), loss[0] = sum (softmax(s)_k - m_k)^2 / (npix K).  Backward, student only (the
+ * teacher carries no gradient): d = 2 gscale[0] (p - m) / (npix K), ds = p (d - <d, p>).  Workspace as above. */
+size_t cy_softmax_mixmse_ws_bytes(int N, long HW);
+int cy_softmax_mixmse_fwd(const float* student, const float* teacher, const int32_t* index, float w_self,
+                          float w_other, float* loss, int N, long HW, int K, void* ws, size_t ws_bytes, void* stream);
+int cy_softmax_mixmse_bwd(const float* student, const float* teacher, const int32_t* index, float w_self,
+                          float w_other, const float* gscale, float* dstudent, int N, long HW, int K, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
