@@ -789,6 +789,68 @@ class MixSoftmaxMSEFn(torch.autograd.Function):
         return ops.softmax_mixmse_bwd(student, teacher, index, *ctx.args, gs), None, None, None, None
 
 
+class DAELossFn(torch.autograd.Function):
+    """F.mse_loss(act(conv1x1(logits)), image) with the 1x1 convolution K -> 1 of weight [1,K,1,1] (or [K]) and bias
+    [1], act "sigmoid" or "tanh" (semi_seg/hooks/autoencoder.py:52-57).  Gradients go to the logits, the weight and
+    the bias, none to the image.  One pass over the logits each way; no reconstruction or difference map is formed.
+    A contiguous f32 image -- the one-channel input of the U-Net -- is read in place."""
+
+    @staticmethod
+    def forward(ctx, logits: Tensor, weight: Tensor, bias: Tensor, image: Tensor, activation: str = "sigmoid"):
+        ops.require_gpu(logits, weight, bias, image)
+        if activation not in ops.PRIOR_ACTS:
+            raise ValueError(f"activation must be 'sigmoid' or 'tanh', got {activation!r}")
+        K = logits.shape[1]
+        if weight.numel() != K or bias.numel() != 1:
+            raise ValueError(f"the fused DAE loss reconstructs one channel: expected a weight of {K} elements and a "
+                             f"bias of 1, got {tuple(weight.shape)} and {tuple(bias.shape)}")
+        logits = ops.to_nhwc(logits.float())
+        image = image.detach().float().contiguous()
+        w, b = weight.detach().float().contiguous(), bias.detach().float().contiguous()
+        ctx.save_for_backward(logits, w, b, image)
+        ctx.act = ops.PRIOR_ACTS[activation]
+        ctx.shapes = (weight.shape, bias.shape, weight.dtype, bias.dtype)
+        return ops.dae_fwd(logits, w, b, image, ctx.act)
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        logits, w, b, image = ctx.saved_tensors
+        gs = g.reshape(1).float().contiguous()
+        d, dw, db = ops.dae_bwd(logits, w, b, image, ctx.act, gs)
+        wshape, bshape, wdt, bdt = ctx.shapes
+        return d, dw.view(wshape).to(wdt), db.view(bshape).to(bdt), None, None
+
+
+class OrthoLossFn(torch.autograd.Function):
+    """((n n^T - I)^2).mean() with n = F.normalize(prototypes) (semi_seg/hooks/orthogonal.py:45-50): prototypes [K, C]
+    or [K, C, 1, 1], 2 <= K <= 64, K * C <= 16384.  One launch each way; the backward recomputes n and the Gram matrix.
+    Where the prototypes are a parameter with a live f32 .grad buffer (the flat buffers of FusedRAdam), the gradient
+    is added there in the order of the head's own weight gradient (`ops.ordered`), as the kernels of the network do:
+    autograd's own accumulation would not be ordered against a weight-gradient kernel of another stream."""
+
+    @staticmethod
+    def forward(ctx, prototypes: Tensor):
+        ops.require_gpu(prototypes)
+        if not (prototypes.dim() == 2 or (prototypes.dim() == 4 and tuple(prototypes.shape[2:]) == (1, 1))):
+            raise ValueError(f"prototypes must be [K, C] or [K, C, 1, 1], got {tuple(prototypes.shape)}")
+        v = prototypes.detach().float().reshape(prototypes.shape[0], prototypes.shape[1]).contiguous()
+        ctx.save_for_backward(v)
+        ctx.param = prototypes  # the parameter object (for its .grad sink), not saved data
+        return ops.ortho_fwd(v)
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        (v,) = ctx.saved_tensors
+        p = ctx.param
+        d = ops.ortho_bwd(v, g.reshape(1).float().contiguous()).view(p.shape)
+        sink = ops.grad_sink(p) if p.dtype == torch.float32 else None
+        if sink is not None:
+            with ops.ordered(("head_grad", sink.data_ptr())):
+                sink.add_(d)
+            return None
+        return d.to(p.dtype)
+
+
 class SoftmaxEntropyFn(torch.autograd.Function):
     """Entropy(eps=eps)(logits.softmax(1)), mean reduction (semi_seg/hooks/entmin.py:29-30,
     contrastyou/losses/kl.py:48-56)."""

@@ -1881,6 +1881,70 @@ def softmax_mixmse_bwd(student: Tensor, teacher: Tensor, index: Tensor, w_self: 
     return d
 
 
+# --------------------------------------------------------------------------- DAE prior, orthogonal prototypes (csrc/cy_prior.hip)
+PRIOR_FORMS = {"dae": _lib.CY_PRIOR_DAE, "ortho": _lib.CY_PRIOR_ORTHO}
+PRIOR_ACTS = {"sigmoid": _lib.CY_PRIOR_ACT_SIGMOID, "tanh": _lib.CY_PRIOR_ACT_TANH}
+_PRIOR_PLAN = ("variant", "vec", "fwd_grid", "fwd_trips", "bwd_grid", "bwd_trips", "k_chunks", "fwd_lds", "bwd_lds",
+               "aux")
+
+
+def prior_plan(form: str, K: int, Cc: int, npix: int = 0, align: int = 16) -> dict:
+    """the launch rule of the DAE ("dae": K classes, Cc image channels, npix pixels, the logits' base aligned to `align`
+    bytes) and orthogonality ("ortho": K prototypes of Cc floats) kernels: the values of cy_prior_plan by name.  A
+    host-side query, no GPU needed; what the launches refuse raises HipKernelError with their status."""
+    plan = (C.c_int32 * 10)()
+    _lib.call("cy_prior_plan", PRIOR_FORMS[form], int(npix), int(K), int(Cc), int(align), plan)
+    return dict(zip(_PRIOR_PLAN, (int(v) for v in plan)))
+
+
+def _dae_args(logits: Tensor, weight: Tensor, bias: Tensor, image: Tensor):
+    N, K, H, W = logits.shape
+    assert image.dim() == 4 and image.shape[0] == N and tuple(image.shape[2:]) == (H, W), \
+        (tuple(image.shape), tuple(logits.shape))
+    assert weight.numel() == K and bias.numel() == 1, (tuple(weight.shape), tuple(bias.shape), K)
+    assert image.dtype == torch.float32 and image.is_contiguous(), (image.dtype, image.stride())
+    return N, K, H * W, image.shape[1]
+
+
+def dae_fwd(logits: Tensor, weight: Tensor, bias: Tensor, image: Tensor, act: int) -> Tensor:
+    """logits f32 [N,K,H,W] with NHWC memory, weight f32 [K] (any shape of K elements), bias f32 [1], image f32
+    [N,Cimg,H,W] contiguous -> device scalar: F.mse_loss(act(conv1x1(logits)), image)"""
+    N, K, HW, Cimg = _dae_args(logits, weight, bias, image)
+    nbytes = _lib.load().cy_dae_ws_bytes(N * HW, K, 0)
+    ws = _ws(nbytes, logits.device)
+    loss = _f32(1, logits.device)
+    _lib.call("cy_dae_fwd", logits.data_ptr(), weight.data_ptr(), bias.data_ptr(), image.data_ptr(), loss.data_ptr(),
+              N, HW, K, Cimg, int(act), ws.data_ptr(), nbytes, _stream())
+    return loss.view(())
+
+
+def dae_bwd(logits: Tensor, weight: Tensor, bias: Tensor, image: Tensor, act: int, gscale: Tensor):
+    """-> (dlogits [N,K,H,W] with NHWC memory, dweight [K], dbias [1])"""
+    N, K, HW, Cimg = _dae_args(logits, weight, bias, image)
+    nbytes = _lib.load().cy_dae_ws_bytes(N * HW, K, 1)
+    ws = _ws(nbytes, logits.device)
+    d = empty_nhwc(N, K, logits.shape[2], logits.shape[3], torch.float32, logits.device)
+    dw, db = _f32(K, logits.device), _f32(1, logits.device)
+    _lib.call("cy_dae_bwd", logits.data_ptr(), weight.data_ptr(), bias.data_ptr(), image.data_ptr(), gscale.data_ptr(),
+              d.data_ptr(), dw.data_ptr(), db.data_ptr(), N, HW, K, Cimg, int(act), ws.data_ptr(), nbytes, _stream())
+    return d, dw, db
+
+
+def ortho_fwd(prototypes: Tensor) -> Tensor:
+    """prototypes f32 [K, C] contiguous -> device scalar: ((n n^T - I)^2).mean() of the normalised rows"""
+    K, Cc = prototypes.shape
+    loss = _f32(1, prototypes.device)
+    _lib.call("cy_ortho_fwd", prototypes.data_ptr(), loss.data_ptr(), K, Cc, _stream())
+    return loss.view(())
+
+
+def ortho_bwd(prototypes: Tensor, gscale: Tensor) -> Tensor:
+    K, Cc = prototypes.shape
+    d = _f32(K * Cc, prototypes.device).view(K, Cc)
+    _lib.call("cy_ortho_bwd", prototypes.data_ptr(), gscale.data_ptr(), d.data_ptr(), K, Cc, _stream())
+    return d
+
+
 def dice_counts(logits: Tensor, target: Tensor) -> Tensor:
     """int64 [N,K,2] = per-sample per-class (intersection, union) of argmax(logits) vs target."""
     N, K, H, W = logits.shape

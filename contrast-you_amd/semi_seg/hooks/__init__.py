@@ -1,3 +1,4 @@
+from .autoencoder import AuxiliaryLayer, DenoisingAutoEncoderTrainerHook  # noqa: F401
 from .consistency import ConsistencyTrainerHook  # noqa: F401
 from .cc import CrossCorrelationOnLogitsHook  # noqa: F401
 from .ccblock import ProjectorGeneralHook  # noqa: F401
@@ -15,4 +16,5 @@ from .midl import IIDSegmentationTrainerHook, IMSATTrainHook  # noqa: F401
 from .mixup import MixUpTrainHook  # noqa: F401
 from .mt import (EMAUpdater, ICTMeanTeacherTrainerHook, MeanTeacherTrainerHook,  # noqa: F401
                  UAMeanTeacherTrainerHook)
+from .orthogonal import OrthogonalTrainerHook  # noqa: F401
 from .pseudolabel import PseudoLabelTrainerHook  # noqa: F401

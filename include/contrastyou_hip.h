@@ -1357,6 +1357,57 @@ int cy_softmax_mixmse_fwd(const float* student, const float* teacher, const int3
 int cy_softmax_mixmse_bwd(const float* student, const float* teacher, const int32_t* index, float w_self,
                           float w_other, const float* gscale, float* dstudent, int N, long HW, int K, void* stream);
 
+/* ------------------------------------------------------------------------
+ * DAE prior and orthogonal prototypes (csrc/cy_prior.hip; entries added to ABI v18 -- no existing signature changed,
+ * so cy_abi_version() stays 18).  Every entry checks its arguments before any launch: a NULL pointer, a count < 1 or a
+ * base that is not 4-byte aligned -> CY_ERR_ARG; K, Cimg, the activation or K * C out of range -> CY_ERR_SHAPE; a short
+ * workspace -> CY_ERR_WORKSPACE.  No atomics: two runs give the same bits.  Upstream gradients are device memory.
+ * ------------------------------------------------------------------------ */
+#define CY_PRIOR_DAE 0   /* cy_dae_* */
+#define CY_PRIOR_ORTHO 1 /* cy_ortho_* */
+#define CY_PRIOR_ACT_SIGMOID 0
+#define CY_PRIOR_ACT_TANH 1
+/* The launch rule of both groups (host-side only, launches nothing; the launches take every decision from it), in the
+ * style of cy_mix_plan.  DAE: n = npix, C = Cimg, `align` = the bytes the logits' base is aligned to (16 and more count
+ * as 16).  Orthogonality: K prototypes of C floats; n and align are not looked at.
+ *   plan[0] variant.  DAE: the compiled K (2, 4, 8) where the rows are aligned to their 8 / 16 bytes, else 0 (run-time
+ *           K, the row read 16 floats at a time).  Orthogonality: 0 = a thread per Gram entry (C <= 64), 1 = a wave
+ *   plan[1] vec: floats per access of a logits row: 2 (variant 2), 4 (variants 4, 8; variant 0 where K % 4 == 0 on a
+ *           16-byte base), else 1.  Orthogonality: 1
+ *   plan[2] fwd_grid, plan[4] bwd_grid.  DAE: min(1024, ceil(npix / 256)) blocks = the f64 partials per quantity.
+ *           Orthogonality: 1
+ *   plan[3] fwd_trips, plan[5] bwd_trips.  DAE: loop trips of the busiest block.  Orthogonality: trips of the Gram
+ *           loop (ceil(K^2 / 256), or ceil(K^2 / 4) for the wave form) and of the sweeps over [K][C] (ceil(K C / 256))
+ *   plan[6] k_chunks.  DAE: 16-float pieces a row is read in: ceil(K / 16) for variant 0, else 1.  Orthogonality: 0
+ *   plan[7] fwd_lds, plan[8] bwd_lds: bytes of LDS per block: static for DAE, dynamic for orthogonality (rows, and
+ *           backward the K x K matrix)
+ *   plan[9] DAE: the threads of a block that work in the backward's flat sweep, floor(256 / K) * K.  Orthogonality: the
+ *           floats between two rows in LDS (C | 1 for the thread form, C for the wave form)
+ * Returns what the launches answer: CY_ERR_ARG for a NULL `plan`, an unknown form, npix < 1, C < 1 (orthogonality) or
+ * an align that is no multiple of 4; CY_ERR_SHAPE for K outside 2..64, Cimg outside 1..4 or K * C > 16384. */
+int cy_prior_plan(int form, long n, int K, int C, int align, int32_t* plan /* [10] */);
+/* The denoising-auto-encoder prior (semi_seg/hooks/autoencoder.py:52-57: F.mse_loss(AuxiliaryLayer(logits), image),
+ * the layer a 1x1 convolution K -> 1 and a sigmoid or tanh).  Logits are [npix][K] f32 rows (NHWC), npix = N * HW,
+ * 2 <= K <= 64; w[K], b[1] f32; image [N][Cimg][HW] f32 planar, 1 <= Cimg <= 4; act CY_PRIOR_ACT_*.
+ *   r_p = act(b + sum_k w_k z_pk) (the sum in f64);  loss[0] = sum_p sum_c (r_p - image_pc)^2 / (npix Cimg):
+ * the one-channel reconstruction broadcasts over the image's channels as F.mse_loss broadcasts it.
+ * Backward, with g_p = 2 gscale[0] act'(.) sum_c (r_p - image_pc) / (npix Cimg):  dlogits_pk = g_p w_k,
+ * dw_k = sum_p g_p z_pk, db = sum_p g_p (f64 per block, then in block order).  The image carries no gradient.
+ * ws_bytes >= 8 * min(1024, ceil(npix / 256)) forward, (K + 1) times that backward = cy_dae_ws_bytes (0 for a
+ * count < 1). */
+size_t cy_dae_ws_bytes(long npix, int K, int backward);
+int cy_dae_fwd(const float* logits, const float* w, const float* b, const float* image, float* loss, int N, long HW,
+               int K, int Cimg, int act, void* ws, size_t ws_bytes, void* stream);
+int cy_dae_bwd(const float* logits, const float* w, const float* b, const float* image, const float* gscale,
+               float* dlogits, float* dw, float* db, int N, long HW, int K, int Cimg, int act, void* ws,
+               size_t ws_bytes, void* stream);
+/* The orthogonal-prototype regulariser (semi_seg/hooks/orthogonal.py:45-50).  prototypes [K][C] f32, 2 <= K <= 64,
+ * K * C <= 16384:  n_i = v_i / max(|v_i|_2, 1e-12), G = n n^T, loss[0] = sum (G - I)^2 / K^2.  One block each way; the
+ * backward recomputes n and G and writes dprototypes [K][C] = gscale[0] dloss/dv (a row whose norm was clamped gets
+ * the clamped quotient's derivative, 1e12 times the gradient of its n, as torch gives it). */
+int cy_ortho_fwd(const float* prototypes, float* loss, int K, int C, void* stream);
+int cy_ortho_bwd(const float* prototypes, const float* gscale, float* dprototypes, int K, int C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
