@@ -5,6 +5,7 @@ config/base.yaml:10-13) as ONE HIP kernel launch per parameter group over flat f
 the data-parallel gradient all-reduce (RCCL) folded into `step()`."""
 from torch.optim import SGD, Adam, AdamW  # noqa: F401  (small-parameter fallbacks, e.g. for a discriminator)
 
+from .flat_teacher import FlatTeacher  # noqa: F401
 from .fused_radam import FlatParams, FusedRAdam  # noqa: F401
 from .scheduler import GradualWarmupScheduler  # noqa: F401
 

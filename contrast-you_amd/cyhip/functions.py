@@ -145,6 +145,24 @@ def begin_pass() -> int:
     return _pass_serial
 
 
+class side_pass:
+    """`with side_pass():` -- a network evaluation that is differentiated on its own, forward and backward inside the
+    block, while another step is between its forward and its backward (the teacher of the differentiable mean teacher,
+    inside the student's regularisation).  The pass bookkeeping assumes that one step's passes are differentiated
+    together: the enclosing step's first-pass serial is set aside, so that the evaluation inside is the first pass of a
+    step of its own and the end of its backward re-arms nothing of the outer step, and put back on the way out."""
+
+    def __enter__(self):
+        global _step_first_pass
+        self._outer, _step_first_pass = _step_first_pass, None
+        return self
+
+    def __exit__(self, *exc):
+        global _step_first_pass
+        _step_first_pass = self._outer
+        return False
+
+
 class _Parked:
     __slots__ = ("w", "sink", "src1", "src2", "dy", "mode", "scale", "shift", "stream", "event", "capid")
 
@@ -787,6 +805,29 @@ class MixSoftmaxMSEFn(torch.autograd.Function):
         student, teacher, index = ctx.saved_tensors
         gs = g.reshape(1).float().contiguous()
         return ops.softmax_mixmse_bwd(student, teacher, index, *ctx.args, gs), None, None, None, None
+
+
+class SoftmaxGatherMSEFn(torch.autograd.Function):
+    """nn.MSELoss()(warp(teacher.softmax(1)), student.softmax(1)), the consistency term of the differentiable mean
+    teacher (semi_seg/hooks/dmt.py:138-146): the teacher's PROBABILITIES go through the nearest-neighbour affine map
+    with zero padding, so a pixel warped in from outside the image carries the all-zero vector (SoftmaxMSEFn on warped
+    logits would give it the uniform softmax of zero logits).  `teacher_logits` are unwarped; `source_map` is the int32
+    [N,H,W] map of ops.source_map_from_warped.  The gradient goes to the student alone; neither softmax, nor the warped
+    tensor, nor the difference is formed."""
+
+    @staticmethod
+    def forward(ctx, teacher_logits: Tensor, source_map: Tensor, student_logits: Tensor):
+        ops.require_gpu(teacher_logits, source_map, student_logits)
+        student = ops.to_nhwc(student_logits.float())
+        teacher = ops.to_nhwc(teacher_logits.detach().float())
+        ctx.save_for_backward(teacher, source_map, student)
+        return ops.softmax_gathermse_fwd(teacher, source_map, student)
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        teacher, source_map, student = ctx.saved_tensors
+        gs = g.reshape(1).float().contiguous()
+        return None, None, ops.softmax_gathermse_bwd(teacher, source_map, student, gs)
 
 
 class DAELossFn(torch.autograd.Function):

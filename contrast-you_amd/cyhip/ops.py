@@ -1945,6 +1945,115 @@ def ortho_bwd(prototypes: Tensor, gscale: Tensor) -> Tensor:
     return d
 
 
+# --------------------------------------------------------------------------- differentiable mean teacher (csrc/cy_teacher.hip)
+TEACHER_FORMS = {"adam": _lib.CY_TEACHER_ADAM, "axpy": _lib.CY_TEACHER_AXPY, "ema_multi": _lib.CY_TEACHER_EMA_MULTI,
+                 "gathermse": _lib.CY_TEACHER_GATHERMSE}
+_TEACHER_PLAN = ("variant", "vec", "fwd_grid", "fwd_trips", "bwd_grid", "bwd_trips", "rows")
+EMA_MULTI_MAX = 4096  # tensors of one cy_ema_update_multi launch
+SOURCE_MAP_MAX = 1 << 24  # pixel indices an f32 image carries exactly
+
+
+def teacher_plan(form: str, n: int, K: int = 0, align: int = 16) -> dict:
+    """the launch rule of the teacher kernels (host-side query, no GPU needed): the values of cy_teacher_plan by name.
+    `n`: elements ("adam", "axpy"), tensors ("ema_multi") or pixels ("gathermse").  What the launches refuse raises
+    HipKernelError with their status."""
+    plan = (C.c_int32 * 7)()
+    _lib.call("cy_teacher_plan", TEACHER_FORMS[form], int(n), int(K), int(align), plan)
+    return dict(zip(_TEACHER_PLAN, (int(v) for v in plan)))
+
+
+def _flat_f32(*ts: Tensor) -> int:
+    require_gpu(*ts)
+    n = ts[0].numel()
+    for t in ts:
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n, (t.dtype, t.stride(), t.numel(), n)
+    return n
+
+
+def adam_step(p: Tensor, g: Tensor, m: Tensor, v: Tensor, lr: float, beta1: float, beta2: float, eps: float,
+              wd: float, step: int) -> None:
+    """one torch.optim.Adam update (amsgrad=False, maximize=False) of flat f32 buffers, in place; `step` is the 1-based
+    count after this update"""
+    n = _flat_f32(p, g, m, v)
+    _lib.call("cy_adam_step", p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, float(lr), float(beta1),
+              float(beta2), float(eps), float(wd), int(step), _stream())
+
+
+def axpy(y: Tensor, x: Tensor, a: float) -> None:
+    """y += a * x over flat f32 buffers, in place"""
+    n = _flat_f32(y, x)
+    _lib.call("cy_axpy", y.data_ptr(), x.data_ptr(), n, float(a), _stream())
+
+
+def ema_table(pairs, device) -> Tensor:
+    """the int64 [count, 3] device table of cy_ema_update_multi for (teacher, student) f32 tensor pairs: the two
+    addresses and the element count of each.  Built on the host and uploaded once; the caller caches it and rebuilds
+    it when an address changed."""
+    rows = []
+    for t, s in pairs:
+        require_gpu(t, s)
+        assert t.dtype == s.dtype == torch.float32 and t.is_contiguous() and s.is_contiguous(), (t.dtype, s.dtype)
+        assert t.numel() == s.numel(), (tuple(t.shape), tuple(s.shape))
+        rows.append((t.data_ptr(), s.data_ptr(), t.numel()))
+    if not 1 <= len(rows) <= EMA_MULTI_MAX:
+        raise ValueError(f"a multi-tensor EMA launch covers 1..{EMA_MULTI_MAX} tensors, got {len(rows)}")
+    return torch.tensor(rows, dtype=torch.int64).to(device)
+
+
+def ema_update_multi(table: Tensor, alpha: float, weight_decay: float) -> None:
+    """the update of `ema_update` over every (teacher, student, n) row of an `ema_table`, in one launch"""
+    require_gpu(table)
+    assert table.dtype == torch.int64 and table.dim() == 2 and table.shape[1] == 3 and table.is_contiguous()
+    _lib.call("cy_ema_update_multi", table.data_ptr(), table.shape[0], float(alpha), float(weight_decay), _stream())
+
+
+def source_map_from_warped(warped_index: Tensor) -> Tensor:
+    """int32 [N,H,W] source map of the gather-MSE kernels from what the step's nearest-neighbour warp made of an
+    [N,1,H,W] f32 image holding `pixel index + 1` (ops.source_index_image): the source pixel, or -1 where the warp
+    padded with zero"""
+    N, Cc, H, W = warped_index.shape
+    assert Cc == 1 and warped_index.dtype == torch.float32, (tuple(warped_index.shape), warped_index.dtype)
+    return (warped_index.reshape(N, H, W).to(torch.int32) - 1).contiguous()
+
+
+def source_index_image(N: int, H: int, W: int, device) -> Tensor:
+    """[N,1,H,W] f32, every image holding 1 .. H*W in row-major order: exact in f32 below 2^24 pixels"""
+    assert H * W < SOURCE_MAP_MAX, f"an f32 image carries pixel indices exactly below 2^24 pixels, got {H}x{W}"
+    one = torch.arange(1, H * W + 1, dtype=torch.float32, device=device).view(1, 1, H, W)
+    return one.expand(N, 1, H, W).contiguous()
+
+
+def _gather_args(teacher: Tensor, source_map: Tensor, student: Tensor):
+    N, K, H, W = student.shape
+    assert teacher.shape == student.shape, (tuple(teacher.shape), tuple(student.shape))
+    assert teacher.dtype == student.dtype == torch.float32 and is_nhwc(teacher) and is_nhwc(student)
+    assert source_map.dtype == torch.int32 and source_map.numel() == N * H * W and source_map.is_contiguous(), \
+        (source_map.dtype, tuple(source_map.shape))
+    return N, K, H * W
+
+
+def softmax_gathermse_fwd(teacher: Tensor, source_map: Tensor, student: Tensor) -> Tensor:
+    """teacher (unwarped), student: f32 logits [N,K,H,W] with NHWC memory; source_map int32 [N,H,W] (the source pixel of
+    the same image, or -1) -> device scalar: the mean of (q - softmax(student))^2, q the teacher's softmax at the
+    source or 0 outside"""
+    N, K, HW = _gather_args(teacher, source_map, student)
+    nbytes = _lib.load().cy_softmax_gathermse_ws_bytes(N, HW)
+    ws = _ws(nbytes, student.device)
+    loss = _f32(1, student.device)
+    _lib.call("cy_softmax_gathermse_fwd", teacher.data_ptr(), source_map.data_ptr(), student.data_ptr(),
+              loss.data_ptr(), N, HW, K, ws.data_ptr(), nbytes, _stream())
+    return loss.view(())
+
+
+def softmax_gathermse_bwd(teacher: Tensor, source_map: Tensor, student: Tensor, gscale: Tensor) -> Tensor:
+    """the student's gradient (the teacher side carries none)"""
+    N, K, HW = _gather_args(teacher, source_map, student)
+    d = empty_nhwc(N, K, student.shape[2], student.shape[3], torch.float32, student.device)
+    _lib.call("cy_softmax_gathermse_bwd", teacher.data_ptr(), source_map.data_ptr(), student.data_ptr(),
+              gscale.data_ptr(), d.data_ptr(), N, HW, K, _stream())
+    return d
+
+
 def dice_counts(logits: Tensor, target: Tensor) -> Tensor:
     """int64 [N,K,2] = per-sample per-class (intersection, union) of argmax(logits) vs target."""
     N, K, H, W = logits.shape

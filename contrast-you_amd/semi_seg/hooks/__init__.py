@@ -8,6 +8,7 @@ from .creator import (create_consistency_hook, create_cross_correlation_hooks2, 
                       create_imsat_hook, create_infonce_hooks, create_intermediate_imsat_hook, create_mixup_hook,
                       create_mt_hook, create_orthogonal_hook, create_pseudo_label_hook, create_sp_infonce_hooks,
                       create_superpixel_hooks, create_uamt_hook, feature_until_from_hooks, mt_in_hooks)
+from .dmt import DifferentiableMeanTeacherTrainerHook  # noqa: F401
 from .discretemi import DiscreteIMSATTrainHook, DiscreteMITrainHook  # noqa: F401
 from .entmin import EntropyMinTrainerHook  # noqa: F401
 from .infonce import (INFONCEHook, PScheduler, SelfPacedINFONCEHook, SuperPixelInfoNCEHook,  # noqa: F401

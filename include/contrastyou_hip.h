@@ -1408,6 +1408,59 @@ int cy_dae_bwd(const float* logits, const float* w, const float* b, const float*
 int cy_ortho_fwd(const float* prototypes, float* loss, int K, int C, void* stream);
 int cy_ortho_bwd(const float* prototypes, const float* gscale, float* dprototypes, int K, int C, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Differentiable mean teacher (csrc/cy_teacher.hip; entries added to ABI v18 -- no existing signature changed and no
+ * struct added, so cy_abi_version() stays 18).  The teacher's state lives in flat f32 buffers; every update of it is one
+ * streaming launch.  Every entry checks its arguments before any launch: a NULL pointer, a count < 1, step < 1 or a
+ * base that is not 4-byte aligned -> CY_ERR_ARG; K or the tensor count out of range -> CY_ERR_SHAPE; a short workspace
+ * -> CY_ERR_WORKSPACE.  No atomics: two runs give the same bits.
+ * ------------------------------------------------------------------------ */
+#define CY_TEACHER_ADAM 0      /* cy_adam_step */
+#define CY_TEACHER_AXPY 1      /* cy_axpy */
+#define CY_TEACHER_EMA_MULTI 2 /* cy_ema_update_multi */
+#define CY_TEACHER_GATHERMSE 3 /* cy_softmax_gathermse_* */
+/* The launch rule of the four families (host-side only, launches nothing; the launches take every decision from it), in
+ * the style of cy_mix_plan.  `n`: the elements (Adam, axpy), the tensors (multi-tensor EMA) or the pixels N * HW
+ * (gather-MSE).  `align`: the bytes every tensor base of the call is aligned to (16 and more count as 16).  K is looked
+ * at by gather-MSE only.
+ *   plan[0] variant: gather-MSE: the compiled K (2, 4, 8) where the rows are aligned to their 8 / 16 bytes, else 0
+ *           (run-time K, one float at a time, any 4-byte-aligned base).  Otherwise 0
+ *   plan[1] vec: floats per memory access.  Adam, axpy: 4 where align is a multiple of 16 and n >= 4 (the n % 4 tail
+ *           goes one float at a time), else 1.  Multi-tensor EMA: 1.  Gather-MSE: 2 (variant 2), 4 (variants 4, 8), 1
+ *   plan[2] fwd_grid: Adam, axpy: min(2048, ceil(n / vec / 256)) blocks.  Multi-tensor EMA: the blocks striding over one
+ *           tensor, clamp(8192 / n, 2, 64).  Gather-MSE: min(1024, ceil(n / 256)) blocks = the f64 partials
+ *   plan[3] fwd_trips: loop trips of the busiest block; multi-tensor EMA (the sizes are device data): the elements of a
+ *           tensor that one trip covers, 256 * plan[2]
+ *   plan[4] bwd_grid = 2 * fwd_grid, plan[5] bwd_trips: gather-MSE; otherwise 0, 0
+ *   plan[6] rows: multi-tensor EMA: the grid's second dimension = n; otherwise 0
+ * Returns what the launches answer: CY_ERR_ARG for a NULL `plan`, an unknown form, n < 1 or an align that is no multiple
+ * of 4; CY_ERR_SHAPE for more than 4096 tensors or K outside 2..16. */
+int cy_teacher_plan(int form, long n, int K, int align, int32_t* plan /* [7] */);
+/* torch.optim.Adam(amsgrad=False, maximize=False) on flat f32 buffers of n elements; `step` is the 1-based count after
+ * this update.  g += wd p (wd != 0);  m += (g - m)(1 - beta1);  v = beta2 v + (1 - beta2) g^2;
+ * p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps), bc_i = 1 - beta_i^step formed in f64 on the host as cy_radam_step
+ * forms them, lr / bc1 and sqrt(bc2) rounded to f32 once. */
+int cy_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long n, float lr, float beta1,
+                 float beta2, float eps, float weight_decay, long step, void* stream);
+/* y += a x over flat f32 buffers of n elements, one fused multiply-add per element. */
+int cy_axpy(float* y, const float* x, long n, float a, void* stream);
+/* The expression of cy_ema_update, bit for bit, over `count` tensors in one launch.  `table` is [count][3] int64 in
+ * device memory, 8-byte aligned: the teacher tensor's address, the student's, the number of f32 elements; a row with a
+ * null address or a count < 1 is skipped.  1 <= count <= 4096, anything else is CY_ERR_SHAPE. */
+int cy_ema_update_multi(const int64_t* table, int count, float alpha, float weight_decay, void* stream);
+/* The consistency term of the differentiable mean teacher (semi_seg/hooks/dmt.py:177-197): the MSE of softmax(student)
+ * against the teacher's probabilities warped by the step's nearest-neighbour affine map with zero padding.  teacher and
+ * student are f32 logits [N][HW][K] (NHWC rows), the teacher's unwarped; map is int32 [N][HW]: the source pixel in
+ * [0, HW) of the same image, or -1 (any value outside [0, HW)) for a source outside the image.
+ *   q = softmax(teacher[n][map[n][hw]]) or the all-zero vector outside;  loss[0] = sum (q_k - softmax(s)_k)^2 / (npix K)
+ * Backward, student only, p = softmax(s):  ds_k = gscale[0] (2 / (npix K)) p_k ((p_k - q_k) - sum_j p_j (p_j - q_j)).
+ * 2 <= K <= 16.  ws_bytes >= 8 * min(1024, ceil(npix / 256)) = cy_softmax_gathermse_ws_bytes (0 for a count < 1). */
+size_t cy_softmax_gathermse_ws_bytes(int N, long HW);
+int cy_softmax_gathermse_fwd(const float* teacher, const int32_t* map, const float* student, float* loss, int N,
+                             long HW, int K, void* ws, size_t ws_bytes, void* stream);
+int cy_softmax_gathermse_bwd(const float* teacher, const int32_t* map, const float* student, const float* gscale,
+                             float* dstudent, int N, long HW, int K, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
