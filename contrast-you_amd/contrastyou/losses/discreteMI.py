@@ -10,6 +10,9 @@ contrastyou/losses/discreteMI.py:20-170,201-297:
     IMSATLoss(lamda, eps)(x_out, x_tf_out=None)    -> imsat_loss, or the mean of the two views'   on [n,k] simplexes
     IMSATDynamicWeight(lamda, use_dynamic, eps)(x_out) -> -w * marginal + conditional, w a buffer that follows
                                                       log k - marginal
+    IIDSegmentationSmallPathLoss(lamda, padding, eps, patch_size)(x_out, x_tf_out, mask=None) -> the mean of
+                                                      IIDSegmentationLoss over square patches (discreteMI.py:173-198)
+    patch_generator(feature_map, patch_size, step_size) / patch_origins(L, p, s)   (discreteMI.py:264-272)
 
 The k x k (or (2p+1)^2 x k x k) joint is a contraction over all n*H*W pixels -- HBM-bound, k = 20 --
 done by the HIP joint kernels; the loss on the joint and its gradient come from one single-block
@@ -32,10 +35,11 @@ import torch
 from torch import Tensor, nn
 
 from cyhip import ops
-from cyhip.functions import IIDFn, IMSATFn, IMSATPairFn
+from cyhip.functions import IIDFn, IIDPatchFn, IMSATFn, IMSATPairFn
 
 __all__ = ["IIDLoss", "IIDSegmentationLoss", "compute_joint", "compute_joint_2D",
-           "compute_joint_2D_with_padding_zeros", "IMSATLoss", "IMSATDynamicWeight", "imsat_loss", "imsat_with_entropy"]
+           "compute_joint_2D_with_padding_zeros", "IMSATLoss", "IMSATDynamicWeight", "imsat_loss", "imsat_with_entropy",
+           "IIDSegmentationSmallPathLoss", "patch_generator", "patch_origins"]
 
 
 def _nhwc_f32(x: Tensor) -> Tensor:
@@ -84,6 +88,55 @@ class IIDSegmentationLoss(nn.Module):
         if self._p_i_j is None:
             raise RuntimeError()
         return self._p_i_j.detach().cpu().numpy()
+
+
+def patch_origins(L: int, p: int, s: int):
+    """the origins of the patches of size p, step s, along an axis of length L (discreteMI.py:266-269): the multiples
+    of s below L - p, then max(L - p, 0).  A patch is clipped to the axis, so L <= p gives the one origin 0."""
+    return list(range(0, L - p, s)) + [max(L - p, 0)]
+
+
+def patch_generator(feature_map, patch_size=(32, 32), step_size=(16, 16)):
+    """the views feature_map[:, :, h0:h0+ph, w0:w0+pw] clipped to the map, rows first (discreteMI.py:264-272)"""
+    b, c, h, w = feature_map.shape
+    for _h in patch_origins(h, patch_size[0], step_size[0]):
+        for _w in patch_origins(w, patch_size[1], step_size[1]):
+            yield feature_map[:, :, _h:min(_h + patch_size[0], h), _w:min(_w + patch_size[1], w)]
+
+
+class IIDSegmentationSmallPathLoss(IIDSegmentationLoss):
+    """The mean over square patches (side patch_size, step patch_size // 2, `patch_origins`) of IIDSegmentationLoss on
+    the patch, never symmetric (discreteMI.py:173-198).  The reference loops over the patches in Python; here all joints
+    come from one launch (the zero padding of a displaced read is at the patch border, as a conv2d on the slice has it),
+    one block per patch forms the losses and a fixed-order mean follows (csrc/cy_mi.hip).
+
+    `mask`: the reference multiplies the slice views in place, which alters the caller's tensors and multiplies a pixel
+    of overlapping patches once per patch.  Here the mask is applied out of place, once per map, before the kernels:
+    the same value for 0/1 masks.  The reference's `torch.isnan` check of the patch losses is a host sync and is left
+    out of `forward`, like the `simplex()` assertions of this module."""
+
+    def __init__(self, lamda=1.0, padding=7, eps: float = sys.float_info.epsilon, patch_size=32) -> None:
+        super().__init__(lamda, padding, eps)
+        self._patch_size = (int(patch_size), int(patch_size))
+        self._step_size = (int(patch_size) // 2, int(patch_size) // 2)
+
+    def forward(self, x_out: Tensor, x_tf_out: Tensor, mask: Tensor = None) -> Tensor:
+        assert x_out.shape == x_tf_out.shape and x_out.dim() == 4, (x_out.shape, x_tf_out.shape)
+        ops.require_gpu(x_out, x_tf_out)
+        if mask is not None:
+            x_out, x_tf_out = x_out * mask, x_tf_out * mask
+        a, b = _nhwc_f32(x_out), _nhwc_f32(x_tf_out)
+        loss, self._patch_losses, P = IIDPatchFn.apply(a, b, self.padding, self._patch_size[0], float(self.lamda),
+                                                       float(self._eps))
+        self._p_i_j = P[0, 0]  # the first patch (origin (0, 0)), displacement index 0
+        return loss
+
+    def get_joint_matrix(self):
+        """the [k,k] joint of the FIRST patch (origin (0, 0)) at displacement index 0"""
+        return super().get_joint_matrix()
+
+    def __repr__(self):
+        return f"{self.__class__.__name__} with patch_size={self._patch_size} and padding={self.padding}."
 
 
 @torch.no_grad()

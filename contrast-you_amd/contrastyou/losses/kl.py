@@ -8,6 +8,10 @@ sync.  Mean reduction without class weights runs cy_softmax_kl_*; class weights 
 "sum" and "none" run cy_softmax_wkl_* (csrc/cy_seg_loss.hip), or compose torch ops past 16 classes.
 `Entropy.from_logits(logits)` is the same for `Entropy()(logits.softmax(1))`
 (semi_seg/hooks/entmin.py:29-30).
+
+`JSD_div(reduction, eps)(*maps)` = Entropy(mean of the maps) - mean of the Entropies (kl.py:142-174) and
+`EntropyPrior(reduction="mean", eps)(input_, prior=None)` = log C - KL_div()(prior, input_) (kl.py:63-78) are one
+streaming HIP pass each way (csrc/cy_pica.hip); the reference's `simplex` assertions are host syncs and are left out.
 """
 from __future__ import annotations
 
@@ -16,9 +20,10 @@ from typing import List, Optional, Union
 import torch
 from torch import Tensor, nn
 
-from cyhip.functions import SoftmaxEntropyFn, SoftmaxKLFn, SoftmaxWeightedKLFn
+from cyhip import ops
+from cyhip.functions import EntropyPriorFn, JSDFn, SoftmaxEntropyFn, SoftmaxKLFn, SoftmaxWeightedKLFn
 
-__all__ = ["Entropy", "KL_div"]
+__all__ = ["Entropy", "KL_div", "JSD_div", "EntropyPrior"]
 
 FUSED_KMAX = 16  # classes of the fused kernels (cy_softmax_kl_*, cy_softmax_wkl_*)
 
@@ -106,3 +111,50 @@ class KL_div(nn.Module):
 
     def __repr__(self):
         return f"{self.__class__.__name__}\n, weight={self._weight}"
+
+
+class EntropyPrior(Entropy):
+    """log C - KL_div()(prior, input_) on [n,C] rows, `prior` a [1,C] row (default: uniform) taken as a constant.  Only
+    the mean reduction exists; inputs of more than two dimensions fail the reference's own shape assertion, here too."""
+
+    def __init__(self, reduction="mean", eps=1e-16):
+        super().__init__(reduction, eps)
+        assert reduction == "mean", "only support mean"
+
+    def forward(self, input_: Tensor, prior: Tensor = None) -> Tensor:
+        assert input_.dim() >= 2
+        C = input_.shape[1]
+        if prior is not None:
+            assert isinstance(prior, Tensor)
+            assert prior.shape == (1, *input_.shape[1:]), (prior.shape, input_.shape)
+        assert input_.dim() == 2, f"a prior row of shape [1,{C}] does not match the mean of a {tuple(input_.shape)} input"
+        ops.require_gpu(input_, prior)
+        if C > ops.PICA_KMAX:
+            raise NotImplementedError(f"EntropyPrior runs on up to {ops.PICA_KMAX} classes, got {C}")
+        row = None if prior is None else prior.detach().float().reshape(C).contiguous()
+        return EntropyPriorFn.apply(input_.float(), row, float(self._eps))
+
+
+class JSD_div(nn.Module):
+    """Entropy(mean of the maps) - mean of the Entropies, each in the given reduction (general Jensen-Shannon divergence
+    with equal weights): one fused pass reads the maps once, one backward kernel.  2 to 8 f32 maps of one shape with up
+    to 64 classes on dim 1, NCHW or NHWC (or [n,C] rows); anything else raises NotImplementedError."""
+
+    def __init__(self, reduction="mean", eps=1e-16):
+        super().__init__()
+        _check_reduction_params(reduction)
+        self._reduction = reduction
+        self._eps = eps
+        self._entropy_criterion = Entropy(reduction=reduction, eps=eps)
+
+    def forward(self, *input_: Tensor) -> Tensor:
+        assert all(x.shape == input_[0].shape for x in input_), "input tensor should have the same dimension"
+        lo, hi = ops.JSD_MAPS
+        if not (lo <= len(input_) <= hi) or input_[0].dim() < 2 or input_[0].shape[1] > ops.PICA_KMAX or any(
+                x.dtype != torch.float32 for x in input_):
+            raise NotImplementedError(
+                f"JSD_div runs on {lo} to {hi} float32 maps of up to {ops.PICA_KMAX} classes (NCHW or NHWC), got "
+                f"{len(input_)} of shape {tuple(input_[0].shape) if input_ else None} and dtypes "
+                f"{[str(x.dtype) for x in input_]}")
+        ops.require_gpu(*input_)
+        return JSDFn.apply(self._reduction, float(self._eps), *input_)

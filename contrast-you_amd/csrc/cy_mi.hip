@@ -5,6 +5,7 @@
 //   compute_joint_2D (displaced, padding > 0)     contrastyou/losses/discreteMI.py:225-243
 //   compute_joint_2D_with_padding_zeros           contrastyou/losses/discreteMI.py:246-261
 //   IIDLoss / IIDSegmentationLoss                 contrastyou/losses/discreteMI.py:90-170
+//   IIDSegmentationSmallPathLoss, patch_generator contrastyou/losses/discreteMI.py:173-198,264-272
 //
 // The k x k joint of two [pixels][k] probability maps is a skinny contraction over N*H*W pixels
 // (k = 20): HBM-bound, 2*k*4 bytes read per pixel, k*k FMAs.  It is NOT reshaped into an MFMA
@@ -483,11 +484,13 @@ __device__ __forceinline__ double block_min(double v, double* sred) {
 // mode 2: vectors (IIDLoss): symmetrise + normalise to 1
 // ws: 4 arrays of TT*kk floats (p1, p2/p, dP, tmp) + (2*TT*k) marginals
 // out[0] = loss, out[1] = loss with lambda = 1 (mode 2 only); P = final joint; dJ = dloss/dJ.
-__global__ void __launch_bounds__(256)
-    iid_loss_kernel(const float* __restrict__ J, float* __restrict__ out, float* __restrict__ P,
-                    float* __restrict__ dJ, float* __restrict__ ws, int TT, int k, int mode,
-                    int symmetric, float lamda, float eps) {
-  __shared__ double sred[256];
+// The body is shared by iid_loss_kernel (one joint) and iid_patch_loss_kernel (one block per patch): out0 / out1 (may be
+// NULL) take the two loss values, dJ is multiplied by gmul (1 for the single joint, which leaves its bits as they were;
+// 1/P for the patch-wise mean).
+__device__ __forceinline__ void iid_loss_body(const float* __restrict__ J, float* __restrict__ out0,
+                                              float* __restrict__ out1, float* __restrict__ P,
+                                              float* __restrict__ dJ, float* __restrict__ ws, int TT, int k, int mode,
+                                              int symmetric, float lamda, float eps, double gmul, double* sred) {
   const int tid = threadIdx.x;
   const int kk = k * k, n = TT * kk;
   float* p1 = ws;            // per-displacement normalised (mode 1) / raw
@@ -558,8 +561,8 @@ __global__ void __launch_bounds__(256)
   l = block_sum(l, sred);
   l1 = block_sum(l1, sred);
   if (tid == 0) {
-    out[0] = (float)(l * invTT);
-    out[1] = (float)(l1 * invTT);
+    out0[0] = (float)(l * invTT);
+    if (out1) out1[0] = (float)(l1 * invTT);
   }
   if (!dJ) return;
   // ---- backward through the normalisations
@@ -582,17 +585,352 @@ __global__ void __launch_bounds__(256)
       for (int e = tid; e < kk; e += 256) dot += (double)dp1[d * kk + e] * (double)p1[d * kk + e];
       dot = block_sum(dot, sred);
       const double s = S[d];
-      for (int e = tid; e < kk; e += 256) dJ[d * kk + e] = (float)(((double)dp1[d * kk + e] - dot) / s);
+      for (int e = tid; e < kk; e += 256) dJ[d * kk + e] = (float)((((double)dp1[d * kk + e] - dot) / s) * gmul);
     }
   } else {
-    for (int e = tid; e < n; e += 256) dJ[e] = dp1[e];
+    for (int e = tid; e < n; e += 256) dJ[e] = (float)((double)dp1[e] * gmul);
   }
+}
+
+__global__ void __launch_bounds__(256)
+    iid_loss_kernel(const float* __restrict__ J, float* __restrict__ out, float* __restrict__ P,
+                    float* __restrict__ dJ, float* __restrict__ ws, int TT, int k, int mode,
+                    int symmetric, float lamda, float eps) {
+  __shared__ double sred[256];
+  iid_loss_body(J, out, out + 1, P, dJ, ws, TT, k, mode, symmetric, lamda, eps, 1.0, sred);
 }
 
 inline int joint_blocks(long npix) {
   long b = (npix + 1023) / 1024;  // >= 3 blocks per CU at the config sizes
   return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
 }
+
+// ---------------------------------------------------------------- patch-wise joints
+// IIDSegmentationSmallPathLoss / patch_generator (contrastyou/losses/discreteMI.py:173-198,264-272): the loss of
+// IIDSegmentationLoss on every square patch of the maps (side `patch`, step patch / 2), averaged.  Patch origins along an
+// axis of length L: 0, s, 2s, ... below L - p, then max(L - p, 0); every patch is clipped to the map, so all patches of
+// one call have the same extents eh x ew.  The zero padding of a displaced read is at the PATCH border.
+//   J[q][d][i][j] = sum_n sum_{(h,w) in q, (h+du,w+dv) in q} x1[n][h+du][w+dv][i] * x2[n][h][w][j]
+__host__ __device__ inline int patch_count(int L, int p) {
+  const int s = p / 2;
+  return L > p ? (L - p + s - 1) / s + 1 : 1;
+}
+__host__ __device__ inline int patch_origin(int i, int n, int L, int p) {
+  return i < n - 1 ? i * (p / 2) : (L > p ? L - p : 0);
+}
+
+// joint_fwd_multi_kernel on a patch: a block owns (patch blockIdx.z, group of <= 9 displacements blockIdx.y) and walks
+// the (image, tile of R patch rows) pairs with stride gridDim.x.  It stages the R rows of x2 and the R + 2 pad rows of x1
+// around them with pad zero columns on both sides; rows and columns outside the patch are zero.  With gridDim.x == 1 the
+// block's sums are the joint and go straight to J (times scale, rounded as joint_reduce_kernel rounds); otherwise to
+// part[q][d][blockIdx.x][k*k].
+__global__ void __launch_bounds__(256, 2)
+    joint_patch_fwd_kernel(const float* __restrict__ x1, const float* __restrict__ x2, float* __restrict__ part,
+                           float* __restrict__ J, int N, int H, int W, int k, int pad, int R, int patch, int nph,
+                           int npw, int eh, int ew, double scale) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int kp = (k + 3) & ~3, k4 = kp >> 2;
+  const int tps = k4 * k4, nsl = 256 / tps;
+  const int Wp = ew + 2 * pad, Rp = R + 2 * pad;
+  float* xs1 = sm;                          // [Rp][Wp][kp]
+  float* xs2 = xs1 + (size_t)Rp * Wp * kp;  // [R][ew][kp]
+  float* red = sm;                          // [nsl][kp*kp]: over the tiles once they are done
+  const int tid = threadIdx.x;
+  const int T = 2 * pad + 1, TT = T * T;
+  const int q = (int)blockIdx.z;
+  const int h0 = patch_origin(q / npw, nph, H, patch), w0 = patch_origin(q % npw, npw, W, patch);
+  const int d0 = (int)blockIdx.y * JM_D;
+  const int nd = TT - d0 < JM_D ? TT - d0 : JM_D;
+  const int sl = tid / tps, tt = tid - sl * tps;
+  const int ti = tt / k4, tj = tt - ti * k4;
+  const bool active = sl < nsl;
+  float acc[JM_D][4][4];
+#pragma unroll
+  for (int d = 0; d < JM_D; ++d)
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int b = 0; b < 4; ++b) acc[d][a][b] = 0.f;
+  int doff[JM_D];
+#pragma unroll
+  for (int d = 0; d < JM_D; ++d) {
+    const int dd = d0 + (d < nd ? d : 0);
+    doff[d] = ((dd / T - pad) * Wp + (dd % T - pad)) * kp;
+  }
+  const int tiles_h = (eh + R - 1) / R;
+  const int ntile = N * tiles_h;
+  if (kp == k)  // the zero columns left and right of every staged x1 row
+    for (int e = tid; e < Rp * 2 * pad * kp; e += 256) {
+      const int r = e / (2 * pad * kp), c = e - r * (2 * pad * kp);
+      const int col = c / kp < pad ? c / kp : ew + c / kp;
+      xs1[(r * Wp + col) * kp + c % kp] = 0.f;
+    }
+  for (int t = blockIdx.x; t < ntile; t += gridDim.x) {
+    const int n = t / tiles_h, r0 = (t - n * tiles_h) * R;
+    const int rows = eh - r0 < R ? eh - r0 : R;
+    __syncthreads();
+    if (kp == k) {  // a patch row is one contiguous, 16-byte aligned span of ew*k floats in memory and in the tile
+      const int row4 = ew * k / 4;
+      for (int r = 0; r < Rp; ++r) {
+        const int pr = r0 - pad + r;
+        const bool ok = r < rows + 2 * pad && pr >= 0 && pr < eh;
+        const float* src = x1 + (((long)n * H + h0 + (ok ? pr : 0)) * W + w0) * k;
+        float* dst = xs1 + (r * Wp + pad) * kp;
+        for (int e4 = tid; e4 < row4; e4 += 256) {
+          f32x4 v = {0.f, 0.f, 0.f, 0.f};
+          if (ok) v = *reinterpret_cast<const f32x4*>(src + 4 * e4);
+          *reinterpret_cast<f32x4*>(dst + 4 * e4) = v;
+        }
+      }
+      for (int e4 = tid; e4 < R * row4; e4 += 256) {
+        const int r = e4 / row4, c4 = e4 - r * row4;
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (r < rows) v = *reinterpret_cast<const f32x4*>(x2 + (((long)n * H + h0 + r0 + r) * W + w0) * k + 4 * c4);
+        *reinterpret_cast<f32x4*>(xs2 + 4 * e4) = v;
+      }
+    } else {
+      for (int e = tid; e < Rp * Wp * kp; e += 256) {
+        const int c = e % kp;
+        const int p = e / kp;
+        const int cw = p % Wp, r = p / Wp;
+        const int pr = r0 - pad + r, pc = cw - pad;
+        float v = 0.f;
+        if (c < k && r < rows + 2 * pad && pr >= 0 && pr < eh && pc >= 0 && pc < ew)
+          v = x1[(((long)n * H + h0 + pr) * W + w0 + pc) * k + c];
+        xs1[e] = v;
+      }
+      for (int e = tid; e < R * ew * kp; e += 256) {
+        const int c = e % kp;
+        const int p = e / kp;
+        const int w = p % ew, r = p / ew;
+        xs2[e] = (c < k && r < rows) ? x2[(((long)n * H + h0 + r0 + r) * W + w0 + w) * k + c] : 0.f;
+      }
+    }
+    __syncthreads();
+    if (active) {
+      int r = 0, w = sl;
+      while (w >= ew) w -= ew, ++r;
+      for (; r < rows;) {
+        const f32x4 b = *reinterpret_cast<const f32x4*>(xs2 + (r * ew + w) * kp + 4 * tj);
+        const float* a0 = xs1 + ((r + pad) * Wp + (w + pad)) * kp + 4 * ti;
+#pragma unroll
+        for (int d = 0; d < JM_D; ++d) {
+          if (d < nd) {  // wave-uniform
+            const f32x4 a = *reinterpret_cast<const f32x4*>(a0 + doff[d]);
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+              for (int j = 0; j < 4; ++j) acc[d][i][j] = fmaf(a[i], b[j], acc[d][i][j]);
+          }
+        }
+        w += nsl;
+        while (w >= ew) w -= ew, ++r;
+      }
+    }
+  }
+#pragma unroll
+  for (int d = 0; d < JM_D; ++d) {  // (no early exit: the accumulators must stay statically indexed = in registers)
+    if (d >= nd) continue;          // block-uniform
+    __syncthreads();
+    if (active) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) red[sl * kp * kp + (4 * ti + i) * kp + 4 * tj + j] = acc[d][i][j];
+    }
+    __syncthreads();
+    const size_t qd = (size_t)q * TT + d0 + d;
+    for (int e = tid; e < k * k; e += 256) {
+      const int i = e / k, j = e - i * k;
+      float s = 0.f;
+      for (int u = 0; u < nsl; ++u) s += red[u * kp * kp + i * kp + j];
+      if (gridDim.x == 1)
+        J[qd * (k * k) + e] = (float)((double)s * scale);
+      else
+        part[(qd * gridDim.x + blockIdx.x) * (k * k) + e] = s;
+    }
+  }
+}
+
+// The fallback, joint_fwd_kernel on a patch: one displacement per block (blockIdx.y), 64-pixel tiles of the patch's
+// N*eh*ew pixels, the displaced read bounds-tested against the patch.  Same partial layout.
+__global__ void __launch_bounds__(256)
+    joint_patch_fwd1_kernel(const float* __restrict__ x1, const float* __restrict__ x2, float* __restrict__ part,
+                            float* __restrict__ J, int N, int H, int W, int k, int pad, int patch, int nph, int npw,
+                            int eh, int ew, double scale) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int kp = (k + 3) & ~3, k4 = kp >> 2;
+  const int tps = k4 * k4, nsl = 256 / tps;
+  float* xs1 = sm;                 // [J_P][kp]
+  float* xs2 = sm + J_P * kp;      // [J_P][kp]
+  float* red = sm + 2 * J_P * kp;  // [nsl][kp*kp]
+  const int tid = threadIdx.x;
+  const int T = 2 * pad + 1, TT = T * T;
+  const int q = (int)blockIdx.z;
+  const int h0 = patch_origin(q / npw, nph, H, patch), w0 = patch_origin(q % npw, npw, W, patch);
+  const int du = (int)blockIdx.y / T - pad, dv = (int)blockIdx.y % T - pad;
+  const int sl = tid / tps, tt = tid - sl * tps;
+  const int ti = tt / k4, tj = tt - ti * k4;
+  const bool active = sl < nsl;
+  float acc[4][4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) acc[a][b] = 0.f;
+  const long npp = (long)N * eh * ew;
+  const long per = ((npp + gridDim.x - 1) / gridDim.x + J_P - 1) / J_P * J_P;
+  const long p0 = (long)blockIdx.x * per;
+  const long p1 = p0 + per < npp ? p0 + per : npp;
+  for (long pt = p0; pt < p1; pt += J_P) {
+    __syncthreads();
+    for (int e = tid; e < J_P * kp; e += 256) {
+      const int p = e / kp, c = e - p * kp;
+      const long pp = pt + p;
+      float a = 0.f, b = 0.f;
+      if (pp < p1 && c < k) {
+        const int wl = (int)(pp % ew);
+        const long t = pp / ew;
+        const int hl = (int)(t % eh);
+        const long n = t / eh;
+        b = x2[((n * H + h0 + hl) * W + w0 + wl) * k + c];
+        const int hh = hl + du, ww = wl + dv;
+        if (hh >= 0 && hh < eh && ww >= 0 && ww < ew) a = x1[((n * H + h0 + hh) * W + w0 + ww) * k + c];
+      }
+      xs1[e] = a;
+      xs2[e] = b;
+    }
+    __syncthreads();
+    if (active) {
+      for (int p = sl; p < J_P; p += nsl) {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(xs1 + p * kp + 4 * ti);
+        const f32x4 b = *reinterpret_cast<const f32x4*>(xs2 + p * kp + 4 * tj);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(a[i], b[j], acc[i][j]);
+      }
+    }
+  }
+  __syncthreads();
+  if (active) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) red[sl * kp * kp + (4 * ti + i) * kp + 4 * tj + j] = acc[i][j];
+  }
+  __syncthreads();
+  const size_t qd = (size_t)q * TT + blockIdx.y;
+  for (int e = tid; e < k * k; e += 256) {
+    const int i = e / k, j = e - i * k;
+    float s = 0.f;
+    for (int u = 0; u < nsl; ++u) s += red[u * kp * kp + i * kp + j];
+    if (gridDim.x == 1)
+      J[qd * (k * k) + e] = (float)((double)s * scale);
+    else
+      part[(qd * gridDim.x + blockIdx.x) * (k * k) + e] = s;
+  }
+}
+
+// one block per patch on J[P][TT][k][k]: losses[q], Pj[q] (may be NULL) and dJ[q] (may be NULL) = (1/P) dloss_q/dJ_q
+__global__ void __launch_bounds__(256)
+    iid_patch_loss_kernel(const float* __restrict__ J, float* __restrict__ losses, float* __restrict__ Pj,
+                          float* __restrict__ dJ, float* __restrict__ ws, size_t ws_floats, int TT, int k, int mode,
+                          float lamda, float eps) {
+  __shared__ double sred[256];
+  const size_t q = blockIdx.x, n = (size_t)TT * k * k;
+  iid_loss_body(J + q * n, losses + q, nullptr, Pj ? Pj + q * n : nullptr, dJ ? dJ + q * n : nullptr,
+                ws + q * ws_floats, TT, k, mode, 0, lamda, eps, 1.0 / (double)gridDim.x, sred);
+}
+
+// loss[0] = mean of losses[P]: strided f64 sums per thread, then the block tree -- a fixed order
+__global__ void __launch_bounds__(256)
+    patch_mean_kernel(const float* __restrict__ losses, float* __restrict__ loss, int P) {
+  __shared__ double sred[256];
+  double s = 0.0;
+  for (int q = threadIdx.x; q < P; q += 256) s += (double)losses[q];
+  s = block_sum(s, sred);
+  if (threadIdx.x == 0) loss[0] = (float)(s / (double)P);
+}
+
+// Adjoint of the patch joints in gather form: every output pixel walks the patches that contain it in ascending patch
+// order and, inside each, the displacements whose other end lies in the same patch.  dJ is read from memory (P joints do
+// not fit the LDS); neighbouring pixels read the same rows of it.
+//   which = 0: dx1[pix][i] = g*scale * sum_q sum_{d,j} dJ[q][d][i][j] * x2[pix - disp(d)][j]
+//   which = 1: dx2[pix][j] = g*scale * sum_q sum_{d,i} dJ[q][d][i][j] * x1[pix + disp(d)][i]
+template <int V>  // V = 4: one thread per (pixel, 4 channels), k % 4 == 0; V = 1: one thread per (pixel, channel)
+__global__ void __launch_bounds__(256)
+    joint_patch_bwd_kernel(const float* __restrict__ other, const float* __restrict__ dJ,
+                           const float* __restrict__ gscale, float* __restrict__ dx, int N, int H, int W, int k, int pad,
+                           int patch, int nph, int npw, int eh, int ew, float scale, int which) {
+  const int T = 2 * pad + 1, TT = T * T, kv = k / V, kk = k * k;
+  const float g = gscale[0] * scale;
+  const long total = (long)N * H * W * kv;
+  const int sgn = which ? 1 : -1;
+  for (long e = blockIdx.x * 256L + threadIdx.x; e < total; e += (long)gridDim.x * 256L) {
+    const int c = (int)(e % kv) * V;
+    const long pix = e / kv;
+    const int w = (int)(pix % W);
+    const int h = (int)((pix / W) % H);
+    float s[V];
+#pragma unroll
+    for (int u = 0; u < V; ++u) s[u] = 0.f;
+    for (int ih = 0; ih < nph; ++ih) {
+      const int lh = h - patch_origin(ih, nph, H, patch);
+      if (lh < 0 || lh >= eh) continue;
+      for (int iw = 0; iw < npw; ++iw) {
+        const int lw = w - patch_origin(iw, npw, W, patch);
+        if (lw < 0 || lw >= ew) continue;
+        const float* dq = dJ + (size_t)(ih * npw + iw) * TT * kk;
+        // 0 <= lh + sgn*du < eh  and  |du| <= pad
+        const int ulo = which ? max(-pad, -lh) : max(-pad, lh - eh + 1), uhi = which ? min(pad, eh - 1 - lh) : min(pad, lh);
+        const int vlo = which ? max(-pad, -lw) : max(-pad, lw - ew + 1), vhi = which ? min(pad, ew - 1 - lw) : min(pad, lw);
+        for (int du = ulo; du <= uhi; ++du)
+          for (int dv = vlo; dv <= vhi; ++dv) {
+            const float* o = other + (pix + sgn * ((long)du * W + dv)) * k;
+            const float* m = dq + ((du + pad) * T + dv + pad) * kk;
+            if (V == 4) {
+              for (int j4 = 0; j4 < kv; ++j4) {
+                const f32x4 ov = *reinterpret_cast<const f32x4*>(o + 4 * j4);
+                if (which) {
+#pragma unroll
+                  for (int t = 0; t < 4; ++t) {
+                    const f32x4 mv = *reinterpret_cast<const f32x4*>(m + (4 * j4 + t) * k + c);
+#pragma unroll
+                    for (int u = 0; u < V; ++u) s[u] = fmaf(mv[u], ov[t], s[u]);
+                  }
+                } else {
+#pragma unroll
+                  for (int u = 0; u < V; ++u) {
+                    const f32x4 mv = *reinterpret_cast<const f32x4*>(m + (c + u) * k + 4 * j4);
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) s[u] = fmaf(mv[t], ov[t], s[u]);
+                  }
+                }
+              }
+            } else if (which) {
+              for (int i = 0; i < k; ++i) s[0] = fmaf(m[i * k + c], o[i], s[0]);
+            } else {
+              for (int j = 0; j < k; ++j) s[0] = fmaf(m[c * k + j], o[j], s[0]);
+            }
+          }
+      }
+    }
+    if (V == 4) {
+      f32x4 r = {g * s[0], g * s[V > 1 ? 1 : 0], g * s[V > 2 ? 2 : 0], g * s[V > 3 ? 3 : 0]};
+      *reinterpret_cast<f32x4*>(dx + pix * k + c) = r;
+    } else {
+      dx[e] = g * s[0];
+    }
+  }
+}
+
+constexpr int JP_PLAN = 16;       // values of cy_joint_patch_plan
+constexpr int JP_TARGET = 1024;   // blocks the staged forward aims at (4 per CU) before a block walks several tiles
+
+struct patch_plan {
+  int P, nph, npw, eh, ew, kernel, R, tiles_h, ntile, nbx, grid_y, fwd_lds, fwd_vec, staged_fits, bwd_kernel, bwd_grid;
+  size_t ws_bytes;
+};
 
 constexpr int J_FWD_LDS = 150 * 1024;  // the staged tile of joint_fwd_multi_kernel (raised limit)
 constexpr int J_BWD_LDS = 64 * 1024;   // the dJ chunk of the backward kernels (default limit)
@@ -768,6 +1106,149 @@ int cy_iid_loss(const float* J, float* out2, float* P, float* dJ, int TT, int k,
   hipLaunchKernelGGL(iid_loss_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, J, out2, P, dJ,
                      (float*)ws, TT, k, mode, symmetric, lamda, eps);
   CY_CHECK_LAUNCH();
+  return CY_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// The launch rule of the patch-wise entries, once.  kernel: -1 = the rule's choice, 0 / 1 = that forward kernel.
+int patch_plan_of(int N, int H, int W, int k, int pad, int patch, int kernel, patch_plan* out) {
+  if (N <= 0 || H <= 0 || W <= 0 || kernel < -1 || kernel > 1) return CY_ERR_ARG;
+  if (k < 1 || k > J_KMAX || pad < 0 || patch < 2) return CY_ERR_SHAPE;
+  patch_plan p = {};
+  p.nph = patch_count(H, patch);
+  p.npw = patch_count(W, patch);
+  p.eh = H < patch ? H : patch;
+  p.ew = W < patch ? W : patch;
+  if (pad >= p.eh || pad >= p.ew) return CY_ERR_SHAPE;
+  if ((long)p.nph * p.npw > 65535) return CY_ERR_SHAPE;  // gridDim.z
+  p.P = p.nph * p.npw;
+  const int T = 2 * pad + 1, TT = T * T;
+  if ((long)p.P * TT * k * k > 0x7fffffffL) return CY_ERR_SHAPE;  // J is indexed with 32 bits in the reduction
+  const int kp = (k + 3) & ~3, k4 = kp / 4, nsl = 256 / (k4 * k4);
+  const size_t red = (size_t)nsl * kp * kp * sizeof(float);
+  int R = 256 / p.ew;
+  R = R < 1 ? 1 : (R > p.eh ? p.eh : R);
+  size_t smem = ((size_t)(R + 2 * pad) * (p.ew + 2 * pad) * kp + (size_t)R * p.ew * kp) * sizeof(float);
+  if (smem < red) smem = red;
+  p.staged_fits = smem <= (size_t)J_FWD_LDS;
+  if (kernel == 1 && !p.staged_fits) return CY_ERR_SHAPE;
+  p.kernel = kernel < 0 ? p.staged_fits : kernel;
+  const int tiles_h = cy_cdiv(p.eh, R), ntile = N * tiles_h, groups = cy_cdiv(TT, JM_D);
+  int nbx1 = cy_cdiv(JP_TARGET, (long)p.P * groups);
+  nbx1 = nbx1 > ntile ? ntile : nbx1;
+  const int nbx0 = joint_blocks((long)N * p.eh * p.ew);
+  if (p.kernel == 1) {
+    p.R = R;
+    p.tiles_h = tiles_h;
+    p.ntile = ntile;
+    p.nbx = nbx1;
+    p.grid_y = groups;
+    p.fwd_lds = (int)smem;
+    p.fwd_vec = kp == k;
+  } else {
+    p.ntile = cy_cdiv((long)N * p.eh * p.ew, J_P);
+    p.nbx = nbx0;
+    p.grid_y = TT;
+    p.fwd_lds = (int)(2 * J_P * kp * sizeof(float) + red);
+  }
+  // the partial joints of the forward; a forward with one block per (patch, group) writes J itself
+  p.ws_bytes = p.nbx > 1 ? (size_t)p.P * TT * p.nbx * k * k * sizeof(float) : 16;
+  p.bwd_kernel = (k & 3) == 0;
+  p.bwd_grid = grid_for(p.bwd_kernel ? (long)N * H * W * (k / 4) : (long)N * H * W * k);
+  *out = p;
+  return CY_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cy_joint_patch_plan(int N, int H, int W, int k, int pad, int patch, int kernel, int32_t* plan) {
+  if (!plan) return CY_ERR_ARG;
+  patch_plan p;
+  const int rc = patch_plan_of(N, H, W, k, pad, patch, kernel, &p);
+  if (rc != CY_OK) return rc;
+  const int v[JP_PLAN] = {p.P, p.nph, p.npw, p.eh, p.ew, p.kernel, p.R, p.tiles_h, p.ntile, p.nbx, p.grid_y, p.fwd_lds,
+                          p.fwd_vec, p.staged_fits, p.bwd_kernel, p.bwd_grid};
+  for (int i = 0; i < JP_PLAN; ++i) plan[i] = v[i];
+  return CY_OK;
+}
+
+size_t cy_joint_patch_ws_bytes(int N, int H, int W, int k, int pad, int patch, int kernel) {
+  patch_plan p;
+  if (patch_plan_of(N, H, W, k, pad, patch, kernel, &p) != CY_OK) return 0;
+  return p.ws_bytes;
+}
+
+int cy_joint_patch_fwd(const float* x1, const float* x2, float* J, int N, int H, int W, int k, int pad, int patch,
+                       int normalise, int kernel, void* ws, size_t ws_bytes, void* stream) {
+  if (!x1 || !x2 || !J) return CY_ERR_ARG;
+  patch_plan p;
+  const int rc = patch_plan_of(N, H, W, k, pad, patch, kernel, &p);
+  if (rc != CY_OK) return rc;
+  if (!ws || ws_bytes < p.ws_bytes) return CY_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const int T = 2 * pad + 1, TT = T * T;
+  const double scale = normalise ? 1.0 / ((double)N * p.eh * p.ew) : 1.0;
+  if (p.kernel == 1) {
+    if (!cy_lds_limit_once<joint_patch_fwd_kernel>(J_FWD_LDS)) return CY_ERR_LAUNCH;
+    hipLaunchKernelGGL(joint_patch_fwd_kernel, dim3(p.nbx, p.grid_y, p.P), dim3(256), (size_t)p.fwd_lds, st, x1, x2,
+                       (float*)ws, J, N, H, W, k, pad, p.R, patch, p.nph, p.npw, p.eh, p.ew, scale);
+  } else {
+    hipLaunchKernelGGL(joint_patch_fwd1_kernel, dim3(p.nbx, p.grid_y, p.P), dim3(256), (size_t)p.fwd_lds, st, x1, x2,
+                       (float*)ws, J, N, H, W, k, pad, patch, p.nph, p.npw, p.eh, p.ew, scale);
+  }
+  CY_CHECK_LAUNCH();
+  if (p.nbx > 1) {
+    hipLaunchKernelGGL(joint_reduce_kernel, dim3(cy_cdiv((long)p.P * TT * k * k, 4)), dim3(256), 0, st,
+                       (const float*)ws, J, p.P * TT, p.nbx, k * k, scale);
+    CY_CHECK_LAUNCH();
+  }
+  return CY_OK;
+}
+
+size_t cy_iid_patch_loss_ws_bytes(int P, int TT, int k) {
+  if (P <= 0 || TT <= 0 || k <= 0 || k > J_KMAX) return 0;
+  return (size_t)P * cy_iid_loss_ws_bytes(TT, k);
+}
+
+int cy_iid_patch_loss(const float* J, float* loss, float* losses, float* Pj, float* dJ, int P, int TT, int k, int mode,
+                      float lamda, float eps, void* ws, size_t ws_bytes, void* stream) {
+  if (!J || !loss || !losses || P <= 0 || TT <= 0 || k <= 0) return CY_ERR_ARG;
+  if (mode < 0 || mode > 1 || k > J_KMAX) return CY_ERR_SHAPE;
+  if (!ws || ws_bytes < cy_iid_patch_loss_ws_bytes(P, TT, k)) return CY_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(iid_patch_loss_kernel, dim3(P), dim3(256), 0, st, J, losses, Pj, dJ, (float*)ws,
+                     cy_iid_loss_ws_bytes(TT, k) / sizeof(float), TT, k, mode, lamda, eps);
+  CY_CHECK_LAUNCH();
+  hipLaunchKernelGGL(patch_mean_kernel, dim3(1), dim3(256), 0, st, (const float*)losses, loss, P);
+  CY_CHECK_LAUNCH();
+  return CY_OK;
+}
+
+int cy_joint_patch_bwd(const float* x1, const float* x2, const float* dJ, const float* gscale, float* dx1, float* dx2,
+                       int N, int H, int W, int k, int pad, int patch, int normalise, void* stream) {
+  if (!x1 || !x2 || !dJ || !gscale) return CY_ERR_ARG;
+  patch_plan p;
+  const int rc = patch_plan_of(N, H, W, k, pad, patch, -1, &p);
+  if (rc != CY_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const float scale = normalise ? (float)(1.0 / ((double)N * p.eh * p.ew)) : 1.f;
+  for (int which = 0; which < 2; ++which) {
+    float* dst = which ? dx2 : dx1;
+    const float* other = which ? x1 : x2;
+    if (!dst) continue;
+    if (p.bwd_kernel)
+      hipLaunchKernelGGL(joint_patch_bwd_kernel<4>, dim3(p.bwd_grid), dim3(256), 0, st, other, dJ, gscale, dst, N, H, W,
+                         k, pad, patch, p.nph, p.npw, p.eh, p.ew, scale, which);
+    else
+      hipLaunchKernelGGL(joint_patch_bwd_kernel<1>, dim3(p.bwd_grid), dim3(256), 0, st, other, dJ, gscale, dst, N, H, W,
+                         k, pad, patch, p.nph, p.npw, p.eh, p.ew, scale, which);
+    CY_CHECK_LAUNCH();
+  }
   return CY_OK;
 }
 

@@ -1313,6 +1313,133 @@ class IIDFn(torch.autograd.Function):
         return d1, d2, None, None, None, None, None
 
 
+class IIDPatchFn(torch.autograd.Function):
+    """patch-wise IIC (IIDSegmentationSmallPathLoss, contrastyou/losses/discreteMI.py:173-198) in one autograd node:
+    the joints of all patches in one launch, one block per patch for the losses, their mean.
+    x1, x2: f32 [N,H,W,k] contiguous.  Returns (loss, per-patch losses [P], final joints [P,T*T,k,k])."""
+
+    @staticmethod
+    def forward(ctx, x1: Tensor, x2: Tensor, pad: int, patch: int, lamda: float, eps: float):
+        ops.require_gpu(x1, x2)
+        normalise = pad == 0
+        J = ops.joint_patch_fwd(x1, x2, pad, patch, normalise)
+        need = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        loss, losses, Pj, dJ = ops.iid_patch_loss(J, 0 if pad == 0 else 1, lamda, eps, want_grad=need)
+        ctx.save_for_backward(x1, x2, dJ)
+        ctx.cfg = (pad, patch, normalise)
+        ctx.mark_non_differentiable(losses, Pj)
+        return loss[0], losses, Pj
+
+    @staticmethod
+    def backward(ctx, g: Tensor, _gl, _gP):
+        x1, x2, dJ = ctx.saved_tensors
+        pad, patch, normalise = ctx.cfg
+        gs = g.reshape(1).float().contiguous()
+        d1, d2 = ops.joint_patch_bwd(x1, x2, dJ, gs, pad, patch, normalise, ctx.needs_input_grad[0],
+                                     ctx.needs_input_grad[1])
+        return d1, d2, None, None, None, None
+
+
+class PUIFn(torch.autograd.Function):
+    """PUILoss (contrastyou/losses/pica_loss.py:10-39) on f32 [N,K] contiguous rows: the numerator from cy_joint_fwd, the
+    column norms and means from one column reduction, one finishing block; the gradient flows back through all three."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, y: Tensor, lamda: float):
+        need = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        out, dJ, coef = ops.pui_loss(x, y, lamda, want_grad=need)
+        ctx.save_for_backward(x, y, dJ, coef)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        x, y, dJ, coef = ctx.saved_tensors
+        dx, dy = ops.pui_loss_bwd(x, y, dJ, coef, g.reshape(1).float().contiguous(), ctx.needs_input_grad[0],
+                                  ctx.needs_input_grad[1])
+        return dx, dy, None
+
+
+class PUISegFn(torch.autograd.Function):
+    """PUISegLoss (contrastyou/losses/pica_loss.py:42-85) on f32 [N,H,W,k] contiguous maps: cy_joint_fwd, the streaming
+    balance term over x1, one finishing block."""
+
+    @staticmethod
+    def forward(ctx, x1: Tensor, x2: Tensor, pad: int, lamda: float):
+        need = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        out, dJ = ops.puiseg_loss(x1, x2, pad, lamda, want_grad=need)
+        ctx.save_for_backward(x1, x2, dJ)
+        ctx.cfg = (pad, lamda)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        x1, x2, dJ = ctx.saved_tensors
+        pad, lamda = ctx.cfg
+        d1, d2 = ops.puiseg_loss_bwd(x1, x2, dJ, g.reshape(1).float().contiguous(), pad, lamda,
+                                     ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return d1, d2, None, None
+
+
+def _jsd_layout(t: Tensor):
+    """-> (buffer, R, C, S, shape of the unreduced output, back): rows and NHWC maps are read as [R][C] (S = 1), every
+    other map as contiguous NCHW with S positions per image; `back` maps a gradient buffer to the input's shape"""
+    Cc = t.shape[1]
+    if t.dim() == 2:
+        b = t.contiguous()
+        return b, b.shape[0], Cc, 1, (t.shape[0],), lambda gr: gr
+    if ops.is_nhwc(t) and not t.is_contiguous():
+        b = t.permute(0, 2, 3, 1)  # contiguous [N,H,W,C]
+        return b, b.numel() // Cc, Cc, 1, (t.shape[0], *t.shape[2:]), lambda gr: gr.permute(0, 3, 1, 2)
+    b = t.contiguous()
+    S = b.numel() // (b.shape[0] * Cc)
+    return b, b.shape[0] * S, Cc, S, (t.shape[0], *t.shape[2:]), lambda gr: gr
+
+
+class JSDFn(torch.autograd.Function):
+    """JSD_div (contrastyou/losses/kl.py:142-174): Entropy(mean of the maps) - mean of the Entropies, one fused pass over
+    the maps each way.  apply(reduction, eps, *maps)"""
+
+    @staticmethod
+    def forward(ctx, reduction: str, eps: float, *maps: Tensor):
+        ops.require_gpu(*maps)
+        first, R, Cc, S, out_shape, back = _jsd_layout(maps[0])
+        bufs = [first]
+        for t in maps[1:]:  # the layout of the first map for all
+            if S == 1 and t.dim() > 2:
+                bufs.append(t.permute(0, 2, 3, 1).contiguous())
+            else:
+                bufs.append(t.contiguous())
+        out = ops.jsd_fwd(bufs, R, Cc, S, reduction, eps)
+        ctx.save_for_backward(*bufs)
+        ctx.cfg = (R, Cc, S, reduction, eps, back)
+        return out.view(out_shape) if reduction == "none" else out[0]
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        R, Cc, S, reduction, eps, back = ctx.cfg
+        grads = ops.jsd_bwd(ctx.saved_tensors, g.reshape(-1).float().contiguous(), ctx.needs_input_grad[2:], R, Cc, S,
+                            reduction, eps)
+        return (None, None, *[None if gr is None else back(gr) for gr in grads])
+
+
+class EntropyPriorFn(torch.autograd.Function):
+    """EntropyPrior (contrastyou/losses/kl.py:63-78): log C - KL_div()(prior, x) on f32 [R,C] rows with a broadcast
+    prior row (None: uniform), which is a constant."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, prior, eps: float):
+        x = x.contiguous()
+        out = ops.entropy_prior_fwd(x, prior, eps)
+        ctx.save_for_backward(x, prior)
+        ctx.eps = eps
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        x, prior = ctx.saved_tensors
+        return ops.entropy_prior_bwd(x, prior, g.reshape(1).float().contiguous(), ctx.eps), None, None
+
+
 class JointFn(torch.autograd.Function):
     """the k x k joint of two probability maps, (1/npix) sum_p x1[p,:] x2[p,:]^T, as its own autograd node
     (compute_joint_2D_with_padding_zeros, contrastyou/losses/discreteMI.py:246-261, before symmetrisation):

@@ -2608,6 +2608,169 @@ def iid_loss(J: Tensor, mode: int, symmetric: bool, lamda: float, eps: float, wa
     return out2, P, dJ
 
 
+_JOINT_PATCH_PLAN = ("P", "nph", "npw", "eh", "ew", "fwd_kernel", "R", "tiles_h", "ntile", "nbx", "grid_y", "fwd_lds",
+                     "fwd_vec", "staged_fits", "bwd_kernel", "bwd_grid")
+JOINT_PATCH_KERNELS = {None: -1, "per_displacement": 0, "staged": 1}  # the forward kernel: the rule's choice, or forced
+
+
+def joint_patch_plan(N: int, H: int, W: int, k: int, pad: int, patch: int, kernel: Optional[str] = None) -> dict:
+    """the launch rule of the patch-wise joint kernels (host-side query, no GPU needed): the values of
+    cy_joint_patch_plan by name, and "ws_bytes", the forward's workspace.  What the launches refuse raises
+    HipKernelError with their status."""
+    plan = (C.c_int32 * 16)()
+    _lib.call("cy_joint_patch_plan", int(N), int(H), int(W), int(k), int(pad), int(patch),
+              JOINT_PATCH_KERNELS[kernel], plan)
+    out = dict(zip(_JOINT_PATCH_PLAN, (int(v) for v in plan)))
+    out["ws_bytes"] = int(_lib.load().cy_joint_patch_ws_bytes(int(N), int(H), int(W), int(k), int(pad), int(patch),
+                                                              JOINT_PATCH_KERNELS[kernel]))
+    return out
+
+
+def joint_patch_fwd(x1: Tensor, x2: Tensor, pad: int, patch: int, normalise: bool, kernel: Optional[str] = None,
+                    J: Optional[Tensor] = None) -> Tensor:
+    """x1, x2: f32 NHWC-contiguous [N,H,W,k] buffers -> J f32 [P, T*T, k, k], the displaced joint of every patch of
+    side `patch` (step patch // 2), zero-padded at the patch border; `J` may be given as a contiguous f32 view to write
+    into, `kernel` forces a forward kernel (JOINT_PATCH_KERNELS)"""
+    require_gpu(x1, x2)
+    N, H, W, k = x1.shape
+    assert x2.shape == x1.shape, (x1.shape, x2.shape)
+    plan = joint_patch_plan(N, H, W, k, pad, patch, kernel)
+    T = 2 * pad + 1
+    J = _f32(plan["P"] * T * T * k * k, x1.device) if J is None else J
+    ws = _ws(plan["ws_bytes"], x1.device)
+    _lib.call("cy_joint_patch_fwd", x1.data_ptr(), x2.data_ptr(), J.data_ptr(), N, H, W, k, int(pad), int(patch),
+              int(normalise), JOINT_PATCH_KERNELS[kernel], ws.data_ptr(), plan["ws_bytes"], _stream())
+    return J.view(plan["P"], T * T, k, k)
+
+
+def iid_patch_loss(J: Tensor, mode: int, lamda: float, eps: float, want_grad: bool = True, want_joint: bool = True,
+                   out: Optional[Tuple[Tensor, ...]] = None):
+    """J: f32 [P, TT, k, k] -> (loss [1] = mean of the patch losses, losses [P], Pj [P,TT,k,k] final joints or None,
+    dJ [P,TT,k,k] = d loss / d J or None); `out` may give the four as contiguous f32 views to write into"""
+    require_gpu(J)
+    P, TT, k = J.shape[0], J.shape[1], J.shape[2]
+    if out is None:
+        out = (_f32(1, J.device), _f32(P, J.device), torch.empty_like(J) if want_joint else None,
+               torch.empty_like(J) if want_grad else None)
+    loss, losses, Pj, dJ = out
+    nbytes = _lib.load().cy_iid_patch_loss_ws_bytes(P, TT, k)
+    ws = _ws(nbytes, J.device)
+    _lib.call("cy_iid_patch_loss", J.data_ptr(), loss.data_ptr(), losses.data_ptr(), _ptr(Pj), _ptr(dJ), P, TT, k,
+              int(mode), float(lamda), float(eps), ws.data_ptr(), nbytes, _stream())
+    return loss, losses, Pj, dJ
+
+
+def joint_patch_bwd(x1: Tensor, x2: Tensor, dJ: Tensor, gscale: Tensor, pad: int, patch: int, normalise: bool,
+                    need1: bool = True, need2: bool = True, d1: Optional[Tensor] = None, d2: Optional[Tensor] = None):
+    """-> (dx1, dx2) [N,H,W,k] = gscale[0] * the adjoint of joint_patch_fwd applied to dJ; either may be skipped"""
+    require_gpu(x1, x2, dJ, gscale)
+    N, H, W, k = x1.shape
+    d1 = (torch.empty_like(x1) if d1 is None else d1) if need1 else None
+    d2 = (torch.empty_like(x2) if d2 is None else d2) if need2 else None
+    _lib.call("cy_joint_patch_bwd", x1.data_ptr(), x2.data_ptr(), dJ.data_ptr(), gscale.data_ptr(), _ptr(d1), _ptr(d2),
+              N, H, W, k, int(pad), int(patch), int(normalise), _stream())
+    return d1, d2
+
+
+# --------------------------------------------------------------------------- PICA, JSD, entropy prior
+PICA_KMAX = 64  # classes of csrc/cy_pica.hip
+JSD_MAPS = (2, 8)  # fewest and most maps of cy_jsd_*
+REDUCTIONS = {"none": 0, "mean": 1, "sum": 2}
+
+
+def pui_loss(x: Tensor, y: Tensor, lamda: float, want_grad: bool = True):
+    """x, y: f32 [N, K] contiguous rows -> (out [1], dJ [K,K] or None, coef [3,K]) of cy_pui_loss"""
+    require_gpu(x, y)
+    N, K = x.shape
+    J = joint_fwd(x, y, N, 1, 1, K, 0, False)
+    stats = _f32(3 * K, x.device)
+    _lib.call("cy_pui_stats", x.data_ptr(), y.data_ptr(), stats.data_ptr(), N, K, _stream())
+    out, coef = _f32(1, x.device), _f32(3 * K, x.device)
+    dJ = torch.empty_like(J) if want_grad else None
+    _lib.call("cy_pui_loss", J.data_ptr(), stats.data_ptr(), out.data_ptr(), _ptr(dJ), coef.data_ptr(), N, K,
+              float(lamda), _stream())
+    return out, dJ, coef.view(3, K)
+
+
+def pui_loss_bwd(x: Tensor, y: Tensor, dJ: Tensor, coef: Tensor, g: Tensor, need_x: bool, need_y: bool):
+    N, K = x.shape
+    dx, dy = joint_bwd(x, y, dJ, g, N, 1, 1, K, 0, False, need_x, need_y)
+    if need_x:
+        _lib.call("cy_rows_axpb", x.data_ptr(), coef[0].data_ptr(), coef[2].data_ptr(), g.data_ptr(), dx.data_ptr(),
+                  N, K, _stream())
+    if need_y:
+        _lib.call("cy_rows_axpb", y.data_ptr(), coef[1].data_ptr(), None, g.data_ptr(), dy.data_ptr(), N, K, _stream())
+    return dx, dy
+
+
+def puiseg_loss(x1: Tensor, x2: Tensor, pad: int, lamda: float, want_grad: bool = True):
+    """x1, x2: f32 NHWC-contiguous [N,H,W,k] -> (out [1], dJ [T*T,k,k] or None) of cy_puiseg_loss"""
+    require_gpu(x1, x2)
+    N, H, W, k = x1.shape
+    J = joint_fwd(x1, x2, N, H, W, k, pad, False)
+    TT, M = J.shape[0], N * H * W
+    out = _f32(1, x1.device)
+    dJ = torch.empty_like(J) if want_grad else None
+    nbytes = _lib.load().cy_puiseg_ws_bytes(M, TT, k)
+    ws = _ws(nbytes, x1.device)
+    _lib.call("cy_puiseg_loss", J.data_ptr(), x1.data_ptr(), out.data_ptr(), _ptr(dJ), TT, k, M, float(lamda),
+              ws.data_ptr(), nbytes, _stream())
+    return out, dJ
+
+
+def puiseg_loss_bwd(x1: Tensor, x2: Tensor, dJ: Tensor, g: Tensor, pad: int, lamda: float, need1: bool, need2: bool):
+    N, H, W, k = x1.shape
+    d1, d2 = joint_bwd(x1, x2, dJ, g, N, H, W, k, pad, False, need1, need2)
+    if need1:
+        _lib.call("cy_puiseg_balance_bwd", x1.data_ptr(), g.data_ptr(), d1.data_ptr(), N * H * W, k, float(lamda),
+                  _stream())
+    return d1, d2
+
+
+def _ptr_table(ts):
+    return (C.c_void_p * len(ts))(*[_ptr(t) for t in ts])
+
+
+def jsd_fwd(maps, R: int, Cc: int, S: int, reduction: str, eps: float) -> Tensor:
+    """maps: 2..8 f32 buffers of one layout (cy_jsd_fwd) -> out [R] ("none") or [1]"""
+    require_gpu(*maps)
+    dev = maps[0].device
+    out = _f32(R if reduction == "none" else 1, dev)
+    nbytes = _lib.load().cy_stream_sum_ws_bytes(R)
+    ws = _ws(nbytes, dev)
+    _lib.call("cy_jsd_fwd", _ptr_table(maps), len(maps), out.data_ptr(), R, Cc, S, REDUCTIONS[reduction], float(eps),
+              ws.data_ptr(), nbytes, _stream())
+    return out
+
+
+def jsd_bwd(maps, g: Tensor, needs, R: int, Cc: int, S: int, reduction: str, eps: float):
+    """g: f32 [R] ("none") or [1] on the device -> the gradients of the maps asked for (None for the others)"""
+    grads = [torch.empty_like(t) if need else None for t, need in zip(maps, needs)]
+    _lib.call("cy_jsd_bwd", _ptr_table(maps), len(maps), g.data_ptr(), _ptr_table(grads), R, Cc, S,
+              REDUCTIONS[reduction], float(eps), _stream())
+    return grads
+
+
+def entropy_prior_fwd(x: Tensor, prior: Optional[Tensor], eps: float) -> Tensor:
+    """x: f32 [R, C] contiguous rows, prior f32 [C] or None (uniform) -> out [1] = log C - KL(prior, x)"""
+    require_gpu(x, prior)
+    R, Cc = x.shape
+    out = _f32(1, x.device)
+    nbytes = _lib.load().cy_stream_sum_ws_bytes(R)
+    ws = _ws(nbytes, x.device)
+    _lib.call("cy_entropy_prior_fwd", x.data_ptr(), _ptr(prior), out.data_ptr(), R, Cc, float(eps), ws.data_ptr(),
+              nbytes, _stream())
+    return out
+
+
+def entropy_prior_bwd(x: Tensor, prior: Optional[Tensor], g: Tensor, eps: float) -> Tensor:
+    R, Cc = x.shape
+    dx = torch.empty_like(x)
+    _lib.call("cy_entropy_prior_bwd", x.data_ptr(), _ptr(prior), g.data_ptr(), dx.data_ptr(), R, Cc, float(eps),
+              _stream())
+    return dx
+
+
 # --------------------------------------------------------------------------- GroupNorm + SiLU, bilinear
 def gn_silu_fwd(y: Tensor, bias: Optional[Tensor], gamma: Tensor, beta: Tensor, groups: int, eps: float):
     require_gpu(y, gamma, beta)

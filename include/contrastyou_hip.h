@@ -955,6 +955,93 @@ int cy_group_softmax_plan(long M, int S, int k, cy_group_softmax_plan_t* out);
 size_t cy_iid_loss_ws_bytes(int TT, int k);
 int cy_iid_loss(const float* J, float* out2, float* P, float* dJ, int TT, int k, int mode,
                 int symmetric, float lamda, float eps, void* ws, size_t ws_bytes, void* stream);
+/* Patch-wise IIC (IIDSegmentationSmallPathLoss / patch_generator, contrastyou/losses/discreteMI.py:173-198,264-272;
+ * entries added to ABI v18 -- no existing signature changed and no struct added).  The maps are cut into square patches
+ * of side `patch` with step patch / 2: the origins along an axis of length L are 0, s, 2s, ... below L - patch, then
+ * max(L - patch, 0); every patch is clipped to the map, so all P = nph * npw patches have the same extents eh x ew =
+ * min(patch, H) x min(patch, W).  Patch q = ih * npw + iw.  With d = (du+pad)*T + (dv+pad), T = 2 pad + 1:
+ *   J[q][d][i][j] = scale * sum_n sum_{(h,w) in q, (h+du,w+dv) in q} x1[n][h+du][w+dv][i] * x2[n][h][w][j]
+ * -- the zero padding is at the PATCH border, not the image border -- scale = 1/(N eh ew) if normalise else 1.
+ * Checked before any launch: a NULL pointer, a size < 1 or an unknown `kernel` -> CY_ERR_ARG; k outside 1..64, pad < 0,
+ * patch < 2, pad >= min(eh, ew), more than 65535 patches, J of 2^31 elements or more, or a forced staged kernel whose
+ * tile exceeds 150 KB of LDS ->
+ * CY_ERR_SHAPE; a short workspace -> CY_ERR_WORKSPACE.  No atomics anywhere: two runs give the same bits.
+ * cy_joint_patch_plan (host-side only, launches nothing) writes the launch rule:
+ *   plan[0] P, [1] nph, [2] npw, [3] eh, [4] ew
+ *   plan[5] forward kernel: 1 = a block owns (patch, group of <= 9 displacements) and walks the (image, R patch rows)
+ *           tiles staged in LDS with their zero border; 0 = one displacement per block, 64-pixel tiles, bounds-tested
+ *           reads (where the staged tile exceeds 150 KB).  `kernel` = -1 asks for the rule's choice, 0 / 1 force one
+ *   plan[6] R = min(eh, max(1, 256 / ew)), [7] tiles_h = ceil(eh / R) (kernel 1; else 0, 0)
+ *   plan[8] tiles: N * tiles_h (kernel 1), ceil(N eh ew / 64) (kernel 0)
+ *   plan[9] nbx, blocks per (patch, group) = partial joints: kernel 1 min(tiles, ceil(1024 / (P * groups))), kernel 0
+ *           min(2048, ceil(N eh ew / 1024)); 1 = the forward writes J itself and no reduction is launched
+ *   plan[10] gridDim.y: ceil(T*T / 9) (kernel 1), T*T (kernel 0); [11] dynamic LDS bytes; [12] 16-byte staging (k % 4 == 0)
+ *   plan[13] 1 if the staged tile fits; [14] backward kernel: 1 = four channels per thread (k % 4 == 0); [15] its grid
+ * cy_joint_patch_ws_bytes = 4 P T*T k*k nbx, the partial joints of that `kernel`, or 16 with nbx = 1 (0 where the sizes
+ * are refused). */
+int cy_joint_patch_plan(int N, int H, int W, int k, int pad, int patch, int kernel, int32_t* plan /* [16] */);
+size_t cy_joint_patch_ws_bytes(int N, int H, int W, int k, int pad, int patch, int kernel);
+int cy_joint_patch_fwd(const float* x1, const float* x2, float* J, int N, int H, int W, int k, int pad, int patch,
+                       int normalise, int kernel, void* ws, size_t ws_bytes, void* stream);
+/* The loss of cy_iid_loss (mode 0 or 1, never symmetric) on each of the P joints J[P][TT][k][k], one block per patch:
+ * losses[q]; Pj (may be NULL) [P][TT][k][k] the final joints; dJ (may be NULL) = (1/P) dlosses[q]/dJ[q];
+ * loss[0] = mean_q losses[q] in a fixed order.  ws_bytes >= P * cy_iid_loss_ws_bytes(TT, k). */
+size_t cy_iid_patch_loss_ws_bytes(int P, int TT, int k);
+int cy_iid_patch_loss(const float* J, float* loss, float* losses, float* Pj, float* dJ, int P, int TT, int k, int mode,
+                      float lamda, float eps, void* ws, size_t ws_bytes, void* stream);
+/* dx1, dx2 [N][H][W][k] (either may be NULL) = gscale[0] * adjoint of cy_joint_patch_fwd applied to dJ[P][T*T][k][k], in
+ * gather form: every pixel adds its patches in ascending q, then the displacements valid inside that patch. */
+int cy_joint_patch_bwd(const float* x1, const float* x2, const float* dJ, const float* gscale, float* dx1, float* dx2,
+                       int N, int H, int W, int k, int pad, int patch, int normalise, void* stream);
+
+/* ------------------------------------------------------------------------
+ * PICA losses, Jensen-Shannon divergence, entropy prior (csrc/cy_pica.hip; entries added to ABI v18 -- no existing
+ * signature changed and no struct added).  Every entry checks its arguments before any launch: a NULL required pointer
+ * or a count < 1 -> CY_ERR_ARG; classes outside 1..64 or maps outside 2..8 -> CY_ERR_SHAPE; a short workspace ->
+ * CY_ERR_WORKSPACE.  f64 inside, no atomics, fixed-order sums.  Upstream gradients are device memory.
+ * ------------------------------------------------------------------------ */
+/* PUILoss (contrastyou/losses/pica_loss.py:10-39) on rows x, y [N][K]; J[K][K] = sum_n x_ni y_nj is cy_joint_fwd with
+ * H = W = 1.  cy_pui_stats (one block): stats[3][K] = column sums of x^2, of y^2 and of x.
+ * cy_pui_loss (one block): a_i = max(|x_.i|_2, 1e-12), b_j likewise, pui_ij = J_ij / (a_i b_j), p = mean_n x,
+ *   out[0] = mean_i [logsumexp_j pui_ij - pui_ii] + lamda (log K + sum_i p_i log p_i)   (no eps);
+ * dJ (may be NULL) = dout/dJ at fixed norms; coef[3][K]: the rest of the gradient,
+ *   dout/dx_ni = (adjoint of J)(dJ) + x_ni coef[0][i] + coef[2][i],  dout/dy_nj = (adjoint)(dJ) + y_nj coef[1][j]
+ * (a clamped norm is a constant).  cy_rows_axpb: dx[r][c] += g[0] (x[r][c] a[c] + b[c]) over rows [R][K], b may be NULL. */
+int cy_pui_stats(const float* x, const float* y, float* stats, long N, int K, void* stream);
+int cy_pui_loss(const float* J, const float* stats, float* out, float* dJ, float* coef, long N, int K, float lamda,
+                void* stream);
+int cy_rows_axpb(const float* x, const float* a, const float* b, const float* g, float* dx, long R, int K, void* stream);
+/* PUISegLoss (pica_loss.py:42-85).  J[TT][k][k] is cy_joint_fwd of (x_out, x_tf_out) at the loss's padding, x the NHWC
+ * x_out as M = N H W rows of k.  q_d = (J_d - min J + 1e-16) / sum(J_d - min J + 1e-16), P = mean_d (q_d + q_d^T) / 2,
+ *   out[0] = -(1/k^2) sum_i log(P_ii + 1e-16) + lamda (log M + sum_m p_m log p_m),  p_m = (1/k) sum_c x[m][c]
+ * (the balance term runs over the permuted tensor, so p is the per-pixel mean over the classes; no eps).  dJ (may be
+ * NULL) = dout/dJ with the minimum held constant.  Two launches: the streaming sum of p log p, then one block.
+ * cy_puiseg_balance_bwd: dx[m][c] += g[0] lamda (log p_m + 1) / k.
+ * ws_bytes >= 8 * (min(1024, ceil(M / 256)) + 2 TT) = cy_puiseg_ws_bytes (0 where the sizes are refused). */
+size_t cy_puiseg_ws_bytes(long M, int TT, int k);
+int cy_puiseg_loss(const float* J, const float* x, float* out, float* dJ, int TT, int k, long M, float lamda, void* ws,
+                   size_t ws_bytes, void* stream);
+int cy_puiseg_balance_bwd(const float* x, const float* g, float* dx, long M, int k, float lamda, void* stream);
+/* JSD_div (contrastyou/losses/kl.py:142-174) of m maps (2..8; `maps` is a host array of m device pointers), C <= 64
+ * classes, R positions.  Position r, class c is element r*C + c (rows / NHWC: S = 1) or (r / S)*C*S + c*S + r % S (NCHW
+ * with S positions per image; R % S == 0).  v_r = H(mean_i x_i[r]) - mean_i H(x_i[r]), H(p) = -sum_c p log(p + eps).
+ * reduction 0: out[R] = v; 1: out[0] = mean_r v_r; 2: out[0] = sum_r v_r (f64 block partials, fixed-order final sum;
+ * ws_bytes >= 8 * min(1024, ceil(R / 256)) = cy_stream_sum_ws_bytes(R); reduction 0 needs no workspace).
+ * Backward, one launch: dmaps[i] (host array of m device pointers in the maps' layout; an entry may be NULL) =
+ * u_r (1/m) [(log(x + eps) + x / (x + eps)) - (log(mean + eps) + mean / (mean + eps))], u_r = g[r], g[0] / R or g[0]. */
+size_t cy_stream_sum_ws_bytes(long R);
+int cy_jsd_fwd(const float* const* maps, int m, float* out, long R, int C, long S, int reduction, float eps, void* ws,
+               size_t ws_bytes, void* stream);
+int cy_jsd_bwd(const float* const* maps, int m, const float* g, float* const* dmaps, long R, int C, long S,
+               int reduction, float eps, void* stream);
+/* EntropyPrior (kl.py:63-78) on rows x [R][C], prior [C] (NULL: uniform):
+ *   out[0] = log C + (1/R) sum_r sum_c x_rc (log(prior_c + eps) - log(x_rc + eps))   = log C - KL_div()(prior, x);
+ *   dx = g[0] / R (log(prior_c + eps) - log(x + eps) - x / (x + eps)); the prior is a constant.
+ * ws_bytes >= cy_stream_sum_ws_bytes(R). */
+int cy_entropy_prior_fwd(const float* x, const float* prior, float* out, long R, int C, float eps, void* ws,
+                         size_t ws_bytes, void* stream);
+int cy_entropy_prior_bwd(const float* x, const float* prior, const float* g, float* dx, long R, int C, float eps,
+                         void* stream);
 
 /* ------------------------------------------------------------------------
  * UNet2.Block = Conv2d(3x3, bias) -> GroupNorm(G, C) -> SiLU
