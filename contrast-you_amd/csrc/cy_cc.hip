@@ -7,6 +7,7 @@
 // two runs give the same bits.  Nothing is kept between forward and backward but the inputs: the backward
 // recomputes the five window sums on a tile with a halo of 2*(k/2) and box-sums the per-window derivatives.
 #include "cy_common.h"
+#include "cy_reduce.h"
 
 #include <math.h>
 
@@ -17,12 +18,6 @@ constexpr int EXT_BLOCKS = 32;   // workgroups (= extrema partials) per slice of
 constexpr int CC_WIN_MIN = 3, CC_WIN_MAX = 15;
 constexpr int ENT_KMAX = 128;
 constexpr size_t LDS_LIMIT = 160 * 1024;
-
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
-  return v;
-}
 
 // min / max over a 256-thread workgroup, result in every thread
 __device__ __forceinline__ void block_minmax(float& mn, float& mx, float* sh /* [8] */) {
@@ -37,17 +32,6 @@ __device__ __forceinline__ void block_minmax(float& mn, float& mx, float* sh /* 
   __syncthreads();
   mn = fminf(fminf(sh[0], sh[1]), fminf(sh[2], sh[3]));
   mx = fmaxf(fmaxf(sh[4], sh[5]), fmaxf(sh[6], sh[7]));
-}
-
-// ordered sum over a 256-thread workgroup (tree of fixed shape), result in thread 0
-__device__ __forceinline__ double block_sum_ordered(double v, double* sh /* [256] */) {
-  sh[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-    __syncthreads();
-  }
-  return sh[0];
 }
 
 // ---------------------------------------------------------------- edge strength, raw (ccblock.py:287-293)
@@ -294,17 +278,14 @@ __global__ void __launch_bounds__(256)
       acc += w.cross * w.cross / (w.iv * w.jv);
     }
   }
-  __syncthreads();
-  const double tot = block_sum_ordered(acc, rs);  // 5 * plane >= 256
+  const double tot = block_sum_d(acc, rs);  // 5 * plane >= 256; its first barrier ends the reads of the row sums
   if (threadIdx.x == 0) partial[((long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = tot;
 }
 
 __global__ void __launch_bounds__(256)
     ccloss_final_kernel(const double* __restrict__ partial, int nblk, double count, float* __restrict__ loss) {
   __shared__ double shd[256];
-  double acc = 0.0;
-  for (int i = threadIdx.x; i < nblk; i += 256) acc += partial[i];
-  const double tot = block_sum_ordered(acc, shd);
+  const double tot = sum_partials_d(partial, nblk, 1, shd);
   if (threadIdx.x == 0) loss[0] = (float)(-tot / count);
 }
 

@@ -11,6 +11,7 @@ typedef __bf16 bf16;
 typedef _Float16 f16;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
+typedef __attribute__((ext_vector_type(2))) float f32x2;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
@@ -129,17 +130,21 @@ __device__ __forceinline__ void st16(void* p, const u32x4& v) {
   *reinterpret_cast<u32x4*>(p) = v;
 }
 
-// wave64 sum over all lanes (result in every lane)
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 static inline int cy_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 static inline int cy_roundup(int a, int b) { return ((a + b - 1) / b) * b; }
+
+// launch size of a grid-stride kernel: blocks of `per_block` items for `items`, at least 1, at most `cap`
+constexpr int cy_blocks(long items, long per_block, long cap) {
+  const long b = (items + per_block - 1) / per_block;
+  return (int)(b < 1 ? 1 : (b > cap ? cap : b));
+}
+// trips of its loop: how often `blocks` blocks of `per_block` items step to cover `items`
+constexpr int cy_trips(long items, long blocks, long per_block) {
+  const long span = blocks * per_block, t = (items + span - 1) / span;
+  return (int)(t > INT32_MAX ? INT32_MAX : t);
+}
+static_assert(cy_blocks(0, 256, 8192) == 1 && cy_blocks(1, 256, 8192) == 1 && cy_blocks(256, 256, 8192) == 1);
+static_assert(cy_blocks(257, 256, 8192) == 2 && cy_blocks(8192L * 256 + 1, 256, 8192) == 8192);
+static_assert(cy_blocks(1025, 1024, 2048) == 2);
+static_assert(cy_trips(1, 1, 256) == 1 && cy_trips(8192L * 256 + 1, 8192, 256) == 2);
+static_assert(cy_trips((1L << 40), 1, 256) == INT32_MAX);

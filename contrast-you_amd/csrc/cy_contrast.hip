@@ -5,6 +5,7 @@
 // Everything here is f32: the embedding x embedding similarity and the
 // G*P products run on the exact f32 MFMA (v_mfma_f32_32x32x2_f32).
 #include "cy_common.h"
+#include "cy_reduce.h"
 
 namespace {
 
@@ -985,12 +986,7 @@ __global__ void __launch_bounds__(256)
   if (db && i == 0) db[o] = accumulate ? db[o] + sbias : sbias;
 }
 
-inline int grid_for(long total) {
-  long b = (total + 255) / 256;
-  if (b > 8192) b = 8192;
-  if (b < 1) b = 1;
-  return (int)b;
-}
+constexpr int GRID_CAP = 8192;  // blocks of 256 of the elementwise kernels; the rest is their grid-stride loop
 
 }  // namespace
 
@@ -1025,7 +1021,7 @@ int cy_supcon_bwd(const float* P, const int32_t* labels, const uint8_t* pos_mask
   if (n <= 0 || D <= 0 || !(t > 0.f)) return CY_ERR_SHAPE;
   hipStream_t st = (hipStream_t)stream;
   const int R = 2 * n;
-  hipLaunchKernelGGL(supcon_gsym_kernel, dim3(grid_for((long)R * R)), dim3(256), 0, st, S,
+  hipLaunchKernelGGL(supcon_gsym_kernel, dim3(cy_blocks((long)R * R, 256, GRID_CAP)), dim3(256), 0, st, S,
                      row_stats, labels, pos_mask, gscale, G, n);
   CY_CHECK_LAUNCH();
   return launch_sgemm(G, P, dP, R, D, R, 1.f / t, 0, st);
@@ -1056,8 +1052,8 @@ int cy_supcon_excl_bwd(const float* P, const int32_t* labels, const uint8_t* pos
   if (n <= 0 || D <= 0 || !(t > 0.f)) return CY_ERR_SHAPE;
   hipStream_t st = (hipStream_t)stream;
   const int R = 2 * n;
-  hipLaunchKernelGGL(supcon_excl_gsym_kernel, dim3(grid_for((long)R * R)), dim3(256), 0, st, S, row_stats,
-                     tmp + (size_t)4 * R, labels, pos_mask, gscale, G, n);
+  hipLaunchKernelGGL(supcon_excl_gsym_kernel, dim3(cy_blocks((long)R * R, 256, GRID_CAP)), dim3(256), 0, st, S,
+                     row_stats, tmp + (size_t)4 * R, labels, pos_mask, gscale, G, n);
   CY_CHECK_LAUNCH();
   return launch_sgemm(G, P, dP, R, D, R, 1.f / t, 0, st);
 }
@@ -1122,8 +1118,8 @@ int cy_supcon_fused_bwd(const float* P, const int32_t* labels, const uint8_t* po
                        gscale, dpart, n, D, 1.f / t, ns);
   CY_CHECK_LAUNCH();
   const long total = (long)R * D;
-  hipLaunchKernelGGL(supcon_dpart_reduce_kernel, dim3(grid_for(total)), dim3(256), 0, st, dpart, dP, total, ns,
-                     1.f / t);
+  hipLaunchKernelGGL(supcon_dpart_reduce_kernel, dim3(cy_blocks(total, 256, GRID_CAP)), dim3(256), 0, st, dpart, dP,
+                     total, ns, 1.f / t);
   CY_CHECK_LAUNCH();
   return CY_OK;
 }
@@ -1133,7 +1129,7 @@ int cy_supcon_matrices(const float* S, const float* row_stats, const int32_t* la
                        float* pos_out, float* neg_out, int n, void* stream) {
   if (!S || !row_stats || (!labels && !pos_mask) || n <= 0) return CY_ERR_ARG;
   const int R = 2 * n;
-  hipLaunchKernelGGL(supcon_matrices_kernel, dim3(grid_for((long)R * R)), dim3(256), 0,
+  hipLaunchKernelGGL(supcon_matrices_kernel, dim3(cy_blocks((long)R * R, 256, GRID_CAP)), dim3(256), 0,
                      (hipStream_t)stream, S, row_stats, labels, pos_mask, sim_logits, sim_exp,
                      pos_out, neg_out, n);
   CY_CHECK_LAUNCH();
@@ -1162,7 +1158,7 @@ int cy_avgpool_fwd(const void* x, float* pooled, int N, int HW, int C, int dtype
 int cy_avgpool_bwd(const float* dpooled, void* dx, int N, int HW, int C, int dtype, void* stream) {
   if (!dpooled || !dx || N <= 0 || HW <= 0 || C <= 0) return CY_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
-  const int grid = grid_for((long)N * HW * C);
+  const int grid = cy_blocks((long)N * HW * C, 256, GRID_CAP);
   if (dtype == CY_BF16)
     hipLaunchKernelGGL(avgpool_bwd_kernel<bf16>, dim3(grid), dim3(256), 0, st, dpooled, (bf16*)dx,
                        N, HW, C);

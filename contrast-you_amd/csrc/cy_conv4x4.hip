@@ -22,6 +22,7 @@
 #include <limits.h>
 
 #include "cy_common.h"
+#include "cy_reduce.h"
 
 namespace {
 
@@ -553,10 +554,7 @@ __global__ void __launch_bounds__(256)
 // ---------------------------------------------------------------- host side
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-inline int flat_blocks(long total) {
-  const long b = (total + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > (1L << 20) ? (1L << 20) : b));
-}
+constexpr long FLAT_GRID_CAP = 1L << 20;  // blocks of 256 of the pack / sum kernels; the rest is grid-stride
 
 int make_geo(int N, int H, int W, int Cin, int Cout, int ksize, int stride, int pad, Geo* g) {
   if (N < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || ksize < 1 || stride < 1 || pad < 0) return CY_ERR_ARG;
@@ -607,8 +605,8 @@ extern "C" {
 
 int cy_conv4x4_pack_weights(const float* w, float* packed, int Cin, int Cout, int transposed, void* stream) {
   if (!w || !packed || Cin < 1 || Cout < 1 || Cin > MAX_CH || Cout > MAX_CH) return CY_ERR_ARG;
-  hipLaunchKernelGGL(pack_kernel, dim3(flat_blocks((long)Cout * Cin * 16)), dim3(256), 0, (hipStream_t)stream, w,
-                     packed, Cin, Cout, transposed);
+  hipLaunchKernelGGL(pack_kernel, dim3(cy_blocks((long)Cout * Cin * 16, 256, FLAT_GRID_CAP)), dim3(256), 0,
+                     (hipStream_t)stream, w, packed, Cin, Cout, transposed);
   CY_CHECK_LAUNCH();
   return CY_OK;
 }
@@ -656,7 +654,7 @@ int cy_conv4x4_dgrad(const float* dy, const float* wpt, float* dx, int N, int H,
     }
 #undef CY_NARROW
   } else if (Cout < SMALL_COUT || Cin < SMALL_COUT) {
-    const dim3 grid(flat_blocks((long)N * H * W * Cin));
+    const dim3 grid(cy_blocks((long)N * H * W * Cin, 256, FLAT_GRID_CAP));
     if (v)
       hipLaunchKernelGGL(dgrad_small_kernel<true>, grid, dim3(256), 0, st, dy, wpt, dx, g);
     else
@@ -707,8 +705,8 @@ int cy_conv4x4_wgrad(const float* x, const float* dy, float* dw, int N, int H, i
       hipLaunchKernelGGL((wgrad_mfma_kernel<false, false>), grid, dim3(256), 0, st, x, dy, part, g, rps);
   }
   CY_CHECK_LAUNCH();
-  hipLaunchKernelGGL(wgrad_sum_kernel, dim3(flat_blocks((long)Cout * g.K)), dim3(256), 0, st, part, dw, Cin, Cout,
-                     splits);
+  hipLaunchKernelGGL(wgrad_sum_kernel, dim3(cy_blocks((long)Cout * g.K, 256, FLAT_GRID_CAP)), dim3(256), 0, st, part,
+                     dw, Cin, Cout, splits);
   CY_CHECK_LAUNCH();
   return CY_OK;
 }

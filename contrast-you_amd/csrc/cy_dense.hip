@@ -388,10 +388,7 @@ __global__ void __launch_bounds__(256)
   }
 }
 
-inline int grid_for(long n) {
-  long b = (n + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
-}
+constexpr int GRID_CAP = 8192;  // blocks of 256 of the elementwise kernels; the rest is their grid-stride loop
 
 inline int dp_bwd_blocks(int nb) { return nb < 256 ? nb : 256; }
 
@@ -522,7 +519,7 @@ int cy_adaptive_avgpool_bwd(const float* dpool, void* dx, int N, int H, int W, i
   if (!dpool || !dx || N <= 0) return CY_ERR_ARG;
   if (ldx < C || sh <= 0 || sw <= 0 || sh > H || sw > W) return CY_ERR_SHAPE;
   hipStream_t st = (hipStream_t)stream;
-  const int grid = grid_for((long)N * H * W * C);
+  const int grid = cy_blocks((long)N * H * W * C, 256, GRID_CAP);
   if (dtype == CY_BF16)
     hipLaunchKernelGGL(adaptive_pool_bwd_kernel<bf16>, dim3(grid), dim3(256), 0, st, dpool,
                        (bf16*)dx, N, H, W, C, ldx, sh, sw);
@@ -561,7 +558,7 @@ int cy_adaptive_maxpool_bwd(const float* dpool, const int32_t* arg, void* dx, in
   if (!dpool || !arg || !dx || N <= 0) return CY_ERR_ARG;
   if (ldx < C || sh <= 0 || sw <= 0 || sh > H || sw > W) return CY_ERR_SHAPE;
   hipStream_t st = (hipStream_t)stream;
-  const int grid = grid_for((long)N * H * W * C);
+  const int grid = cy_blocks((long)N * H * W * C, 256, GRID_CAP);
 #define CY_AMP(TT)                                                                                              \
   hipLaunchKernelGGL(adaptive_maxpool_bwd_kernel<TT>, dim3(grid), dim3(256), 0, st, dpool, arg, (TT*)dx, N, H, W, \
                      C, ldx, sh, sw)
@@ -577,7 +574,7 @@ int cy_adaptive_maxpool_bwd(const float* dpool, const int32_t* arg, void* dx, in
 int cy_gather_rows_fwd(const float* src, const int32_t* idx, float* out, int M, int D,
                        void* stream) {
   if (!src || !idx || !out || M <= 0 || D <= 0) return CY_ERR_ARG;
-  hipLaunchKernelGGL(gather_rows_kernel, dim3(grid_for((long)M * D)), dim3(256), 0,
+  hipLaunchKernelGGL(gather_rows_kernel, dim3(cy_blocks((long)M * D, 256, GRID_CAP)), dim3(256), 0,
                      (hipStream_t)stream, src, idx, out, M, D);
   CY_CHECK_LAUNCH();
   return CY_OK;
@@ -586,7 +583,7 @@ int cy_gather_rows_fwd(const float* src, const int32_t* idx, float* out, int M, 
 int cy_gather_rows_bwd(const float* dout, const int32_t* idx, float* dsrc, int M, int D,
                        void* stream) {
   if (!dout || !idx || !dsrc || M <= 0 || D <= 0) return CY_ERR_ARG;
-  hipLaunchKernelGGL(scatter_rows_kernel, dim3(grid_for((long)M * D)), dim3(256), 0,
+  hipLaunchKernelGGL(scatter_rows_kernel, dim3(cy_blocks((long)M * D, 256, GRID_CAP)), dim3(256), 0,
                      (hipStream_t)stream, dout, idx, dsrc, M, D);
   CY_CHECK_LAUNCH();
   return CY_OK;

@@ -9,6 +9,7 @@
 // checked before any launch.
 #include "cy_common.h"
 #include "cy_pixel_loss.h"
+#include "cy_reduce.h"
 
 namespace {
 
@@ -391,10 +392,7 @@ inline bool bad_ci(int Ci) { return Ci < 0 || Ci > CI_MAX; }
 inline bool bad_c(int C) { return C < 1 || C > BN_C_MAX; }
 inline bool bad_label(float l) { return !(l == 0.f || l == 1.f); }
 inline bool misaligned(const void* p) { return ((uintptr_t)p & 15) != 0; }
-inline int flat_blocks(long n) {
-  long b = (n + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
-}
+constexpr int FLAT_GRID_CAP = 2048;  // blocks of 256 of the flat sweeps (256 CUs x 8); the rest is grid-stride
 
 // launch KERNEL<4> or KERNEL<1> over the BatchNorm geometry `G`
 #define CY_BN_LAUNCH(KERNEL, G, ST, ...)                                                                   \
@@ -415,11 +413,11 @@ int cy_softmax_cat_fwd(const float* image, const float* logits, float* out, long
   if (K == 4 && (misaligned(logits) || (Ci == 0 && misaligned(out)))) return CY_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   if (K == 4)
-    hipLaunchKernelGGL(softmax_cat_fwd_kernel<4>, dim3(flat_blocks(npix)), dim3(256), 0, st, image, logits, out, npix,
-                       Ci, K);
+    hipLaunchKernelGGL(softmax_cat_fwd_kernel<4>, dim3(cy_blocks(npix, 256, FLAT_GRID_CAP)), dim3(256), 0, st, image,
+                       logits, out, npix, Ci, K);
   else
-    hipLaunchKernelGGL(softmax_cat_fwd_kernel<0>, dim3(flat_blocks(npix)), dim3(256), 0, st, image, logits, out, npix,
-                       Ci, K);
+    hipLaunchKernelGGL(softmax_cat_fwd_kernel<0>, dim3(cy_blocks(npix, 256, FLAT_GRID_CAP)), dim3(256), 0, st, image,
+                       logits, out, npix, Ci, K);
   CY_CHECK_LAUNCH();
   return CY_OK;
 }
@@ -430,11 +428,11 @@ int cy_softmax_cat_bwd(const float* logits, const float* dout, float* dlogits, l
   if (K == 4 && (misaligned(logits) || misaligned(dlogits))) return CY_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   if (K == 4)
-    hipLaunchKernelGGL(softmax_cat_bwd_kernel<4>, dim3(flat_blocks(npix)), dim3(256), 0, st, logits, dout, dlogits,
-                       npix, Ci, K);
+    hipLaunchKernelGGL(softmax_cat_bwd_kernel<4>, dim3(cy_blocks(npix, 256, FLAT_GRID_CAP)), dim3(256), 0, st, logits,
+                       dout, dlogits, npix, Ci, K);
   else
-    hipLaunchKernelGGL(softmax_cat_bwd_kernel<0>, dim3(flat_blocks(npix)), dim3(256), 0, st, logits, dout, dlogits,
-                       npix, Ci, K);
+    hipLaunchKernelGGL(softmax_cat_bwd_kernel<0>, dim3(cy_blocks(npix, 256, FLAT_GRID_CAP)), dim3(256), 0, st, logits,
+                       dout, dlogits, npix, Ci, K);
   CY_CHECK_LAUNCH();
   return CY_OK;
 }
@@ -510,13 +508,13 @@ int cy_leaky_relu_fwd(const float* x, float* y, long n, float slope, void* strea
   hipStream_t st = (hipStream_t)stream;
   const long nv = (misaligned(x) || misaligned(y)) ? 0 : n / 4;
   if (nv) {
-    hipLaunchKernelGGL((leaky_relu_kernel<false, 4>), dim3(flat_blocks(nv)), dim3(256), 0, st, x, (const float*)nullptr,
-                       y, 0L, nv, slope);
+    hipLaunchKernelGGL((leaky_relu_kernel<false, 4>), dim3(cy_blocks(nv, 256, FLAT_GRID_CAP)), dim3(256), 0, st, x,
+                       (const float*)nullptr, y, 0L, nv, slope);
     CY_CHECK_LAUNCH();
   }
   if (n - 4 * nv) {
-    hipLaunchKernelGGL((leaky_relu_kernel<false, 1>), dim3(flat_blocks(n - 4 * nv)), dim3(256), 0, st, x,
-                       (const float*)nullptr, y, 4 * nv, n - 4 * nv, slope);
+    hipLaunchKernelGGL((leaky_relu_kernel<false, 1>), dim3(cy_blocks(n - 4 * nv, 256, FLAT_GRID_CAP)), dim3(256), 0, st,
+                       x, (const float*)nullptr, y, 4 * nv, n - 4 * nv, slope);
     CY_CHECK_LAUNCH();
   }
   return CY_OK;
@@ -527,26 +525,26 @@ int cy_leaky_relu_bwd(const float* x, const float* dy, float* dx, long n, float 
   hipStream_t st = (hipStream_t)stream;
   const long nv = (misaligned(x) || misaligned(dy) || misaligned(dx)) ? 0 : n / 4;
   if (nv) {
-    hipLaunchKernelGGL((leaky_relu_kernel<true, 4>), dim3(flat_blocks(nv)), dim3(256), 0, st, x, dy, dx, 0L, nv,
-                       slope);
+    hipLaunchKernelGGL((leaky_relu_kernel<true, 4>), dim3(cy_blocks(nv, 256, FLAT_GRID_CAP)), dim3(256), 0, st, x, dy,
+                       dx, 0L, nv, slope);
     CY_CHECK_LAUNCH();
   }
   if (n - 4 * nv) {
-    hipLaunchKernelGGL((leaky_relu_kernel<true, 1>), dim3(flat_blocks(n - 4 * nv)), dim3(256), 0, st, x, dy, dx,
-                       4 * nv, n - 4 * nv, slope);
+    hipLaunchKernelGGL((leaky_relu_kernel<true, 1>), dim3(cy_blocks(n - 4 * nv, 256, FLAT_GRID_CAP)), dim3(256), 0, st,
+                       x, dy, dx, 4 * nv, n - 4 * nv, slope);
     CY_CHECK_LAUNCH();
   }
   return CY_OK;
 }
 
-size_t cy_sigmoid_bce_ws_bytes(long n) { return n < 1 ? 0 : (size_t)loss_blocks(n) * sizeof(double); }
+size_t cy_sigmoid_bce_ws_bytes(long n) { return n < 1 ? 0 : (size_t)cy_blocks(n, 256, LOSS_GRID_CAP) * sizeof(double); }
 
 int cy_sigmoid_bce_fwd(const float* scores, float label, float* loss, long n, void* ws, size_t ws_bytes,
                        void* stream) {
   if (!scores || !loss || !ws || n <= 0 || bad_label(label)) return CY_ERR_ARG;
   if (ws_bytes < cy_sigmoid_bce_ws_bytes(n)) return CY_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const int nblk = loss_blocks(n);
+  const int nblk = cy_blocks(n, 256, LOSS_GRID_CAP);
   hipLaunchKernelGGL(sigmoid_bce_fwd_kernel, dim3(nblk), dim3(256), 0, st, scores, (double*)ws, n,
                      label == 1.f ? 1 : 0);
   CY_CHECK_LAUNCH();
@@ -557,8 +555,8 @@ int cy_sigmoid_bce_fwd(const float* scores, float label, float* loss, long n, vo
 
 int cy_sigmoid_bce_bwd(const float* scores, float label, const float* gscale, float* dscores, long n, void* stream) {
   if (!scores || !gscale || !dscores || n <= 0 || bad_label(label)) return CY_ERR_ARG;
-  hipLaunchKernelGGL(sigmoid_bce_bwd_kernel, dim3(flat_blocks(n)), dim3(256), 0, (hipStream_t)stream, scores, gscale,
-                     dscores, n, label == 1.f ? 1 : 0);
+  hipLaunchKernelGGL(sigmoid_bce_bwd_kernel, dim3(cy_blocks(n, 256, FLAT_GRID_CAP)), dim3(256), 0, (hipStream_t)stream,
+                     scores, gscale, dscores, n, label == 1.f ? 1 : 0);
   CY_CHECK_LAUNCH();
   return CY_OK;
 }

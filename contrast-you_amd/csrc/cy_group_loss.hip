@@ -11,8 +11,9 @@
 //                 of iterations (rows past the end recompute the last pixel and contribute nothing).
 // Loss partials are one f64 per block, summed in a fixed order by mean_finalize_kernel: two runs give the same bits.
 #include "cy_common.h"
-#include "cy_pixel_loss.h"  // KMAX, softmax_k, load_logits, block_sum_d, mean_finalize_kernel, loss_blocks
-#include "cy_row_loss.h"    // KROW, ROW, ROWS, row_sum, row_max, load_row4, store_row4, row_exp, part_in, row_blocks
+#include "cy_pixel_loss.h"  // KMAX, softmax_k, load_logits
+#include "cy_reduce.h"      // block_sum_d, mean_finalize_kernel, LOSS_GRID_CAP
+#include "cy_row_loss.h"    // KROW, ROW, ROWS, row_sum, row_max, load_row4, store_row4, row_exp, part_in
 
 namespace {
 
@@ -246,7 +247,9 @@ __global__ void __launch_bounds__(256)
     atomicAdd(&counts[(size_t)n * G * 2 + threadIdx.x], (unsigned long long)sc[threadIdx.x]);
 }
 
-inline int group_kl_blocks(long npix, int K) { return K <= KMAX ? loss_blocks(npix) : row_blocks(npix, 1024); }
+inline int group_kl_blocks(long npix, int K) {
+  return K <= KMAX ? cy_blocks(npix, 256, LOSS_GRID_CAP) : cy_blocks(npix, ROWS, 1024);
+}
 
 }  // namespace
 
@@ -254,7 +257,7 @@ inline int group_kl_blocks(long npix, int K) { return K <= KMAX ? loss_blocks(np
 // are checked there; nblk partials fit the workspace of cy_softmax_mse_ws_bytes
 int cy_softmax_mse_row_fwd(const float* a, const float* b, float* loss, long npix, int K, void* ws, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  const int nblk = loss_blocks(npix);
+  const int nblk = cy_blocks(npix, 256, LOSS_GRID_CAP);
   if (K % 4 == 0)
     hipLaunchKernelGGL(softmax_mse_fwd_row_kernel<true>, dim3(nblk), dim3(256), 0, st, a, b, (double*)ws, npix, K);
   else
@@ -269,7 +272,7 @@ int cy_softmax_mse_row_fwd(const float* a, const float* b, float* loss, long npi
 int cy_softmax_mse_row_bwd(const float* a, const float* b, const float* gscale, float* da, float* db, long npix, int K,
                            void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  const int nblk = row_blocks(npix, 4096);
+  const int nblk = cy_blocks(npix, ROWS, 4096);
   if (K % 4 == 0)
     hipLaunchKernelGGL(softmax_mse_bwd_row_kernel<true>, dim3(nblk), dim3(256), 0, st, a, b, gscale, da, db, npix, K);
   else
@@ -311,14 +314,14 @@ int cy_softmax_group_kl_bwd(const float* logits, const int64_t* target, const fl
   hipStream_t st = (hipStream_t)stream;
   const int m = K / G;
   if (K <= KMAX)
-    hipLaunchKernelGGL(group_kl_bwd_kernel, dim3(loss_blocks(npix) * 2), dim3(256), 0, st, logits, target, gscale,
-                       dlogits, npix, K, m, eps);
+    hipLaunchKernelGGL(group_kl_bwd_kernel, dim3(cy_blocks(npix, 256, LOSS_GRID_CAP) * 2), dim3(256), 0, st, logits,
+                       target, gscale, dlogits, npix, K, m, eps);
   else if (K % 4 == 0)
-    hipLaunchKernelGGL(group_kl_bwd_row_kernel<true>, dim3(row_blocks(npix, 4096)), dim3(256), 0, st, logits, target,
-                       gscale, dlogits, npix, K, m, eps);
+    hipLaunchKernelGGL(group_kl_bwd_row_kernel<true>, dim3(cy_blocks(npix, ROWS, 4096)), dim3(256), 0, st, logits,
+                       target, gscale, dlogits, npix, K, m, eps);
   else
-    hipLaunchKernelGGL(group_kl_bwd_row_kernel<false>, dim3(row_blocks(npix, 4096)), dim3(256), 0, st, logits, target,
-                       gscale, dlogits, npix, K, m, eps);
+    hipLaunchKernelGGL(group_kl_bwd_row_kernel<false>, dim3(cy_blocks(npix, ROWS, 4096)), dim3(256), 0, st, logits,
+                       target, gscale, dlogits, npix, K, m, eps);
   CY_CHECK_LAUNCH();
   return CY_OK;
 }
@@ -336,7 +339,7 @@ int cy_group_dice_counts(const float* logits, const int64_t* target, int64_t* co
     hipLaunchKernelGGL(group_dice_counts_kernel, dim3(bps, N), dim3(256), 0, st, logits, target,
                        (unsigned long long*)counts, HW, K, G, m);
   } else {
-    const int bps = row_blocks(HW, 256);
+    const int bps = cy_blocks(HW, ROWS, 256);
     if (K % 4 == 0)
       hipLaunchKernelGGL(group_dice_counts_row_kernel<true>, dim3(bps, N), dim3(256), 0, st, logits, target,
                          (unsigned long long*)counts, HW, K, G, m);

@@ -30,10 +30,7 @@ template <typename T> __device__ __forceinline__ void store8(T* p, const float* 
   }
 }
 
-inline int grid_for(long n) {
-  long b = (n + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
-}
+constexpr int GRID_CAP = 8192;  // blocks of 256 of the elementwise kernels; the rest is their grid-stride loop
 
 // Generic per-(image, split) channel reduction of NV values per element.
 // grid (GN_SPLIT, N); thread layout: gpp 8-channel groups x rows pixel lanes.
@@ -388,7 +385,7 @@ static int gn_silu_fwd_impl(const void* y, int ldy, const float* bias, const flo
   float* part = (float*)ws;
   float* xcoef = part + (size_t)N * GN_SPLIT * 3 * C;  // [N][2][C] behind the partial sums (cy_gn_ws_bytes has 6*N*C there)
   const size_t smem = reduce_smem(C, 2);
-  const int grid = grid_for((long)N * HW * (C / 8));
+  const int grid = cy_blocks((long)N * HW * (C / 8), 256, GRID_CAP);
   if (dtype == CY_BF16) {
     hipLaunchKernelGGL(gn_stats_kernel<bf16>, dim3(GN_SPLIT, N), dim3(256), smem, st, (const bf16*)y,
                        ldy, bias, HW, C, part);
@@ -454,7 +451,7 @@ static int gn_silu_bwd_impl(const void* y, int ldy, const void* dz, int ldd, con
   float* pgrad = coef + 3 * (size_t)N * C;
   float* xt = pgrad + 3 * (size_t)N * C;  // [N][4][C]
   const size_t smem = reduce_smem(C, 3);
-  const int grid = grid_for((long)N * HW * (C / 8));
+  const int grid = cy_blocks((long)N * HW * (C / 8), 256, GRID_CAP);
   hipLaunchKernelGGL(gn_bwd_coef_kernel, dim3(cy_cdiv((long)N * C, 256)), dim3(256), 0, st, bias, gamma, beta,
                      mean_rstd, xt, N, C, G, mod_s, mod_t);
   CY_CHECK_LAUNCH();
@@ -511,7 +508,7 @@ int cy_bilinear_fwd(const void* x, void* out, int N, int H, int W, int C, int h,
                     void* stream) {
   if (!x || !out || N <= 0 || H <= 0 || W <= 0 || C <= 0 || h <= 0 || w <= 0) return CY_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
-  const int grid = grid_for((long)N * h * w * C);
+  const int grid = cy_blocks((long)N * h * w * C, 256, GRID_CAP);
   if (dtype == CY_BF16)
     hipLaunchKernelGGL(bilinear_kernel<bf16>, dim3(grid), dim3(256), 0, st, (const bf16*)x,
                        (bf16*)out, N, H, W, C, h, w);

@@ -7,7 +7,8 @@
 //   UniversalDice intersections / unions          contrastyou/meters/general_dice_meter.py:37-110
 // All of it is HBM-streaming work over [pixels][K] f32 logits (K = classes).
 #include "cy_common.h"
-#include "cy_pixel_loss.h"  // KMAX, softmax_k, load_logits, block_sum_d, mean_finalize_kernel, loss_blocks
+#include "cy_pixel_loss.h"  // KMAX, softmax_k, load_logits
+#include "cy_reduce.h"      // block_sum_d, mean_finalize_kernel, LOSS_GRID_CAP
 
 // the wide head on the matrix-core kernels of cy_cluster_head.hip (same shared object); wave count and grids come from
 // cy_head_wide_plan through cy_head1x1_plan
@@ -247,15 +248,6 @@ __global__ void __launch_bounds__(256)
   }
 }
 
-// blocks of 256 threads over `work` items, at most `cap`; and the trips of the grid-stride loop that gives
-inline int capped_blocks(long work, long cap) {
-  long b = (work + 255) / 256;
-  if (b > cap) b = cap;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-inline int stride_trips(long work, int blocks) { return (int)((work + blocks * 256L - 1) / (blocks * 256L)); }
-
 // ---------------------------------------------------------------- softmax + KL(one-hot)
 __global__ void __launch_bounds__(256)
     softmax_kl_fwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target,
@@ -415,14 +407,14 @@ int cy_head1x1_plan(long npix, int C, int K, int need_dx, int need_dw, cy_head_p
     return CY_OK;
   }
   p.fwd_kernel = K <= KMAX ? 0 : 1;  // segmentation classes : stacked cluster sub-heads (DenseClusterHead: 5 x 20 outputs)
-  p.fwd_grid = loss_blocks(npix) * 2;
-  p.fwd_trips = stride_trips(npix, p.fwd_grid);
+  p.fwd_grid = cy_blocks(npix, 256, LOSS_GRID_CAP) * 2;
+  p.fwd_trips = cy_trips(npix, p.fwd_grid, 256);
   if (need_dx) {
     const bool wide = K > KMAX && K % 4 == 0 && C % 32 == 0;  // dl rows as 16-byte vectors, 32 channels per thread
     const long work = npix * (wide ? C / 32 : C / 8);
     p.dx_kernel = wide ? 1 : 0;
-    p.dx_grid = capped_blocks(work, wide ? 8192 : 4096);
-    p.dx_trips = stride_trips(work, p.dx_grid);
+    p.dx_grid = cy_blocks(work, 256, wide ? 8192 : 4096);
+    p.dx_trips = cy_trips(work, p.dx_grid, 256);
   }
   if (need_dw) {
     const int G = C / 8;
@@ -431,7 +423,7 @@ int cy_head1x1_plan(long npix, int C, int K, int need_dx, int need_dw, cy_head_p
     const int groups = (K + p.dw_group - 1) / p.dw_group;
     p.dw_vec_groups = K % 4 == 0 ? K / p.dw_group : 0;  // whole groups of a K that keeps the dl rows 16-byte aligned
     p.dw_scalar_groups = groups - p.dw_vec_groups;
-    p.dw_blocks = capped_blocks(npix, 512);
+    p.dw_blocks = cy_blocks(npix, 256, 512);
     p.dw_rows = 256 / G;
     p.dw_per = (int)((npix + p.dw_blocks - 1) / p.dw_blocks);
   }
@@ -575,7 +567,7 @@ static int head1x1_bwd_impl(const void* x, const float* w, const float* dlogits,
   return CY_OK;
 }
 
-size_t cy_softmax_kl_ws_bytes(long npix) { return (size_t)loss_blocks(npix) * sizeof(double); }
+size_t cy_softmax_kl_ws_bytes(long npix) { return (size_t)cy_blocks(npix, 256, LOSS_GRID_CAP) * sizeof(double); }
 
 int cy_softmax_kl_fwd(const float* logits, const int64_t* target, float* loss, long npix, int K,
                       float eps, void* ws, size_t ws_bytes, void* stream) {
@@ -583,7 +575,7 @@ int cy_softmax_kl_fwd(const float* logits, const int64_t* target, float* loss, l
   if (K < 1 || K > KMAX) return CY_ERR_SHAPE;
   if (ws_bytes < cy_softmax_kl_ws_bytes(npix)) return CY_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const int nblk = loss_blocks(npix);
+  const int nblk = cy_blocks(npix, 256, LOSS_GRID_CAP);
   hipLaunchKernelGGL(softmax_kl_fwd_kernel, dim3(nblk), dim3(256), 0, st, logits, target,
                      (double*)ws, npix, K, eps);
   CY_CHECK_LAUNCH();
@@ -597,13 +589,13 @@ int cy_softmax_kl_bwd(const float* logits, const int64_t* target, const float* g
                       float* dlogits, long npix, int K, float eps, void* stream) {
   if (!logits || !target || !gscale || !dlogits || npix <= 0) return CY_ERR_ARG;
   if (K < 1 || K > KMAX) return CY_ERR_SHAPE;
-  hipLaunchKernelGGL(softmax_kl_bwd_kernel, dim3(loss_blocks(npix) * 2), dim3(256), 0,
+  hipLaunchKernelGGL(softmax_kl_bwd_kernel, dim3(cy_blocks(npix, 256, LOSS_GRID_CAP) * 2), dim3(256), 0,
                      (hipStream_t)stream, logits, target, gscale, dlogits, npix, K, eps);
   CY_CHECK_LAUNCH();
   return CY_OK;
 }
 
-size_t cy_softmax_mse_ws_bytes(long npix) { return (size_t)loss_blocks(npix) * sizeof(double); }
+size_t cy_softmax_mse_ws_bytes(long npix) { return (size_t)cy_blocks(npix, 256, LOSS_GRID_CAP) * sizeof(double); }
 
 int cy_softmax_mse_fwd(const float* a, const float* b, float* loss, long npix, int K, void* ws,
                        size_t ws_bytes, void* stream) {
@@ -612,7 +604,7 @@ int cy_softmax_mse_fwd(const float* a, const float* b, float* loss, long npix, i
   if (ws_bytes < cy_softmax_mse_ws_bytes(npix)) return CY_ERR_WORKSPACE;
   if (K > KMAX) return cy_softmax_mse_row_fwd(a, b, loss, npix, K, ws, stream);
   hipStream_t st = (hipStream_t)stream;
-  const int nblk = loss_blocks(npix);
+  const int nblk = cy_blocks(npix, 256, LOSS_GRID_CAP);
   hipLaunchKernelGGL(softmax_mse_fwd_kernel, dim3(nblk), dim3(256), 0, st, a, b, (double*)ws, npix,
                      K);
   CY_CHECK_LAUNCH();
@@ -627,7 +619,7 @@ int cy_softmax_mse_bwd(const float* a, const float* b, const float* gscale, floa
   if (!a || !b || !gscale || (!da && !db) || npix <= 0) return CY_ERR_ARG;
   if (K < 1 || K > KROW) return CY_ERR_SHAPE;
   if (K > KMAX) return cy_softmax_mse_row_bwd(a, b, gscale, da, db, npix, K, stream);
-  hipLaunchKernelGGL(softmax_mse_bwd_kernel, dim3(loss_blocks(npix) * 2), dim3(256), 0,
+  hipLaunchKernelGGL(softmax_mse_bwd_kernel, dim3(cy_blocks(npix, 256, LOSS_GRID_CAP) * 2), dim3(256), 0,
                      (hipStream_t)stream, a, b, gscale, da, db, npix, K);
   CY_CHECK_LAUNCH();
   return CY_OK;

@@ -20,6 +20,7 @@
 
 #include "cy_common.h"
 #include "cy_pixel_loss.h"
+#include "cy_reduce.h"
 
 namespace {
 
@@ -81,10 +82,10 @@ int plan_fill(int form, long R, int K, int align, ImsatPlan* o) {
     o->slots = form == CY_IMSAT_PAIR ? 3 + 2 * K : 1 + K;
     tiles = (R * (long)K + o->tile - 1) / o->tile;
   }
-  o->fwd_grid = (int)(tiles < IMSAT_FWD_CAP ? tiles : IMSAT_FWD_CAP);
-  o->bwd_grid = (int)(tiles < IMSAT_BWD_CAP ? tiles : IMSAT_BWD_CAP);
-  o->fwd_trips = (int)((tiles + o->fwd_grid - 1) / o->fwd_grid);
-  o->bwd_trips = (int)((tiles + o->bwd_grid - 1) / o->bwd_grid);
+  o->fwd_grid = cy_blocks(tiles, 1, IMSAT_FWD_CAP);  // a block takes whole tiles
+  o->bwd_grid = cy_blocks(tiles, 1, IMSAT_BWD_CAP);
+  o->fwd_trips = cy_trips(tiles, o->fwd_grid, 1);
+  o->bwd_trips = cy_trips(tiles, o->bwd_grid, 1);
   return CY_OK;
 }
 
@@ -137,7 +138,6 @@ __device__ __forceinline__ void column_sums(const double* acc, double* sh, int K
 }
 
 __device__ __forceinline__ void scalar_sum(double v, double* sh, double* __restrict__ ws, int slot) {
-  __syncthreads();
   const double tot = block_sum_d(v, sh);
   if (threadIdx.x == 0) ws[(size_t)slot * gridDim.x + blockIdx.x] = tot;
 }
@@ -204,8 +204,7 @@ __global__ void __launch_bounds__(256)
   for (int s = wave; s < slots; s += 4) {
     double acc = 0.0;
     for (int b = lane; b < nblk; b += 64) acc += ws[(size_t)s * nblk + b];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    acc = wave_sum(acc);
     if (lane == 0) tot[s] = acc;
   }
   __syncthreads();

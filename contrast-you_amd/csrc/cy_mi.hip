@@ -13,16 +13,14 @@
 // LDS-staged tile; block partials are reduced in a fixed order (deterministic).
 // Layouts: probability maps are NHWC f32 [N][H][W][k]; joints are [T*T][k][k], T = 2*padding+1.
 #include "cy_common.h"
+#include "cy_reduce.h"
 
 namespace {
 
 constexpr int J_P = 64;      // pixels per staged tile
 constexpr int J_KMAX = 64;   // max clusters
 
-inline int grid_for(long n) {
-  long b = (n + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
-}
+constexpr int GRID_CAP = 8192;  // blocks of 256 of the elementwise backward kernels; the rest is grid-stride
 
 // ---------------------------------------------------------------- grouped softmax
 // in  [M][S*k] logits  ->  out [S][M][k] probabilities of softmax(logits * invT) per group.
@@ -453,33 +451,6 @@ __global__ void __launch_bounds__(256)
 }
 
 // ---------------------------------------------------------------- loss on the joint (one block)
-__device__ __forceinline__ double block_sum(double v, double* sred) {
-  const int tid = threadIdx.x;
-  __syncthreads();
-  sred[tid] = v;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) sred[tid] += sred[tid + o];
-    __syncthreads();
-  }
-  const double r = sred[0];
-  __syncthreads();
-  return r;
-}
-__device__ __forceinline__ double block_min(double v, double* sred) {
-  const int tid = threadIdx.x;
-  __syncthreads();
-  sred[tid] = v;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) sred[tid] = fmin(sred[tid], sred[tid + o]);
-    __syncthreads();
-  }
-  const double r = sred[0];
-  __syncthreads();
-  return r;
-}
-
 // mode 0: segmentation, padding 0 (no normalisation)      mode 1: segmentation, padding > 0
 // mode 2: vectors (IIDLoss): symmetrise + normalise to 1
 // ws: 4 arrays of TT*kk floats (p1, p2/p, dP, tmp) + (2*TT*k) marginals
@@ -505,11 +476,11 @@ __device__ __forceinline__ void iid_loss_body(const float* __restrict__ J, float
   if (mode == 1) {
     double mn = 1e300;
     for (int e = tid; e < n; e += 256) mn = fmin(mn, (double)J[e]);
-    mn = block_min(mn, sred);
+    mn = block_min_d(mn, sred);
     for (int d = 0; d < TT; ++d) {
       double s = 0.0;
       for (int e = tid; e < kk; e += 256) s += (double)J[d * kk + e] - mn + 1e-8;
-      s = block_sum(s, sred);
+      s = block_sum_d(s, sred);
       if (tid == 0) S[d] = (float)s;
       for (int e = tid; e < kk; e += 256) p1[d * kk + e] = (float)(((double)J[d * kk + e] - mn + 1e-8) / s);
     }
@@ -527,7 +498,7 @@ __device__ __forceinline__ void iid_loss_body(const float* __restrict__ J, float
       z += (double)v;
     }
     if (mode != 0) {
-      Z = block_sum(z, sred);
+      Z = block_sum_d(z, sred);
       for (int e = tid; e < n; e += 256) p[e] = (float)((double)p[e] / Z);
     }
   }
@@ -558,8 +529,8 @@ __device__ __forceinline__ void iid_loss_body(const float* __restrict__ J, float
     dP[e] = (float)(g * invTT);
     if (P) P[e] = (float)pv;
   }
-  l = block_sum(l, sred);
-  l1 = block_sum(l1, sred);
+  l = block_sum_d(l, sred);
+  l1 = block_sum_d(l1, sred);
   if (tid == 0) {
     out0[0] = (float)(l * invTT);
     if (out1) out1[0] = (float)(l1 * invTT);
@@ -569,7 +540,7 @@ __device__ __forceinline__ void iid_loss_body(const float* __restrict__ J, float
   if (mode != 0) {  // p = p2 / Z
     double dot = 0.0;
     for (int e = tid; e < n; e += 256) dot += (double)dP[e] * (double)p[e];
-    dot = block_sum(dot, sred);
+    dot = block_sum_d(dot, sred);
     for (int e = tid; e < n; e += 256) dP[e] = (float)(((double)dP[e] - dot) / Z);
   }
   __syncthreads();
@@ -583,7 +554,7 @@ __device__ __forceinline__ void iid_loss_body(const float* __restrict__ J, float
     for (int d = 0; d < TT; ++d) {
       double dot = 0.0;
       for (int e = tid; e < kk; e += 256) dot += (double)dp1[d * kk + e] * (double)p1[d * kk + e];
-      dot = block_sum(dot, sred);
+      dot = block_sum_d(dot, sred);
       const double s = S[d];
       for (int e = tid; e < kk; e += 256) dJ[d * kk + e] = (float)((((double)dp1[d * kk + e] - dot) / s) * gmul);
     }
@@ -600,10 +571,8 @@ __global__ void __launch_bounds__(256)
   iid_loss_body(J, out, out + 1, P, dJ, ws, TT, k, mode, symmetric, lamda, eps, 1.0, sred);
 }
 
-inline int joint_blocks(long npix) {
-  long b = (npix + 1023) / 1024;  // >= 3 blocks per CU at the config sizes
-  return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
-}
+constexpr int JOINT_PIX = 1024;       // pixels per block of the joint kernels: >= 3 blocks per CU at the config sizes
+constexpr int JOINT_GRID_CAP = 2048;  // 256 CUs x 8
 
 // ---------------------------------------------------------------- patch-wise joints
 // IIDSegmentationSmallPathLoss / patch_generator (contrastyou/losses/discreteMI.py:173-198,264-272): the loss of
@@ -848,7 +817,7 @@ __global__ void __launch_bounds__(256)
   __shared__ double sred[256];
   double s = 0.0;
   for (int q = threadIdx.x; q < P; q += 256) s += (double)losses[q];
-  s = block_sum(s, sred);
+  s = block_sum_d(s, sred);
   if (threadIdx.x == 0) loss[0] = (float)(s / (double)P);
 }
 
@@ -952,7 +921,7 @@ int cy_joint_plan(int N, int H, int W, int k, int pad, cy_joint_plan_t* out) {
   p.kp = kp;
   p.nsl = nsl;
   p.idle = 256 - nsl * k4 * k4;
-  p.nblk = joint_blocks(npix);
+  p.nblk = cy_blocks(npix, JOINT_PIX, JOINT_GRID_CAP);
   p.reduce_trips = cy_cdiv(p.nblk, 64);
   const size_t red = (size_t)nsl * kp * kp * sizeof(float);
   // padding > 0: every displacement from one staged tile of R rows, if it fits the LDS
@@ -980,7 +949,7 @@ int cy_joint_plan(int N, int H, int W, int k, int pad, cy_joint_plan_t* out) {
   }
   p.bwd_kernel = (k & 3) == 0;
   const long work = p.bwd_kernel ? npix * (k / 4) : npix * k;
-  p.bwd_grid = grid_for(work);
+  p.bwd_grid = cy_blocks(work, 256, GRID_CAP);
   p.bwd_trips = cy_cdiv(work, 256L * p.bwd_grid);
   const int fit = J_BWD_LDS / (k * k * (int)sizeof(float));  // >= 4 because k <= 64
   p.bwd_dchunk = fit < TT ? fit : TT;
@@ -1139,7 +1108,7 @@ int patch_plan_of(int N, int H, int W, int k, int pad, int patch, int kernel, pa
   const int tiles_h = cy_cdiv(p.eh, R), ntile = N * tiles_h, groups = cy_cdiv(TT, JM_D);
   int nbx1 = cy_cdiv(JP_TARGET, (long)p.P * groups);
   nbx1 = nbx1 > ntile ? ntile : nbx1;
-  const int nbx0 = joint_blocks((long)N * p.eh * p.ew);
+  const int nbx0 = cy_blocks((long)N * p.eh * p.ew, JOINT_PIX, JOINT_GRID_CAP);
   if (p.kernel == 1) {
     p.R = R;
     p.tiles_h = tiles_h;
@@ -1157,7 +1126,7 @@ int patch_plan_of(int N, int H, int W, int k, int pad, int patch, int kernel, pa
   // the partial joints of the forward; a forward with one block per (patch, group) writes J itself
   p.ws_bytes = p.nbx > 1 ? (size_t)p.P * TT * p.nbx * k * k * sizeof(float) : 16;
   p.bwd_kernel = (k & 3) == 0;
-  p.bwd_grid = grid_for(p.bwd_kernel ? (long)N * H * W * (k / 4) : (long)N * H * W * k);
+  p.bwd_grid = cy_blocks(p.bwd_kernel ? (long)N * H * W * (k / 4) : (long)N * H * W * k, 256, GRID_CAP);
   *out = p;
   return CY_OK;
 }

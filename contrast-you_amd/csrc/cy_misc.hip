@@ -161,12 +161,7 @@ __global__ void __launch_bounds__(256)
   }
 }
 
-inline int grid_for(long total) {
-  long b = (total + 255) / 256;
-  if (b > 8192) b = 8192;
-  if (b < 1) b = 1;
-  return (int)b;
-}
+constexpr int GRID_CAP = 8192;  // blocks of 256 items; the rest is the kernels' grid-stride loop
 
 }  // namespace
 
@@ -176,7 +171,7 @@ int cy_affine_nearest_fwd(const void* x, void* out, const float* theta, const fl
                           int C, int H, int W, int dtype, void* stream) {
   if (!x || !out || !theta || N <= 0 || C <= 0 || H <= 0 || W <= 0) return CY_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
-  const int grid = grid_for((long)N * H * W * ((C + 7) / 8));
+  const int grid = cy_blocks((long)N * H * W * ((C + 7) / 8), 256, GRID_CAP);
   if (dtype == CY_BF16)
     hipLaunchKernelGGL(affine_fwd_kernel<bf16>, dim3(grid), dim3(256), 0, st, (const bf16*)x,
                        (bf16*)out, theta, gamma, N, C, H, W);
@@ -196,7 +191,7 @@ int cy_affine_nearest_bwd(const void* dout, void* dx, const float* theta, int N,
                           int W, int dtype, void* stream) {
   if (!dout || !dx || !theta || N <= 0 || C <= 0 || H <= 0 || W <= 0) return CY_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
-  const int grid = grid_for((long)N * H * W * ((C + 7) / 8));
+  const int grid = cy_blocks((long)N * H * W * ((C + 7) / 8), 256, GRID_CAP);
   if (dtype == CY_BF16)
     hipLaunchKernelGGL(affine_bwd_kernel<bf16>, dim3(grid), dim3(256), 0, st, (const bf16*)dout,
                        (bf16*)dx, theta, N, C, H, W);
@@ -215,7 +210,7 @@ int cy_affine_nearest_bwd(const void* dout, void* dx, const float* theta, int N,
 int cy_ema_update(float* teacher, const float* student, long n, float alpha, float weight_decay,
                   void* stream) {
   if (!teacher || !student || n <= 0) return CY_ERR_ARG;
-  hipLaunchKernelGGL(ema_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, teacher,
+  hipLaunchKernelGGL(ema_kernel, dim3(cy_blocks(n, 256, GRID_CAP)), dim3(256), 0, (hipStream_t)stream, teacher,
                      student, n, alpha, 1.f - weight_decay);
   CY_CHECK_LAUNCH();
   return CY_OK;
@@ -238,7 +233,7 @@ int cy_radam_step(float* param, const float* grad, float* exp_avg, float* exp_av
                          ((rho_inf - 4.0) * (rho_inf - 2.0) * rho_t));
   else
     s.rect = -1.f;
-  hipLaunchKernelGGL(radam_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, param,
+  hipLaunchKernelGGL(radam_kernel, dim3(cy_blocks(n, 256, GRID_CAP)), dim3(256), 0, (hipStream_t)stream, param,
                      grad, exp_avg, exp_avg_sq, n, s);
   CY_CHECK_LAUNCH();
   return CY_OK;

@@ -20,8 +20,9 @@
 #pragma clang fp contract(off)
 
 #include "cy_common.h"
-#include "cy_pixel_loss.h"  // KMAX, load_logits, block_sum_d, mean_finalize_kernel, loss_blocks
-#include "cy_row_loss.h"    // KROW, ROW, ROWS, row_sum, load_row4, store_row4, row_exp, row_blocks
+#include "cy_pixel_loss.h"  // KMAX, load_logits
+#include "cy_reduce.h"      // block_sum_d, mean_finalize_kernel, LOSS_GRID_CAP
+#include "cy_row_loss.h"    // KROW, ROW, ROWS, row_sum, load_row4, store_row4, row_exp
 
 namespace {
 
@@ -350,7 +351,9 @@ __global__ void __launch_bounds__(256)
     atomicAdd(&counts[(size_t)n * C * 2 + threadIdx.x], (unsigned long long)sc[threadIdx.x]);
 }
 
-inline int mix_kl_blocks(long npix, int K) { return K <= KMAX ? loss_blocks(npix) : row_blocks(npix, 1024); }
+inline int mix_kl_blocks(long npix, int K) {
+  return K <= KMAX ? cy_blocks(npix, 256, LOSS_GRID_CAP) : cy_blocks(npix, ROWS, 1024);
+}
 
 inline int bucket(int v) { return v <= 4 ? 4 : (v <= 8 ? 8 : 16); }
 
@@ -394,7 +397,7 @@ int cy_softmax_mix_kl_fwd(const float* logits, const int64_t* target, const floa
 
 size_t cy_softmax_mix_kl_bwd_ws_bytes(long npix, int K, int C) {
   if (npix < 1 || K < 1 || C < 1) return 0;
-  return (size_t)row_blocks(npix, DM_BLOCKS) * K * C * sizeof(float);
+  return (size_t)cy_blocks(npix, ROWS, DM_BLOCKS) * K * C * sizeof(float);
 }
 
 int cy_softmax_mix_kl_bwd(const float* logits, const int64_t* target, const float* mix, const float* gscale,
@@ -408,18 +411,18 @@ int cy_softmax_mix_kl_bwd(const float* logits, const int64_t* target, const floa
   int nblk;
   if (!dmix) {
     if (thread_form) {
-      nblk = loss_blocks(npix) * 2;
+      nblk = cy_blocks(npix, 256, LOSS_GRID_CAP) * 2;
       MIX_BWD_THREAD(KMAX, 0);
     } else {
-      nblk = row_blocks(npix, 4096);
+      nblk = cy_blocks(npix, ROWS, 4096);
       if (vec) MIX_BWD_ROW(true, 0); else MIX_BWD_ROW(false, 0);
     }
     CY_CHECK_LAUNCH();
     return CY_OK;
   }
-  // nblk <= row_blocks(npix, DM_BLOCKS), the count behind cy_softmax_mix_kl_bwd_ws_bytes
+  // nblk <= cy_blocks(npix, ROWS, DM_BLOCKS), the count behind cy_softmax_mix_kl_bwd_ws_bytes
   if (thread_form) {
-    nblk = loss_blocks(npix);
+    nblk = cy_blocks(npix, 256, LOSS_GRID_CAP);
     switch (bucket(K) * 100 + bucket(C)) {
       case 404: MIX_BWD_THREAD(4, 4); break;
       case 408: MIX_BWD_THREAD(4, 8); break;
@@ -431,7 +434,7 @@ int cy_softmax_mix_kl_bwd(const float* logits, const int64_t* target, const floa
       default: MIX_BWD_THREAD(16, 8); break;
     }
   } else {
-    nblk = row_blocks(npix, DM_BLOCKS);
+    nblk = cy_blocks(npix, ROWS, DM_BLOCKS);
     switch (bucket(C) + (vec ? 100 : 0)) {
       case 104: MIX_BWD_ROW(true, 4); break;
       case 108: MIX_BWD_ROW(true, 8); break;
@@ -460,7 +463,7 @@ int cy_mix_dice_counts(const float* logits, const int64_t* target, const float* 
     hipLaunchKernelGGL(mix_dice_counts_kernel, dim3(bps, N), dim3(256), 0, st, logits, target, mix,
                        (unsigned long long*)counts, HW, K, C);
   } else {
-    const int bps = row_blocks(HW, 256);
+    const int bps = cy_blocks(HW, ROWS, 256);
     if (K % 4 == 0)
       hipLaunchKernelGGL(mix_dice_counts_row_kernel<true>, dim3(bps, N), dim3(256), 0, st, logits, target, mix,
                          (unsigned long long*)counts, HW, K, C);

@@ -11,6 +11,7 @@
 // one-block launch (no atomics: two runs give the same bits), one launch for the backward.
 #include "cy_common.h"
 #include "cy_pixel_loss.h"
+#include "cy_reduce.h"
 
 namespace {
 
@@ -210,11 +211,9 @@ int mix_plan(int form, int N, long per_image, int K, int align, MixPlan* pl) {
     pl->kt = 0;
     const long per = per_image / pl->vec;
     pl->rows = min_int(N, IMG_ROWS_CAP);
-    long gx = (per + 255) / 256;
-    const long cap = IMG_GRID_CAP / pl->rows;
-    if (gx > cap) gx = cap;
-    pl->fwd_grid = (int)gx * pl->rows;
-    const long trips = ((per + gx * 256 - 1) / (gx * 256)) * ((N + pl->rows - 1) / pl->rows);
+    const int gx = cy_blocks(per, 256, IMG_GRID_CAP / pl->rows);
+    pl->fwd_grid = gx * pl->rows;
+    const long trips = (long)cy_trips(per, gx, 256) * ((N + pl->rows - 1) / pl->rows);
     pl->fwd_trips = trips > INT32_MAX ? INT32_MAX : (int)trips;
     pl->bwd_grid = pl->bwd_trips = 0;
     return CY_OK;
@@ -227,10 +226,10 @@ int mix_plan(int form, int N, long per_image, int K, int align, MixPlan* pl) {
   if (align % 4 != 0) return CY_ERR_ARG;
   pl->vec = pl->kt == 2 ? 2 : pl->kt ? 4 : 1;
   const long npix = (long)N * per_image;
-  pl->fwd_grid = loss_blocks(npix);
+  pl->fwd_grid = cy_blocks(npix, 256, LOSS_GRID_CAP);
   pl->bwd_grid = pl->fwd_grid * 2;
-  pl->fwd_trips = (int)((npix + pl->fwd_grid * 256L - 1) / (pl->fwd_grid * 256L));
-  pl->bwd_trips = (int)((npix + pl->bwd_grid * 256L - 1) / (pl->bwd_grid * 256L));
+  pl->fwd_trips = cy_trips(npix, pl->fwd_grid, 256);
+  pl->bwd_trips = cy_trips(npix, pl->bwd_grid, 256);
   pl->rows = 0;
   return CY_OK;
 }
@@ -251,7 +250,7 @@ int mix_plan(int form, int N, long per_image, int K, int align, MixPlan* pl) {
 
 inline size_t mix_ws_bytes(int N, long HW) {
   if (N < 1 || HW < 1) return 0;
-  return (size_t)loss_blocks((long)N * HW) * sizeof(double);
+  return (size_t)cy_blocks((long)N * HW, 256, LOSS_GRID_CAP) * sizeof(double);
 }
 
 }  // namespace

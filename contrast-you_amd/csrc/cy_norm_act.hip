@@ -691,26 +691,10 @@ __global__ void __launch_bounds__(256) bn_running_update_kernel(const BnRunArgs 
 
 // grid of the folding elementwise kernels: every workgroup reads the accumulator, so few, long-running workgroups of
 // 1024 threads (one per CU)
-inline int fold_grid(long items) {
-  long b = (items + 1023) / 1024;
-  if (b > 256) b = 256;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
-inline int stream_grid(long total_threads) {
-  long b = (total_threads + 255) / 256;
-  if (b > 2048 * 4) b = 2048 * 4;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
+constexpr int FOLD_GRID_CAP = 256;
+constexpr int STREAM_GRID_CAP = 2048 * 4;  // workgroups of 256 threads of the other elementwise kernels
 // workgroups of the fused pool / upsample backward: one partial row (or one accumulator add per channel) each
-inline int stats_grid(long items) {
-  long b = (items + 255) / 256;
-  if (b > 1024) b = 1024;
-  return (int)(b < 1 ? 1 : b);
-}
+constexpr int STATS_GRID_CAP = 1024;
 
 // workgroups of the backward reduce: 128 pixels per workgroup; small maps (fewer than 512 such workgroups) get 32 pixels
 // per workgroup and the deep-prefetch form of the kernel
@@ -755,7 +739,8 @@ void na_plan(int kind, long n, int C, int dtype, int fold, cy_norm_act_plan_t* p
       p->kernel = (pool ? 2 : 0) + (ew_fold ? 1 : 0);
       p->threads = ew_fold ? 1024 : 256;
       // (the pooled fold form sizes its grid by pixels, four per item)
-      p->grid = ew_fold ? fold_grid(pool ? items * 4 : items) : stream_grid(items);
+      p->grid = ew_fold ? cy_blocks(pool ? items * 4 : items, 1024, FOLD_GRID_CAP)
+                        : cy_blocks(items, 256, STREAM_GRID_CAP);
       p->lds_bytes = ew_fold ? (int)((size_t)2 * C * sizeof(float) + ((size_t)4 * C + 2) * 8) : 0;
       loop(items, ew_fold ? 256 : 2048 * 4);
       gather(true);
@@ -802,7 +787,7 @@ void na_plan(int kind, long n, int C, int dtype, int fold, cy_norm_act_plan_t* p
     case CY_NA_BWD_APPLY:
       p->kernel = ew_fold ? 7 : 6;
       p->threads = ew_fold ? 1024 : 256;
-      p->grid = ew_fold ? fold_grid(items) : stream_grid(items);
+      p->grid = ew_fold ? cy_blocks(items, 1024, FOLD_GRID_CAP) : cy_blocks(items, 256, STREAM_GRID_CAP);
       p->lds_bytes = ew_fold ? (int)((size_t)4 * C * sizeof(float) + ((size_t)4 * C + 2) * 8) : 0;
       p->pow2 = G > 0 && (G & (G - 1)) == 0;
       loop(items, ew_fold ? 256 : 2048 * 4);
@@ -820,7 +805,7 @@ void na_plan(int kind, long n, int C, int dtype, int fold, cy_norm_act_plan_t* p
       const bool stats = bn && p->fused_ok;
       p->kernel = (pool ? 8 : 10) + (stats ? 1 : 0);
       p->threads = 256;
-      p->grid = stats ? stats_grid(items) : stream_grid(items);
+      p->grid = stats ? cy_blocks(items, 256, STATS_GRID_CAP) : cy_blocks(items, 256, STREAM_GRID_CAP);
       p->lds_bytes = stats ? 256 * 16 * (int)sizeof(float) : 0;
       loop(items, stats ? 1024 : 2048 * 4);
       if (stats) {

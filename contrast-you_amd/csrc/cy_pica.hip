@@ -6,43 +6,14 @@
 // the balance terms.  JSD and the entropy prior are one streaming pass each way: one thread per position, f64 block
 // partials, a fixed-order final sum.  No atomics anywhere.
 #include "cy_common.h"
+#include "cy_reduce.h"
 
 namespace {
 
 constexpr int PK_KMAX = 64;  // max classes (J_KMAX of cy_mi.hip)
 constexpr int JSD_MMAX = 8;  // max maps of JSD_div
 
-inline int stream_grid(long n) {
-  long b = (n + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 1024 ? 1024 : b));
-}
-
-__device__ __forceinline__ double block_sum(double v, double* sred) {
-  const int tid = threadIdx.x;
-  __syncthreads();
-  sred[tid] = v;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) sred[tid] += sred[tid + o];
-    __syncthreads();
-  }
-  const double r = sred[0];
-  __syncthreads();
-  return r;
-}
-__device__ __forceinline__ double block_min(double v, double* sred) {
-  const int tid = threadIdx.x;
-  __syncthreads();
-  sred[tid] = v;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) sred[tid] = fmin(sred[tid], sred[tid + o]);
-    __syncthreads();
-  }
-  const double r = sred[0];
-  __syncthreads();
-  return r;
-}
+constexpr int STREAM_GRID_CAP = 1024;  // blocks of 256 positions (= f64 partials) of the streaming kernels
 
 // ---------------------------------------------------------------- PUILoss on [N][K] rows
 // stats[0][K] = sum_n x^2, stats[1][K] = sum_n y^2, stats[2][K] = sum_n x.  One block: thread (slice, column), rows
@@ -101,7 +72,7 @@ __global__ void __launch_bounds__(256)
     l = (lse[tid] - (double)J[tid * K + tid] / (a[tid] * b[tid])) / (double)K + (double)lamda * p * log(p);
     if (coef) coef[2 * K + tid] = (float)((double)lamda * (log(p) + 1.0) / (double)N);
   }
-  l = block_sum(l, sred);
+  l = block_sum_d(l, sred);
   if (tid == 0) out[0] = (float)(l + (double)lamda * log((double)K));
   if (!dJ) return;
   // dpui_ij = (softmax_ij - delta_ij) / K;  dJ_ij = dpui_ij / (a_i b_j);  da_i = -sum_j dpui_ij pui_ij / a_i
@@ -150,7 +121,7 @@ __global__ void __launch_bounds__(256)
     p /= (double)k;
     s += p * log(p);
   }
-  s = block_sum(s, sred);
+  s = block_sum_d(s, sred);
   if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
@@ -181,11 +152,11 @@ __global__ void __launch_bounds__(256)
   double* S = ws;  // [TT]
   double mn = 1e300;
   for (int e = tid; e < n; e += 256) mn = fmin(mn, (double)J[e]);
-  mn = block_min(mn, sred);
+  mn = block_min_d(mn, sred);
   for (int d = 0; d < TT; ++d) {
     double s = 0.0;
     for (int e = tid; e < kk; e += 256) s += (double)J[d * kk + e] - mn + 1e-16;
-    s = block_sum(s, sred);
+    s = block_sum_d(s, sred);
     if (tid == 0) S[d] = s;
   }
   __syncthreads();
@@ -199,8 +170,8 @@ __global__ void __launch_bounds__(256)
   double l = tid < k ? -log(diag[tid] + 1e-16) / (double)kk : 0.0;
   double ne = 0.0;
   for (int b = tid; b < nblk; b += 256) ne += part[b];
-  l = block_sum(l, sred);
-  ne = block_sum(ne, sred);
+  l = block_sum_d(l, sred);
+  ne = block_sum_d(ne, sred);
   if (tid == 0) out[0] = (float)(l + (double)lamda * (log((double)M) + ne));
   if (!dJ) return;
   // dq_d[i][j] = delta_ij dP_i / TT;  dJ_d = (dq_d - <dq_d, q_d>) / S_d
@@ -253,7 +224,7 @@ __global__ void __launch_bounds__(256)
     s += v;
   }
   if (part) {
-    s = block_sum(s, sred);
+    s = block_sum_d(s, sred);
     if (threadIdx.x == 0) part[blockIdx.x] = s;
   }
 }
@@ -262,9 +233,7 @@ __global__ void __launch_bounds__(256)
 __global__ void __launch_bounds__(256)
     final_sum_kernel(const double* __restrict__ part, int n, float* __restrict__ out, double scale, double add) {
   __shared__ double sred[256];
-  double s = 0.0;
-  for (int b = threadIdx.x; b < n; b += 256) s += part[b];
-  s = block_sum(s, sred);
+  const double s = sum_partials_d(part, n, 1, sred);
   if (threadIdx.x == 0) out[0] = (float)(add + scale * s);
 }
 
@@ -304,7 +273,7 @@ __global__ void __launch_bounds__(256)
       const double v = (double)x[r * C + c];
       s += v * (lp[c] - log(v + eps));
     }
-  s = block_sum(s, sred);
+  s = block_sum_d(s, sred);
   if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
@@ -357,17 +326,19 @@ int cy_rows_axpb(const float* x, const float* a, const float* b, const float* g,
                  void* stream) {
   if (!x || !a || !g || !dx || R < 1) return CY_ERR_ARG;
   if (K < 1 || K > PK_KMAX) return CY_ERR_SHAPE;
-  hipLaunchKernelGGL(rows_axpb_kernel, dim3(stream_grid(R * K)), dim3(256), 0, (hipStream_t)stream, x, a, b, g, dx,
-                     R * K, K);
+  hipLaunchKernelGGL(rows_axpb_kernel, dim3(cy_blocks(R * K, 256, STREAM_GRID_CAP)), dim3(256), 0, (hipStream_t)stream,
+                     x, a, b, g, dx, R * K, K);
   CY_CHECK_LAUNCH();
   return CY_OK;
 }
 
-size_t cy_stream_sum_ws_bytes(long R) { return R < 1 ? 0 : (size_t)stream_grid(R) * sizeof(double); }
+size_t cy_stream_sum_ws_bytes(long R) {
+  return R < 1 ? 0 : (size_t)cy_blocks(R, 256, STREAM_GRID_CAP) * sizeof(double);
+}
 
 size_t cy_puiseg_ws_bytes(long M, int TT, int k) {
   if (M < 1 || TT < 1 || k < 1 || k > PK_KMAX) return 0;
-  return ((size_t)stream_grid(M) + 2 * (size_t)TT) * sizeof(double);
+  return ((size_t)cy_blocks(M, 256, STREAM_GRID_CAP) + 2 * (size_t)TT) * sizeof(double);
 }
 
 int cy_puiseg_loss(const float* J, const float* x, float* out, float* dJ, int TT, int k, long M, float lamda, void* ws,
@@ -376,7 +347,7 @@ int cy_puiseg_loss(const float* J, const float* x, float* out, float* dJ, int TT
   if (k < 1 || k > PK_KMAX) return CY_ERR_SHAPE;
   if (!ws || ws_bytes < cy_puiseg_ws_bytes(M, TT, k)) return CY_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const int nblk = stream_grid(M);
+  const int nblk = cy_blocks(M, 256, STREAM_GRID_CAP);
   double* part = (double*)ws;
   hipLaunchKernelGGL(pixmean_entropy_fwd_kernel, dim3(nblk), dim3(256), 0, st, x, part, M, k);
   CY_CHECK_LAUNCH();
@@ -389,8 +360,8 @@ int cy_puiseg_loss(const float* J, const float* x, float* out, float* dJ, int TT
 int cy_puiseg_balance_bwd(const float* x, const float* g, float* dx, long M, int k, float lamda, void* stream) {
   if (!x || !g || !dx || M < 1) return CY_ERR_ARG;
   if (k < 1 || k > PK_KMAX) return CY_ERR_SHAPE;
-  hipLaunchKernelGGL(pixmean_entropy_bwd_kernel, dim3(stream_grid(M)), dim3(256), 0, (hipStream_t)stream, x, g, dx, M, k,
-                     lamda);
+  hipLaunchKernelGGL(pixmean_entropy_bwd_kernel, dim3(cy_blocks(M, 256, STREAM_GRID_CAP)), dim3(256), 0,
+                     (hipStream_t)stream, x, g, dx, M, k, lamda);
   CY_CHECK_LAUNCH();
   return CY_OK;
 }
@@ -404,7 +375,7 @@ int cy_jsd_fwd(const float* const* maps, int m, float* out, long R, int C, long 
   hipStream_t st = (hipStream_t)stream;
   maps_t x = {};
   for (int i = 0; i < m; ++i) x.p[i] = maps[i];
-  const int nblk = stream_grid(R);
+  const int nblk = cy_blocks(R, 256, STREAM_GRID_CAP);
   hipLaunchKernelGGL(jsd_fwd_kernel, dim3(nblk), dim3(256), 0, st, x, m, reduction == 0 ? out : (float*)nullptr,
                      reduction == 0 ? (double*)nullptr : (double*)ws, R, C, S, (double)eps);
   CY_CHECK_LAUNCH();
@@ -424,8 +395,8 @@ int cy_jsd_bwd(const float* const* maps, int m, const float* g, float* const* dm
   maps_t x = {};
   grads_t dx = {};
   for (int i = 0; i < m; ++i) x.p[i] = maps[i], dx.p[i] = dmaps[i];
-  hipLaunchKernelGGL(jsd_bwd_kernel, dim3(stream_grid(R)), dim3(256), 0, (hipStream_t)stream, x, dx, m, g,
-                     reduction == 0, reduction == 1 ? 1.0 / (double)R : 1.0, R, C, S, (double)eps);
+  hipLaunchKernelGGL(jsd_bwd_kernel, dim3(cy_blocks(R, 256, STREAM_GRID_CAP)), dim3(256), 0, (hipStream_t)stream, x, dx,
+                     m, g, reduction == 0, reduction == 1 ? 1.0 / (double)R : 1.0, R, C, S, (double)eps);
   CY_CHECK_LAUNCH();
   return CY_OK;
 }
@@ -436,7 +407,7 @@ int cy_entropy_prior_fwd(const float* x, const float* prior, float* out, long R,
   if (C < 1 || C > PK_KMAX) return CY_ERR_SHAPE;
   if (!ws || ws_bytes < cy_stream_sum_ws_bytes(R)) return CY_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const int nblk = stream_grid(R);
+  const int nblk = cy_blocks(R, 256, STREAM_GRID_CAP);
   hipLaunchKernelGGL(prior_fwd_kernel, dim3(nblk), dim3(256), 0, st, x, prior, (double*)ws, R, C, (double)eps);
   CY_CHECK_LAUNCH();
   hipLaunchKernelGGL(final_sum_kernel, dim3(1), dim3(256), 0, st, (const double*)ws, nblk, out, 1.0 / (double)R,
@@ -449,8 +420,8 @@ int cy_entropy_prior_bwd(const float* x, const float* prior, const float* g, flo
                          void* stream) {
   if (!x || !g || !dx || R < 1) return CY_ERR_ARG;
   if (C < 1 || C > PK_KMAX) return CY_ERR_SHAPE;
-  hipLaunchKernelGGL(prior_bwd_kernel, dim3(stream_grid(R * C)), dim3(256), 0, (hipStream_t)stream, x, prior, g, dx, R,
-                     C, (double)eps);
+  hipLaunchKernelGGL(prior_bwd_kernel, dim3(cy_blocks(R * C, 256, STREAM_GRID_CAP)), dim3(256), 0, (hipStream_t)stream,
+                     x, prior, g, dx, R, C, (double)eps);
   CY_CHECK_LAUNCH();
   return CY_OK;
 }

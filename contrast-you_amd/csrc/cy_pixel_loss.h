@@ -1,12 +1,11 @@
 // Helpers of the pixel-wise loss kernels over [pixels][K] f32 logits (cy_head_loss.hip, cy_pixel_reg.hip,
 // cy_seg_loss.hip):
-// one thread per pixel, grid-stride; per-block f64 partials summed by a one-block finalize launch in a fixed order.
+// one thread per pixel, grid-stride: the logits rows and their softmax.  The per-block f64 partials, their one-block
+// finalize launch and the block count are in cy_reduce.h.
 #pragma once
 #include "cy_common.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(2))) float f32x2;
 
 constexpr int KMAX = 16;  // segmentation classes
 
@@ -72,34 +71,6 @@ template <int KT> __device__ __forceinline__ void store_row(float* d, long p, in
     for (int k = 0; k < KMAX; ++k)
       if (k < K) d[p * K + k] = v[k];
   }
-}
-
-__device__ __forceinline__ double block_sum_d(double v, double* sh) {
-  const int tid = threadIdx.x;
-  sh[tid] = v;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) sh[tid] += sh[tid + o];
-    __syncthreads();
-  }
-  return sh[0];
-}
-
-__global__ void __launch_bounds__(256)
-    mean_finalize_kernel(const double* __restrict__ partial, int nblk, double denom,
-                         float* __restrict__ loss) {
-  __shared__ double sh[256];
-  double acc = 0.0;
-  for (int i = threadIdx.x; i < nblk; i += 256) acc += partial[i];
-  const double tot = block_sum_d(acc, sh);
-  if (threadIdx.x == 0) loss[0] = (float)(tot / denom);
-}
-
-inline int loss_blocks(long npix) {
-  long b = (npix + 255) / 256;
-  if (b > 1024) b = 1024;
-  if (b < 1) b = 1;
-  return (int)b;
 }
 
 // launch `KERNEL<KT>` with KT = K for the compiled class counts, 0 otherwise

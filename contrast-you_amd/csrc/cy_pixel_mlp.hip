@@ -25,6 +25,7 @@
 // and the same lane for the whole launch -- and one reduce launch adds the slabs in slab order: no atomics, the same
 // bits every run.
 #include "cy_conv_tile.h"
+#include "cy_reduce.h"
 
 namespace {
 

@@ -10,6 +10,7 @@
 // (exact register arrays, 8- / 16-byte row accesses); any other K takes the run-time form.
 #include "cy_common.h"
 #include "cy_pixel_loss.h"
+#include "cy_reduce.h"
 
 namespace {
 
@@ -186,13 +187,8 @@ __global__ void __launch_bounds__(256)
 __global__ void __launch_bounds__(256)
     uamt_finalize_kernel(const double* __restrict__ partial, int nblk, double npix, float* __restrict__ out) {
   __shared__ double sh1[256], sh2[256];
-  double a = 0.0, c = 0.0;
-  for (int i = threadIdx.x; i < nblk; i += 256) {
-    a += partial[2 * i];
-    c += partial[2 * i + 1];
-  }
-  const double s1 = block_sum_d(a, sh1);
-  const double s2 = block_sum_d(c, sh2);
+  const double s1 = sum_partials_d(partial, nblk, 2, sh1);
+  const double s2 = sum_partials_d(partial + 1, nblk, 2, sh2);
   if (threadIdx.x == 0) {
     const float mask_mean = (float)(s2 / npix);
     out[0] = (float)((s1 / npix) / ((double)mask_mean + UAMT_DENOM_EPS));
@@ -235,14 +231,14 @@ inline bool bad_k(int K) { return K < 2 || K > KMAX; }
 
 extern "C" {
 
-size_t cy_softmax_entropy_ws_bytes(long npix) { return (size_t)loss_blocks(npix) * sizeof(double); }
+size_t cy_softmax_entropy_ws_bytes(long npix) { return (size_t)cy_blocks(npix, 256, LOSS_GRID_CAP) * sizeof(double); }
 
 int cy_softmax_entropy_fwd(const float* logits, float* loss, long npix, int K, float eps, void* ws, size_t ws_bytes,
                            void* stream) {
   if (!logits || !loss || !ws || npix <= 0 || bad_k(K)) return CY_ERR_ARG;
   if (ws_bytes < cy_softmax_entropy_ws_bytes(npix)) return CY_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const int nblk = loss_blocks(npix);
+  const int nblk = cy_blocks(npix, 256, LOSS_GRID_CAP);
   CY_LAUNCH_BY_K(softmax_entropy_fwd_kernel, nblk, st, logits, (double*)ws, npix, K, eps);
   hipLaunchKernelGGL(mean_finalize_kernel, dim3(1), dim3(256), 0, st, (const double*)ws, nblk, (double)npix, loss);
   CY_CHECK_LAUNCH();
@@ -252,19 +248,19 @@ int cy_softmax_entropy_fwd(const float* logits, float* loss, long npix, int K, f
 int cy_softmax_entropy_bwd(const float* logits, const float* gscale, float* dlogits, long npix, int K, float eps,
                            void* stream) {
   if (!logits || !gscale || !dlogits || npix <= 0 || bad_k(K)) return CY_ERR_ARG;
-  CY_LAUNCH_BY_K(softmax_entropy_bwd_kernel, loss_blocks(npix) * 2, (hipStream_t)stream, logits, gscale, dlogits,
-                 npix, K, eps);
+  CY_LAUNCH_BY_K(softmax_entropy_bwd_kernel, cy_blocks(npix, 256, LOSS_GRID_CAP) * 2, (hipStream_t)stream, logits,
+                 gscale, dlogits, npix, K, eps);
   return CY_OK;
 }
 
-size_t cy_softmax_selfmse_ws_bytes(long npix) { return (size_t)loss_blocks(npix) * sizeof(double); }
+size_t cy_softmax_selfmse_ws_bytes(long npix) { return (size_t)cy_blocks(npix, 256, LOSS_GRID_CAP) * sizeof(double); }
 
 int cy_softmax_selfmse_fwd(const float* logits, float* loss, long npix, int K, void* ws, size_t ws_bytes,
                            void* stream) {
   if (!logits || !loss || !ws || npix <= 0 || bad_k(K)) return CY_ERR_ARG;
   if (ws_bytes < cy_softmax_selfmse_ws_bytes(npix)) return CY_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const int nblk = loss_blocks(npix);
+  const int nblk = cy_blocks(npix, 256, LOSS_GRID_CAP);
   CY_LAUNCH_BY_K(softmax_selfmse_fwd_kernel, nblk, st, logits, (double*)ws, npix, K);
   hipLaunchKernelGGL(mean_finalize_kernel, dim3(1), dim3(256), 0, st, (const double*)ws, nblk,
                      (double)npix * (double)K, loss);
@@ -274,19 +270,19 @@ int cy_softmax_selfmse_fwd(const float* logits, float* loss, long npix, int K, v
 
 int cy_softmax_selfmse_bwd(const float* logits, const float* gscale, float* dlogits, long npix, int K, void* stream) {
   if (!logits || !gscale || !dlogits || npix <= 0 || bad_k(K)) return CY_ERR_ARG;
-  CY_LAUNCH_BY_K(softmax_selfmse_bwd_kernel, loss_blocks(npix) * 2, (hipStream_t)stream, logits, gscale, dlogits,
-                 npix, K);
+  CY_LAUNCH_BY_K(softmax_selfmse_bwd_kernel, cy_blocks(npix, 256, LOSS_GRID_CAP) * 2, (hipStream_t)stream, logits,
+                 gscale, dlogits, npix, K);
   return CY_OK;
 }
 
-size_t cy_uamt_mse_ws_bytes(long npix) { return (size_t)loss_blocks(npix) * 2 * sizeof(double); }
+size_t cy_uamt_mse_ws_bytes(long npix) { return (size_t)cy_blocks(npix, 256, LOSS_GRID_CAP) * 2 * sizeof(double); }
 
 int cy_uamt_mse_fwd(const float* teacher, const float* student, float* result, long npix, int K, float thr, int hard,
                     void* ws, size_t ws_bytes, void* stream) {
   if (!teacher || !student || !result || !ws || npix <= 0 || bad_k(K)) return CY_ERR_ARG;
   if (ws_bytes < cy_uamt_mse_ws_bytes(npix)) return CY_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const int nblk = loss_blocks(npix);
+  const int nblk = cy_blocks(npix, 256, LOSS_GRID_CAP);
   CY_LAUNCH_BY_K(uamt_mse_fwd_kernel, nblk, st, teacher, student, (double*)ws, npix, K, thr, hard);
   hipLaunchKernelGGL(uamt_finalize_kernel, dim3(1), dim3(256), 0, st, (const double*)ws, nblk, (double)npix, result);
   CY_CHECK_LAUNCH();
@@ -296,8 +292,8 @@ int cy_uamt_mse_fwd(const float* teacher, const float* student, float* result, l
 int cy_uamt_mse_bwd(const float* teacher, const float* student, const float* result, const float* gscale,
                     float* dstudent, long npix, int K, float thr, int hard, void* stream) {
   if (!teacher || !student || !result || !gscale || !dstudent || npix <= 0 || bad_k(K)) return CY_ERR_ARG;
-  CY_LAUNCH_BY_K(uamt_mse_bwd_kernel, loss_blocks(npix) * 2, (hipStream_t)stream, teacher, student, result, gscale,
-                 dstudent, npix, K, thr, hard);
+  CY_LAUNCH_BY_K(uamt_mse_bwd_kernel, cy_blocks(npix, 256, LOSS_GRID_CAP) * 2, (hipStream_t)stream, teacher, student,
+                 result, gscale, dstudent, npix, K, thr, hard);
   return CY_OK;
 }
 

@@ -12,7 +12,7 @@
 // Gram matrix in f64 -- a thread per entry for short rows, a wave per entry for long ones -- and, backward, recomputes
 // all of it and writes dV; nothing is saved but the input.
 #include "cy_common.h"
-#include "cy_pixel_loss.h"
+#include "cy_reduce.h"
 
 namespace {
 
@@ -154,7 +154,6 @@ __global__ void __launch_bounds__(256)
     for (int q = tid; q < T; q += K) s += sh[q];
     partial[(long)tid * gridDim.x + blockIdx.x] = s;
   }
-  __syncthreads();
   const double tot = block_sum_d(acc_b, sh);
   if (tid == 0) partial[(long)K * gridDim.x + blockIdx.x] = tot;
 }
@@ -165,9 +164,7 @@ __global__ void __launch_bounds__(256)
                               float* __restrict__ db) {
   __shared__ double sh[256];
   const int k = blockIdx.x;
-  double acc = 0.0;
-  for (int i = threadIdx.x; i < nblk; i += 256) acc += partial[(long)k * nblk + i];
-  const double tot = block_sum_d(acc, sh);
+  const double tot = sum_partials_d(partial + (long)k * nblk, nblk, 1, sh);
   if (threadIdx.x == 0) {
     if (k < K)
       dw[k] = (float)tot;
@@ -177,12 +174,6 @@ __global__ void __launch_bounds__(256)
 }
 
 // ---------------------------------------------------------------- orthogonality
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // rows into LDS, their norms (snorm: the 2-norm, sden: clamped as F.normalize clamps it), then n = v / sden in place
 __device__ __forceinline__ void ortho_normalise(const float* __restrict__ V, float* sN, float* snorm, float* sden, int K,
                                                 int C, int stride) {
@@ -199,7 +190,7 @@ __device__ __forceinline__ void ortho_normalise(const float* __restrict__ V, flo
       const double v = (double)sN[i * stride + c];
       ss = fma(v, v, ss);
     }
-    ss = wave_sum_d(ss);
+    ss = wave_sum(ss);
     if (lane == 0) {
       const float nrm = (float)sqrt(ss);
       snorm[i] = nrm;
@@ -225,7 +216,7 @@ __device__ __forceinline__ void ortho_gram(const float* sN, int K, int C, int st
       const int i = e / K, j = e - i * K;
       double dot = 0.0;
       for (int c = lane; c < C; c += 64) dot = fma((double)sN[i * stride + c], (double)sN[j * stride + c], dot);
-      dot = wave_sum_d(dot);
+      dot = wave_sum(dot);
       if (lane == 0) f(e, dot - (i == j ? 1.0 : 0.0));
     }
   } else {
@@ -313,8 +304,8 @@ int prior_plan(int form, long n, int K, int C, int align, PriorPlan* pl) {
     else
       pl->variant = 0, pl->vec = (K % 4 == 0 && align % 16 == 0) ? 4 : 1;
     pl->k_chunks = pl->variant ? 1 : (K + DAE_CHUNK - 1) / DAE_CHUNK;
-    pl->fwd_grid = pl->bwd_grid = loss_blocks(n);
-    pl->fwd_trips = pl->bwd_trips = (int)((n + pl->fwd_grid * 256L - 1) / (pl->fwd_grid * 256L));
+    pl->fwd_grid = pl->bwd_grid = cy_blocks(n, 256, LOSS_GRID_CAP);
+    pl->fwd_trips = pl->bwd_trips = cy_trips(n, pl->fwd_grid, 256);
     pl->fwd_lds = 256 * 8 + PRIOR_KMAX * 4;
     pl->bwd_lds = pl->fwd_lds + 256 * 4;
     pl->aux = (256 / K) * K;
@@ -363,7 +354,7 @@ int prior_plan(int form, long n, int K, int C, int align, PriorPlan* pl) {
 
 inline size_t dae_ws_bytes(long npix, int K, int backward) {
   if (npix < 1 || K < 1) return 0;
-  return (size_t)loss_blocks(npix) * sizeof(double) * (backward ? (size_t)K + 1 : 1);
+  return (size_t)cy_blocks(npix, 256, LOSS_GRID_CAP) * sizeof(double) * (backward ? (size_t)K + 1 : 1);
 }
 
 inline bool dae_act_ok(int act) { return act == CY_PRIOR_ACT_SIGMOID || act == CY_PRIOR_ACT_TANH; }

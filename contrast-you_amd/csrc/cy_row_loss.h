@@ -71,11 +71,4 @@ __device__ __forceinline__ float part_in(const float* v, int k0, int lo, int hi)
   return s;
 }
 
-inline int row_blocks(long npix, int cap) {
-  long b = (npix + ROWS - 1) / ROWS;
-  if (b > cap) b = cap;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
 }  // namespace

@@ -17,6 +17,7 @@
 // A forward block never spans two images: the grid is N x blocks-per-image.
 #include "cy_common.h"
 #include "cy_pixel_loss.h"
+#include "cy_reduce.h"
 
 namespace {
 
@@ -117,26 +118,14 @@ __global__ void __launch_bounds__(256)
 }
 
 // ---------------------------------------------------------------- soft Dice of the softmax
-// blocks per image: one per 256 pixels, the whole grid held to loss_blocks' cap of 1024 (at least one per image)
+// blocks per image: one per 256 pixels, the whole grid held to LOSS_GRID_CAP (at least one per image)
 inline int dice_blocks_per_image(int N, long HW) {
-  long cap = 1024 / (N < 1 ? 1 : N);
+  long cap = LOSS_GRID_CAP / (N < 1 ? 1 : N);
   if (cap < 1) cap = 1;
   long b = (HW + 255) / 256;
   if (b > cap) b = cap;
   if (b < 1) b = 1;
   return (int)b;
-}
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 // block (n, b) of the N x bpi grid: part[blk][k] = {A, B} over its pixels of image n, cnt[blk][k] = T
@@ -173,8 +162,8 @@ __global__ void __launch_bounds__(256)
 #pragma unroll
   for (int k = 0; k < KMAX; ++k)
     if (k < K) {
-      const double a = wave_sum_d(A[k]), bb = wave_sum_d(B[k]);
-      const int tt = wave_sum_i(T[k]);
+      const double a = wave_sum(A[k]), bb = wave_sum(B[k]);
+      const int tt = wave_sum(T[k]);
       if (lane == 0) sh[wave][2 * k] = a, sh[wave][2 * k + 1] = bb, shc[wave][k] = tt;
     }
   __syncthreads();
@@ -278,7 +267,7 @@ __global__ void __launch_bounds__(256)
 
 extern "C" {
 
-size_t cy_softmax_wkl_ws_bytes(long npix) { return (size_t)loss_blocks(npix) * sizeof(double); }
+size_t cy_softmax_wkl_ws_bytes(long npix) { return (size_t)cy_blocks(npix, 256, LOSS_GRID_CAP) * sizeof(double); }
 
 int cy_softmax_wkl_fwd(const float* logits, const int64_t* target, const float* weight, float* loss, long npix, int K,
                        float eps, double denom, void* ws, size_t ws_bytes, void* stream) {
@@ -286,7 +275,7 @@ int cy_softmax_wkl_fwd(const float* logits, const int64_t* target, const float* 
   if (bad_k(K)) return CY_ERR_SHAPE;
   if (ws_bytes < cy_softmax_wkl_ws_bytes(npix)) return CY_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const int nblk = loss_blocks(npix);
+  const int nblk = cy_blocks(npix, 256, LOSS_GRID_CAP);
   CY_LAUNCH_BY_K(softmax_wkl_fwd_kernel, nblk, st, logits, target, weight, (double*)ws, npix, K, eps);
   hipLaunchKernelGGL(mean_finalize_kernel, dim3(1), dim3(256), 0, st, (const double*)ws, nblk, denom, loss);
   CY_CHECK_LAUNCH();
@@ -297,8 +286,8 @@ int cy_softmax_wkl_map_fwd(const float* logits, const int64_t* target, const flo
                            int K, float eps, void* stream) {
   if (!logits || !target || !map || npix <= 0) return CY_ERR_ARG;
   if (bad_k(K)) return CY_ERR_SHAPE;
-  CY_LAUNCH_BY_K(softmax_wkl_map_fwd_kernel, loss_blocks(npix) * 2, (hipStream_t)stream, logits, target, weight, map,
-                 npix, K, eps);
+  CY_LAUNCH_BY_K(softmax_wkl_map_fwd_kernel, cy_blocks(npix, 256, LOSS_GRID_CAP) * 2, (hipStream_t)stream, logits,
+                 target, weight, map, npix, K, eps);
   return CY_OK;
 }
 
@@ -306,8 +295,8 @@ int cy_softmax_wkl_bwd(const float* logits, const int64_t* target, const float* 
                        float* dlogits, long npix, int K, float eps, double denom, void* stream) {
   if (!logits || !target || !gscale || !dlogits || npix <= 0 || !(denom > 0.0)) return CY_ERR_ARG;
   if (bad_k(K)) return CY_ERR_SHAPE;
-  CY_LAUNCH_BY_K(softmax_wkl_bwd_kernel, loss_blocks(npix) * 2, (hipStream_t)stream, logits, target, weight, gscale,
-                 dlogits, npix, K, eps, denom);
+  CY_LAUNCH_BY_K(softmax_wkl_bwd_kernel, cy_blocks(npix, 256, LOSS_GRID_CAP) * 2, (hipStream_t)stream, logits, target,
+                 weight, gscale, dlogits, npix, K, eps, denom);
   return CY_OK;
 }
 
@@ -315,8 +304,8 @@ int cy_softmax_wkl_map_bwd(const float* logits, const int64_t* target, const flo
                            float* dlogits, long npix, int K, float eps, void* stream) {
   if (!logits || !target || !dmap || !dlogits || npix <= 0) return CY_ERR_ARG;
   if (bad_k(K)) return CY_ERR_SHAPE;
-  CY_LAUNCH_BY_K(softmax_wkl_map_bwd_kernel, loss_blocks(npix) * 2, (hipStream_t)stream, logits, target, weight, dmap,
-                 dlogits, npix, K, eps);
+  CY_LAUNCH_BY_K(softmax_wkl_map_bwd_kernel, cy_blocks(npix, 256, LOSS_GRID_CAP) * 2, (hipStream_t)stream, logits,
+                 target, weight, dmap, dlogits, npix, K, eps);
   return CY_OK;
 }
 

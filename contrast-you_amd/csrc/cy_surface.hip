@@ -10,7 +10,7 @@
 // squared distance, at most 3 * 1023^2, stays below it.  A pass never raises a value (j = i is among the candidates).
 #define CY_SURFACE_SENTINEL (1 << 30)
 #define CY_SURFACE_LINES 8             // adjacent lines a block takes in the H and D passes: 8 * 1024 * 4 = 32 KB of LDS
-#define CY_SURFACE_BLOCKS 1024         // cap of the partial-sum grid (the loss_blocks shape)
+#define CY_SURFACE_BLOCKS 1024         // cap of the partial-sum grid (blocks of 256 voxels)
 
 namespace {
 
@@ -163,10 +163,6 @@ __global__ void __launch_bounds__(256)
 }
 
 inline size_t surface_border_bytes(long V) { return (size_t)((2 * V + 15) / 16 * 16); }
-inline int surface_blocks(long V) {
-  const long b = (V + 255) / 256;
-  return (int)(b > CY_SURFACE_BLOCKS ? CY_SURFACE_BLOCKS : b);
-}
 
 // every refusal of the family, before any launch
 inline int surface_check(int D, int H, int W) {
@@ -211,7 +207,7 @@ int cy_surface_stats(const int64_t* pred, const int64_t* target, const int32_t* 
   uint8_t* ws_border = (uint8_t*)ws;
   int32_t* ws_d2 = (int32_t*)((uint8_t*)ws + surface_border_bytes(V));
   SurfacePartial* partials = (SurfacePartial*)(ws_d2 + 2 * V);
-  const int nb = surface_blocks(V);
+  const int nb = cy_blocks(V, 256, CY_SURFACE_BLOCKS);  // V >= 1 (surface_check)
   for (int r = 0; r < R; ++r) {
     // with map output the passes work in the caller's buffers ([direction][class][voxel]), else in the workspace
     uint8_t* b0 = border_maps ? border_maps + (long)r * V : ws_border;

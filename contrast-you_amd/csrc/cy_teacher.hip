@@ -11,6 +11,7 @@
 // atomics; neither softmax, nor the warped tensor, nor the difference is stored.
 #include "cy_common.h"
 #include "cy_pixel_loss.h"
+#include "cy_reduce.h"
 
 namespace {
 
@@ -186,8 +187,6 @@ struct TeacherPlan {
   int variant, vec, fwd_grid, fwd_trips, bwd_grid, bwd_trips, rows;
 };
 
-inline int clamp_trips(long t) { return t > INT32_MAX ? INT32_MAX : (int)t; }
-
 // the one place the four families take their kernel form and grid from; a status as the launches return it
 int teacher_plan(int form, long n, int K, int align, TeacherPlan* pl) {
   if (!pl || n < 1 || align < 1 || align % 4 != 0) return CY_ERR_ARG;
@@ -195,10 +194,8 @@ int teacher_plan(int form, long n, int K, int align, TeacherPlan* pl) {
   if (form == CY_TEACHER_ADAM || form == CY_TEACHER_AXPY) {
     pl->vec = (align % 16 == 0 && n >= 4) ? 4 : 1;
     const long groups = n / pl->vec;
-    long b = (groups + 255) / 256;
-    if (b > FLAT_GRID_CAP) b = FLAT_GRID_CAP;
-    pl->fwd_grid = (int)b;
-    pl->fwd_trips = clamp_trips((groups + b * 256 - 1) / (b * 256));
+    pl->fwd_grid = cy_blocks(groups, 256, FLAT_GRID_CAP);
+    pl->fwd_trips = cy_trips(groups, pl->fwd_grid, 256);
     return CY_OK;
   }
   if (form == CY_TEACHER_EMA_MULTI) {  // n: the tensors
@@ -216,10 +213,10 @@ int teacher_plan(int form, long n, int K, int align, TeacherPlan* pl) {
     const int row = K == 2 ? 8 : 16;  // bytes of a row access of the compiled forms
     pl->variant = ((K == 2 || K == 4 || K == 8) && align % row == 0) ? K : 0;
     pl->vec = pl->variant == 2 ? 2 : pl->variant ? 4 : 1;
-    pl->fwd_grid = loss_blocks(n);
+    pl->fwd_grid = cy_blocks(n, 256, LOSS_GRID_CAP);
     pl->bwd_grid = pl->fwd_grid * 2;
-    pl->fwd_trips = clamp_trips((n + pl->fwd_grid * 256L - 1) / (pl->fwd_grid * 256L));
-    pl->bwd_trips = clamp_trips((n + pl->bwd_grid * 256L - 1) / (pl->bwd_grid * 256L));
+    pl->fwd_trips = cy_trips(n, pl->fwd_grid, 256);
+    pl->bwd_trips = cy_trips(n, pl->bwd_grid, 256);
     return CY_OK;
   }
   return CY_ERR_ARG;
@@ -241,7 +238,7 @@ int teacher_plan(int form, long n, int K, int align, TeacherPlan* pl) {
 
 inline size_t gather_ws_bytes(int N, long HW) {
   if (N < 1 || HW < 1) return 0;
-  return (size_t)loss_blocks((long)N * HW) * sizeof(double);
+  return (size_t)cy_blocks((long)N * HW, 256, LOSS_GRID_CAP) * sizeof(double);
 }
 
 }  // namespace

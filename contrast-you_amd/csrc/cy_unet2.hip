@@ -9,6 +9,7 @@
 // None of this is on the SemiSupervisedEpocher + InfoNCE hot path: sized for correctness and full-chip launches,
 // not tuned per shape.
 #include "cy_common.h"
+#include "cy_reduce.h"
 
 namespace {
 
@@ -356,28 +357,15 @@ __global__ void __launch_bounds__(256)
 }
 
 // rows of the attention matrix (unet2.py:296-297): softmax over the last axis, in place.  One workgroup per row.
-__device__ __forceinline__ float block_reduce(float v, float* sred, bool is_max) {
-  const int tid = threadIdx.x;
-  sred[tid] = v;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) sred[tid] = is_max ? fmaxf(sred[tid], sred[tid + o]) : sred[tid] + sred[tid + o];
-    __syncthreads();
-  }
-  const float r = sred[0];
-  __syncthreads();
-  return r;
-}
-
 __global__ void __launch_bounds__(256) row_softmax_fwd_kernel(float* __restrict__ x, int n) {
   __shared__ float sred[256];
   float* row = x + (long)blockIdx.x * n;
   float m = -INFINITY;
   for (int j = threadIdx.x; j < n; j += 256) m = fmaxf(m, row[j]);
-  m = block_reduce(m, sred, true);
+  m = block_max_f(m, sred);
   float s = 0.f;
   for (int j = threadIdx.x; j < n; j += 256) s += expf(row[j] - m);
-  s = block_reduce(s, sred, false);
+  s = block_sum_f(s, sred);
   const float r = 1.0f / s;
   for (int j = threadIdx.x; j < n; j += 256) row[j] = expf(row[j] - m) * r;
 }
@@ -390,14 +378,11 @@ __global__ void __launch_bounds__(256)
   float* dr = dp + (long)blockIdx.x * n;
   float s = 0.f;
   for (int j = threadIdx.x; j < n; j += 256) s += pr[j] * dr[j];
-  s = block_reduce(s, sred, false);
+  s = block_sum_f(s, sred);
   for (int j = threadIdx.x; j < n; j += 256) dr[j] = pr[j] * (dr[j] - s);
 }
 
-inline int grid_for(long total) {
-  long g = (total + 255) / 256;
-  return (int)(g < 1 ? 1 : (g > 16384 ? 16384 : g));
-}
+constexpr int GRID_CAP = 16384;  // blocks of 256 of the elementwise kernels; the rest is their grid-stride loop
 
 inline MatL to_l(const cy_mat_layout* l) { return MatL{l->rs, l->cs, l->s1, l->s2}; }
 
@@ -495,8 +480,8 @@ int cy_gemm_strided(const float* A, const cy_mat_layout* la, const float* B, con
 #undef CY_GEMM
   CY_CHECK_LAUNCH();
   if (ksplit > 1) {
-    hipLaunchKernelGGL(gemm_reduce_kernel, dim3(grid_for(nbatch * M * N)), dim3(256), 0, st, ws, C, to_l(lc), bias, M,
-                       N, nb2, (int)nbatch, alpha, accumulate, ksplit);
+    hipLaunchKernelGGL(gemm_reduce_kernel, dim3(cy_blocks(nbatch * M * N, 256, GRID_CAP)), dim3(256), 0, st, ws, C,
+                       to_l(lc), bias, M, N, nb2, (int)nbatch, alpha, accumulate, ksplit);
     CY_CHECK_LAUNCH();
   }
   return CY_OK;
@@ -508,7 +493,7 @@ int cy_im2col(const float* x, float* cols, int N, int H, int W, int C, int KH, i
   if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || KH <= 0 || KW <= 0 || stride <= 0 || pad < 0) return CY_ERR_SHAPE;
   const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
   if (Ho <= 0 || Wo <= 0) return CY_ERR_SHAPE;
-  hipLaunchKernelGGL(im2col_kernel, dim3(grid_for((long)N * Ho * Wo * KH * KW * C)), dim3(256), 0,
+  hipLaunchKernelGGL(im2col_kernel, dim3(cy_blocks((long)N * Ho * Wo * KH * KW * C, 256, GRID_CAP)), dim3(256), 0,
                      (hipStream_t)stream, x, cols, N, H, W, C, Ho, Wo, KH, KW, stride, pad);
   CY_CHECK_LAUNCH();
   return CY_OK;
@@ -520,8 +505,8 @@ int cy_col2im(const float* cols, const float* bias, float* out, int N, int H, in
   if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || KH <= 0 || KW <= 0 || stride <= 0 || pad < 0) return CY_ERR_SHAPE;
   const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
   if (Ho <= 0 || Wo <= 0) return CY_ERR_SHAPE;
-  hipLaunchKernelGGL(col2im_kernel, dim3(grid_for((long)N * H * W * C)), dim3(256), 0, (hipStream_t)stream, cols,
-                     bias, out, N, H, W, C, Ho, Wo, KH, KW, stride, pad);
+  hipLaunchKernelGGL(col2im_kernel, dim3(cy_blocks((long)N * H * W * C, 256, GRID_CAP)), dim3(256), 0,
+                     (hipStream_t)stream, cols, bias, out, N, H, W, C, Ho, Wo, KH, KW, stride, pad);
   CY_CHECK_LAUNCH();
   return CY_OK;
 }
@@ -542,7 +527,8 @@ int cy_colsum(const float* x, float* out, long M, int N, int accumulate, float* 
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(colsum_partial_kernel, dim3(cy_cdiv(N, 256), S), dim3(256), 0, st, x, ws, M, N, rows_per);
   CY_CHECK_LAUNCH();
-  hipLaunchKernelGGL(slab_sum_kernel, dim3(grid_for(N)), dim3(256), 0, st, ws, out, S, (long)N, accumulate);
+  hipLaunchKernelGGL(slab_sum_kernel, dim3(cy_blocks(N, 256, GRID_CAP)), dim3(256), 0, st, ws, out, S, (long)N,
+                     accumulate);
   CY_CHECK_LAUNCH();
   return CY_OK;
 }
@@ -551,7 +537,8 @@ int cy_chan_layernorm_fwd(const float* x, const float* g, const float* b, float*
                           void* stream) {
   if (!x || !g || !b || !y) return CY_ERR_ARG;
   if (M <= 0 || C <= 0) return CY_ERR_SHAPE;
-  hipLaunchKernelGGL(chan_ln_fwd_kernel, dim3(grid_for(M)), dim3(256), 0, (hipStream_t)stream, x, g, b, y, M, C, eps);
+  hipLaunchKernelGGL(chan_ln_fwd_kernel, dim3(cy_blocks(M, 256, GRID_CAP)), dim3(256), 0, (hipStream_t)stream, x, g, b,
+                     y, M, C, eps);
   CY_CHECK_LAUNCH();
   return CY_OK;
 }
@@ -568,7 +555,8 @@ int cy_chan_layernorm_bwd(const float* x, const float* g, const float* dy, float
   hipStream_t st = (hipStream_t)stream;
   float* stats = ws;
   float* part = ws + 2 * M;
-  hipLaunchKernelGGL(chan_ln_bwd_dx_kernel, dim3(grid_for(M)), dim3(256), 0, st, x, g, dy, dx, stats, M, C, eps);
+  hipLaunchKernelGGL(chan_ln_bwd_dx_kernel, dim3(cy_blocks(M, 256, GRID_CAP)), dim3(256), 0, st, x, g, dy, dx, stats, M,
+                     C, eps);
   CY_CHECK_LAUNCH();
   if (dg && db) {
     const int S = slices_for(M);
@@ -576,9 +564,10 @@ int cy_chan_layernorm_bwd(const float* x, const float* g, const float* dy, float
     hipLaunchKernelGGL(chan_ln_bwd_param_kernel, dim3(cy_cdiv(C, 256), S), dim3(256), 0, st, x, dy, stats, part, M, C,
                        rows_per);
     CY_CHECK_LAUNCH();
-    hipLaunchKernelGGL(slab_sum_kernel, dim3(grid_for(C)), dim3(256), 0, st, part, dg, S, (long)C, 0);
+    hipLaunchKernelGGL(slab_sum_kernel, dim3(cy_blocks(C, 256, GRID_CAP)), dim3(256), 0, st, part, dg, S, (long)C, 0);
     CY_CHECK_LAUNCH();
-    hipLaunchKernelGGL(slab_sum_kernel, dim3(grid_for(C)), dim3(256), 0, st, part + (size_t)S * C, db, S, (long)C, 0);
+    hipLaunchKernelGGL(slab_sum_kernel, dim3(cy_blocks(C, 256, GRID_CAP)), dim3(256), 0, st, part + (size_t)S * C, db,
+                       S, (long)C, 0);
     CY_CHECK_LAUNCH();
   }
   return CY_OK;
@@ -588,8 +577,8 @@ int cy_head_softmax_fwd(const float* x, int ld, int off, float* y, long M, int h
                         void* stream) {
   if (!x || !y) return CY_ERR_ARG;
   if (M <= 0 || heads <= 0 || dh <= 0 || off < 0 || ld < off + heads * dh) return CY_ERR_SHAPE;
-  hipLaunchKernelGGL(head_softmax_fwd_kernel, dim3(grid_for(M * heads)), dim3(256), 0, (hipStream_t)stream, x, ld, off,
-                     y, M, heads, dh, scale);
+  hipLaunchKernelGGL(head_softmax_fwd_kernel, dim3(cy_blocks(M * heads, 256, GRID_CAP)), dim3(256), 0,
+                     (hipStream_t)stream, x, ld, off, y, M, heads, dh, scale);
   CY_CHECK_LAUNCH();
   return CY_OK;
 }
@@ -598,8 +587,8 @@ int cy_head_softmax_bwd(const float* y, const float* dy, float* dx, int ld_dx, i
                         float scale, void* stream) {
   if (!y || !dy || !dx) return CY_ERR_ARG;
   if (M <= 0 || heads <= 0 || dh <= 0 || off < 0 || ld_dx < off + heads * dh || scale == 0.f) return CY_ERR_SHAPE;
-  hipLaunchKernelGGL(head_softmax_bwd_kernel, dim3(grid_for(M * heads)), dim3(256), 0, (hipStream_t)stream, y, dy, dx,
-                     ld_dx, off, M, heads, dh, scale);
+  hipLaunchKernelGGL(head_softmax_bwd_kernel, dim3(cy_blocks(M * heads, 256, GRID_CAP)), dim3(256), 0,
+                     (hipStream_t)stream, y, dy, dx, ld_dx, off, M, heads, dh, scale);
   CY_CHECK_LAUNCH();
   return CY_OK;
 }
@@ -628,8 +617,8 @@ int cy_col_softmax_fwd(const float* x, int ld, int off, float* y, int B, int n, 
   CY_CHECK_LAUNCH();
   hipLaunchKernelGGL(col_softmax_final_kernel, dim3(cy_cdiv(B * Ch, 256)), dim3(256), 0, st, part, stat, B, S, Ch);
   CY_CHECK_LAUNCH();
-  hipLaunchKernelGGL(col_softmax_apply_kernel, dim3(grid_for((long)B * n * Ch)), dim3(256), 0, st, x, ld, off, stat, y,
-                     (long)B, n, Ch);
+  hipLaunchKernelGGL(col_softmax_apply_kernel, dim3(cy_blocks((long)B * n * Ch, 256, GRID_CAP)), dim3(256), 0, st, x,
+                     ld, off, stat, y, (long)B, n, Ch);
   CY_CHECK_LAUNCH();
   return CY_OK;
 }
@@ -638,8 +627,8 @@ int cy_col_softmax_bwd(const float* y, const float* dy, const float* t, float* d
                        int Ch, void* stream) {
   if (!y || !dy || !t || !dx) return CY_ERR_ARG;
   if (B <= 0 || n <= 0 || Ch <= 0 || off < 0 || ld_dx < off + Ch) return CY_ERR_SHAPE;
-  hipLaunchKernelGGL(col_softmax_bwd_kernel, dim3(grid_for((long)B * n * Ch)), dim3(256), 0, (hipStream_t)stream, y,
-                     dy, t, dx, ld_dx, off, (long)B, n, Ch);
+  hipLaunchKernelGGL(col_softmax_bwd_kernel, dim3(cy_blocks((long)B * n * Ch, 256, GRID_CAP)), dim3(256), 0,
+                     (hipStream_t)stream, y, dy, t, dx, ld_dx, off, (long)B, n, Ch);
   CY_CHECK_LAUNCH();
   return CY_OK;
 }

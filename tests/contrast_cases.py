@@ -27,7 +27,7 @@ TOL_16 = {"f32": TOL_GRAD, "bf16": 1.2e-2, "f16": 2e-3}   # dfeat / dx in the st
 # ---------------------------------------------------------------- restated launch geometry (coverage only)
 SC_TM = 64          # cy_contrast.hip: constexpr int SC_TM, rows / columns of a fused tile
 SC_SPLIT_BUDGET = 256   # cy_contrast.hip: sc_nsplit(), `ns = 256 / rb`, at most rb, at least 1
-GRID_CAP = 8192     # cy_contrast.hip: grid_for(), `b > 8192 ? 8192 : b`, blocks of 256
+GRID_CAP = 8192     # cy_contrast.hip: `constexpr int GRID_CAP = 8192;`, cy_blocks(items, 256, GRID_CAP)
 SGEMM_KSTAGE = 16   # cy_contrast.hip: sgemm_kernel stages K 16 at a time
 DP_TILE = 32        # cy_contrast.hip: supcon_fused_bwd_kernel, `nct = (D + 31) / 32` column tiles of dP, 8 at most
 PH_NT, PH_NW = 1024, 16   # cy_contrast.hip: threads and waves of the one-launch head
@@ -96,7 +96,7 @@ FUSED_WIDTHS = (8, 40, 96, 136, 248, 256)
 # refuses (above 256; 257 is no multiple of 8 either), 1 and 17 are no multiples of 8
 MATERIALISED_WIDTHS = (1, 17, 257, 264)
 
-# ---------------------------------------------------------------- SupCon: past the block cap of grid_for
+# ---------------------------------------------------------------- SupCon: past the block cap GRID_CAP
 CAP_N, CAP_D = 725, 8   # R = 1450: R * R = 2 102 500 > 8192 * 256, through cy_supcon_bwd, _excl_bwd and _matrices
 MASK_D_VALUES = (0, 1, -1, 2)   # a mask "of kind (d)": asymmetric, these values, all-ones diagonal
 

@@ -17,7 +17,7 @@ from collections import namedtuple
 TYPES = ("f32", "bf16", "f16")
 
 # ---------------------------------------------------------------- restated launch geometry (coverage only)
-GRID_CAP = 8192             # cy_misc.hip: grid_for(), `if (b > 8192) b = 8192;`
+GRID_CAP = 8192             # cy_misc.hip: `constexpr int GRID_CAP = 8192;`, the cap of every cy_blocks(items, 256, GRID_CAP)
 ONE_TRIP = GRID_CAP * 256   # items one trip of the grid-stride loops covers (256 threads per workgroup)
 
 

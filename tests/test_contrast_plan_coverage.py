@@ -135,7 +135,7 @@ def test_widths_and_which_of_them_the_fused_path_refuses(lib):
 
 def test_block_cap_is_exceeded_and_not_by_a_multiple():
     R = 2 * cc.CAP_N
-    assert R == 1450 and R * R > cc.GRID_CAP * 256 == 2097152 and (R * R) % (cc.GRID_CAP * 256), "R = 1450 past grid_for's cap"
+    assert R == 1450 and R * R > cc.GRID_CAP * 256 == 2097152 and (R * R) % (cc.GRID_CAP * 256), "R = 1450 past GRID_CAP"
     N, HW, Cc = cc.POOL_CAP
     assert 0 < N * HW * Cc - cc.GRID_CAP * 256 < 1024, "avgpool backward just above 2 097 152 elements"
     assert cc.GSCALE != 1 and cc.SGEMM_ALPHA != 1

@@ -135,7 +135,7 @@ def test_workspace_sizes(lib, npix):
     B = min(ceil(HW / 256), max(1, 1024 // N)) blocks, each K pairs of f64 and K int64 counts"""
     blocks = min(max((npix + 255) // 256, 1), 1024)
     assert lib.cy_softmax_wkl_ws_bytes(npix) == 8 * blocks
-    assert lib.cy_softmax_wkl_ws_bytes(npix) == lib.cy_softmax_kl_ws_bytes(npix)  # the shared loss_blocks
+    assert lib.cy_softmax_wkl_ws_bytes(npix) == lib.cy_softmax_kl_ws_bytes(npix)  # the shared cy_blocks(npix, 256, LOSS_GRID_CAP)
     for N in (1, 2, 3, 16, 1025):
         for K in (1, 4, 5, 16):
             B = min((npix + 255) // 256, max(1, 1024 // N))

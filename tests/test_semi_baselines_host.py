@@ -91,7 +91,7 @@ def test_workspace_sizes(lib, npix):
     assert lib.cy_softmax_entropy_ws_bytes(npix) == blocks * 8
     assert lib.cy_softmax_selfmse_ws_bytes(npix) == blocks * 8
     assert lib.cy_uamt_mse_ws_bytes(npix) == blocks * 16
-    assert lib.cy_softmax_mse_ws_bytes(npix) == blocks * 8  # the shared loss_blocks
+    assert lib.cy_softmax_mse_ws_bytes(npix) == blocks * 8  # the shared cy_blocks(npix, 256, LOSS_GRID_CAP)
 
 
 def test_every_factory_of_the_reference_hook_creator_is_importable(golden_dir):

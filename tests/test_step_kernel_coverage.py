@@ -33,9 +33,11 @@ def contributions(theta, H, W):
 
 def test_grid_cap_matches_the_source():
     text = (REPO / "contrast-you_amd" / "csrc" / "cy_misc.hip").read_text()
-    body = re.search(r"inline int grid_for\(long total\) \{(.*?)\n\}", text, flags=re.S).group(1)
-    assert re.findall(r"if \(b > (\d+)\) b = (\d+);", body) == [(str(sc.GRID_CAP),) * 2], "the cap of grid_for()"
-    assert "(total + 255) / 256" in body and sc.ONE_TRIP == sc.GRID_CAP * 256
+    assert re.findall(r"constexpr int GRID_CAP = (\d+);", text) == [str(sc.GRID_CAP)], "the cap of the four grids"
+    # every grid of the file is cy_blocks(items, 256, GRID_CAP) (csrc/cy_common.h): 256 items per block, that cap
+    calls = re.findall(r"\bcy_blocks\((.*?), (\w+), (\w+)\)[;)]", text)
+    assert len(calls) == 4 and {c[1:] for c in calls} == {("256", "GRID_CAP")}, calls
+    assert sc.ONE_TRIP == sc.GRID_CAP * 256
     # every kernel of the four walks `+= (long)gridDim.x * 256L` from `blockIdx.x * 256L + threadIdx.x`
     assert text.count("+= (long)gridDim.x * 256L") == 4 and text.count("dim3(256)") >= 4
 

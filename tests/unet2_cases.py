@@ -28,8 +28,8 @@ TOL_ACT = 1e-5
 
 # ---------------------------------------------------------------- restated launch geometry (coverage only)
 GN_SPLIT = 32          # cy_groupnorm.hip: constexpr int GN_SPLIT
-GN_GRID_CAP = 8192     # cy_groupnorm.hip: grid_for(), `b > 8192 ? 8192 : b`
-U2_GRID_CAP = 16384    # cy_unet2.hip: grid_for(), `g > 16384 ? 16384 : g`
+GN_GRID_CAP = 8192     # cy_groupnorm.hip: `constexpr int GRID_CAP = 8192;`, cy_blocks(items, 256, GRID_CAP)
+U2_GRID_CAP = 16384    # cy_unet2.hip: `constexpr int GRID_CAP = 16384;`, cy_blocks(items, 256, GRID_CAP)
 ACT_GRID_CAP = 4096    # cy_unet2.hip: cy_act_fwd / cy_act_bwd, `b > 4096 ? 4096 : b`
 SLICE_CAP = 512        # cy_unet2.hip: slices_for(); only used to NAME the cap, the count comes from *_ws_bytes
 COL_SLICE_CAP = 256    # cy_unet2.hip: col_slices(); likewise
