@@ -22,7 +22,7 @@ import torch
 from torch import Tensor, nn
 
 from cyhip import ops
-from cyhip.functions import SgemmFn, SupConFn
+from cyhip.functions import SelfPacedSupConFn, SgemmFn, SupConFn
 
 
 def is_normalized(feature: Tensor, dim=1) -> bool:
@@ -70,6 +70,20 @@ def _rejoin(a: Tensor, b: Tensor) -> Tensor:
     return torch.cat([a, b], dim=0)
 
 
+def _raise_pending(pending, t):
+    """the reference's two checks on the device-side evidence (min S_ii, max S_ii, loss) of the calls since the last
+    validate(): AssertionError (inputs not unit norm), RuntimeError (NaN loss)"""
+    if not pending:
+        return
+    ends = torch.stack([p[0] for p in pending] + [p[1] for p in pending])  # extreme S_ii = |P_i|^2 / t
+    errs = (ends * t - 1).abs().max()
+    losses = torch.stack([p[2] for p in pending])
+    bad_norm, has_nan = (errs > 1e-4).item(), torch.isnan(losses).any().item()
+    assert not bad_norm, "features need to be normalized first"
+    if has_nan:
+        raise RuntimeError(losses)
+
+
 class SupConLoss1(nn.Module):
     def __init__(self, temperature=0.07, exclude_other_pos=False):
         super().__init__()
@@ -107,15 +121,7 @@ class SupConLoss1(nn.Module):
     def validate(self):
         """raise like the reference: AssertionError (inputs not unit norm), RuntimeError (NaN loss)"""
         pending, self._pending = self._pending, []
-        if not pending:
-            return
-        ends = torch.stack([p[0] for p in pending] + [p[1] for p in pending])  # extreme S_ii = |P_i|^2 / t
-        errs = (ends * self._t - 1).abs().max()
-        losses = torch.stack([p[2] for p in pending])
-        bad_norm, has_nan = (errs > 1e-4).item(), torch.isnan(losses).any().item()
-        assert not bad_norm, "features need to be normalized first"
-        if has_nan:
-            raise RuntimeError(losses)
+        _raise_pending(pending, self._t)
 
     def _matrices(self):
         if self._last is None:
@@ -145,15 +151,33 @@ class SelfPacedSupConLoss(nn.Module):
     """`SelfPacedSupConLoss` (contrastyou/losses/contrastive.py:103-212): SupConLoss1 whose positive pairs are
     weighted by a self-paced mask computed (without gradient) from their own log-likelihood,
     hard: [l_ij <= gamma], soft: max(1 - l_ij / gamma, 0); gamma -> infinity recovers SupConLoss1 (the identity
-    the reference checks in its __main__, :241-248).  The similarity GEMM P P^T / t runs on the f32 MFMA kernel
-    (cyhip.functions.SgemmFn, differentiable); the 2n x 2n elementwise part is plain autograd -- this loss is
-    used at a few dozen rows by SelfPacedINFONCEHook, never at C5 sizes."""
+    the reference checks in its __main__, :241-248).
+
+    For embeddings the fused SupCon kernels take (D <= 256, D % 8 == 0) and gamma > 0 the loss runs on
+    `SelfPacedSupConFn`: two passes over the similarity tiles forward, one backward, the 2n x 2n matrix never written
+    (csrc/cy_contrast.hip).  Otherwise `_composition` runs: the similarity GEMM on the f32 MFMA kernel
+    (cyhip.functions.SgemmFn, differentiable) and the 2n x 2n elementwise part as plain autograd, with the reference's
+    host syncs.
+
+    The two checks of the reference (unit-norm inputs -> AssertionError, NaN loss -> RuntimeError) follow
+    `SupConLoss1`: evaluated on the device, raised by `validate()`; with `defer_checks=False` (default) validate() runs
+    inside forward and `downgrade_ratio` is a Python float, in deferred mode `downgrade_ratio` is a 0-dim device
+    tensor and forward does not wait for the device -- given a list of labels seen before (cached on the device), a
+    label tensor or a mask already on the device; a mask on the host, a new label list or float labels are uploaded or
+    encoded with a wait.  `sim_exp`, `sim_logits`, `pos_mask`, `neg_mask` and `sp_mask` are materialised on first
+    access; for that the criterion keeps a reference to P, the row statistics and the labels or mask of its last call
+    until the next one (at 4096 x 256 that holds 4 MiB of the projector's output alive between steps), as
+    `SupConLoss1` does."""
 
     def __init__(self, temperature=0.07, weight_update="hard", correct_grad=False, **kwargs):
         super().__init__()
         assert weight_update in ("hard", "soft"), weight_update
         self._t, self._weight_update, self._correct_grad = temperature, weight_update, correct_grad
         self._gamma = 1e6
+        self.defer_checks = False
+        self._pending = []
+        self._last = None   # fused path: (P, stats, labels, pos, gamma) of the last call, for the matrices
+        self._mats = None   # the five matrices, once formed
 
     def __repr__(self):
         return f"{self.__class__.__name__} with T: {self._t}, method: {self._weight_update} gamma: {self._gamma}"
@@ -168,6 +192,41 @@ class SelfPacedSupConLoss(nn.Module):
     def forward(self, proj_feat1: Tensor, proj_feat2: Tensor, target=None, mask: Optional[Tensor] = None, **kwargs):
         assert proj_feat1.shape == proj_feat2.shape, (proj_feat1.shape, proj_feat2.shape)
         ops.require_gpu(proj_feat1, proj_feat2)
+        if not (ops.supcon_fused_ok(proj_feat1) and self._gamma > 0):
+            return self._composition(proj_feat1, proj_feat2, target, mask)
+        n, dev = proj_feat1.shape[0], proj_feat1.device
+        labels = pos = None
+        if mask is not None:
+            assert mask.shape == torch.Size([n, n])
+            # contrastive.py:120-121: pos = mask == 1, neg = mask == 0, any other value is neither; uint8 codes 1 / 0 / 2,
+            # formed on the device (a mask that lives on the host is copied over first, and that copy makes the host wait)
+            mask = mask.to(dev)
+            pos = torch.where(mask == 1, 1, torch.where(mask == 0, 0, 2)).to(torch.uint8).contiguous()
+        elif target is not None:
+            labels = _encode_target(target, n, dev)
+        else:
+            labels = torch.arange(n, dtype=torch.int32, device=dev)
+        P = _rejoin(proj_feat1, proj_feat2)
+        loss, ratio, diag, stats = SelfPacedSupConFn.apply(P, labels, pos, float(self._t), self._gamma,
+                                                           self._weight_update == "soft", bool(self._correct_grad))
+        self._last, self._mats = (P.detach(), stats, labels, pos, self._gamma), None
+        mn, mx = torch.aminmax(diag)
+        self._pending.append((mn, mx, loss.detach()))
+        if self.defer_checks:
+            self.downgrade_ratio = ratio
+        else:
+            self.downgrade_ratio = ratio.item()
+            self.validate()
+        return loss
+
+    def validate(self):
+        """raise like the reference: AssertionError (inputs not unit norm), RuntimeError (NaN loss)"""
+        pending, self._pending = self._pending, []
+        _raise_pending(pending, self._t)
+
+    def _composition(self, proj_feat1: Tensor, proj_feat2: Tensor, target=None, mask: Optional[Tensor] = None):
+        """the loss as a composition of the similarity GEMM and torch elementwise ops on 2n x 2n tensors: what runs
+        for widths the fused kernels refuse, and the baseline of tools/bench_selfpaced.py"""
         n, dev = proj_feat1.shape[0], proj_feat1.device
         if mask is not None:
             assert mask.shape == torch.Size([n, n])
@@ -189,7 +248,6 @@ class SelfPacedSupConLoss(nn.Module):
         assert norm_err.item() < 1e-4, "features need to be normalized first"
         sim_logits = sim - sim.max().detach()
         sim_exp = torch.exp(sim_logits)
-        self.sim_exp, self.sim_logits, self.pos_mask, self.neg_mask = sim_exp, sim_logits, pos_mask, neg_mask
         pos_count = pos_mask.sum(1)
         denom = ((sim_exp * pos_mask).sum(1, keepdim=True) + (sim_exp * neg_mask).sum(1, keepdim=True))
         llh = sim_logits - torch.log(denom + 1e-16)
@@ -200,7 +258,8 @@ class SelfPacedSupConLoss(nn.Module):
             else:
                 w = torch.clamp(1 - l_ij / self._gamma, min=0)
             sp_mask = torch.max(w, 1 - pos_mask)
-        self.sp_mask = sp_mask
+        self._last = None
+        self._mats = dict(sim_exp=sim_exp, sim_logits=sim_logits, pos_mask=pos_mask, neg_mask=neg_mask, sp_mask=sp_mask)
         self.downgrade_ratio = torch.masked_select(sp_mask, pos_mask.bool()).mean().item()
         loss = -(((llh * sp_mask) * pos_mask).sum(1) / pos_count).mean()
         if self._correct_grad and self.downgrade_ratio > 0:
@@ -208,3 +267,36 @@ class SelfPacedSupConLoss(nn.Module):
         if torch.isnan(loss):
             raise RuntimeError(loss)
         return loss
+
+    def _matrices(self):
+        if self._mats is None:
+            if self._last is None:
+                raise AttributeError("call the criterion first")
+            P, stats, labels, pos, gamma = self._last  # (inspection aids: the similarity is formed on demand)
+            S = ops.sgemm(P.float().contiguous(), P.float().contiguous(), 1.0 / float(self._t), b_trans=True)
+            sim_logits, sim_exp, pos_mask, neg_mask = ops.supcon_matrices(S, stats, labels, pos)
+            l_ij = torch.log(stats[:, :1]) - sim_logits
+            w = (l_ij <= gamma).float() if self._weight_update == "hard" else torch.clamp(1 - l_ij / gamma, min=0)
+            self._mats = dict(sim_exp=sim_exp, sim_logits=sim_logits, pos_mask=pos_mask, neg_mask=neg_mask,
+                              sp_mask=torch.max(w, 1 - pos_mask))
+        return self._mats
+
+    @property
+    def sim_logits(self) -> Tensor:
+        return self._matrices()["sim_logits"]
+
+    @property
+    def sim_exp(self) -> Tensor:
+        return self._matrices()["sim_exp"]
+
+    @property
+    def pos_mask(self) -> Tensor:
+        return self._matrices()["pos_mask"]
+
+    @property
+    def neg_mask(self) -> Tensor:
+        return self._matrices()["neg_mask"]
+
+    @property
+    def sp_mask(self) -> Tensor:
+        return self._matrices()["sp_mask"]

@@ -631,6 +631,288 @@ inline int sc_nsplit(int R) {
   return ns;
 }
 
+// ---------------------------------------------------------------- SupCon, self-paced: the fused kernels with weights
+// SelfPacedSupConLoss (contrastive.py:103-212): every positive pair carries a constant weight w_ij of its own negative
+// log-likelihood l_ij = -llh_ij, llh_ij = (S_ij - M) - log D_i -- hard [l_ij <= gamma], soft max(1 - l_ij / gamma, 0):
+//   loss = -(1/R) sum_i (1/c_i) sum_pos w_ij llh_ij,   ratio = sum_pos w_ij / sum_i c_i
+// w_ij needs the finished D_i, so the forward runs over the tiles twice: supcon_fused_fwd_kernel for (l, ps, cnt), then
+// supcon_sp_fwd_kernel for (sum_pos w llh, sum_pos w); the backward recomputes w from row_stats on both sides of
+//   G_ij + G_ji = -(g scale / R) [pos_ij w_ij / c_i + pos_ji w_ji / c_j - e_ij (in_ij W_i / (c_i D_i) + in_ji W_j / (c_j D_j))]
+// Same tiles, same exact f32 MFMA, same fixed orders as above.  S_ij is rounded before M is subtracted (no fused
+// multiply-add) and llh is formed as (S_ij - M) - log D_i in every kernel: the hard weight is a threshold, forward and
+// backward must come down on the same side of it.
+
+// D_i and c_i of a row: the column splits of the first pass summed in order -- the one place this sum is written
+__device__ __forceinline__ void sp_row_sums(const float* __restrict__ partA, int R, int nsplit, int row, float& Di,
+                                            float& ci) {
+  float li = 0.f, cnt = 0.f;
+  for (int s = 0; s < nsplit; ++s) {
+    const float* p = partA + ((size_t)s * R + row) * 3;
+    li += p[0], cnt += p[2];
+  }
+  Di = li + 1e-16f;
+  ci = cnt;
+}
+
+template <bool SOFT>
+__device__ __forceinline__ float sp_weight(float llh, float gamma) {
+  const float l = -llh;
+  return SOFT ? fmaxf(1.f - l / gamma, 0.f) : (l <= gamma ? 1.f : 0.f);
+}
+
+// grid (row blocks, column splits), as supcon_fused_fwd_kernel.  partB[split][R][2] = (sum w llh, sum w) over the
+// positives among the split's columns.
+template <bool MASK, bool SOFT>
+__global__ void __launch_bounds__(256)
+    supcon_sp_fwd_kernel(const float* __restrict__ P, const int32_t* __restrict__ labels,
+                         const uint8_t* __restrict__ pm, const float* __restrict__ Mptr,
+                         const float* __restrict__ partA, float* __restrict__ partB, int n, int D, float inv_t,
+                         float gamma, int nsplit) {
+  extern __shared__ float sm[];
+  const int R = 2 * n;
+  float* sPi = sm;
+  float* sPj = sm + sc_block_floats(D);
+  float* sred = sPj;                           // reused at the end: [2 wn][64 rows][2]
+  float* sLog = sPj + sc_block_floats(D);      // [64]: log D_i of the row block
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 1, wn = wave & 1;
+  const int i = lane & 31, kk = lane >> 5;
+  const int m0 = blockIdx.x * SC_TM;
+  const int ncb = (R + SC_TM - 1) / SC_TM;
+  const int cb0 = (ncb * (int)blockIdx.y) / nsplit, cb1 = (ncb * ((int)blockIdx.y + 1)) / nsplit;
+  const float M = Mptr[0];
+  sc_stage(P, sPi, m0, R, D, tid);
+  if (tid < SC_TM) {
+    float Di = 1.f, ci = 0.f;
+    if (m0 + tid < R) sp_row_sums(partA, R, nsplit, m0 + tid, Di, ci);
+    sLog[tid] = logf(Di);
+  }
+  __syncthreads();
+  float wl[16], wsum[16], logD[16];
+  ScRow rws[16];
+#pragma unroll
+  for (int q = 0; q < 16; ++q) {
+    const int rr = wm * 32 + (q & 3) + 8 * (q >> 2) + 4 * kk;
+    wl[q] = wsum[q] = 0.f;
+    logD[q] = sLog[rr];
+    rws[q] = sc_row(labels, n, m0 + rr);
+  }
+  for (int cb = cb0; cb < cb1; ++cb) {
+    const int n0 = cb * SC_TM;
+    __syncthreads();  // previous tile's reads of sPj are done
+    sc_stage(P, sPj, n0, R, D, tid);
+    __syncthreads();
+    const f32x16 acc = sc_tile(sPi, sPj, D, wm, wn, i, kk);
+    const int col = n0 + wn * 32 + i;
+    const ScRow cq = sc_row(labels, n, col);
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) {
+      const int row = m0 + wm * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * kk;
+      if (row < R && col < R && row != col) {
+        const bool pos = MASK ? sc_code(rws[reg], cq, pm, n) == 1 : sc_pos(rws[reg], cq, labels, pm, n);
+        if (pos) {
+          const float llh = (__fmul_rn(acc[reg], inv_t) - M) - logD[reg];
+          const float w = sp_weight<SOFT>(llh, gamma);
+          wl[reg] += w * llh;
+          wsum[reg] += w;
+        }
+      }
+    }
+  }
+  // row totals: over the 32 lanes that share kk (fixed xor tree), then over the two column halves (wn)
+#pragma unroll
+  for (int reg = 0; reg < 16; ++reg)
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) {
+      wl[reg] += __shfl_xor(wl[reg], o, 64);
+      wsum[reg] += __shfl_xor(wsum[reg], o, 64);
+    }
+  __syncthreads();
+  if (i == 0) {
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) {
+      const int rr = wm * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * kk;
+      float* d = sred + (wn * SC_TM + rr) * 2;
+      d[0] = wl[reg], d[1] = wsum[reg];
+    }
+  }
+  __syncthreads();
+  for (int e = tid; e < SC_TM * 2; e += 256) {
+    const int rr = e / 2;
+    if (m0 + rr < R) partB[((size_t)blockIdx.y * R + m0 + rr) * 2 + e % 2] = sred[e] + sred[SC_TM * 2 + e];
+  }
+}
+
+// single block: row_stats[R][4] = (D_i, c_i, W_i, M), aux[4] = (loss, ratio, scale, sum c); rows summed in f64
+__global__ void __launch_bounds__(256)
+    supcon_sp_finalize_kernel(const float* __restrict__ partA, const float* __restrict__ partB,
+                              const float* __restrict__ Mptr, float* __restrict__ row_stats, float* __restrict__ aux,
+                              int R, int nsplit, int correct_grad) {
+  __shared__ double ssum[3][256];
+  const int tid = threadIdx.x;
+  const float M = Mptr[0];
+  double al = 0.0, aw = 0.0, ac = 0.0;
+  for (int i = tid; i < R; i += 256) {
+    float Di, ci, wl = 0.f, W = 0.f;
+    sp_row_sums(partA, R, nsplit, i, Di, ci);
+    for (int s = 0; s < nsplit; ++s) {
+      const float* q = partB + ((size_t)s * R + i) * 2;
+      wl += q[0], W += q[1];
+    }
+    al += (double)(wl / ci);  // c_i == 0 -> NaN like the reference
+    aw += (double)W;
+    ac += (double)ci;
+    row_stats[i * 4 + 0] = Di;
+    row_stats[i * 4 + 1] = ci;
+    row_stats[i * 4 + 2] = W;
+    row_stats[i * 4 + 3] = M;
+  }
+  ssum[0][tid] = al, ssum[1][tid] = aw, ssum[2][tid] = ac;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o)
+      for (int k = 0; k < 3; ++k) ssum[k][tid] += ssum[k][tid + o];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    const double ratio = ssum[1][0] / ssum[2][0];
+    const double scale = (correct_grad && ratio > 0.0) ? 1.0 / ratio : 1.0;
+    aux[0] = (float)(-ssum[0][0] / (double)R * scale);
+    aux[1] = (float)ratio;
+    aux[2] = (float)scale;
+    aux[3] = (float)ssum[2][0];
+  }
+}
+
+// grid (row blocks, column splits), as supcon_fused_bwd_kernel; rs = row_stats of the forward, aux[2] = scale
+template <bool MASK, bool SOFT>
+__global__ void __launch_bounds__(256)
+    supcon_sp_bwd_kernel(const float* __restrict__ P, const int32_t* __restrict__ labels,
+                         const uint8_t* __restrict__ pm, const float* __restrict__ rs, const float* __restrict__ aux,
+                         const float* __restrict__ gscale, float* __restrict__ dpart, int n, int D, float inv_t,
+                         float gamma, int nsplit) {
+  extern __shared__ float sm[];
+  const int R = 2 * n, ldg = SC_TM + 1;
+  const int ld2 = sc_ld2(D), pl = sc_plane(D);
+  float* sPi = sm;
+  float* sPj = sm + sc_block_floats(D);
+  float* sG = sPj + sc_block_floats(D);
+  float* sRow = sG + SC_TM * ldg;  // [64][3]: W_i / (c_i D_i), 1 / c_i, log D_i of the row block
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 1, wn = wave & 1;
+  const int i = lane & 31, kk = lane >> 5;
+  const int m0 = blockIdx.x * SC_TM;
+  const int ncb = (R + SC_TM - 1) / SC_TM;
+  const int cb0 = (ncb * (int)blockIdx.y) / nsplit, cb1 = (ncb * ((int)blockIdx.y + 1)) / nsplit;
+  const float M = rs[3];
+  const float gs = gscale[0] * aux[2] / (float)R;
+  sc_stage(P, sPi, m0, R, D, tid);
+  if (tid < SC_TM) {
+    const int row = m0 + tid;
+    float a = 0.f, ic = 0.f, lg = 0.f;
+    if (row < R) {
+      const float Di = rs[row * 4 + 0], ci = rs[row * 4 + 1];
+      a = rs[row * 4 + 2] / (ci * Di), ic = 1.f / ci, lg = logf(Di);
+    }
+    sRow[tid * 3 + 0] = a, sRow[tid * 3 + 1] = ic, sRow[tid * 3 + 2] = lg;
+  }
+  const int nct = (D + 31) / 32;          // 32-wide column tiles of dP
+  f32x16 acc2[4];                          // this wave's column tiles: wn, wn + 2, wn + 4, wn + 6
+#pragma unroll
+  for (int c = 0; c < 4; ++c)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) acc2[c][q] = 0.f;
+  for (int cb = cb0; cb < cb1; ++cb) {
+    const int n0 = cb * SC_TM;
+    __syncthreads();  // previous tile: the second product has read sG and sPj
+    sc_stage(P, sPj, n0, R, D, tid);
+    __syncthreads();
+    const f32x16 acc = sc_tile(sPi, sPj, D, wm, wn, i, kk);
+    const int col = n0 + wn * 32 + i;
+    const ScRow cq = sc_row(labels, n, col);
+    float aj = 0.f, icj = 0.f, lgj = 0.f;
+    if (col < R) {
+      const float Dj = rs[col * 4 + 0], cj = rs[col * 4 + 1];
+      aj = rs[col * 4 + 2] / (cj * Dj), icj = 1.f / cj, lgj = logf(Dj);
+    }
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) {
+      const int rr = wm * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * kk;
+      const int row = m0 + rr;
+      float v = 0.f;
+      if (row < R && col < R && row != col) {
+        const float sl = __fmul_rn(acc[reg], inv_t) - M;
+        const ScRow rq = sc_row(labels, n, row);
+        bool pij, pji, iij = true, iji = true;
+        if (MASK) {
+          const int cij = sc_code(rq, cq, pm, n), cji = sc_code(cq, rq, pm, n);
+          pij = cij == 1, pji = cji == 1, iij = cij <= 1, iji = cji <= 1;
+        } else {
+          pij = pji = sc_pos(rq, cq, labels, pm, n);
+        }
+        float p = 0.f;
+        if (pij) p += sp_weight<SOFT>(sl - sRow[rr * 3 + 2], gamma) * sRow[rr * 3 + 1];
+        if (pji) p += sp_weight<SOFT>(sl - lgj, gamma) * icj;
+        const float q = (iij ? sRow[rr * 3 + 0] : 0.f) + (iji ? aj : 0.f);
+        v = -gs * (p - expf(sl) * q);
+      }
+      sG[rr * ldg + wn * 32 + i] = v;
+    }
+    __syncthreads();
+    // dP rows (wm block) += G[64 rows][64 j] * P_j[64 j][D]
+    const float* ga = sG + (wm * 32 + i) * ldg + kk;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int ct = wn + 2 * c;
+      if (ct < nct) {
+        const int dcol = ct * 32 + i;  // P_j[j][dcol] sits at [dcol & 1][j][dcol >> 1]
+        const float* pb = sPj + (dcol & 1) * pl + kk * ld2 + (dcol >> 1);
+#pragma unroll 8
+        for (int js = 0; js < SC_TM; js += 2)
+          acc2[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(ga[js], pb[js * ld2], acc2[c], 0, 0, 0);
+      }
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const int ct = wn + 2 * c;
+    const int dcol = ct * 32 + i;
+    if (ct < nct && dcol < D) {
+#pragma unroll
+      for (int reg = 0; reg < 16; ++reg) {
+        const int row = m0 + wm * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * kk;
+        if (row < R) dpart[((size_t)blockIdx.y * R + row) * D + dcol] = acc2[c][reg];
+      }
+    }
+  }
+}
+
+constexpr int SP_FWD_LDS_FLOATS = SC_TM;                         // log D_i
+constexpr int SP_BWD_LDS_FLOATS = SC_TM * (SC_TM + 1) + SC_TM * 3;   // the G tile and the row staging
+
+template <bool MASK, bool SOFT>
+int launch_sp_fwd(const float* P, const int32_t* labels, const uint8_t* pm, const float* Mv, const float* partA,
+                  float* partB, int n, int D, float t, float gamma, int rb, int ns, hipStream_t st) {
+  const size_t smem = ((size_t)2 * sc_block_floats(D) + SP_FWD_LDS_FLOATS) * sizeof(float);
+  hipLaunchKernelGGL((supcon_sp_fwd_kernel<MASK, SOFT>), dim3(rb, ns), dim3(256), smem, st, P, labels, pm, Mv, partA,
+                     partB, n, D, 1.f / t, gamma, ns);
+  CY_CHECK_LAUNCH();
+  return CY_OK;
+}
+
+template <bool MASK, bool SOFT>
+int launch_sp_bwd(const float* P, const int32_t* labels, const uint8_t* pm, const float* rs, const float* aux,
+                  const float* gscale, float* dpart, int n, int D, float t, float gamma, int rb, int ns,
+                  hipStream_t st) {
+  const size_t smem = ((size_t)2 * sc_block_floats(D) + SP_BWD_LDS_FLOATS) * sizeof(float);
+  hipLaunchKernelGGL((supcon_sp_bwd_kernel<MASK, SOFT>), dim3(rb, ns), dim3(256), smem, st, P, labels, pm, rs, aux,
+                     gscale, dpart, n, D, 1.f / t, gamma, ns);
+  CY_CHECK_LAUNCH();
+  return CY_OK;
+}
+
 // ---------------------------------------------------------------- avg pool
 template <typename T>
 __global__ void __launch_bounds__(256)
@@ -1117,6 +1399,87 @@ int cy_supcon_fused_bwd(const float* P, const int32_t* labels, const uint8_t* po
     hipLaunchKernelGGL(supcon_fused_bwd_kernel<true>, dim3(rb, ns), dim3(256), smem, st, P, labels, pos_mask, row_stats,
                        gscale, dpart, n, D, 1.f / t, ns);
   CY_CHECK_LAUNCH();
+  const long total = (long)R * D;
+  hipLaunchKernelGGL(supcon_dpart_reduce_kernel, dim3(cy_blocks(total, 256, GRID_CAP)), dim3(256), 0, st, dpart, dP,
+                     total, ns, 1.f / t);
+  CY_CHECK_LAUNCH();
+  return CY_OK;
+}
+
+size_t cy_supcon_sp_ws_bytes(int n, int D) {
+  if (n <= 0 || D <= 0) return 0;
+  const size_t R = 2 * (size_t)n;
+  const size_t ns = (size_t)sc_nsplit((int)R);
+  // diag[R] + M[4] + forward partials [ns][R][3] and [ns][R][2] | backward partials [ns][R][D]
+  const size_t fwd = ns * R * 5, bwd = ns * R * (size_t)D;
+  return (R + 4 + (fwd > bwd ? fwd : bwd)) * sizeof(float);
+}
+
+int cy_supcon_sp_fwd(const float* P, const int32_t* labels, const uint8_t* pos_mask, float* aux, float* row_stats,
+                     float* diag_out, void* ws, size_t ws_bytes, int n, int D, float t, float gamma, int soft,
+                     int correct_grad, void* stream) {
+  if (!P || (!labels && !pos_mask) || !aux || !row_stats || !ws) return CY_ERR_ARG;
+  if (n <= 0 || D <= 0 || D > 256 || D % 8 || !(t > 0.f) || !(gamma > 0.f)) return CY_ERR_SHAPE;
+  if (ws_bytes < cy_supcon_sp_ws_bytes(n, D)) return CY_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const int R = 2 * n, ns = sc_nsplit(R), rb = cy_cdiv(R, SC_TM);
+  float* diag = diag_out ? diag_out : (float*)ws;
+  float* Mv = (float*)ws + R;
+  float* partA = Mv + 4;
+  float* partB = partA + (size_t)ns * R * 3;
+  hipLaunchKernelGGL(supcon_diag_kernel, dim3(cy_cdiv(R, 4)), dim3(256), 0, st, P, diag, R, D, 1.f / t);
+  CY_CHECK_LAUNCH();
+  hipLaunchKernelGGL(supcon_max_kernel, dim3(1), dim3(256), 0, st, diag, Mv, R);
+  CY_CHECK_LAUNCH();
+  const size_t smem = (size_t)2 * sc_block_floats(D) * sizeof(float);
+  if (!cy_lds_limit_once<supcon_fused_fwd_kernel<false>, supcon_fused_fwd_kernel<true>>(2 * sc_block_floats(256) * 4))
+    return CY_ERR_LAUNCH;
+  if (!cy_lds_limit_once<supcon_sp_fwd_kernel<false, false>, supcon_sp_fwd_kernel<false, true>,
+                         supcon_sp_fwd_kernel<true, false>, supcon_sp_fwd_kernel<true, true>>(
+          (2 * sc_block_floats(256) + SP_FWD_LDS_FLOATS) * 4))
+    return CY_ERR_LAUNCH;
+  if (labels)
+    hipLaunchKernelGGL(supcon_fused_fwd_kernel<false>, dim3(rb, ns), dim3(256), smem, st, P, labels, pos_mask, Mv, partA,
+                       n, D, 1.f / t, ns);
+  else
+    hipLaunchKernelGGL(supcon_fused_fwd_kernel<true>, dim3(rb, ns), dim3(256), smem, st, P, labels, pos_mask, Mv, partA,
+                       n, D, 1.f / t, ns);
+  CY_CHECK_LAUNCH();
+  int rc;
+  if (labels)
+    rc = soft ? launch_sp_fwd<false, true>(P, labels, pos_mask, Mv, partA, partB, n, D, t, gamma, rb, ns, st)
+              : launch_sp_fwd<false, false>(P, labels, pos_mask, Mv, partA, partB, n, D, t, gamma, rb, ns, st);
+  else
+    rc = soft ? launch_sp_fwd<true, true>(P, labels, pos_mask, Mv, partA, partB, n, D, t, gamma, rb, ns, st)
+              : launch_sp_fwd<true, false>(P, labels, pos_mask, Mv, partA, partB, n, D, t, gamma, rb, ns, st);
+  if (rc != CY_OK) return rc;
+  hipLaunchKernelGGL(supcon_sp_finalize_kernel, dim3(1), dim3(256), 0, st, partA, partB, Mv, row_stats, aux, R, ns,
+                     correct_grad);
+  CY_CHECK_LAUNCH();
+  return CY_OK;
+}
+
+int cy_supcon_sp_bwd(const float* P, const int32_t* labels, const uint8_t* pos_mask, const float* row_stats,
+                     const float* aux, const float* gscale, float* dP, void* ws, size_t ws_bytes, int n, int D, float t,
+                     float gamma, int soft, void* stream) {
+  if (!P || (!labels && !pos_mask) || !row_stats || !aux || !gscale || !dP || !ws) return CY_ERR_ARG;
+  if (n <= 0 || D <= 0 || D > 256 || D % 8 || !(t > 0.f) || !(gamma > 0.f)) return CY_ERR_SHAPE;
+  if (ws_bytes < cy_supcon_sp_ws_bytes(n, D)) return CY_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const int R = 2 * n, ns = sc_nsplit(R), rb = cy_cdiv(R, SC_TM);
+  float* dpart = (float*)ws + R + 4;
+  if (!cy_lds_limit_once<supcon_sp_bwd_kernel<false, false>, supcon_sp_bwd_kernel<false, true>,
+                         supcon_sp_bwd_kernel<true, false>, supcon_sp_bwd_kernel<true, true>>(
+          (2 * sc_block_floats(256) + SP_BWD_LDS_FLOATS) * 4))
+    return CY_ERR_LAUNCH;
+  int rc;
+  if (labels)
+    rc = soft ? launch_sp_bwd<false, true>(P, labels, pos_mask, row_stats, aux, gscale, dpart, n, D, t, gamma, rb, ns, st)
+              : launch_sp_bwd<false, false>(P, labels, pos_mask, row_stats, aux, gscale, dpart, n, D, t, gamma, rb, ns, st);
+  else
+    rc = soft ? launch_sp_bwd<true, true>(P, labels, pos_mask, row_stats, aux, gscale, dpart, n, D, t, gamma, rb, ns, st)
+              : launch_sp_bwd<true, false>(P, labels, pos_mask, row_stats, aux, gscale, dpart, n, D, t, gamma, rb, ns, st);
+  if (rc != CY_OK) return rc;
   const long total = (long)R * D;
   hipLaunchKernelGGL(supcon_dpart_reduce_kernel, dim3(cy_blocks(total, 256, GRID_CAP)), dim3(256), 0, st, dpart, dP,
                      total, ns, 1.f / t);

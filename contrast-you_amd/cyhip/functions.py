@@ -1089,6 +1089,32 @@ class SupConFn(torch.autograd.Function):
         return ops.supcon_bwd(P, ctx.labels, ctx.pos_mask, S, stats, gs, ctx.t), None, None, None, None
 
 
+class SelfPacedSupConFn(torch.autograd.Function):
+    """SelfPacedSupConLoss (contrastyou/losses/contrastive.py:103-212) on P = cat(z1, z2), D <= 256 and D % 8 == 0: the
+    fused SupCon tiles with a second forward pass for the self-paced weights.  Returns the loss, the self-paced ratio
+    (both 0-dim device tensors), the diagonal of the similarity matrix and the row statistics (D_i, c_i, W_i, M); only
+    the loss is differentiable -- the weights and the ratio are constants of the gradient, as in the reference."""
+
+    @staticmethod
+    def forward(ctx, P: Tensor, labels: Optional[Tensor], pos_mask: Optional[Tensor], t: float, gamma: float,
+                soft: bool, correct_grad: bool):
+        ops.require_gpu(P)
+        P = P.float().contiguous()
+        aux, diag, stats = ops.supcon_sp_fwd(P, labels, pos_mask, t, gamma, soft, correct_grad)
+        ctx.save_for_backward(P, stats, aux)
+        ctx.labels, ctx.pos_mask, ctx.t, ctx.gamma, ctx.soft = labels, pos_mask, t, gamma, soft
+        loss, ratio = aux[0], aux[1]
+        ctx.mark_non_differentiable(ratio, diag, stats)
+        return loss, ratio, diag, stats
+
+    @staticmethod
+    def backward(ctx, g: Tensor, _gr, _gd, _gstats):
+        P, stats, aux = ctx.saved_tensors
+        gs = g.reshape(1).float().contiguous()
+        dP = ops.supcon_sp_bwd(P, ctx.labels, ctx.pos_mask, stats, aux, gs, ctx.t, ctx.gamma, ctx.soft)
+        return dP, None, None, None, None, None, None
+
+
 class AffineFn(torch.autograd.Function):
     """Nearest-neighbour affine resampling (+gamma), the in-step augmentation of
     semi_seg/augment.py:297-311 with the geometry given explicitly as theta."""

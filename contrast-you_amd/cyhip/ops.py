@@ -2301,6 +2301,35 @@ def supcon_bwd_fused(P: Tensor, labels, pos_mask, stats: Tensor, gscale: Tensor,
     return dP
 
 
+def supcon_sp_fwd(P: Tensor, labels: Optional[Tensor], pos_mask: Optional[Tensor], t: float, gamma: float, soft: bool,
+                  correct_grad: bool):
+    """SelfPacedSupConLoss on the fused kernels: aux = (loss, ratio, scale, sum of positive counts), diag(S), row
+    statistics (D_i, c_i, W_i, M); the similarity matrix is never materialised (csrc/cy_contrast.hip)"""
+    R, D = P.shape
+    n = R // 2
+    nbytes = _lib.load().cy_supcon_sp_ws_bytes(n, D)
+    ws = _ws(nbytes, P.device)
+    stats = _f32(R * 4, P.device).view(R, 4)
+    diag = _f32(R, P.device)
+    aux = _f32(4, P.device)
+    _lib.call("cy_supcon_sp_fwd", P.data_ptr(), _ptr(labels), _ptr(pos_mask), aux.data_ptr(), stats.data_ptr(),
+              diag.data_ptr(), ws.data_ptr(), nbytes, n, D, float(t), float(gamma), int(bool(soft)),
+              int(bool(correct_grad)), _stream())
+    return aux, diag, stats
+
+
+def supcon_sp_bwd(P: Tensor, labels, pos_mask, stats: Tensor, aux: Tensor, gscale: Tensor, t: float, gamma: float,
+                  soft: bool) -> Tensor:
+    R, D = P.shape
+    nbytes = _lib.load().cy_supcon_sp_ws_bytes(R // 2, D)
+    ws = _ws(nbytes, P.device)
+    dP = torch.empty_like(P)
+    _lib.call("cy_supcon_sp_bwd", P.data_ptr(), _ptr(labels), _ptr(pos_mask), stats.data_ptr(), aux.data_ptr(),
+              gscale.data_ptr(), dP.data_ptr(), ws.data_ptr(), nbytes, R // 2, D, float(t), float(gamma),
+              int(bool(soft)), _stream())
+    return dP
+
+
 def supcon_matrices(S: Tensor, stats: Tensor, labels, pos_mask):
     R = S.shape[0]
     outs = [_f32(R * R, S.device).view(R, R) for _ in range(4)]

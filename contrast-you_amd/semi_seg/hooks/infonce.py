@@ -129,7 +129,7 @@ class SelfPacedINFONCEHook(INFONCEHook):
 
     def __init__(self, *, name, model: nn.Module, feature_name: str, weight: float = 1.0, spatial_size=(1, 1),
                  data_name: str, contrast_on: str, mode="soft", p=0.5, begin_value=1e6, end_value=1e6,
-                 correct_grad: bool = False, max_epoch: int) -> None:
+                 correct_grad: bool = False, max_epoch: int, global_negatives: bool = False) -> None:
         self._mode = mode
         self._p = float(p)
         self._begin_value = float(begin_value)
@@ -137,7 +137,7 @@ class SelfPacedINFONCEHook(INFONCEHook):
         self._max_epoch = int(max_epoch)
         self._correct_grad = correct_grad
         super().__init__(name=name, model=model, feature_name=feature_name, weight=weight, spatial_size=spatial_size,
-                         data_name=data_name, contrast_on=contrast_on)
+                         data_name=data_name, contrast_on=contrast_on, global_negatives=global_negatives)
 
     def init_criterion(self) -> SelfPacedSupConLoss:
         self._scheduler = PScheduler(max_epoch=self._max_epoch, begin_value=self._begin_value,
@@ -151,7 +151,7 @@ class SelfPacedINFONCEHook(INFONCEHook):
         self._criterion.set_gamma(gamma)
         return _SPINFONCEEpochHook(name=self._hook_name, weight=self._weight, extractor=self._extractor,
                                    projector=self._projector, criterion=self._criterion,
-                                   label_generator=self._label_generator)
+                                   label_generator=self._label_generator, global_negatives=self._global_negatives)
 
 
 class SuperPixelInfoNCEHook(INFONCEHook):
@@ -182,7 +182,7 @@ class _INFONCEEpochHook(EpocherHook):
         self._weight = weight
         self._projector = projector
         self._criterion = criterion
-        self._criterion.defer_checks = True  # (SupConLoss1: checks once per epoch; a no-op attribute elsewhere)
+        self._criterion.defer_checks = True  # (both criteria: checks once per epoch, device scalars in between)
         self._label_generator = label_generator
         self._n = 0
 
@@ -240,7 +240,7 @@ class _SPINFONCEEpochHook(_INFONCEEpochHook):
 
     def _call_implementation(self, **kwargs):
         loss = super()._call_implementation(**kwargs)
-        self.meters["sp_weight"].add(self._criterion.downgrade_ratio)
+        self.meters["sp_weight"].add(self._criterion.downgrade_ratio)  # (deferred mode: a device scalar, no host read)
         self.meters["age_param"].add(self._criterion.age_param)
         return loss
 

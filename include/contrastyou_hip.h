@@ -628,6 +628,30 @@ int cy_supcon_fused_bwd(const float* P, const int32_t* labels, const uint8_t* po
 int cy_supcon_matrices(const float* S, const float* row_stats, const int32_t* labels,
                        const uint8_t* pos_mask, float* sim_logits, float* sim_exp,
                        float* pos_out, float* neg_out, int n, void* stream);
+/* SelfPacedSupConLoss (losses/contrastive.py:103-212) on the tile machinery of the fused entries above: the loss of
+ * cy_supcon_fused_fwd with every positive pair weighted by a constant w_ij of its own negative log-likelihood,
+ *   llh_ij = (S_ij - M) - log D_i,  l_ij = -llh_ij,  D_i = sum_{k != i, pos or neg} E_ik + 1e-16,  c_i = |pos(i)|
+ *   w_ij = [l_ij <= gamma] (soft == 0)  or  max(1 - l_ij / gamma, 0) (soft != 0)
+ *   loss = -(1/R) sum_i (1/c_i) sum_{pos} w_ij llh_ij;   ratio = sum_{pos} w_ij / sum_i c_i
+ *   correct_grad != 0 and ratio > 0: loss / ratio, the ratio a constant of the gradient
+ * w needs the finished D_i: two passes over the tiles (row sums, then the weighted sums), S never written.
+ *   row_stats f32 [R][4] = (D_i, c_i, W_i = sum_{pos} w_ij, M);  aux f32 [4] = (loss, ratio, scale, sum_i c_i) with
+ *   scale = 1 / ratio or 1: what the backward multiplies the upstream gradient with.  diag_out as above (optional).
+ * backward: dP = (1/t)(G + G^T) P,  G_ij = -(gscale[0] scale / R) [pos_ij w_ij / c_i - in_ij E_ij W_i / (c_i D_i)],
+ * the weights recomputed from row_stats exactly as the forward formed them.
+ * Checked before any launch: NULL P, outputs or ws, or labels and pos_mask both NULL -> CY_ERR_ARG; n <= 0, D <= 0,
+ * D > 256, D % 8, !(t > 0), !(gamma > 0) -> CY_ERR_SHAPE; a short workspace -> CY_ERR_WORKSPACE.  Fixed summation
+ * orders: two runs give the same bits.  ws: cy_supcon_sp_ws_bytes(n, D) bytes (0 where n or D is refused), one size
+ * for both calls as with cy_supcon_fused_ws_bytes: diag[R] + M[4] + max(ns R 5, ns R D) floats for ns column splits.
+ * The forward uses the first R + 4 + ns R 5 of them (0.4 MB at R = 4096, where the query answers 16 MiB for the
+ * backward's [ns][R][D] partials); a caller that keeps one buffer for both directions allocates once. */
+size_t cy_supcon_sp_ws_bytes(int n, int D);
+int cy_supcon_sp_fwd(const float* P, const int32_t* labels, const uint8_t* pos_mask, float* aux, float* row_stats,
+                     float* diag_out, void* ws, size_t ws_bytes, int n, int D, float t, float gamma, int soft,
+                     int correct_grad, void* stream);
+int cy_supcon_sp_bwd(const float* P, const int32_t* labels, const uint8_t* pos_mask, const float* row_stats,
+                     const float* aux, const float* gscale, float* dP, void* ws, size_t ws_bytes, int n, int D, float t,
+                     float gamma, int soft, void* stream);
 /* f32 GEMM on the f32 MFMA: C[M][N] = alpha * A[M][K] * op(B); b_trans=1: B is
  * [N][K] (C = A B^T), b_trans=0: B is [K][N]. */
 int cy_sgemm(const float* A, const float* B, float* C, int M, int N, int K, float alpha,
