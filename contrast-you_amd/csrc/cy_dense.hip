@@ -395,6 +395,7 @@ inline int dp_bwd_blocks(int nb) { return nb < 256 ? nb : 256; }
 }  // namespace
 
 #include "cy_dense_mfma.h"
+#include "cy_dense_wide.h"
 
 extern "C" {
 
@@ -406,10 +407,21 @@ int cy_dense_proj_fwd(const void* x, const float* w1, const float* b1, const int
     return CY_ERR_SHAPE;
   if (!bins && nb != N * sh * sw) return CY_ERR_SHAPE;
   hipStream_t st = (hipStream_t)stream;
-  if (dpm_applicable(dtype, C, hid, slope)) {
+  DpPlan P;
+  if (dtype != CY_BF16 && dtype != CY_F16 && dtype != CY_F32) return CY_ERR_DTYPE;
+  const int prc = dp_plan(C, hid, dtype, slope, P);
+  if (prc != CY_OK) return prc;
+  if (P.form == CY_DENSE_PROJ_MFMA_REG) {
     if (dtype == CY_BF16)
       return dpm_launch_fwd<bf16>((const bf16*)x, w1, b1, bins, nb, hpool, H, W, ldx, C, hid, sh, sw, slope, st);
     return dpm_launch_fwd<f16>((const f16*)x, w1, b1, bins, nb, hpool, H, W, ldx, C, hid, sh, sw, slope, st);
+  }
+  if (P.form == CY_DENSE_PROJ_MFMA_STREAM) {
+#define CY_DPW_FWD(T_, CB_) \
+  dpw_launch_fwd<T_, CB_>(P, (const T_*)x, w1, b1, bins, nb, hpool, H, W, ldx, hid, sh, sw, slope, st)
+    if (dtype == CY_BF16) return C == 256 ? CY_DPW_FWD(bf16, 8) : CY_DPW_FWD(bf16, 16);
+    return C == 256 ? CY_DPW_FWD(f16, 8) : CY_DPW_FWD(f16, 16);
+#undef CY_DPW_FWD
   }
   if (dtype == CY_BF16)
     hipLaunchKernelGGL(dense_proj_fwd_kernel<bf16>, dim3(nb), dim3(256), 0, st, (const bf16*)x, w1,
@@ -426,10 +438,25 @@ int cy_dense_proj_fwd(const void* x, const float* w1, const float* b1, const int
   return CY_OK;
 }
 
+int cy_dense_proj_plan(int C, int hid, int dtype, float slope, int32_t* plan) {
+  if (!plan) return CY_ERR_ARG;
+  DpPlan P;
+  const int rc = dp_plan(C, hid, dtype, slope, P);
+  if (rc != CY_OK) return rc;
+  plan[0] = P.form, plan[1] = P.cb, plan[2] = P.fwd_pass, plan[3] = P.dw_pass;
+  plan[4] = P.lds_fwd > P.lds_dx ? P.lds_fwd : P.lds_dx;
+  plan[5] = dp_plan_launches(P, false), plan[6] = dp_plan_launches(P, true), plan[7] = P.w_global;
+  return CY_OK;
+}
+
 size_t cy_dense_proj_bwd_ws_bytes(int nb, int C, int hid) {
   const size_t valu = (size_t)dp_bwd_blocks(nb) * ((size_t)hid * C + hid) * sizeof(float);
-  // workgroup partials + the job table (cells: N (2 sh - 1)(2 sw - 1) < 4 nb records)
-  const size_t mfma = (size_t)DPM_WGS * DPM_PART * sizeof(float) + (size_t)4 * (nb > 0 ? nb : 1) * sizeof(DpRec);
+  // workgroup partials + the job table (cells: N (2 sh - 1)(2 sw - 1) < 4 nb records) + the streamed form's 16-bit image of
+  // W1 (the query has no dtype or slope: it covers whichever form the call will run; the streamed form uses the VALU
+  // slabs first and the job table and image afterwards, in the same block)
+  size_t mfma = (size_t)DPM_WGS * DPM_PART * sizeof(float) + (size_t)4 * (nb > 0 ? nb : 1) * sizeof(DpRec);
+  DpPlan P;
+  if (dp_plan(C, hid, CY_BF16, 0.f, P) == CY_OK && P.w_global) mfma += dp_wide_image_bytes(C, hid);
   return valu > mfma ? valu : mfma;
 }
 
@@ -445,7 +472,10 @@ int cy_dense_proj_bwd(const void* x, const float* w1, const float* b1, const int
   if (dtype != CY_BF16 && dtype != CY_F32 && dtype != CY_F16) return CY_ERR_DTYPE;
   if (!ws || ws_bytes < cy_dense_proj_bwd_ws_bytes(nb, C, hid)) return CY_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  if (dpm_applicable(dtype, C, hid, slope)) {
+  DpPlan P;
+  const int prc = dp_plan(C, hid, dtype, slope, P);
+  if (prc != CY_OK) return prc;
+  if (P.form == CY_DENSE_PROJ_MFMA_REG) {
     if (dtype == CY_BF16)
       return dpm_launch_bwd<bf16>((const bf16*)x, w1, b1, bins, nb, dhpool, (bf16*)dx, dw1, db1, accumulate, N, H, W,
                                   ldx, C, hid, sh, sw, slope, (float*)ws, st);
@@ -469,6 +499,21 @@ int cy_dense_proj_bwd(const void* x, const float* w1, const float* b1, const int
                          (const float*)x, w1, b1, bins, nb, dhpool, (float*)nullptr, (float*)ws, H, W, C,
                          ldx, hid, sh, sw, slope, -1);
     CY_CHECK_LAUNCH();
+  }
+  if (P.form == CY_DENSE_PROJ_MFMA_STREAM) {
+    // 256 / 512 channels: the parameter gradients stay on the VALU kernel above (its slabs are summed before the job
+    // table reuses the workspace); dx runs the streamed matrix-core kernels
+    if (dw1 || db1) {
+      hipLaunchKernelGGL(slot_reduce_kernel, dim3(cy_cdiv((long)slot, 256)), dim3(256), 0, st,
+                         (const float*)ws, dw1, db1, G, hid * C, hid, accumulate);
+      CY_CHECK_LAUNCH();
+    }
+    if (!dx) return CY_OK;
+#define CY_DPW_DX(T_, CB_) \
+  dpw_launch_dx_all<T_, CB_>(P, (const T_*)x, w1, b1, bins, nb, dhpool, (T_*)dx, N, H, W, ldx, hid, sh, sw, slope, (float*)ws, st)
+    if (dtype == CY_BF16) return C == 256 ? CY_DPW_DX(bf16, 8) : CY_DPW_DX(bf16, 16);
+    return C == 256 ? CY_DPW_DX(f16, 8) : CY_DPW_DX(f16, 16);
+#undef CY_DPW_DX
   }
   for (int colour = 0; dx && colour < 4; ++colour) {
     if (dtype == CY_BF16)

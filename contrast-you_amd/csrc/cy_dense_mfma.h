@@ -4,8 +4,14 @@
 // contrastyou/projectors/heads.py:31-41,99-123).  The kernels were written for C = 32; with CB = C / 32 channel
 // blocks the pre-activations accumulate over the blocks (rows and the W1 image carry a block index) and the backward
 // kernels' second product (dW1, dx) is done for ONE selected block per launch (`cbs`): CB launches, each recomputing
-// the cheap pre-activations, instead of the VALU kernels' 9-15 ms.  (C = 256 would need 192 registers of rows in
-// flight: it stays on the VALU kernels.)
+// the cheap pre-activations, instead of the VALU kernels' 9-15 ms.
+// This is the REGISTER-RESIDENT form: every channel block's pixel rows of a 32-pixel block are in flight in registers
+// (24 per block and buffer set) and W1 sits in registers (forward) or in a static LDS image of CB x 16 KB (backward).
+// C = 256 would need 192 registers of rows and a 128 KB static image: the forward and the dx product of 256 and 512
+// channels run the streamed form of cy_dense_wide.h, which keeps the accumulator in registers instead, streams the rows
+// through a bounded window and holds W1 in dynamic LDS (their dW1 / db1 stay on the VALU kernel).  Which form a call runs is decided in one place, dp_plan
+// (cy_dense_wide.h) = cy_dense_proj_plan; everything else -- other C or hidden sizes, f32 maps, slope > 1,
+// CY_DENSE_MFMA=0 -- stays on the VALU kernels of cy_dense.hip.
 //
 // No workgroup-level cooperation: a WAVE owns a job (a bin, or a cell of the bin partition) and walks its
 // pixels 32 at a time.  The 1x1 convolution of a block of 32 pixels is 2 x (hid/32) MFMAs whose operands need no
@@ -684,19 +690,6 @@ __global__ void __launch_bounds__(256, 2)
 #pragma unroll
     for (int cb = 0; cb < CB; ++cb) f0[cb][0] = n0[cb][0], f0[cb][1] = n0[cb][1];
   }
-}
-
-inline bool dpm_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("CY_DENSE_MFMA");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
-inline bool dpm_applicable(int dtype, int C, int hid, float slope) {
-  return dpm_enabled() && (dtype == CY_BF16 || dtype == CY_F16) && (C == 32 || C == 64 || C == 128) && (hid == 128 || hid == 256) &&
-         slope <= 1.f;  // (the forward kernel forms lrelu as max(t, slope * t))
 }
 
 template <typename T, int CB>

@@ -2390,6 +2390,18 @@ def _bins_tensor(bins, device) -> Optional[Tensor]:
     return pinned.upload(torch.as_tensor(bins, dtype=torch.int32).reshape(-1, 3).contiguous(), device)
 
 
+_DENSE_PROJ_PLAN = ("form", "channel_blocks", "fwd_passes", "dw_passes", "lds_bytes", "bwd_launches", "bwd_launches_list",
+                    "w1_image_in_ws")
+
+
+def dense_proj_plan(C_in: int, hid: int, dtype: torch.dtype = torch.bfloat16, slope: float = 0.01) -> dict:
+    """which kernels cy_dense_proj_fwd / _bwd run for this map (host-side query, no GPU needed): form is
+    _lib.CY_DENSE_PROJ_VALU, _MFMA_REG (C = 32 / 64 / 128) or _MFMA_STREAM (C = 256 / 512)"""
+    plan = (C.c_int32 * 8)()
+    _lib.call("cy_dense_proj_plan", int(C_in), int(hid), dtype_code(dtype), float(slope), plan)
+    return dict(zip(_DENSE_PROJ_PLAN, (int(v) for v in plan)))
+
+
 def dense_proj_fwd(x: Tensor, w1: Tensor, b1: Tensor, size: Tuple[int, int], bins: Optional[Tensor],
                    slope: float = 0.01) -> Tensor:
     """x NHWC [N,C,H,W]; w1 f32 [hid,C]; -> hpool f32 [nb, hid] = mean over each bin of lrelu(w1 x + b1)"""

@@ -861,6 +861,21 @@ int cy_dense_proj_bwd(const void* x, const float* w1, const float* b1, const int
                       const float* dhpool, void* dx, float* dw1, float* db1, int accumulate, int N,
                       int H, int W, int C, int ldx, int hid, int sh, int sw, float slope, int dtype,
                       void* ws, size_t ws_bytes, void* stream);
+/* cy_dense_proj_plan (host side, no GPU needed) is the rule cy_dense_proj_fwd, cy_dense_proj_bwd and
+ * cy_dense_proj_bwd_ws_bytes follow when they choose their kernels (an added entry: no signature changed):
+ *   plan[0] kernel form (CY_DENSE_PROJ_*), [1] channel blocks of 32 (VALU: staged chunks), [2] passes over the hidden
+ *   units of the forward kernel, [3] ... of the dW1 kernel, [4] dynamic LDS bytes (the largest of the three kernels';
+ *   <= 160 KiB), [5] launches of a backward with all bins that asks for dx and the parameter gradients, [6] ... with a
+ *   bin list, [7] 1 when the dx kernel reads W1 from a 16-bit image in the workspace (hid * C * 2 bytes behind the
+ *   partials and the job table, counted by cy_dense_proj_bwd_ws_bytes), else 0.
+ * The matrix-core forms take 16-bit maps, 128 or 256 hidden units and slope <= 1: C = 32, 64, 128 the register-resident
+ * form, C = 256, 512 the streamed form (forward and dx; its dW1 / db1 run the VALU kernel: one pass); everything else, and every call when CY_DENSE_MFMA=0 is set (read once per
+ * process), runs the VALU kernels.  plan == NULL -> CY_ERR_ARG; C < 1, C % 8 != 0 or hid < 1 -> CY_ERR_SHAPE; an
+ * unknown dtype -> CY_ERR_DTYPE. */
+#define CY_DENSE_PROJ_VALU 0        /* any dtype, any C % 8 == 0 */
+#define CY_DENSE_PROJ_MFMA_REG 1    /* pixel rows and W1 resident in registers / static LDS */
+#define CY_DENSE_PROJ_MFMA_STREAM 2 /* forward, dx: accumulator resident, rows streamed, W1 in dynamic LDS per pass */
+int cy_dense_proj_plan(int C, int hid, int dtype, float slope, int32_t* plan /* [8] */);
 /* nn.AdaptiveAvgPool2d((sh,sw)) on an NHWC map -> f32 [nb][C] (same bin list
  * convention); backward for the all-bins case (gather form, deterministic). */
 int cy_adaptive_avgpool_fwd(const void* x, const int32_t* bins, int nb, float* out, int N, int H,

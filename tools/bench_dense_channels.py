@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""the dense projector over feature-map channel counts (the decoder taps of UNet(max_channel=512)), N = 32, 256 hidden units:
+"""the dense projector over feature-map channel counts (the decoder taps of UNet(max_channel=512), and Up_conv5 of
+max_channel=1024: 512 channels at 14x14), N = 32, 256 hidden units:
     python tools/bench_dense_channels.py            (on the GPU box; times are host-paced events in ms -> us)"""
 import sys, torch
 from pathlib import Path
@@ -8,7 +9,7 @@ sys.path.insert(0, str(REPO / "contrast-you_amd")); sys.path.insert(0, str(REPO 
 from cyhip import ops
 from bench_next import timed
 dev, dt = "cuda", torch.bfloat16
-for (n, c, hw) in ((32, 32, 224), (32, 64, 112), (32, 128, 56), (32, 256, 28)):
+for (n, c, hw) in ((32, 32, 224), (32, 64, 112), (32, 128, 56), (32, 256, 28), (32, 512, 14)):
     s, hid = 20 if hw >= 112 else 14, 256
     x = torch.randn(n, hw, hw, c, device=dev).to(dt).permute(0, 3, 1, 2)
     w1 = torch.randn(hid, c, device=dev) * 0.1
