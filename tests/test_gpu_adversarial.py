@@ -22,6 +22,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import disc_flat_cases as dc
 from adversarial_fixture import (ARMS, BN_ROWS, BUFFERS, CASES, HIDDEN, K, PARAMS, SCORE_SHAPE, StoredLogits, arm_tag,
                                  decode, generator_gradient64, pin, replica, state_dict_of)
 from test_gpu_hooks_dice import Loader, blob_batch
@@ -133,13 +134,10 @@ def _cat_formula(image, z, G):
     return out.detach(), z.grad
 
 
-@pytest.mark.parametrize("Ci", [0, 1, 3])
-@pytest.mark.parametrize("Kc", [2, 4, 5, 16])
-def test_softmax_cat_kernel(Kc, Ci):
-    """npix = 286 = 2 x 13 x 11: one full block plus a tail; rows h < 3 are all-zero logits"""
+def _softmax_cat_check(Kc, Ci, N, H, W):
+    """rows h < 3 are all-zero logits"""
     from cyhip.functions import SoftmaxCatFn
     gen = torch.Generator().manual_seed(100 * Kc + Ci)
-    N, H, W = 2, 13, 11
     z = torch.randn(N, Kc, H, W, generator=gen) * (torch.rand(N, 1, H, W, generator=gen) * 4)
     z[:, :, :3] = 0
     image = torch.rand(N, Ci, H, W, generator=gen) if Ci else None
@@ -157,6 +155,19 @@ def test_softmax_cat_kernel(Kc, Ci):
     assert torch.equal(out[:, Ci:, :3].cpu(), torch.full((N, Kc, 3, W), 1.0 / Kc).float())  # a zero row: exactly 1 / K
 
 
+@pytest.mark.parametrize("Ci", dc.CAT_CI)
+@pytest.mark.parametrize("Kc", dc.CAT_K)
+def test_softmax_cat_kernel(Kc, Ci):
+    """npix = 286 = 2 x 13 x 11: one full block plus a tail; Ci up to CI_MAX"""
+    _softmax_cat_check(Kc, Ci, *dc.CAT_SMALL_NHW)
+
+
+@pytest.mark.parametrize("Kc,Ci", [c[:2] for c in dc.CAT_PAST_CAP])
+def test_softmax_cat_kernel_past_the_grid_cap(Kc, Ci):
+    """525 625 pixels: the grid-stride loops of both kernels go round a second time, in each of their three forms"""
+    _softmax_cat_check(Kc, Ci, 1, dc.CAT_SIDE, dc.CAT_SIDE)
+
+
 # ---------------------------------------------------------------------------------------------- 2. BatchNorm + LeakyReLU
 def _bn_formula(x, gamma, beta, rm, rv, dy):
     """training-mode batch_norm + leaky_relu in the dtype of x -> (y, running_mean, running_var, dx, dgamma, dbeta)"""
@@ -167,10 +178,10 @@ def _bn_formula(x, gamma, beta, rm, rv, dy):
     return y.detach(), rm, rv, x.grad, gamma.grad, beta.grad
 
 
-@pytest.mark.parametrize("M,C", [(48, 512), (770, 128), (257, 20), (2, 4), (259, 7), (45, 1023)])
+@pytest.mark.parametrize("M,C", list(dc.BN_SHAPES))
 def test_bn_lrelu_kernels(M, C):
-    """column 0 is exactly constant, column 1 sits at 1e3 (what a one-pass f32 variance would get wrong); the two extra
-    shapes take the 4-byte row accesses (C % 4 != 0), the second of them with sixteen column tiles"""
+    """column 0 is exactly constant, column 1 sits at 1e3 (what a one-pass f32 variance would get wrong); what each
+    shape reaches (16- and 4-byte row accesses, column tiles, the capped row chunks): tests/disc_flat_cases.py"""
     from cyhip.functions import BNLeakyReLUFn
     gen = torch.Generator().manual_seed(7 * M + C)
     x = torch.randn(M, C, generator=gen) * (0.5 + torch.rand(1, C, generator=gen)) + torch.randn(1, C, generator=gen)
@@ -229,8 +240,8 @@ def test_bn_lrelu_eval_mode_uses_the_running_statistics():
 
 
 # ---------------------------------------------------------------------------------------------- 3. plain LeakyReLU
-@pytest.mark.parametrize("n", [1, 1023, 1025])
-def test_leaky_relu_kernels(n):
+def _lrelu_check(n, on_device):
+    """`on_device` puts the f32 input [1, 1, n, 1] on the GPU as a leaf"""
     from cyhip.functions import LeakyReLUFn
     gen = torch.Generator().manual_seed(n)
     x, dy = torch.randn(n, generator=gen), torch.randn(n, generator=gen)
@@ -242,7 +253,7 @@ def test_leaky_relu_kernels(n):
     xc = x.clone().requires_grad_(True)
     y32 = F.leaky_relu(xc, SLOPE)
     (y32 * dy).sum().backward()
-    xg = gpu_leaf(x.reshape(1, 1, n, 1))
+    xg = on_device(x.reshape(1, 1, n, 1))
     y = LeakyReLUFn.apply(xg, SLOPE)
     (y * dy.reshape(1, 1, n, 1).to(DEV)).sum().backward()
     check_tensor(f"LeakyReLU n {n} fwd", y.reshape(n), want, measured(y32.detach(), want))
@@ -252,6 +263,32 @@ def test_leaky_relu_kernels(n):
         assert yc[1] == 0 and not torch.signbit(yc[1]) and yc[2] == 0 and torch.signbit(yc[2]) and torch.signbit(yc[-1])
         gz = xg.grad.reshape(n).cpu()
         assert torch.equal(gz[[1, 2, -1]], (dy[[1, 2, -1]] * torch.tensor(SLOPE)))  # a zero input: the slope side
+
+
+@pytest.mark.parametrize("n", list(dc.LRELU_ALIGNED))
+def test_leaky_relu_kernels(n):
+    """16-byte aligned buffers: the vector kernel over n // 4 vectors, the scalar kernel over the tail"""
+    def aligned(x):
+        xg = gpu_leaf(x)
+        assert xg.data_ptr() % 16 == 0
+        return xg
+
+    _lrelu_check(n, aligned)
+
+
+def test_leaky_relu_scalar_kernel_alone_past_the_grid_cap():
+    """the input is a view one float into its allocation: no 16-byte access is possible, the scalar kernel runs as the
+    whole launch, forward and backward, and past its cap"""
+    n = dc.LRELU_MISALIGNED
+
+    def misaligned(x):
+        xg = dc.one_float_in(n, DEV)
+        xg.copy_(x.reshape(n))
+        xg = xg.reshape(x.shape).requires_grad_(True)
+        assert xg.data_ptr() % 16 == 4 and xg.is_leaf
+        return xg
+
+    _lrelu_check(n, misaligned)
 
 
 # ---------------------------------------------------------------------------------------------- 4. sigmoid + BCE
@@ -278,7 +315,7 @@ def _bce_check(what, fx, s, label):
 
 
 @pytest.mark.parametrize("label", [1, 0])
-@pytest.mark.parametrize("n", [1, 6, 363, 1025])
+@pytest.mark.parametrize("n", list(dc.BCE_SIZES))
 def test_sigmoid_bce_kernels(fx, n, label):
     gen = torch.Generator().manual_seed(10 * n + label)
     s = (torch.rand(n, generator=gen) * 24 - 12).reshape(1, 1, n, 1)
@@ -319,6 +356,30 @@ def test_two_runs_of_the_kernels_give_the_same_bits():
         loss = SigmoidBCEFn.apply(sg, 0.0)
         loss.backward()
         runs.append([t.detach().cpu() for t in (y, rm, rv, xg.grad, gg.grad, bg.grad, loss, sg.grad)])
+    for a, b in zip(*runs):
+        assert torch.equal(a, b)
+
+
+def test_two_runs_past_the_caps_give_the_same_bits():
+    """capped row chunks of the BatchNorm sums; f64 partials of more than one trip in the BCE forward"""
+    from cyhip.functions import BNLeakyReLUFn, SigmoidBCEFn
+    gen = torch.Generator().manual_seed(78)
+    M, C = dc.SAME_BITS_BN
+    x, dy = torch.randn(1, C, M, 1, generator=gen), torch.randn(1, C, M, 1, generator=gen).to(DEV)
+    scores = [torch.randn(1, 1, n, 1, generator=gen) * 5 for n in dc.SAME_BITS_BCE]
+    runs = []
+    for _ in range(2):
+        xg, gg, bg = gpu_leaf(x), gpu_leaf(torch.ones(C)), gpu_leaf(torch.zeros(C))
+        rm, rv = torch.zeros(C, device=DEV), torch.ones(C, device=DEV)
+        y = BNLeakyReLUFn.apply(xg, gg, bg, rm, rv, None, True, MOMENTUM, EPS, SLOPE)
+        (y * dy).sum().backward()
+        out = [y, rm, rv, xg.grad, gg.grad, bg.grad]
+        for s, label in zip(scores, (0.0, 1.0)):
+            sg = gpu_leaf(s)
+            loss = SigmoidBCEFn.apply(sg, label)
+            loss.backward()
+            out += [loss, sg.grad]
+        runs.append([t.detach().cpu() for t in out])
     for a, b in zip(*runs):
         assert torch.equal(a, b)
 
