@@ -10,11 +10,9 @@
 // (exact register arrays, 8- / 16-byte row accesses); any other K takes the run-time form.
 #include "cy_common.h"
 #include "cy_pixel_loss.h"
-#include "cy_reduce.h"
+#include "cy_reduce.h"  // block_sum_d, mean_finalize_kernel, uamt_finalize_kernel, UAMT_DENOM_EPS
 
 namespace {
-
-constexpr double UAMT_DENOM_EPS = 1e-2;  // mt.py:246: loss.mean() / (mask.mean().item() + 1e-2)
 
 // first maximal index (torch.argmax's rule; the warp's padding rows are all-zero logits: class 0)
 __device__ __forceinline__ int argmax_k(const float* z, int K) {
@@ -180,19 +178,6 @@ __global__ void __launch_bounds__(256)
   if (threadIdx.x == 0) {
     partial[2 * blockIdx.x] = t1;
     partial[2 * blockIdx.x + 1] = t2;
-  }
-}
-
-// out[0] = (S1 / P) / (S2 / P + 1e-2), out[1] = S2 / P
-__global__ void __launch_bounds__(256)
-    uamt_finalize_kernel(const double* __restrict__ partial, int nblk, double npix, float* __restrict__ out) {
-  __shared__ double sh1[256], sh2[256];
-  const double s1 = sum_partials_d(partial, nblk, 2, sh1);
-  const double s2 = sum_partials_d(partial + 1, nblk, 2, sh2);
-  if (threadIdx.x == 0) {
-    const float mask_mean = (float)(s2 / npix);
-    out[0] = (float)((s1 / npix) / ((double)mask_mean + UAMT_DENOM_EPS));
-    out[1] = mask_mean;
   }
 }
 

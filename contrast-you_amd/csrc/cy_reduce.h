@@ -72,4 +72,19 @@ __global__ void __launch_bounds__(256)
   if (threadIdx.x == 0) loss[0] = (float)(tot / denom);
 }
 
+// the end of the UA-MT forward in both of its forms (cy_pixel_reg.hip, cy_wide_reg.hip): partial holds (sum, count) per
+// block; out[0] = (S1 / P) / (S2 / P + 1e-2), out[1] = S2 / P
+constexpr double UAMT_DENOM_EPS = 1e-2;  // mt.py:246: loss.mean() / (mask.mean().item() + 1e-2)
+__global__ void __launch_bounds__(256)
+    uamt_finalize_kernel(const double* __restrict__ partial, int nblk, double npix, float* __restrict__ out) {
+  __shared__ double sh1[256], sh2[256];
+  const double s1 = sum_partials_d(partial, nblk, 2, sh1);
+  const double s2 = sum_partials_d(partial + 1, nblk, 2, sh2);
+  if (threadIdx.x == 0) {
+    const float mask_mean = (float)(s2 / npix);
+    out[0] = (float)((s1 / npix) / ((double)mask_mean + UAMT_DENOM_EPS));
+    out[1] = mask_mean;
+  }
+}
+
 }  // namespace

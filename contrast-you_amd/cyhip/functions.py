@@ -788,7 +788,7 @@ class MixupKLFn(torch.autograd.Function):
 class MixSoftmaxMSEFn(torch.autograd.Function):
     """MSELoss(reduction="none")(student.softmax(1), w_self * teacher.softmax(1) + w_other * teacher.softmax(1)[index])
     .mean() (semi_seg/hooks/mt.py:301-319).  The gradient goes to the student alone; the mixed target lives in
-    registers."""
+    registers.  Up to 64 classes (past 16: csrc/cy_wide_reg.hip)."""
 
     @staticmethod
     def forward(ctx, student_logits: Tensor, teacher_logits: Tensor, index: Tensor, w_self: float, w_other: float):
@@ -894,7 +894,7 @@ class OrthoLossFn(torch.autograd.Function):
 
 class SoftmaxEntropyFn(torch.autograd.Function):
     """Entropy(eps=eps)(logits.softmax(1)), mean reduction (semi_seg/hooks/entmin.py:29-30,
-    contrastyou/losses/kl.py:48-56)."""
+    contrastyou/losses/kl.py:48-56).  Up to 64 classes (past 16: csrc/cy_wide_reg.hip)."""
 
     @staticmethod
     def forward(ctx, logits: Tensor, eps: float):
@@ -913,7 +913,7 @@ class SoftmaxEntropyFn(torch.autograd.Function):
 
 class SoftmaxSelfMSEFn(torch.autograd.Function):
     """nn.MSELoss()(p, one_hot(p.max(1)[1])) with p = logits.softmax(1); the one-hot carries no gradient and is never
-    materialised (semi_seg/hooks/pseudolabel.py:30-36)."""
+    materialised (semi_seg/hooks/pseudolabel.py:30-36).  Up to 64 classes (past 16: csrc/cy_wide_reg.hip)."""
 
     @staticmethod
     def forward(ctx, logits: Tensor):
@@ -933,7 +933,7 @@ class UAMTLossFn(torch.autograd.Function):
     """(loss, mask_mean) of the uncertainty-aware mean teacher (semi_seg/hooks/mt.py:242-248,266-267): the MSE of
     softmax(teacher) [hard: its arg-max one-hot] and softmax(student) over the pixels whose teacher entropy lies below
     `thr`, over (mask_mean + 1e-2).  Both stay on the device; mask_mean is not differentiable, the teacher gets no
-    gradient."""
+    gradient.  Up to 64 classes (past 16: csrc/cy_wide_reg.hip)."""
 
     @staticmethod
     def forward(ctx, teacher_logits: Tensor, student_logits: Tensor, thr: float, hard: bool):

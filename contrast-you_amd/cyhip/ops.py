@@ -1629,58 +1629,83 @@ def softmax_mix_kl_bwd(logits: Tensor, target: Tensor, mix: Tensor, gscale: Tens
     return d, dmix
 
 
+# The four regularisers below (entropy, self-MSE, UA-MT, ICT's mix-MSE) have two sets of entry points with the same
+# arguments: one thread per pixel up to 16 classes (csrc/cy_pixel_reg.hip, csrc/cy_mixup.hip) and sixteen lanes per
+# pixel for multi-prototype logits, 16 < K <= 64 (csrc/cy_wide_reg.hip).  Any other K goes to the first set, whose
+# refusal is the error the caller sees.
+WIDE_REG_KMIN, WIDE_REG_KMAX = 17, 64
+WIDE_REG_FAMILIES = {"entropy": _lib.CY_WIDE_ENTROPY, "selfmse": _lib.CY_WIDE_SELFMSE, "uamt": _lib.CY_WIDE_UAMT,
+                     "mixmse": _lib.CY_WIDE_MIXMSE}
+_WIDE_REG_PLAN = ("vec", "rows_per_block", "fwd_grid", "fwd_trips", "bwd_grid", "bwd_trips")
+
+
+def wide_reg_plan(family: str, npix: int, K: int, align: int = 16) -> dict:
+    """the launch rule of the wide-K regularisers (host-side query, no GPU needed): the values of cy_wide_reg_plan by
+    name.  `align`: the bytes every base pointer of the call is aligned to.  What the launches refuse raises
+    HipKernelError with their status."""
+    plan = (C.c_int32 * 6)()
+    _lib.call("cy_wide_reg_plan", WIDE_REG_FAMILIES[family], int(npix), int(K), int(align), plan)
+    return dict(zip(_WIDE_REG_PLAN, (int(v) for v in plan)))
+
+
+def _by_k(name: str, K: int) -> str:
+    """'softmax_entropy' -> the stem of its entry points for K classes"""
+    return f"cy_{name}_row" if WIDE_REG_KMIN <= K <= WIDE_REG_KMAX else f"cy_{name}"
+
+
 def _pixel_loss_fwd(name: str, x: Tensor, out: int = 1):
-    """what the forward of a pixel-wise regulariser (csrc/cy_pixel_reg.hip) takes: (npix, K, workspace, its bytes, the
-    `out` device floats of the result)"""
+    """what the forward of a pixel-wise regulariser (csrc/cy_pixel_reg.hip, csrc/cy_wide_reg.hip) takes: (its entry
+    point, npix, K, workspace, its bytes, the `out` device floats of the result)"""
     N, K, H, W = x.shape
     npix = N * H * W
-    nbytes = getattr(_lib.load(), f"cy_{name}_ws_bytes")(npix)
+    stem = _by_k(name, K)
+    nbytes = getattr(_lib.load(), f"{stem}_ws_bytes")(npix)
     ws = _ws(nbytes, x.device)
     res = _f32(out, x.device)
-    return npix, K, ws, nbytes, res
+    return f"{stem}_fwd", npix, K, ws, nbytes, res
 
 
 def softmax_entropy_fwd(logits: Tensor, eps: float) -> Tensor:
-    npix, K, ws, nbytes, loss = _pixel_loss_fwd("softmax_entropy", logits)
-    _lib.call("cy_softmax_entropy_fwd", logits.data_ptr(), loss.data_ptr(), npix, K, float(eps), ws.data_ptr(), nbytes,
-              _stream())
+    entry, npix, K, ws, nbytes, loss = _pixel_loss_fwd("softmax_entropy", logits)
+    _lib.call(entry, logits.data_ptr(), loss.data_ptr(), npix, K, float(eps), ws.data_ptr(), nbytes, _stream())
     return loss.view(())
 
 
 def softmax_entropy_bwd(logits: Tensor, gscale: Tensor, eps: float) -> Tensor:
     N, K, H, W = logits.shape
     d = empty_nhwc(N, K, H, W, torch.float32, logits.device)
-    _lib.call("cy_softmax_entropy_bwd", logits.data_ptr(), gscale.data_ptr(), d.data_ptr(), N * H * W, K, float(eps),
-              _stream())
+    _lib.call(_by_k("softmax_entropy", K) + "_bwd", logits.data_ptr(), gscale.data_ptr(), d.data_ptr(), N * H * W, K,
+              float(eps), _stream())
     return d
 
 
 def softmax_selfmse_fwd(logits: Tensor) -> Tensor:
-    npix, K, ws, nbytes, loss = _pixel_loss_fwd("softmax_selfmse", logits)
-    _lib.call("cy_softmax_selfmse_fwd", logits.data_ptr(), loss.data_ptr(), npix, K, ws.data_ptr(), nbytes, _stream())
+    entry, npix, K, ws, nbytes, loss = _pixel_loss_fwd("softmax_selfmse", logits)
+    _lib.call(entry, logits.data_ptr(), loss.data_ptr(), npix, K, ws.data_ptr(), nbytes, _stream())
     return loss.view(())
 
 
 def softmax_selfmse_bwd(logits: Tensor, gscale: Tensor) -> Tensor:
     N, K, H, W = logits.shape
     d = empty_nhwc(N, K, H, W, torch.float32, logits.device)
-    _lib.call("cy_softmax_selfmse_bwd", logits.data_ptr(), gscale.data_ptr(), d.data_ptr(), N * H * W, K, _stream())
+    _lib.call(_by_k("softmax_selfmse", K) + "_bwd", logits.data_ptr(), gscale.data_ptr(), d.data_ptr(), N * H * W, K,
+              _stream())
     return d
 
 
 def uamt_mse_fwd(teacher: Tensor, student: Tensor, thr: float, hard: bool) -> Tensor:
     """-> device f32 [2] = (loss, mask_mean)"""
-    npix, K, ws, nbytes, res = _pixel_loss_fwd("uamt_mse", teacher, out=2)
-    _lib.call("cy_uamt_mse_fwd", teacher.data_ptr(), student.data_ptr(), res.data_ptr(), npix, K, float(thr),
-              int(bool(hard)), ws.data_ptr(), nbytes, _stream())
+    entry, npix, K, ws, nbytes, res = _pixel_loss_fwd("uamt_mse", teacher, out=2)
+    _lib.call(entry, teacher.data_ptr(), student.data_ptr(), res.data_ptr(), npix, K, float(thr), int(bool(hard)),
+              ws.data_ptr(), nbytes, _stream())
     return res
 
 
 def uamt_mse_bwd(teacher: Tensor, student: Tensor, result: Tensor, gscale: Tensor, thr: float, hard: bool) -> Tensor:
     N, K, H, W = student.shape
     d = empty_nhwc(N, K, H, W, torch.float32, student.device)
-    _lib.call("cy_uamt_mse_bwd", teacher.data_ptr(), student.data_ptr(), result.data_ptr(), gscale.data_ptr(),
-              d.data_ptr(), N * H * W, K, float(thr), int(bool(hard)), _stream())
+    _lib.call(_by_k("uamt_mse", K) + "_bwd", teacher.data_ptr(), student.data_ptr(), result.data_ptr(),
+              gscale.data_ptr(), d.data_ptr(), N * H * W, K, float(thr), int(bool(hard)), _stream())
     return d
 
 
@@ -1862,11 +1887,12 @@ def softmax_mixmse_fwd(student: Tensor, teacher: Tensor, index: Tensor, w_self: 
     N, K, H, W = student.shape
     assert teacher.shape == student.shape, (tuple(teacher.shape), tuple(student.shape))
     idx = mix_index(index, N, student.device)
-    nbytes = _lib.load().cy_softmax_mixmse_ws_bytes(N, H * W)
+    stem = _by_k("softmax_mixmse", K)
+    nbytes = getattr(_lib.load(), f"{stem}_ws_bytes")(N, H * W)
     ws = _ws(nbytes, student.device)
     loss = _f32(1, student.device)
-    _lib.call("cy_softmax_mixmse_fwd", student.data_ptr(), teacher.data_ptr(), idx.data_ptr(), float(w_self),
-              float(w_other), loss.data_ptr(), N, H * W, K, ws.data_ptr(), nbytes, _stream())
+    _lib.call(f"{stem}_fwd", student.data_ptr(), teacher.data_ptr(), idx.data_ptr(), float(w_self), float(w_other),
+              loss.data_ptr(), N, H * W, K, ws.data_ptr(), nbytes, _stream())
     return loss.view(())
 
 
@@ -1876,8 +1902,8 @@ def softmax_mixmse_bwd(student: Tensor, teacher: Tensor, index: Tensor, w_self: 
     N, K, H, W = student.shape
     idx = mix_index(index, N, student.device)
     d = empty_nhwc(N, K, H, W, torch.float32, student.device)
-    _lib.call("cy_softmax_mixmse_bwd", student.data_ptr(), teacher.data_ptr(), idx.data_ptr(), float(w_self),
-              float(w_other), gscale.data_ptr(), d.data_ptr(), N, H * W, K, _stream())
+    _lib.call(_by_k("softmax_mixmse", K) + "_bwd", student.data_ptr(), teacher.data_ptr(), idx.data_ptr(),
+              float(w_self), float(w_other), gscale.data_ptr(), d.data_ptr(), N, H * W, K, _stream())
     return d
 
 

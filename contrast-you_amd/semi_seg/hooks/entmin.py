@@ -1,5 +1,6 @@
 """Entropy minimisation (semi_seg/hooks/entmin.py:7-33): weight * Entropy()(softmax(unlabeled_logits_tf)), through
-`Entropy.from_logits` -- one fused HIP pass over the logits each way (cy_softmax_entropy_*), no probability tensor.
+`Entropy.from_logits` -- one fused HIP pass over the logits each way (cy_softmax_entropy_*; cy_softmax_entropy_row_*
+on multi-prototype logits, 16 < K <= 64), no probability tensor.
 The reference's `assert not simplex(logits)` is a host sync and is left out; the meter receives a device scalar."""
 from __future__ import annotations
 

@@ -16,7 +16,10 @@ its transformed view in two no-grad forwards (it is in train mode: each has its 
 seed one (lam, index) is drawn for the 2B batch with alpha = 0.2, the student runs on the mixed images
 (`ops.mix_images`), and weight * mean((softmax(student) - (lam * p + (1 - lam) * p[index]))^2), p the teacher's
 softmax, is added.  `MixSoftmaxMSEFn` (cy_softmax_mixmse_*) recomputes both teacher softmaxes and their blend in
-registers: neither probability tensor, nor the gathered copy, nor the mixed target is formed."""
+registers: neither probability tensor, nor the gathered copy, nor the mixed target is formed.
+
+All three run on multi-prototype logits up to K = 64 outputs: the plain mean teacher on the row form of
+cy_softmax_mse_*, UA-MT and ICT on cy_uamt_mse_row_* and cy_softmax_mixmse_row_* (csrc/cy_wide_reg.hip) past 16."""
 from __future__ import annotations
 
 import math

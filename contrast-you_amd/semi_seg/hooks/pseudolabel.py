@@ -1,6 +1,7 @@
 """Pseudo-label regulariser (semi_seg/hooks/pseudolabel.py:9-38): weight * MSELoss()(p, one_hot(argmax p)) with
 p = softmax(unlabeled_logits_tf) and the one-hot a constant -- one fused HIP pass over the logits each way
-(cy_softmax_selfmse_*), no probability, label or one-hot tensor.  The meter receives a device scalar."""
+(cy_softmax_selfmse_*; cy_softmax_selfmse_row_* on multi-prototype logits, 16 < K <= 64), no probability, label or
+one-hot tensor.  The meter receives a device scalar."""
 from __future__ import annotations
 
 from torch.nn import MSELoss

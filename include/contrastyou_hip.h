@@ -1587,6 +1587,56 @@ int cy_softmax_gathermse_fwd(const float* teacher, const int32_t* map, const flo
 int cy_softmax_gathermse_bwd(const float* teacher, const int32_t* map, const float* student, const float* gscale,
                              float* dstudent, int N, long HW, int K, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Wide-K regularisers (csrc/cy_wide_reg.hip; entries added to ABI v18 -- no existing signature changed and no struct
+ * added, so cy_abi_version() stays 18).  The entropy, self-MSE, UA-MT and ICT losses above on multi-prototype logits,
+ * 16 < K <= 64: the same arguments, values and launch counts as cy_softmax_entropy_*, cy_softmax_selfmse_*,
+ * cy_uamt_mse_* and cy_softmax_mixmse_*, in the sixteen-lanes-per-pixel form of cy_softmax_group_kl_* (lane j of a row
+ * holds logits 4j..4j+3; 16 pixels per block and loop trip).  The arg-max of self-MSE and hard UA-MT is the first
+ * maximal index.  Every entry checks its arguments before any launch: a NULL pointer, a count < 1 or a base that is not
+ * 4-byte aligned -> CY_ERR_ARG; K outside 17..64 -> CY_ERR_SHAPE (the entries above keep K <= 16); a short workspace ->
+ * CY_ERR_WORKSPACE.  The forward writes one f64 partial per block (UA-MT two) and one block sums them in block order,
+ * the backward is one launch.  No atomics: two runs give the same bits.  Upstream gradients are device memory.
+ * ------------------------------------------------------------------------ */
+#define CY_WIDE_ENTROPY 0 /* cy_softmax_entropy_row_* */
+#define CY_WIDE_SELFMSE 1 /* cy_softmax_selfmse_row_* */
+#define CY_WIDE_UAMT 2    /* cy_uamt_mse_row_* */
+#define CY_WIDE_MIXMSE 3  /* cy_softmax_mixmse_row_* */
+/* The launch rule of the four families (host-side only, launches nothing; the launches take every decision from it), in
+ * the style of cy_mix_plan.  `npix`: the pixels N * HW.  `align`: the bytes every tensor base pointer of the call is
+ * aligned to (the launches work it out from their pointers; 16 and more count as 16).
+ *   plan[0] vec: floats per memory access: 4 where K % 4 == 0 and align is a multiple of 16, else 1
+ *   plan[1] rows_per_block: pixels a block covers per loop trip, 16
+ *   plan[2] fwd_grid: min(4096, ceil(npix / 16)) blocks = the f64 partials (UA-MT: two per block)
+ *   plan[3] fwd_trips: loop trips of every block
+ *   plan[4] bwd_grid = fwd_grid, plan[5] bwd_trips
+ * Returns what the launches answer: CY_ERR_ARG for a NULL `plan`, an unknown family, npix < 1 or an align that is no
+ * multiple of 4; CY_ERR_SHAPE for K outside 17..64; otherwise CY_OK. */
+int cy_wide_reg_plan(int family, long npix, int K, int align, int32_t* plan /* [6] */);
+/* ws_bytes >= 8 * fwd_grid (16 * fwd_grid for UA-MT) = the *_row_ws_bytes queries (0 for a count < 1). */
+size_t cy_softmax_entropy_row_ws_bytes(long npix);
+int cy_softmax_entropy_row_fwd(const float* logits, float* loss, long npix, int K, float eps, void* ws,
+                               size_t ws_bytes, void* stream);
+int cy_softmax_entropy_row_bwd(const float* logits, const float* gscale, float* dlogits, long npix, int K, float eps,
+                               void* stream);
+size_t cy_softmax_selfmse_row_ws_bytes(long npix);
+int cy_softmax_selfmse_row_fwd(const float* logits, float* loss, long npix, int K, void* ws, size_t ws_bytes,
+                               void* stream);
+int cy_softmax_selfmse_row_bwd(const float* logits, const float* gscale, float* dlogits, long npix, int K,
+                               void* stream);
+size_t cy_uamt_mse_row_ws_bytes(long npix);
+int cy_uamt_mse_row_fwd(const float* teacher, const float* student, float* result, long npix, int K, float thr,
+                        int hard, void* ws, size_t ws_bytes, void* stream);
+int cy_uamt_mse_row_bwd(const float* teacher, const float* student, const float* result, const float* gscale,
+                        float* dstudent, long npix, int K, float thr, int hard, void* stream);
+size_t cy_softmax_mixmse_row_ws_bytes(int N, long HW);
+int cy_softmax_mixmse_row_fwd(const float* student, const float* teacher, const int32_t* index, float w_self,
+                              float w_other, float* loss, int N, long HW, int K, void* ws, size_t ws_bytes,
+                              void* stream);
+int cy_softmax_mixmse_row_bwd(const float* student, const float* teacher, const int32_t* index, float w_self,
+                              float w_other, const float* gscale, float* dstudent, int N, long HW, int K,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif
