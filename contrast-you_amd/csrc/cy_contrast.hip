@@ -1,9 +1,8 @@
-// Projection head pieces and the InfoNCE / SupCon loss.
-//   contrastyou/projectors/heads.py:14-22,81-96 + projectors/nn.py:47-54
-//     AdaptiveAvgPool2d(1) -> Linear -> LeakyReLU(0.01) -> Linear -> L2 normalise
-//   contrastyou/losses/contrastive.py:14-20,31-100  (exp_sim_temperature, SupConLoss1)
+// The InfoNCE / SupCon loss and the f32 GEMM under its materialised path.
+//   contrastyou/losses/contrastive.py:14-20,31-212  (exp_sim_temperature, SupConLoss1, SelfPacedSupConLoss)
 // Everything here is f32: the embedding x embedding similarity and the
 // G*P products run on the exact f32 MFMA (v_mfma_f32_32x32x2_f32).
+// (The projection head that produces the embeddings is cy_proj_head.hip.)
 #include "cy_common.h"
 #include "cy_reduce.h"
 
@@ -324,9 +323,16 @@ constexpr int SC_TM = 64;  // rows / columns of a tile
 // and the two parity planes 16 floats out of step -- the f32 MFMA takes one k per half-wave (lane >> 5), so a lane's
 // operands for four successive k-steps are one ds_read_b128, and a column-wise read (second product of the
 // backward pass) alternates planes lane by lane without bank conflicts
-__device__ __host__ __forceinline__ int sc_ld2(int D) { return D / 2 + 4; }
-__device__ __host__ __forceinline__ int sc_plane(int D) { return SC_TM * sc_ld2(D) + 16; }
-__device__ __host__ __forceinline__ int sc_block_floats(int D) { return 2 * sc_plane(D); }
+__device__ __host__ constexpr int sc_ld2(int D) { return D / 2 + 4; }
+__device__ __host__ constexpr int sc_plane(int D) { return SC_TM * sc_ld2(D) + 16; }
+__device__ __host__ constexpr int sc_block_floats(int D) { return 2 * sc_plane(D); }
+// dynamic LDS of the sweeps below, in bytes.  Forward: the row and the column block, then `extra` floats of the kernel's
+// own.  Backward: the two blocks, the G tile [64][65] and `nrow` staged floats per row of the block.
+constexpr int SC_MAXD = 256;
+constexpr int sc_fwd_lds(int D, int extra) { return (2 * sc_block_floats(D) + extra) * (int)sizeof(float); }
+constexpr int sc_bwd_lds(int D, int nrow) {
+  return (2 * sc_block_floats(D) + SC_TM * (SC_TM + 1) + SC_TM * nrow) * (int)sizeof(float);
+}
 
 __global__ void __launch_bounds__(256)
     supcon_diag_kernel(const float* __restrict__ P, float* __restrict__ diag, int R, int D, float inv_t) {
@@ -390,87 +396,202 @@ __device__ __forceinline__ int sc_code(const ScRow& r, const ScRow& c, const uin
   return pm[(size_t)r.a * n + c.a];
 }
 
-// grid (row blocks, column splits).  part[split][R][3] = (l, ps, cnt) of the split's columns.  MASK: positives from
-// the explicit mask's codes (labels == NULL); the labels instantiation is the one the training hooks run.
-template <bool MASK>
-__global__ void __launch_bounds__(256)
-    supcon_fused_fwd_kernel(const float* __restrict__ P, const int32_t* __restrict__ labels,
-                            const uint8_t* __restrict__ pm, const float* __restrict__ Mptr,
-                            float* __restrict__ part, int n, int D, float inv_t, int nsplit) {
-  extern __shared__ float sm[];
-  const int R = 2 * n;
+// ---- the sweep over the S tiles, one per direction, shared by the fused and the self-paced kernels ----
+// Grid (row blocks, column splits), 256 threads: four waves (wm, wn), each the 32x32 accumulator of a quarter tile.
+// What a thread is in its block:
+struct ScBlock {
+  int R, m0;               // rows of S (2n); first row of this block
+  int cb0, cb1;            // this split's column blocks [cb0, cb1)
+  int tid, wm, wn, i, kk;  // wave row / column in the tile; the lane's column in the wave and its k half
+};
+__device__ __forceinline__ ScBlock sc_block(int n, int nsplit) {
+  ScBlock b;
+  b.R = 2 * n;
+  b.tid = threadIdx.x;
+  const int lane = b.tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(b.tid >> 6);
+  b.wm = wave >> 1, b.wn = wave & 1;
+  b.i = lane & 31, b.kk = lane >> 5;
+  b.m0 = blockIdx.x * SC_TM;
+  const int ncb = (b.R + SC_TM - 1) / SC_TM;
+  b.cb0 = (ncb * (int)blockIdx.y) / nsplit, b.cb1 = (ncb * ((int)blockIdx.y + 1)) / nsplit;
+  return b;
+}
+// row within the block that accumulator register `reg` of this lane holds (f32 32x32 MFMA layout)
+__device__ __forceinline__ int sc_rr(const ScBlock& b, int reg) {
+  return b.wm * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * b.kk;
+}
+
+// Forward: part[split][R][NV] = per-row sums over the split's columns.  term(reg, a, row, col, v0, v1, v2) adds the
+// element with raw accumulator value a (S_ij t) to the first NV sums of its register; it sees live off-diagonal
+// elements only.
+// LDS: the row block, the column block (reused for the totals at the end), then whatever the caller keeps behind.
+template <int NV, class Term>
+__device__ __forceinline__ void sc_fwd_sweep(const ScBlock& b, const float* __restrict__ P,
+                                             const int32_t* __restrict__ labels, float* sm, float* __restrict__ part,
+                                             int n, int D, Term term) {
   float* sPi = sm;
   float* sPj = sm + sc_block_floats(D);
-  float* sred = sPj;  // reused at the end: [2 wn][64 rows][3]
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
-  const int i = lane & 31, kk = lane >> 5;
-  const int m0 = blockIdx.x * SC_TM;
-  const int ncb = (R + SC_TM - 1) / SC_TM;
-  const int cb0 = (ncb * (int)blockIdx.y) / nsplit, cb1 = (ncb * ((int)blockIdx.y + 1)) / nsplit;
-  const float M = Mptr[0];
-  sc_stage(P, sPi, m0, R, D, tid);
-  float l[16], ps[16], cnt[16];
+  float* sred = sPj;  // reused at the end: [2 wn][64 rows][NV]
+  sc_stage(P, sPi, b.m0, b.R, D, b.tid);
+  // the per-register sums, NV <= 3 of them in use.  Three arrays, all three zeroed, and not one [16][NV]: the compiler
+  // drops what is unused, and the register allocation depends on the form -- with one array the labels instantiations
+  // come out about ten VGPRs lower and on another occupancy step than the measured kernels
+  // (profiles/supcon_shared_sweep_ab.txt)
+  static_assert(NV >= 1 && NV <= 3);
+  float s0[16], s1[16], s2[16];
+  auto sum = [&](int reg, int v) -> float& { return v == 0 ? s0[reg] : (v == 1 ? s1[reg] : s2[reg]); };
   ScRow rws[16];
 #pragma unroll
   for (int q = 0; q < 16; ++q) {
-    l[q] = ps[q] = cnt[q] = 0.f;
-    rws[q] = sc_row(labels, n, m0 + wm * 32 + (q & 3) + 8 * (q >> 2) + 4 * kk);
+#pragma unroll
+    for (int v = 0; v < 3; ++v) sum(q, v) = 0.f;
+    rws[q] = sc_row(labels, n, b.m0 + sc_rr(b, q));
   }
-  for (int cb = cb0; cb < cb1; ++cb) {
+  for (int cb = b.cb0; cb < b.cb1; ++cb) {
     const int n0 = cb * SC_TM;
     __syncthreads();  // previous tile's reads of sPj are done
-    sc_stage(P, sPj, n0, R, D, tid);
+    sc_stage(P, sPj, n0, b.R, D, b.tid);
     __syncthreads();
-    const f32x16 acc = sc_tile(sPi, sPj, D, wm, wn, i, kk);
-    const int col = n0 + wn * 32 + i;
+    const f32x16 acc = sc_tile(sPi, sPj, D, b.wm, b.wn, b.i, b.kk);
+    const int col = n0 + b.wn * 32 + b.i;
     const ScRow cq = sc_row(labels, n, col);
 #pragma unroll
     for (int reg = 0; reg < 16; ++reg) {
-      const int row = m0 + wm * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * kk;
-      if (row < R && col < R && row != col) {
-        const float s = acc[reg] * inv_t;
-        if (MASK) {
-          const int code = sc_code(rws[reg], cq, pm, n);
-          if (code <= 1) l[reg] += expf(s - M);  // (neither: in no sum)
-          if (code == 1) {
-            ps[reg] += s;
-            cnt[reg] += 1.f;
-          }
-        } else {
-          l[reg] += expf(s - M);
-          if (sc_pos(rws[reg], cq, labels, pm, n)) {
-            ps[reg] += s;
-            cnt[reg] += 1.f;
-          }
-        }
-      }
+      const int row = b.m0 + sc_rr(b, reg);
+      if (row < b.R && col < b.R && row != col) term(reg, acc[reg], rws[reg], cq, s0[reg], s1[reg], s2[reg]);
     }
   }
   // row totals: over the 32 lanes that share kk (fixed xor tree), then over the two column halves (wn)
 #pragma unroll
   for (int reg = 0; reg < 16; ++reg)
 #pragma unroll
-    for (int o = 16; o > 0; o >>= 1) {
-      l[reg] += __shfl_xor(l[reg], o, 64);
-      ps[reg] += __shfl_xor(ps[reg], o, 64);
-      cnt[reg] += __shfl_xor(cnt[reg], o, 64);
-    }
+    for (int o = 16; o > 0; o >>= 1)
+#pragma unroll
+      for (int v = 0; v < NV; ++v) sum(reg, v) += __shfl_xor(sum(reg, v), o, 64);
   __syncthreads();
-  if (i == 0) {
+  if (b.i == 0) {
 #pragma unroll
     for (int reg = 0; reg < 16; ++reg) {
-      const int rr = wm * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * kk;
-      float* d = sred + (wn * SC_TM + rr) * 3;
-      d[0] = l[reg], d[1] = ps[reg], d[2] = cnt[reg];
+      float* d = sred + (b.wn * SC_TM + sc_rr(b, reg)) * NV;
+#pragma unroll
+      for (int v = 0; v < NV; ++v) d[v] = sum(reg, v);
     }
   }
   __syncthreads();
-  for (int e = tid; e < SC_TM * 3; e += 256) {
-    const int rr = e / 3;
-    if (m0 + rr < R) part[((size_t)blockIdx.y * R + m0 + rr) * 3 + e % 3] = sred[e] + sred[SC_TM * 3 + e];
+  for (int e = b.tid; e < SC_TM * NV; e += 256) {
+    const int rr = e / NV;
+    if (b.m0 + rr < b.R)
+      part[((size_t)blockIdx.y * b.R + b.m0 + rr) * NV + e % NV] = sred[e] + sred[SC_TM * NV + e];
   }
+}
+
+// Backward: dpart[split][R][D] = sum over the split's columns of (G_ij + G_ji) P_j.  The S tile is recomputed, turned
+// into the G tile element by element, passed through LDS into operand layout and multiplied with the resident P_j.
+// Elem supplies  NROW floats staged per row of the block (stage_row),  a Col of per-column values (load_col)  and
+// g(a, row, col, staged row, Col) = G_ij + G_ji of a live off-diagonal element with raw accumulator value a.
+template <class Elem>
+__device__ __forceinline__ void sc_bwd_sweep(const ScBlock& b, const float* __restrict__ P,
+                                             const int32_t* __restrict__ labels, float* sm, float* __restrict__ dpart,
+                                             int n, int D, Elem elem) {
+  constexpr int ldg = SC_TM + 1, NROW = Elem::NROW;
+  const int ld2 = sc_ld2(D), pl = sc_plane(D);
+  float* sPi = sm;
+  float* sPj = sm + sc_block_floats(D);
+  float* sG = sPj + sc_block_floats(D);
+  float* sRow = sG + SC_TM * ldg;  // [64][NROW]
+  sc_stage(P, sPi, b.m0, b.R, D, b.tid);
+  if (b.tid < SC_TM) elem.stage_row(sRow + b.tid * NROW, b.m0 + b.tid, b.R);
+  const int nct = (D + 31) / 32;          // 32-wide column tiles of dP
+  f32x16 acc2[4];                          // this wave's column tiles: wn, wn + 2, wn + 4, wn + 6
+#pragma unroll
+  for (int c = 0; c < 4; ++c)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) acc2[c][q] = 0.f;
+  for (int cb = b.cb0; cb < b.cb1; ++cb) {
+    const int n0 = cb * SC_TM;
+    __syncthreads();  // previous tile: the second product has read sG and sPj
+    sc_stage(P, sPj, n0, b.R, D, b.tid);
+    __syncthreads();
+    const f32x16 acc = sc_tile(sPi, sPj, D, b.wm, b.wn, b.i, b.kk);
+    const int col = n0 + b.wn * 32 + b.i;
+    const ScRow cq = sc_row(labels, n, col);
+    const typename Elem::Col cj = elem.load_col(col, b.R);
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) {
+      const int rr = sc_rr(b, reg);
+      const int row = b.m0 + rr;
+      float v = 0.f;
+      if (row < b.R && col < b.R && row != col)
+        v = elem.g(acc[reg], sc_row(labels, n, row), cq, sRow + rr * NROW, cj);
+      sG[rr * ldg + b.wn * 32 + b.i] = v;
+    }
+    __syncthreads();
+    // dP rows (wm block) += G[64 rows][64 j] * P_j[64 j][D]
+    const float* ga = sG + (b.wm * 32 + b.i) * ldg + b.kk;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int ct = b.wn + 2 * c;
+      if (ct < nct) {
+        const int dcol = ct * 32 + b.i;  // P_j[j][dcol] sits at [dcol & 1][j][dcol >> 1]
+        const float* pb = sPj + (dcol & 1) * pl + b.kk * ld2 + (dcol >> 1);
+#pragma unroll 8
+        for (int js = 0; js < SC_TM; js += 2)
+          acc2[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(ga[js], pb[js * ld2], acc2[c], 0, 0, 0);
+      }
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const int ct = b.wn + 2 * c;
+    const int dcol = ct * 32 + b.i;
+    if (ct < nct && dcol < D) {
+#pragma unroll
+      for (int reg = 0; reg < 16; ++reg) {
+        const int row = b.m0 + sc_rr(b, reg);
+        if (row < b.R) dpart[((size_t)blockIdx.y * b.R + row) * D + dcol] = acc2[c][reg];
+      }
+    }
+  }
+}
+
+// (l, ps, cnt) of an element.  MASK: positives from the explicit mask's codes (labels == NULL); the labels
+// instantiation is the one the training hooks run.
+template <bool MASK>
+struct FusedFwdTerm {
+  const int32_t* labels;
+  const uint8_t* pm;
+  int n;
+  float inv_t, M;
+  __device__ __forceinline__ void operator()(int, float a, const ScRow& r, const ScRow& c, float& l, float& ps,
+                                             float& cnt) const {
+    const float s = a * inv_t;
+    if (MASK) {
+      const int code = sc_code(r, c, pm, n);
+      if (code <= 1) l += expf(s - M);  // (neither: in no sum)
+      if (code == 1) {
+        ps += s;
+        cnt += 1.f;
+      }
+    } else {
+      l += expf(s - M);
+      if (sc_pos(r, c, labels, pm, n)) {
+        ps += s;
+        cnt += 1.f;
+      }
+    }
+  }
+};
+
+// part[split][R][3] = (l, ps, cnt) of the split's columns
+template <bool MASK>
+__global__ void __launch_bounds__(256)
+    supcon_fused_fwd_kernel(const float* __restrict__ P, const int32_t* __restrict__ labels,
+                            const uint8_t* __restrict__ pm, const float* __restrict__ Mptr,
+                            float* __restrict__ part, int n, int D, float inv_t, int nsplit) {
+  extern __shared__ float sm[];
+  const FusedFwdTerm<MASK> term{labels, pm, n, inv_t, Mptr[0]};
+  sc_fwd_sweep<3>(sc_block(n, nsplit), P, labels, sm, part, n, D, term);
 }
 
 // single block: M = max diag (grid-wide value for the other kernels), then (after the fused pass) the loss
@@ -518,8 +639,42 @@ __global__ void __launch_bounds__(256)
   if (tid == 0) loss[0] = (float)(-ssum[0] / (double)R);
 }
 
-// grid (row blocks, column splits).  dpart[split][R][D] = sum over the split's columns of G_ij P_j.  MASK as above:
-// G_ij + G_ji = -(g/R) [pos_ij/c_i + pos_ji/c_j - e_ij (in_ij/D_i + in_ji/D_j)], the transposed terms by pm[j][i]
+// G_ij + G_ji = -(g/R) [pos_ij/c_i + pos_ji/c_j - e_ij (in_ij/D_i + in_ji/D_j)], the transposed terms by pm[j][i].
+// Staged per row: 1/D_i, 1/c_i.  MASK as above.
+template <bool MASK>
+struct FusedBwdElem {
+  static constexpr int NROW = 2;
+  struct Col {
+    float iD, ic;  // 1/D_j, 1/c_j
+  };
+  const int32_t* labels;
+  const uint8_t* pm;
+  const float* rs;
+  int n;
+  float inv_t, M, gs;
+  __device__ __forceinline__ void stage_row(float* d, int row, int R) const {
+    d[0] = row < R ? 1.f / rs[row * 4 + 0] : 0.f;
+    d[1] = row < R ? 1.f / rs[row * 4 + 1] : 0.f;
+  }
+  __device__ __forceinline__ Col load_col(int col, int R) const {
+    Col c;
+    c.iD = col < R ? 1.f / rs[col * 4 + 0] : 0.f;
+    c.ic = col < R ? 1.f / rs[col * 4 + 1] : 0.f;
+    return c;
+  }
+  __device__ __forceinline__ float g(float a, const ScRow& rq, const ScRow& cq, const float* ri, const Col& cj) const {
+    const float e = expf(a * inv_t - M);
+    if (MASK) {
+      const int cij = sc_code(rq, cq, pm, n), cji = sc_code(cq, rq, pm, n);
+      const float p = (cij == 1 ? ri[1] : 0.f) + (cji == 1 ? cj.ic : 0.f);
+      const float q = (cij <= 1 ? ri[0] : 0.f) + (cji <= 1 ? cj.iD : 0.f);
+      return -gs * (p - e * q);
+    }
+    const float pos = sc_pos(rq, cq, labels, pm, n) ? 1.f : 0.f;
+    return -gs * (pos * (ri[1] + cj.ic) - e * (ri[0] + cj.iD));
+  }
+};
+
 template <bool MASK>
 __global__ void __launch_bounds__(256)
     supcon_fused_bwd_kernel(const float* __restrict__ P, const int32_t* __restrict__ labels,
@@ -527,90 +682,8 @@ __global__ void __launch_bounds__(256)
                             const float* __restrict__ gscale, float* __restrict__ dpart, int n, int D,
                             float inv_t, int nsplit) {
   extern __shared__ float sm[];
-  const int R = 2 * n, ldg = SC_TM + 1;
-  const int ld2 = sc_ld2(D), pl = sc_plane(D);
-  float* sPi = sm;
-  float* sPj = sm + sc_block_floats(D);
-  float* sG = sPj + sc_block_floats(D);
-  float* sRow = sG + SC_TM * ldg;  // [64][2]: 1/D_i, 1/c_i of the row block
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
-  const int i = lane & 31, kk = lane >> 5;
-  const int m0 = blockIdx.x * SC_TM;
-  const int ncb = (R + SC_TM - 1) / SC_TM;
-  const int cb0 = (ncb * (int)blockIdx.y) / nsplit, cb1 = (ncb * ((int)blockIdx.y + 1)) / nsplit;
-  const float M = rs[3];
-  const float gs = gscale[0] / (float)R;
-  sc_stage(P, sPi, m0, R, D, tid);
-  if (tid < SC_TM) {
-    const int row = m0 + tid;
-    sRow[tid * 2 + 0] = row < R ? 1.f / rs[row * 4 + 0] : 0.f;
-    sRow[tid * 2 + 1] = row < R ? 1.f / rs[row * 4 + 1] : 0.f;
-  }
-  const int nct = (D + 31) / 32;          // 32-wide column tiles of dP
-  f32x16 acc2[4];                          // this wave's column tiles: wn, wn + 2, wn + 4, wn + 6
-#pragma unroll
-  for (int c = 0; c < 4; ++c)
-#pragma unroll
-    for (int q = 0; q < 16; ++q) acc2[c][q] = 0.f;
-  for (int cb = cb0; cb < cb1; ++cb) {
-    const int n0 = cb * SC_TM;
-    __syncthreads();  // previous tile: the second product has read sG and sPj
-    sc_stage(P, sPj, n0, R, D, tid);
-    __syncthreads();
-    const f32x16 acc = sc_tile(sPi, sPj, D, wm, wn, i, kk);
-    const int col = n0 + wn * 32 + i;
-    const ScRow cq = sc_row(labels, n, col);
-    const float iDj = col < R ? 1.f / rs[col * 4 + 0] : 0.f;
-    const float icj = col < R ? 1.f / rs[col * 4 + 1] : 0.f;
-#pragma unroll
-    for (int reg = 0; reg < 16; ++reg) {
-      const int rr = wm * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * kk;
-      const int row = m0 + rr;
-      float v = 0.f;
-      if (row < R && col < R && row != col) {
-        const float e = expf(acc[reg] * inv_t - M);
-        if (MASK) {
-          const ScRow rq = sc_row(labels, n, row);
-          const int cij = sc_code(rq, cq, pm, n), cji = sc_code(cq, rq, pm, n);
-          const float p = (cij == 1 ? sRow[rr * 2 + 1] : 0.f) + (cji == 1 ? icj : 0.f);
-          const float q = (cij <= 1 ? sRow[rr * 2 + 0] : 0.f) + (cji <= 1 ? iDj : 0.f);
-          v = -gs * (p - e * q);
-        } else {
-          const float pos = sc_pos(sc_row(labels, n, row), cq, labels, pm, n) ? 1.f : 0.f;
-          v = -gs * (pos * (sRow[rr * 2 + 1] + icj) - e * (sRow[rr * 2 + 0] + iDj));
-        }
-      }
-      sG[rr * ldg + wn * 32 + i] = v;
-    }
-    __syncthreads();
-    // dP rows (wm block) += G[64 rows][64 j] * P_j[64 j][D]
-    const float* ga = sG + (wm * 32 + i) * ldg + kk;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const int ct = wn + 2 * c;
-      if (ct < nct) {
-        const int dcol = ct * 32 + i;  // P_j[j][dcol] sits at [dcol & 1][j][dcol >> 1]
-        const float* pb = sPj + (dcol & 1) * pl + kk * ld2 + (dcol >> 1);
-#pragma unroll 8
-        for (int js = 0; js < SC_TM; js += 2)
-          acc2[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(ga[js], pb[js * ld2], acc2[c], 0, 0, 0);
-      }
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    const int ct = wn + 2 * c;
-    const int dcol = ct * 32 + i;
-    if (ct < nct && dcol < D) {
-#pragma unroll
-      for (int reg = 0; reg < 16; ++reg) {
-        const int row = m0 + wm * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * kk;
-        if (row < R) dpart[((size_t)blockIdx.y * R + row) * D + dcol] = acc2[c][reg];
-      }
-    }
-  }
+  const FusedBwdElem<MASK> elem{labels, pm, rs, n, inv_t, rs[3], gscale[0] / (float)(2 * n)};
+  sc_bwd_sweep(sc_block(n, nsplit), P, labels, sm, dpart, n, D, elem);
 }
 
 __global__ void __launch_bounds__(256)
@@ -660,8 +733,28 @@ __device__ __forceinline__ float sp_weight(float llh, float gamma) {
   return SOFT ? fmaxf(1.f - l / gamma, 0.f) : (l <= gamma ? 1.f : 0.f);
 }
 
-// grid (row blocks, column splits), as supcon_fused_fwd_kernel.  partB[split][R][2] = (sum w llh, sum w) over the
-// positives among the split's columns.
+// (w llh, w) of a positive element; logD[reg] = log D_i of the row in accumulator register reg
+template <bool MASK, bool SOFT>
+struct SpFwdTerm {
+  const int32_t* labels;
+  const uint8_t* pm;
+  int n;
+  float inv_t, M, gamma;
+  float logD[16];
+  __device__ __forceinline__ void operator()(int reg, float a, const ScRow& r, const ScRow& c, float& wl, float& wsum,
+                                             float&) const {
+    const bool pos = MASK ? sc_code(r, c, pm, n) == 1 : sc_pos(r, c, labels, pm, n);
+    if (pos) {
+      const float llh = (__fmul_rn(a, inv_t) - M) - logD[reg];
+      const float w = sp_weight<SOFT>(llh, gamma);
+      wl += w * llh;
+      wsum += w;
+    }
+  }
+};
+constexpr int SP_FWD_LDS_FLOATS = SC_TM;  // behind the two blocks: log D_i of the row block
+
+// partB[split][R][2] = (sum w llh, sum w) over the positives among the split's columns
 template <bool MASK, bool SOFT>
 __global__ void __launch_bounds__(256)
     supcon_sp_fwd_kernel(const float* __restrict__ P, const int32_t* __restrict__ labels,
@@ -669,79 +762,18 @@ __global__ void __launch_bounds__(256)
                          const float* __restrict__ partA, float* __restrict__ partB, int n, int D, float inv_t,
                          float gamma, int nsplit) {
   extern __shared__ float sm[];
-  const int R = 2 * n;
-  float* sPi = sm;
-  float* sPj = sm + sc_block_floats(D);
-  float* sred = sPj;                           // reused at the end: [2 wn][64 rows][2]
-  float* sLog = sPj + sc_block_floats(D);      // [64]: log D_i of the row block
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
-  const int i = lane & 31, kk = lane >> 5;
-  const int m0 = blockIdx.x * SC_TM;
-  const int ncb = (R + SC_TM - 1) / SC_TM;
-  const int cb0 = (ncb * (int)blockIdx.y) / nsplit, cb1 = (ncb * ((int)blockIdx.y + 1)) / nsplit;
-  const float M = Mptr[0];
-  sc_stage(P, sPi, m0, R, D, tid);
-  if (tid < SC_TM) {
+  const ScBlock b = sc_block(n, nsplit);
+  float* sLog = sm + 2 * sc_block_floats(D);  // [64]
+  if (b.tid < SC_TM) {
     float Di = 1.f, ci = 0.f;
-    if (m0 + tid < R) sp_row_sums(partA, R, nsplit, m0 + tid, Di, ci);
-    sLog[tid] = logf(Di);
+    if (b.m0 + b.tid < b.R) sp_row_sums(partA, b.R, nsplit, b.m0 + b.tid, Di, ci);
+    sLog[b.tid] = logf(Di);
   }
   __syncthreads();
-  float wl[16], wsum[16], logD[16];
-  ScRow rws[16];
+  SpFwdTerm<MASK, SOFT> term{labels, pm, n, inv_t, Mptr[0], gamma, {}};
 #pragma unroll
-  for (int q = 0; q < 16; ++q) {
-    const int rr = wm * 32 + (q & 3) + 8 * (q >> 2) + 4 * kk;
-    wl[q] = wsum[q] = 0.f;
-    logD[q] = sLog[rr];
-    rws[q] = sc_row(labels, n, m0 + rr);
-  }
-  for (int cb = cb0; cb < cb1; ++cb) {
-    const int n0 = cb * SC_TM;
-    __syncthreads();  // previous tile's reads of sPj are done
-    sc_stage(P, sPj, n0, R, D, tid);
-    __syncthreads();
-    const f32x16 acc = sc_tile(sPi, sPj, D, wm, wn, i, kk);
-    const int col = n0 + wn * 32 + i;
-    const ScRow cq = sc_row(labels, n, col);
-#pragma unroll
-    for (int reg = 0; reg < 16; ++reg) {
-      const int row = m0 + wm * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * kk;
-      if (row < R && col < R && row != col) {
-        const bool pos = MASK ? sc_code(rws[reg], cq, pm, n) == 1 : sc_pos(rws[reg], cq, labels, pm, n);
-        if (pos) {
-          const float llh = (__fmul_rn(acc[reg], inv_t) - M) - logD[reg];
-          const float w = sp_weight<SOFT>(llh, gamma);
-          wl[reg] += w * llh;
-          wsum[reg] += w;
-        }
-      }
-    }
-  }
-  // row totals: over the 32 lanes that share kk (fixed xor tree), then over the two column halves (wn)
-#pragma unroll
-  for (int reg = 0; reg < 16; ++reg)
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) {
-      wl[reg] += __shfl_xor(wl[reg], o, 64);
-      wsum[reg] += __shfl_xor(wsum[reg], o, 64);
-    }
-  __syncthreads();
-  if (i == 0) {
-#pragma unroll
-    for (int reg = 0; reg < 16; ++reg) {
-      const int rr = wm * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * kk;
-      float* d = sred + (wn * SC_TM + rr) * 2;
-      d[0] = wl[reg], d[1] = wsum[reg];
-    }
-  }
-  __syncthreads();
-  for (int e = tid; e < SC_TM * 2; e += 256) {
-    const int rr = e / 2;
-    if (m0 + rr < R) partB[((size_t)blockIdx.y * R + m0 + rr) * 2 + e % 2] = sred[e] + sred[SC_TM * 2 + e];
-  }
+  for (int q = 0; q < 16; ++q) term.logD[q] = sLog[sc_rr(b, q)];
+  sc_fwd_sweep<2>(b, P, labels, sm, partB, n, D, term);
 }
 
 // single block: row_stats[R][4] = (D_i, c_i, W_i, M), aux[4] = (loss, ratio, scale, sum c); rows summed in f64
@@ -785,7 +817,49 @@ __global__ void __launch_bounds__(256)
   }
 }
 
-// grid (row blocks, column splits), as supcon_fused_bwd_kernel; rs = row_stats of the forward, aux[2] = scale
+// G_ij + G_ji as above, the weights recomputed from row_stats on both sides.  Staged per row, and loaded per column:
+// W / (c D), 1 / c, log D.
+template <bool MASK, bool SOFT>
+struct SpBwdElem {
+  static constexpr int NROW = 3;
+  struct Col {
+    float a, ic, lg;
+  };
+  const int32_t* labels;
+  const uint8_t* pm;
+  const float* rs;
+  int n;
+  float inv_t, M, gs, gamma;
+  __device__ __forceinline__ Col load_col(int col, int R) const {
+    Col c{0.f, 0.f, 0.f};
+    if (col < R) {
+      const float Dj = rs[col * 4 + 0], cj = rs[col * 4 + 1];
+      c.a = rs[col * 4 + 2] / (cj * Dj), c.ic = 1.f / cj, c.lg = logf(Dj);
+    }
+    return c;
+  }
+  __device__ __forceinline__ void stage_row(float* d, int row, int R) const {
+    const Col c = load_col(row, R);
+    d[0] = c.a, d[1] = c.ic, d[2] = c.lg;
+  }
+  __device__ __forceinline__ float g(float acc, const ScRow& rq, const ScRow& cq, const float* ri, const Col& cj) const {
+    const float sl = __fmul_rn(acc, inv_t) - M;
+    bool pij, pji, iij = true, iji = true;
+    if (MASK) {
+      const int cij = sc_code(rq, cq, pm, n), cji = sc_code(cq, rq, pm, n);
+      pij = cij == 1, pji = cji == 1, iij = cij <= 1, iji = cji <= 1;
+    } else {
+      pij = pji = sc_pos(rq, cq, labels, pm, n);
+    }
+    float p = 0.f;
+    if (pij) p += sp_weight<SOFT>(sl - ri[2], gamma) * ri[1];
+    if (pji) p += sp_weight<SOFT>(sl - cj.lg, gamma) * cj.ic;
+    const float q = (iij ? ri[0] : 0.f) + (iji ? cj.a : 0.f);
+    return -gs * (p - expf(sl) * q);
+  }
+};
+
+// rs = row_stats of the forward, aux[2] = scale
 template <bool MASK, bool SOFT>
 __global__ void __launch_bounds__(256)
     supcon_sp_bwd_kernel(const float* __restrict__ P, const int32_t* __restrict__ labels,
@@ -793,482 +867,63 @@ __global__ void __launch_bounds__(256)
                          const float* __restrict__ gscale, float* __restrict__ dpart, int n, int D, float inv_t,
                          float gamma, int nsplit) {
   extern __shared__ float sm[];
-  const int R = 2 * n, ldg = SC_TM + 1;
-  const int ld2 = sc_ld2(D), pl = sc_plane(D);
-  float* sPi = sm;
-  float* sPj = sm + sc_block_floats(D);
-  float* sG = sPj + sc_block_floats(D);
-  float* sRow = sG + SC_TM * ldg;  // [64][3]: W_i / (c_i D_i), 1 / c_i, log D_i of the row block
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
-  const int i = lane & 31, kk = lane >> 5;
-  const int m0 = blockIdx.x * SC_TM;
-  const int ncb = (R + SC_TM - 1) / SC_TM;
-  const int cb0 = (ncb * (int)blockIdx.y) / nsplit, cb1 = (ncb * ((int)blockIdx.y + 1)) / nsplit;
-  const float M = rs[3];
-  const float gs = gscale[0] * aux[2] / (float)R;
-  sc_stage(P, sPi, m0, R, D, tid);
-  if (tid < SC_TM) {
-    const int row = m0 + tid;
-    float a = 0.f, ic = 0.f, lg = 0.f;
-    if (row < R) {
-      const float Di = rs[row * 4 + 0], ci = rs[row * 4 + 1];
-      a = rs[row * 4 + 2] / (ci * Di), ic = 1.f / ci, lg = logf(Di);
-    }
-    sRow[tid * 3 + 0] = a, sRow[tid * 3 + 1] = ic, sRow[tid * 3 + 2] = lg;
-  }
-  const int nct = (D + 31) / 32;          // 32-wide column tiles of dP
-  f32x16 acc2[4];                          // this wave's column tiles: wn, wn + 2, wn + 4, wn + 6
-#pragma unroll
-  for (int c = 0; c < 4; ++c)
-#pragma unroll
-    for (int q = 0; q < 16; ++q) acc2[c][q] = 0.f;
-  for (int cb = cb0; cb < cb1; ++cb) {
-    const int n0 = cb * SC_TM;
-    __syncthreads();  // previous tile: the second product has read sG and sPj
-    sc_stage(P, sPj, n0, R, D, tid);
-    __syncthreads();
-    const f32x16 acc = sc_tile(sPi, sPj, D, wm, wn, i, kk);
-    const int col = n0 + wn * 32 + i;
-    const ScRow cq = sc_row(labels, n, col);
-    float aj = 0.f, icj = 0.f, lgj = 0.f;
-    if (col < R) {
-      const float Dj = rs[col * 4 + 0], cj = rs[col * 4 + 1];
-      aj = rs[col * 4 + 2] / (cj * Dj), icj = 1.f / cj, lgj = logf(Dj);
-    }
-#pragma unroll
-    for (int reg = 0; reg < 16; ++reg) {
-      const int rr = wm * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * kk;
-      const int row = m0 + rr;
-      float v = 0.f;
-      if (row < R && col < R && row != col) {
-        const float sl = __fmul_rn(acc[reg], inv_t) - M;
-        const ScRow rq = sc_row(labels, n, row);
-        bool pij, pji, iij = true, iji = true;
-        if (MASK) {
-          const int cij = sc_code(rq, cq, pm, n), cji = sc_code(cq, rq, pm, n);
-          pij = cij == 1, pji = cji == 1, iij = cij <= 1, iji = cji <= 1;
-        } else {
-          pij = pji = sc_pos(rq, cq, labels, pm, n);
-        }
-        float p = 0.f;
-        if (pij) p += sp_weight<SOFT>(sl - sRow[rr * 3 + 2], gamma) * sRow[rr * 3 + 1];
-        if (pji) p += sp_weight<SOFT>(sl - lgj, gamma) * icj;
-        const float q = (iij ? sRow[rr * 3 + 0] : 0.f) + (iji ? aj : 0.f);
-        v = -gs * (p - expf(sl) * q);
-      }
-      sG[rr * ldg + wn * 32 + i] = v;
-    }
-    __syncthreads();
-    // dP rows (wm block) += G[64 rows][64 j] * P_j[64 j][D]
-    const float* ga = sG + (wm * 32 + i) * ldg + kk;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const int ct = wn + 2 * c;
-      if (ct < nct) {
-        const int dcol = ct * 32 + i;  // P_j[j][dcol] sits at [dcol & 1][j][dcol >> 1]
-        const float* pb = sPj + (dcol & 1) * pl + kk * ld2 + (dcol >> 1);
-#pragma unroll 8
-        for (int js = 0; js < SC_TM; js += 2)
-          acc2[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(ga[js], pb[js * ld2], acc2[c], 0, 0, 0);
-      }
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    const int ct = wn + 2 * c;
-    const int dcol = ct * 32 + i;
-    if (ct < nct && dcol < D) {
-#pragma unroll
-      for (int reg = 0; reg < 16; ++reg) {
-        const int row = m0 + wm * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * kk;
-        if (row < R) dpart[((size_t)blockIdx.y * R + row) * D + dcol] = acc2[c][reg];
-      }
-    }
-  }
-}
-
-constexpr int SP_FWD_LDS_FLOATS = SC_TM;                         // log D_i
-constexpr int SP_BWD_LDS_FLOATS = SC_TM * (SC_TM + 1) + SC_TM * 3;   // the G tile and the row staging
-
-template <bool MASK, bool SOFT>
-int launch_sp_fwd(const float* P, const int32_t* labels, const uint8_t* pm, const float* Mv, const float* partA,
-                  float* partB, int n, int D, float t, float gamma, int rb, int ns, hipStream_t st) {
-  const size_t smem = ((size_t)2 * sc_block_floats(D) + SP_FWD_LDS_FLOATS) * sizeof(float);
-  hipLaunchKernelGGL((supcon_sp_fwd_kernel<MASK, SOFT>), dim3(rb, ns), dim3(256), smem, st, P, labels, pm, Mv, partA,
-                     partB, n, D, 1.f / t, gamma, ns);
-  CY_CHECK_LAUNCH();
-  return CY_OK;
-}
-
-template <bool MASK, bool SOFT>
-int launch_sp_bwd(const float* P, const int32_t* labels, const uint8_t* pm, const float* rs, const float* aux,
-                  const float* gscale, float* dpart, int n, int D, float t, float gamma, int rb, int ns,
-                  hipStream_t st) {
-  const size_t smem = ((size_t)2 * sc_block_floats(D) + SP_BWD_LDS_FLOATS) * sizeof(float);
-  hipLaunchKernelGGL((supcon_sp_bwd_kernel<MASK, SOFT>), dim3(rb, ns), dim3(256), smem, st, P, labels, pm, rs, aux,
-                     gscale, dpart, n, D, 1.f / t, gamma, ns);
-  CY_CHECK_LAUNCH();
-  return CY_OK;
-}
-
-// ---------------------------------------------------------------- avg pool
-template <typename T>
-__global__ void __launch_bounds__(256)
-    avgpool_fwd_kernel(const T* __restrict__ x, float* __restrict__ pooled, int HW, int C) {
-  // grid: (N, ceil(C/256)); thread = channel, 4 independent partial sums over pixel phases so that
-  // four loads are in flight (a single chain is latency-bound: 196 dependent steps at Conv5)
-  const int n = blockIdx.x;
-  const int c = blockIdx.y * 256 + threadIdx.x;
-  if (c >= C) return;
-  const T* xp = x + (size_t)n * HW * C + c;
-  float s[4] = {0.f, 0.f, 0.f, 0.f};
-  int p = 0;
-  for (; p + 4 <= HW; p += 4) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) s[u] += to_f32<T>(xp[(size_t)(p + u) * C]);
-  }
-  for (; p < HW; ++p) s[0] += to_f32<T>(xp[(size_t)p * C]);
-  pooled[(size_t)n * C + c] = ((s[0] + s[1]) + (s[2] + s[3])) / (float)HW;
-}
-
-template <typename T>
-__global__ void __launch_bounds__(256)
-    avgpool_bwd_kernel(const float* __restrict__ dpooled, T* __restrict__ dx, int N, int HW,
-                       int C) {
-  const long total = (long)N * HW * C;
-  const float inv = 1.f / (float)HW;
-  for (long e = blockIdx.x * 256L + threadIdx.x; e < total; e += (long)gridDim.x * 256L) {
-    const int c = (int)(e % C);
-    const int n = (int)(e / ((long)HW * C));
-    dx[e] = from_f32<T>(dpooled[(size_t)n * C + c] * inv);
-  }
-}
-
-// ---------------------------------------------------------------- linear
-// one wave per output element y[m][o]
-__global__ void __launch_bounds__(256)
-    linear_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                      const float* __restrict__ b, float* __restrict__ y, int M, int I, int O,
-                      int act, float slope) {
-  const int lane = threadIdx.x & 63;
-  const long e = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (e >= (long)M * O) return;
-  const int m = (int)(e / O), o = (int)(e % O);
-  const float* xr = x + (size_t)m * I;
-  const float* wr = w + (size_t)o * I;
-  float s = 0.f;
-  for (int i = lane; i < I; i += 64) s = fmaf(xr[i], wr[i], s);
-  s = wave_sum(s);
-  if (lane == 0) {
-    if (b) s += b[o];
-    if (act == 1) s = s > 0.f ? s : s * slope;
-    y[e] = s;
-  }
-}
-
-// dz = dy * act'(y) is formed on the fly
-__device__ __forceinline__ float act_grad(float y, float dy, int act, float slope) {
-  return act == 1 ? (y > 0.f ? dy : dy * slope) : dy;
-}
-
-__global__ void __launch_bounds__(256)
-    linear_bwd_dx_kernel(const float* __restrict__ w, const float* __restrict__ y,
-                         const float* __restrict__ dy, float* __restrict__ dx, int M, int I, int O,
-                         int act, float slope) {
-  const long e = blockIdx.x * 256L + threadIdx.x;
-  if (e >= (long)M * I) return;
-  const int m = (int)(e / I), i = (int)(e % I);
-  float s[4] = {0.f, 0.f, 0.f, 0.f};  // four independent chains keep four weight loads in flight
-  int o = 0;
-  for (; o + 4 <= O; o += 4) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-      s[u] = fmaf(act_grad(y[(size_t)m * O + o + u], dy[(size_t)m * O + o + u], act, slope),
-                  w[(size_t)(o + u) * I + i], s[u]);
-  }
-  for (; o < O; ++o)
-    s[0] = fmaf(act_grad(y[(size_t)m * O + o], dy[(size_t)m * O + o], act, slope), w[(size_t)o * I + i],
-                s[0]);
-  dx[e] = (s[0] + s[1]) + (s[2] + s[3]);
-}
-
-__global__ void __launch_bounds__(256)
-    linear_bwd_dw_kernel(const float* __restrict__ x, const float* __restrict__ y,
-                         const float* __restrict__ dy, float* __restrict__ dw,
-                         float* __restrict__ db, int M, int I, int O, int act, float slope, int accumulate) {
-  const long e = blockIdx.x * 256L + threadIdx.x;
-  if (e >= (long)O * I) return;
-  const int o = (int)(e / I), i = (int)(e % I);
-  float s = 0.f, sb = 0.f;
-  for (int m = 0; m < M; ++m) {
-    const float dz = act_grad(y[(size_t)m * O + o], dy[(size_t)m * O + o], act, slope);
-    s = fmaf(dz, x[(size_t)m * I + i], s);
-    sb += dz;
-  }
-  if (dw) dw[e] = accumulate ? dw[e] + s : s;
-  if (db && i == 0) db[o] = accumulate ? db[o] + sb : sb;
-}
-
-// ---------------------------------------------------------------- L2 normalise (wave per row)
-__global__ void __launch_bounds__(256)
-    l2norm_fwd_kernel(const float* __restrict__ x, float* __restrict__ z,
-                      float* __restrict__ norms, int M, int D, float eps) {
-  const int lane = threadIdx.x & 63;
-  const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (m >= M) return;
-  const float* xr = x + (size_t)m * D;
-  float s = 0.f;
-  for (int i = lane; i < D; i += 64) s = fmaf(xr[i], xr[i], s);
-  s = wave_sum(s);
-  const float nrm = sqrtf(s);
-  const float den = fmaxf(nrm, eps);
-  for (int i = lane; i < D; i += 64) z[(size_t)m * D + i] = xr[i] / den;
-  if (lane == 0) norms[m] = nrm;
-}
-
-__global__ void __launch_bounds__(256)
-    l2norm_bwd_kernel(const float* __restrict__ x, const float* __restrict__ norms,
-                      const float* __restrict__ dz, float* __restrict__ dx, int M, int D,
-                      float eps) {
-  const int lane = threadIdx.x & 63;
-  const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (m >= M) return;
-  const float* xr = x + (size_t)m * D;
-  const float* gr = dz + (size_t)m * D;
-  const float nrm = norms[m];
-  if (nrm > eps) {
-    float dot = 0.f;
-    for (int i = lane; i < D; i += 64) dot = fmaf(xr[i], gr[i], dot);
-    dot = wave_sum(dot);
-    const float inv = 1.f / nrm;
-    const float k = dot * inv * inv * inv;
-    for (int i = lane; i < D; i += 64) dx[(size_t)m * D + i] = gr[i] * inv - xr[i] * k;
-  } else {
-    const float inv = 1.f / eps;
-    for (int i = lane; i < D; i += 64) dx[(size_t)m * D + i] = gr[i] * inv;
-  }
-}
-
-// ---------------------------------------------------------------- projection head, one launch per direction
-// ProjectionHead (contrastyou/projectors/heads.py:12-22,81-96): AdaptiveAvgPool2d(1) -> Linear(C, hid) -> LeakyReLU
-// -> Linear(hid, out) -> F.normalize.  The pieces above cost four launches forward and six backward for ~0.4 MFLOP
-// per sample; here one workgroup runs a sample through the whole chain (matrix rows are read coalesced, lanes across
-// the input index, one wave reduction per output), and the parameter gradients -- sums over the samples -- are a
-// second backward kernel with one thread per weight.
-constexpr int PH_MAXC = 512, PH_MAXH = 512;  // one workgroup's LDS: 16 partial vectors of <= 512 floats
-constexpr int PH_NT = 1024, PH_NW = 16;
-
-// y[o] = sum_i w[o][i] * x[i] (+ b[o]); x in LDS.  A wave takes four rows at a time (eight loads in flight for
-// I = 512, four independent reductions): the first version -- four waves, one row per iteration -- spent ~1 us of
-// dependent global latency per output (147 us for 512 -> 256 -> 256).
-__device__ __forceinline__ void ph_matvec(const float* __restrict__ w, const float* __restrict__ b, const float* xs,
-                                          float* ys, int I, int O, int wave, int lane) {
-  for (int o0 = wave * 4; o0 < O; o0 += PH_NW * 4) {
-    float s[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int i = lane * 4; i < I; i += 256) {
-      const f32x4 xv = *reinterpret_cast<const f32x4*>(xs + i);
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int o = o0 + u < O ? o0 + u : O - 1;
-        const f32x4 wv = *reinterpret_cast<const f32x4*>(w + (size_t)o * I + i);
-        s[u] = fmaf(wv[0], xv[0], fmaf(wv[1], xv[1], fmaf(wv[2], xv[2], fmaf(wv[3], xv[3], s[u]))));
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) s[u] = wave_sum(s[u]);
-    if (lane < 4 && o0 + lane < O) {
-      const float v = lane == 0 ? s[0] : (lane == 1 ? s[1] : (lane == 2 ? s[2] : s[3]));
-      ys[o0 + lane] = v + (b ? b[o0 + lane] : 0.f);
-    }
-  }
-}
-
-template <typename T>
-__global__ void __launch_bounds__(PH_NT)
-    proj_head_fwd_kernel(const T* __restrict__ feat, const float* __restrict__ w1, const float* __restrict__ b1,
-                         const float* __restrict__ w2, const float* __restrict__ b2, float* __restrict__ pooled,
-                         float* __restrict__ y1, float* __restrict__ y2, float* __restrict__ z,
-                         float* __restrict__ norms, int HW, int C, int hid, int out, float slope, float eps) {
-  constexpr int EPC = ElemTr<T>::EPC;
-  __shared__ __attribute__((aligned(16))) float spart[PH_NW * PH_MAXC];  // pooling partials [slice][C]
-  __shared__ __attribute__((aligned(16))) float sp[PH_MAXC];
-  __shared__ __attribute__((aligned(16))) float sh[PH_MAXH];
-  __shared__ __attribute__((aligned(16))) float so[PH_MAXH];
-  __shared__ float sred[PH_NW];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int n = blockIdx.x;
-  // average pool: thread = (16-byte channel group, position slice); every load of a thread is independent
-  const int G = C / EPC;
-  const int nsl = PH_NT / G < PH_NW ? PH_NT / G : PH_NW;  // slices (host: G <= 1024)
-  {
-    const int cg = tid % G, sl = tid / G;
-    if (sl < nsl) {
-      float a[EPC];
-#pragma unroll
-      for (int e = 0; e < EPC; ++e) a[e] = 0.f;
-      const T* xp = feat + (size_t)n * HW * C + cg * EPC;
-      for (int p = sl; p < HW; p += nsl) {
-        float f[EPC];
-        Chunk<T>::unpack(ld16(xp + (size_t)p * C), f);
-#pragma unroll
-        for (int e = 0; e < EPC; ++e) a[e] += f[e];
-      }
-#pragma unroll
-      for (int e = 0; e < EPC; ++e) spart[sl * C + cg * EPC + e] = a[e];
-    }
-  }
-  __syncthreads();
-  const float inv = 1.f / (float)HW;
-  for (int c = tid; c < C; c += PH_NT) {
-    float v = 0.f;
-    for (int q = 0; q < nsl; ++q) v += spart[q * C + c];
-    v *= inv;
-    sp[c] = v;
-    pooled[(size_t)n * C + c] = v;
-  }
-  __syncthreads();
-  ph_matvec(w1, b1, sp, sh, C, hid, wave, lane);
-  __syncthreads();
-  for (int j = tid; j < hid; j += PH_NT) {
-    const float v = sh[j] > 0.f ? sh[j] : slope * sh[j];
-    sh[j] = v;
-    y1[(size_t)n * hid + j] = v;
-  }
-  __syncthreads();
-  ph_matvec(w2, b2, sh, so, hid, out, wave, lane);
-  __syncthreads();
-  float ss = 0.f;
-  for (int o = tid; o < out; o += PH_NT) ss = fmaf(so[o], so[o], ss);
-  ss = wave_sum(ss);
-  if (lane == 0) sred[wave] = ss;
-  __syncthreads();
-  float tot = 0.f;
-#pragma unroll
-  for (int q = 0; q < PH_NW; ++q) tot += sred[q];
-  const float nrm = sqrtf(tot);
-  const float den = fmaxf(nrm, eps);
-  for (int o = tid; o < out; o += PH_NT) {
-    y2[(size_t)n * out + o] = so[o];
-    z[(size_t)n * out + o] = so[o] / den;
-  }
-  if (tid == 0) norms[n] = nrm;
-}
-
-// per sample: dy2 (normalise backward), dh = (W2^T dy2) * lrelu'(y1), dpooled = W1^T dh, dfeat = dpooled / HW
-template <typename T>
-__global__ void __launch_bounds__(PH_NT)
-    proj_head_bwd_kernel(const float* __restrict__ dz, const float* __restrict__ y1, const float* __restrict__ y2,
-                         const float* __restrict__ norms, const float* __restrict__ w1,
-                         const float* __restrict__ w2, float* __restrict__ dy2g, float* __restrict__ dhg,
-                         T* __restrict__ dfeat, int HW, int C, int hid, int out, float slope, float eps) {
-  __shared__ __attribute__((aligned(16))) float sa[PH_MAXH];           // dy2, then dh
-  __shared__ __attribute__((aligned(16))) float sb[PH_NW * PH_MAXC];   // per-wave partial columns
-  __shared__ float sred[PH_NW];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int n = blockIdx.x;
-  // dy2 = dz / nrm - y2 * (y2 . dz) / nrm^3   (nrm <= eps: dz / eps), as l2norm_bwd_kernel
-  const float nrm = norms[n];
-  float dot = 0.f;
-  for (int o = tid; o < out; o += PH_NT) dot = fmaf(y2[(size_t)n * out + o], dz[(size_t)n * out + o], dot);
-  dot = wave_sum(dot);
-  if (lane == 0) sred[wave] = dot;
-  __syncthreads();
-  dot = 0.f;
-#pragma unroll
-  for (int q = 0; q < PH_NW; ++q) dot += sred[q];
-  for (int o = tid; o < out; o += PH_NT) {
-    float v;
-    if (nrm > eps) {
-      const float iv = 1.f / nrm;
-      v = dz[(size_t)n * out + o] * iv - y2[(size_t)n * out + o] * (dot * iv * iv * iv);
-    } else {
-      v = dz[(size_t)n * out + o] / eps;
-    }
-    sa[o] = v;
-    dy2g[(size_t)n * out + o] = v;
-  }
-  __syncthreads();
-  // column sums: wave w takes rows w, w + 16, ... of the matrix (loads independent of each other), lanes across
-  // the columns; the sixteen partial vectors meet in LDS
-  auto tmatvec = [&](const float* __restrict__ w, const float* xs, int R, int Ccols) {
-    for (int c0 = lane * 4; c0 < Ccols; c0 += 256) {
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-      for (int rr = wave; rr < R; rr += PH_NW) {
-        const f32x4 wv = *reinterpret_cast<const f32x4*>(w + (size_t)rr * Ccols + c0);
-        const float xv = xs[rr];
-        acc[0] = fmaf(wv[0], xv, acc[0]), acc[1] = fmaf(wv[1], xv, acc[1]);
-        acc[2] = fmaf(wv[2], xv, acc[2]), acc[3] = fmaf(wv[3], xv, acc[3]);
-      }
-      *reinterpret_cast<f32x4*>(&sb[wave * Ccols + c0]) = acc;
-    }
-  };
-  tmatvec(w2, sa, out, hid);
-  __syncthreads();
-  for (int j = tid; j < hid; j += PH_NT) {
-    float g = 0.f;
-#pragma unroll
-    for (int q = 0; q < PH_NW; ++q) g += sb[q * hid + j];
-    const float v = y1[(size_t)n * hid + j] > 0.f ? g : g * slope;
-    sa[j] = v;
-    dhg[(size_t)n * hid + j] = v;
-  }
-  __syncthreads();
-  tmatvec(w1, sa, hid, C);
-  __syncthreads();
-  const float inv = 1.f / (float)HW;
-  float* sdp = sa;  // (dh is in global memory by now)  dpooled / HW, C <= PH_MAXH
-  __syncthreads();
-  for (int c = tid; c < C; c += PH_NT) {
-    float g = 0.f;
-#pragma unroll
-    for (int q = 0; q < PH_NW; ++q) g += sb[q * C + c];
-    sdp[c] = g * inv;
-  }
-  __syncthreads();
-  if (dfeat) {
-    constexpr int EPC = ElemTr<T>::EPC;
-    T* dp = dfeat + (size_t)n * HW * C;
-    const int G = C / EPC;
-    for (long e = tid; e < (long)HW * G; e += PH_NT) {
-      const int cg = (int)(e % G);
-      st16(dp + (e / G) * C + cg * EPC, Chunk<T>::pack(sdp + cg * EPC));
-    }
-  }
-}
-
-// parameter gradients: thread e < out*hid: dW2[o][j] = sum_n dy2[n][o] y1[n][j]; then dW1[j][i] = sum_n dh[n][j] pooled[n][i]
-__global__ void __launch_bounds__(256)
-    proj_head_dw_kernel(const float* __restrict__ dy2, const float* __restrict__ dh, const float* __restrict__ y1,
-                        const float* __restrict__ pooled, float* __restrict__ dw1, float* __restrict__ db1,
-                        float* __restrict__ dw2, float* __restrict__ db2, int B, int C, int hid, int out,
-                        int accumulate) {
-  const long e = blockIdx.x * 256L + threadIdx.x;
-  const long n2 = (long)out * hid, n1 = (long)hid * C;
-  const float *ga, *xa;
-  float *dw, *db;
-  int O, I;
-  long k;
-  if (e < n2) {
-    ga = dy2, xa = y1, dw = dw2, db = db2, O = out, I = hid, k = e;
-  } else if (e < n2 + n1) {
-    ga = dh, xa = pooled, dw = dw1, db = db1, O = hid, I = C, k = e - n2;
-  } else {
-    return;
-  }
-  const int o = (int)(k / I), i = (int)(k % I);
-  float s = 0.f, sbias = 0.f;
-  for (int n = 0; n < B; ++n) {
-    const float g = ga[(size_t)n * O + o];
-    s = fmaf(g, xa[(size_t)n * I + i], s);
-    sbias += g;
-  }
-  if (dw) dw[k] = accumulate ? dw[k] + s : s;
-  if (db && i == 0) db[o] = accumulate ? db[o] + sbias : sbias;
+  const SpBwdElem<MASK, SOFT> elem{labels, pm, rs, n, inv_t, rs[3], gscale[0] * aux[2] / (float)(2 * n), gamma};
+  sc_bwd_sweep(sc_block(n, nsplit), P, labels, sm, dpart, n, D, elem);
 }
 
 constexpr int GRID_CAP = 8192;  // blocks of 256 of the elementwise kernels; the rest is their grid-stride loop
+
+// ---- host side of the fused and the self-paced entries ----
+// what the tiles take (the self-paced entries check gamma in addition)
+inline bool sc_shape_ok(int n, int D, float t) { return n > 0 && D > 0 && D <= SC_MAXD && D % 8 == 0 && t > 0.f; }
+
+// diag[R] + M[4] + forward partials [ns][R][fwd_row_floats] | backward partials [ns][R][D]
+inline size_t sc_ws_bytes(int n, int D, int fwd_row_floats) {
+  if (n <= 0 || D <= 0) return 0;
+  const size_t R = 2 * (size_t)n;
+  const size_t ns = (size_t)sc_nsplit((int)R);
+  const size_t fwd = ns * R * (size_t)fwd_row_floats, bwd = ns * R * (size_t)D;
+  return (R + 4 + (fwd > bwd ? fwd : bwd)) * sizeof(float);
+}
+
+// the workspace of that layout, and the launch geometry that goes with it
+struct ScWs {
+  int R, ns, rb;
+  float* diag;  // diag_out if given (written in place: no device-to-device copy afterwards)
+  float* Mv;
+  float* part;  // (l, ps, cnt) partials of the forward's first pass; dpart of a backward
+  ScWs(void* ws, int n, float* diag_out = nullptr) : R(2 * n), ns(sc_nsplit(R)), rb(cy_cdiv(R, SC_TM)) {
+    diag = diag_out ? diag_out : (float*)ws;
+    Mv = (float*)ws + R;
+    part = Mv + 4;
+  }
+  dim3 grid() const { return dim3(rb, ns); }
+};
+
+// first pass of every forward: diag(S), M = max diag, then (l, ps, cnt) per row and column split into w.part
+int sc_first_pass(const float* P, const int32_t* labels, const uint8_t* pm, const ScWs& w, int n, int D, float t,
+                  hipStream_t st) {
+  hipLaunchKernelGGL(supcon_diag_kernel, dim3(cy_cdiv(w.R, 4)), dim3(256), 0, st, P, w.diag, w.R, D, 1.f / t);
+  CY_CHECK_LAUNCH();
+  hipLaunchKernelGGL(supcon_max_kernel, dim3(1), dim3(256), 0, st, (const float*)w.diag, w.Mv, w.R);
+  CY_CHECK_LAUNCH();
+  if (!cy_lds_limit_once<supcon_fused_fwd_kernel<false>, supcon_fused_fwd_kernel<true>>(sc_fwd_lds(SC_MAXD, 0)))
+    return CY_ERR_LAUNCH;
+  const auto kernel = labels ? supcon_fused_fwd_kernel<false> : supcon_fused_fwd_kernel<true>;
+  hipLaunchKernelGGL(kernel, w.grid(), dim3(256), sc_fwd_lds(D, 0), st, P, labels, pm, (const float*)w.Mv, w.part, n, D,
+                     1.f / t, w.ns);
+  CY_CHECK_LAUNCH();
+  return CY_OK;
+}
+
+// dP = (1/t) * the column splits of w.part summed in order
+int sc_reduce_dpart(const ScWs& w, float* dP, int D, float t, hipStream_t st) {
+  const long total = (long)w.R * D;
+  hipLaunchKernelGGL(supcon_dpart_reduce_kernel, dim3(cy_blocks(total, 256, GRID_CAP)), dim3(256), 0, st,
+                     (const float*)w.part, dP, total, w.ns, 1.f / t);
+  CY_CHECK_LAUNCH();
+  return CY_OK;
+}
 
 }  // namespace
 
@@ -1340,41 +995,20 @@ int cy_supcon_excl_bwd(const float* P, const int32_t* labels, const uint8_t* pos
   return launch_sgemm(G, P, dP, R, D, R, 1.f / t, 0, st);
 }
 
-size_t cy_supcon_fused_ws_bytes(int n, int D) {
-  if (n <= 0 || D <= 0) return 0;
-  const size_t R = 2 * (size_t)n;
-  const size_t ns = (size_t)sc_nsplit((int)R);
-  // diag[R] + M[4] + forward partials [ns][R][3] | backward partials [ns][R][D]
-  const size_t fwd = ns * R * 3, bwd = ns * R * (size_t)D;
-  return (R + 4 + (fwd > bwd ? fwd : bwd)) * sizeof(float);
-}
+size_t cy_supcon_fused_ws_bytes(int n, int D) { return sc_ws_bytes(n, D, 3); }
 
 int cy_supcon_fused_fwd(const float* P, const int32_t* labels, const uint8_t* pos_mask, float* loss,
                         float* row_stats, float* diag_out, void* ws, size_t ws_bytes, int n, int D, float t,
                         void* stream) {
   if (!P || (!labels && !pos_mask) || !loss || !row_stats || !ws) return CY_ERR_ARG;
-  if (n <= 0 || D <= 0 || D > 256 || D % 8 || !(t > 0.f)) return CY_ERR_SHAPE;
+  if (!sc_shape_ok(n, D, t)) return CY_ERR_SHAPE;
   if (ws_bytes < cy_supcon_fused_ws_bytes(n, D)) return CY_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const int R = 2 * n, ns = sc_nsplit(R), rb = cy_cdiv(R, SC_TM);
-  float* diag = diag_out ? diag_out : (float*)ws;  // (written in place: no device-to-device copy afterwards)
-  float* Mv = (float*)ws + R;
-  float* part = Mv + 4;
-  hipLaunchKernelGGL(supcon_diag_kernel, dim3(cy_cdiv(R, 4)), dim3(256), 0, st, P, diag, R, D, 1.f / t);
-  CY_CHECK_LAUNCH();
-  hipLaunchKernelGGL(supcon_max_kernel, dim3(1), dim3(256), 0, st, diag, Mv, R);
-  CY_CHECK_LAUNCH();
-  const size_t smem = (size_t)2 * sc_block_floats(D) * sizeof(float);
-  if (!cy_lds_limit_once<supcon_fused_fwd_kernel<false>, supcon_fused_fwd_kernel<true>>(2 * sc_block_floats(256) * 4))
-    return CY_ERR_LAUNCH;
-  if (labels)
-    hipLaunchKernelGGL(supcon_fused_fwd_kernel<false>, dim3(rb, ns), dim3(256), smem, st, P, labels, pos_mask, Mv, part,
-                       n, D, 1.f / t, ns);
-  else
-    hipLaunchKernelGGL(supcon_fused_fwd_kernel<true>, dim3(rb, ns), dim3(256), smem, st, P, labels, pos_mask, Mv, part,
-                       n, D, 1.f / t, ns);
-  CY_CHECK_LAUNCH();
-  hipLaunchKernelGGL(supcon_fused_finalize_kernel, dim3(1), dim3(256), 0, st, part, Mv, row_stats, loss, R, ns);
+  const ScWs w(ws, n, diag_out);
+  const int rc = sc_first_pass(P, labels, pos_mask, w, n, D, t, st);
+  if (rc != CY_OK) return rc;
+  hipLaunchKernelGGL(supcon_fused_finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)w.part,
+                     (const float*)w.Mv, row_stats, loss, w.R, w.ns);
   CY_CHECK_LAUNCH();
   return CY_OK;
 }
@@ -1383,78 +1017,44 @@ int cy_supcon_fused_bwd(const float* P, const int32_t* labels, const uint8_t* po
                         const float* gscale, float* dP, void* ws, size_t ws_bytes, int n, int D, float t,
                         void* stream) {
   if (!P || (!labels && !pos_mask) || !row_stats || !gscale || !dP || !ws) return CY_ERR_ARG;
-  if (n <= 0 || D <= 0 || D > 256 || D % 8 || !(t > 0.f)) return CY_ERR_SHAPE;
+  if (!sc_shape_ok(n, D, t)) return CY_ERR_SHAPE;
   if (ws_bytes < cy_supcon_fused_ws_bytes(n, D)) return CY_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const int R = 2 * n, ns = sc_nsplit(R), rb = cy_cdiv(R, SC_TM);
-  float* dpart = (float*)ws + R + 4;
-  const size_t smem = ((size_t)2 * sc_block_floats(D) + SC_TM * (SC_TM + 1) + SC_TM * 2) * sizeof(float);
-  if (!cy_lds_limit_once<supcon_fused_bwd_kernel<false>, supcon_fused_bwd_kernel<true>>(
-          (2 * sc_block_floats(256) + SC_TM * (SC_TM + 1) + SC_TM * 2) * 4))
+  const ScWs w(ws, n);
+  constexpr int NROW = FusedBwdElem<false>::NROW;
+  if (!cy_lds_limit_once<supcon_fused_bwd_kernel<false>, supcon_fused_bwd_kernel<true>>(sc_bwd_lds(SC_MAXD, NROW)))
     return CY_ERR_LAUNCH;
-  if (labels)
-    hipLaunchKernelGGL(supcon_fused_bwd_kernel<false>, dim3(rb, ns), dim3(256), smem, st, P, labels, pos_mask, row_stats,
-                       gscale, dpart, n, D, 1.f / t, ns);
-  else
-    hipLaunchKernelGGL(supcon_fused_bwd_kernel<true>, dim3(rb, ns), dim3(256), smem, st, P, labels, pos_mask, row_stats,
-                       gscale, dpart, n, D, 1.f / t, ns);
+  const auto kernel = labels ? supcon_fused_bwd_kernel<false> : supcon_fused_bwd_kernel<true>;
+  hipLaunchKernelGGL(kernel, w.grid(), dim3(256), sc_bwd_lds(D, NROW), st, P, labels, pos_mask, row_stats, gscale,
+                     w.part, n, D, 1.f / t, w.ns);
   CY_CHECK_LAUNCH();
-  const long total = (long)R * D;
-  hipLaunchKernelGGL(supcon_dpart_reduce_kernel, dim3(cy_blocks(total, 256, GRID_CAP)), dim3(256), 0, st, dpart, dP,
-                     total, ns, 1.f / t);
-  CY_CHECK_LAUNCH();
-  return CY_OK;
+  return sc_reduce_dpart(w, dP, D, t, st);
 }
 
-size_t cy_supcon_sp_ws_bytes(int n, int D) {
-  if (n <= 0 || D <= 0) return 0;
-  const size_t R = 2 * (size_t)n;
-  const size_t ns = (size_t)sc_nsplit((int)R);
-  // diag[R] + M[4] + forward partials [ns][R][3] and [ns][R][2] | backward partials [ns][R][D]
-  const size_t fwd = ns * R * 5, bwd = ns * R * (size_t)D;
-  return (R + 4 + (fwd > bwd ? fwd : bwd)) * sizeof(float);
-}
+size_t cy_supcon_sp_ws_bytes(int n, int D) { return sc_ws_bytes(n, D, 3 + 2); }  // the first pass's and (w llh, w)
 
 int cy_supcon_sp_fwd(const float* P, const int32_t* labels, const uint8_t* pos_mask, float* aux, float* row_stats,
                      float* diag_out, void* ws, size_t ws_bytes, int n, int D, float t, float gamma, int soft,
                      int correct_grad, void* stream) {
   if (!P || (!labels && !pos_mask) || !aux || !row_stats || !ws) return CY_ERR_ARG;
-  if (n <= 0 || D <= 0 || D > 256 || D % 8 || !(t > 0.f) || !(gamma > 0.f)) return CY_ERR_SHAPE;
+  if (!sc_shape_ok(n, D, t) || !(gamma > 0.f)) return CY_ERR_SHAPE;
   if (ws_bytes < cy_supcon_sp_ws_bytes(n, D)) return CY_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const int R = 2 * n, ns = sc_nsplit(R), rb = cy_cdiv(R, SC_TM);
-  float* diag = diag_out ? diag_out : (float*)ws;
-  float* Mv = (float*)ws + R;
-  float* partA = Mv + 4;
-  float* partB = partA + (size_t)ns * R * 3;
-  hipLaunchKernelGGL(supcon_diag_kernel, dim3(cy_cdiv(R, 4)), dim3(256), 0, st, P, diag, R, D, 1.f / t);
-  CY_CHECK_LAUNCH();
-  hipLaunchKernelGGL(supcon_max_kernel, dim3(1), dim3(256), 0, st, diag, Mv, R);
-  CY_CHECK_LAUNCH();
-  const size_t smem = (size_t)2 * sc_block_floats(D) * sizeof(float);
-  if (!cy_lds_limit_once<supcon_fused_fwd_kernel<false>, supcon_fused_fwd_kernel<true>>(2 * sc_block_floats(256) * 4))
-    return CY_ERR_LAUNCH;
+  const ScWs w(ws, n, diag_out);
+  float* partB = w.part + (size_t)w.ns * w.R * 3;
   if (!cy_lds_limit_once<supcon_sp_fwd_kernel<false, false>, supcon_sp_fwd_kernel<false, true>,
                          supcon_sp_fwd_kernel<true, false>, supcon_sp_fwd_kernel<true, true>>(
-          (2 * sc_block_floats(256) + SP_FWD_LDS_FLOATS) * 4))
+          sc_fwd_lds(SC_MAXD, SP_FWD_LDS_FLOATS)))
     return CY_ERR_LAUNCH;
-  if (labels)
-    hipLaunchKernelGGL(supcon_fused_fwd_kernel<false>, dim3(rb, ns), dim3(256), smem, st, P, labels, pos_mask, Mv, partA,
-                       n, D, 1.f / t, ns);
-  else
-    hipLaunchKernelGGL(supcon_fused_fwd_kernel<true>, dim3(rb, ns), dim3(256), smem, st, P, labels, pos_mask, Mv, partA,
-                       n, D, 1.f / t, ns);
-  CY_CHECK_LAUNCH();
-  int rc;
-  if (labels)
-    rc = soft ? launch_sp_fwd<false, true>(P, labels, pos_mask, Mv, partA, partB, n, D, t, gamma, rb, ns, st)
-              : launch_sp_fwd<false, false>(P, labels, pos_mask, Mv, partA, partB, n, D, t, gamma, rb, ns, st);
-  else
-    rc = soft ? launch_sp_fwd<true, true>(P, labels, pos_mask, Mv, partA, partB, n, D, t, gamma, rb, ns, st)
-              : launch_sp_fwd<true, false>(P, labels, pos_mask, Mv, partA, partB, n, D, t, gamma, rb, ns, st);
+  const int rc = sc_first_pass(P, labels, pos_mask, w, n, D, t, st);
   if (rc != CY_OK) return rc;
-  hipLaunchKernelGGL(supcon_sp_finalize_kernel, dim3(1), dim3(256), 0, st, partA, partB, Mv, row_stats, aux, R, ns,
-                     correct_grad);
+  const auto kernel = labels ? (soft ? supcon_sp_fwd_kernel<false, true> : supcon_sp_fwd_kernel<false, false>)
+                             : (soft ? supcon_sp_fwd_kernel<true, true> : supcon_sp_fwd_kernel<true, false>);
+  hipLaunchKernelGGL(kernel, w.grid(), dim3(256), sc_fwd_lds(D, SP_FWD_LDS_FLOATS), st, P, labels, pos_mask,
+                     (const float*)w.Mv, (const float*)w.part, partB, n, D, 1.f / t, gamma, w.ns);
+  CY_CHECK_LAUNCH();
+  hipLaunchKernelGGL(supcon_sp_finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)w.part, (const float*)partB,
+                     (const float*)w.Mv, row_stats, aux, w.R, w.ns, correct_grad);
   CY_CHECK_LAUNCH();
   return CY_OK;
 }
@@ -1463,28 +1063,21 @@ int cy_supcon_sp_bwd(const float* P, const int32_t* labels, const uint8_t* pos_m
                      const float* aux, const float* gscale, float* dP, void* ws, size_t ws_bytes, int n, int D, float t,
                      float gamma, int soft, void* stream) {
   if (!P || (!labels && !pos_mask) || !row_stats || !aux || !gscale || !dP || !ws) return CY_ERR_ARG;
-  if (n <= 0 || D <= 0 || D > 256 || D % 8 || !(t > 0.f) || !(gamma > 0.f)) return CY_ERR_SHAPE;
+  if (!sc_shape_ok(n, D, t) || !(gamma > 0.f)) return CY_ERR_SHAPE;
   if (ws_bytes < cy_supcon_sp_ws_bytes(n, D)) return CY_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const int R = 2 * n, ns = sc_nsplit(R), rb = cy_cdiv(R, SC_TM);
-  float* dpart = (float*)ws + R + 4;
+  const ScWs w(ws, n);
+  constexpr int NROW = SpBwdElem<false, false>::NROW;
   if (!cy_lds_limit_once<supcon_sp_bwd_kernel<false, false>, supcon_sp_bwd_kernel<false, true>,
                          supcon_sp_bwd_kernel<true, false>, supcon_sp_bwd_kernel<true, true>>(
-          (2 * sc_block_floats(256) + SP_BWD_LDS_FLOATS) * 4))
+          sc_bwd_lds(SC_MAXD, NROW)))
     return CY_ERR_LAUNCH;
-  int rc;
-  if (labels)
-    rc = soft ? launch_sp_bwd<false, true>(P, labels, pos_mask, row_stats, aux, gscale, dpart, n, D, t, gamma, rb, ns, st)
-              : launch_sp_bwd<false, false>(P, labels, pos_mask, row_stats, aux, gscale, dpart, n, D, t, gamma, rb, ns, st);
-  else
-    rc = soft ? launch_sp_bwd<true, true>(P, labels, pos_mask, row_stats, aux, gscale, dpart, n, D, t, gamma, rb, ns, st)
-              : launch_sp_bwd<true, false>(P, labels, pos_mask, row_stats, aux, gscale, dpart, n, D, t, gamma, rb, ns, st);
-  if (rc != CY_OK) return rc;
-  const long total = (long)R * D;
-  hipLaunchKernelGGL(supcon_dpart_reduce_kernel, dim3(cy_blocks(total, 256, GRID_CAP)), dim3(256), 0, st, dpart, dP,
-                     total, ns, 1.f / t);
+  const auto kernel = labels ? (soft ? supcon_sp_bwd_kernel<false, true> : supcon_sp_bwd_kernel<false, false>)
+                             : (soft ? supcon_sp_bwd_kernel<true, true> : supcon_sp_bwd_kernel<true, false>);
+  hipLaunchKernelGGL(kernel, w.grid(), dim3(256), sc_bwd_lds(D, NROW), st, P, labels, pos_mask, row_stats, aux, gscale,
+                     w.part, n, D, 1.f / t, gamma, w.ns);
   CY_CHECK_LAUNCH();
-  return CY_OK;
+  return sc_reduce_dpart(w, dP, D, t, st);
 }
 
 int cy_supcon_matrices(const float* S, const float* row_stats, const int32_t* labels,
@@ -1495,153 +1088,6 @@ int cy_supcon_matrices(const float* S, const float* row_stats, const int32_t* la
   hipLaunchKernelGGL(supcon_matrices_kernel, dim3(cy_blocks((long)R * R, 256, GRID_CAP)), dim3(256), 0,
                      (hipStream_t)stream, S, row_stats, labels, pos_mask, sim_logits, sim_exp,
                      pos_out, neg_out, n);
-  CY_CHECK_LAUNCH();
-  return CY_OK;
-}
-
-int cy_avgpool_fwd(const void* x, float* pooled, int N, int HW, int C, int dtype, void* stream) {
-  if (!x || !pooled || N <= 0 || HW <= 0 || C <= 0) return CY_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  dim3 grid(N, cy_cdiv(C, 256));
-  if (dtype == CY_BF16)
-    hipLaunchKernelGGL(avgpool_fwd_kernel<bf16>, grid, dim3(256), 0, st, (const bf16*)x, pooled,
-                       HW, C);
-  else if (dtype == CY_F16)
-    hipLaunchKernelGGL(avgpool_fwd_kernel<f16>, grid, dim3(256), 0, st, (const f16*)x, pooled,
-                       HW, C);
-  else if (dtype == CY_F32)
-    hipLaunchKernelGGL(avgpool_fwd_kernel<float>, grid, dim3(256), 0, st, (const float*)x, pooled,
-                       HW, C);
-  else
-    return CY_ERR_DTYPE;
-  CY_CHECK_LAUNCH();
-  return CY_OK;
-}
-
-int cy_avgpool_bwd(const float* dpooled, void* dx, int N, int HW, int C, int dtype, void* stream) {
-  if (!dpooled || !dx || N <= 0 || HW <= 0 || C <= 0) return CY_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  const int grid = cy_blocks((long)N * HW * C, 256, GRID_CAP);
-  if (dtype == CY_BF16)
-    hipLaunchKernelGGL(avgpool_bwd_kernel<bf16>, dim3(grid), dim3(256), 0, st, dpooled, (bf16*)dx,
-                       N, HW, C);
-  else if (dtype == CY_F16)
-    hipLaunchKernelGGL(avgpool_bwd_kernel<f16>, dim3(grid), dim3(256), 0, st, dpooled, (f16*)dx,
-                       N, HW, C);
-  else if (dtype == CY_F32)
-    hipLaunchKernelGGL(avgpool_bwd_kernel<float>, dim3(grid), dim3(256), 0, st, dpooled,
-                       (float*)dx, N, HW, C);
-  else
-    return CY_ERR_DTYPE;
-  CY_CHECK_LAUNCH();
-  return CY_OK;
-}
-
-int cy_linear_fwd(const float* x, const float* w, const float* b, float* y, int M, int I, int O,
-                  int act, float slope, void* stream) {
-  if (!x || !w || !y || M <= 0 || I <= 0 || O <= 0) return CY_ERR_ARG;
-  hipLaunchKernelGGL(linear_fwd_kernel, dim3(cy_cdiv((long)M * O, 4)), dim3(256), 0,
-                     (hipStream_t)stream, x, w, b, y, M, I, O, act, slope);
-  CY_CHECK_LAUNCH();
-  return CY_OK;
-}
-
-static int linear_bwd_impl(const float* x, const float* w, const float* y, const float* dy, float* dx, float* dw,
-                           float* db, int M, int I, int O, int act, float slope, int accumulate, void* stream) {
-  if (!x || !w || !y || !dy || M <= 0 || I <= 0 || O <= 0) return CY_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  if (dx) {
-    hipLaunchKernelGGL(linear_bwd_dx_kernel, dim3(cy_cdiv((long)M * I, 256)), dim3(256), 0, st, w,
-                       y, dy, dx, M, I, O, act, slope);
-    CY_CHECK_LAUNCH();
-  }
-  if (dw || db) {
-    hipLaunchKernelGGL(linear_bwd_dw_kernel, dim3(cy_cdiv((long)O * I, 256)), dim3(256), 0, st, x,
-                       y, dy, dw, db, M, I, O, act, slope, accumulate);
-    CY_CHECK_LAUNCH();
-  }
-  return CY_OK;
-}
-
-int cy_linear_bwd(const float* x, const float* w, const float* y, const float* dy, float* dx,
-                  float* dw, float* db, int M, int I, int O, int act, float slope, void* stream) {
-  return linear_bwd_impl(x, w, y, dy, dx, dw, db, M, I, O, act, slope, 0, stream);
-}
-
-int cy_linear_bwd_into(const float* x, const float* w, const float* y, const float* dy, float* dx,
-                       float* dw, float* db, int M, int I, int O, int act, float slope, void* stream) {
-  return linear_bwd_impl(x, w, y, dy, dx, dw, db, M, I, O, act, slope, 1, stream);
-}
-
-int cy_proj_head_fwd(const void* feat, const float* w1, const float* b1, const float* w2, const float* b2,
-                     float* pooled, float* y1, float* y2, float* z, float* norms, int B, int HW, int C, int hid,
-                     int out, float slope, float eps, int dtype, void* stream) {
-  if (!feat || !w1 || !w2 || !pooled || !y1 || !y2 || !z || !norms || B <= 0 || HW <= 0) return CY_ERR_ARG;
-  if (C <= 0 || C > PH_MAXC || C % 8 || hid <= 0 || hid > PH_MAXH || hid % 4 || out <= 0 || out > PH_MAXH)
-    return CY_ERR_SHAPE;
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == CY_BF16)
-    hipLaunchKernelGGL(proj_head_fwd_kernel<bf16>, dim3(B), dim3(PH_NT), 0, st, (const bf16*)feat, w1, b1, w2, b2,
-                       pooled, y1, y2, z, norms, HW, C, hid, out, slope, eps);
-  else if (dtype == CY_F16)
-    hipLaunchKernelGGL(proj_head_fwd_kernel<f16>, dim3(B), dim3(PH_NT), 0, st, (const f16*)feat, w1, b1, w2, b2,
-                       pooled, y1, y2, z, norms, HW, C, hid, out, slope, eps);
-  else if (dtype == CY_F32)
-    hipLaunchKernelGGL(proj_head_fwd_kernel<float>, dim3(B), dim3(PH_NT), 0, st, (const float*)feat, w1, b1, w2, b2,
-                       pooled, y1, y2, z, norms, HW, C, hid, out, slope, eps);
-  else
-    return CY_ERR_DTYPE;
-  CY_CHECK_LAUNCH();
-  return CY_OK;
-}
-
-size_t cy_proj_head_bwd_ws_bytes(int B, int hid, int out) { return (size_t)B * (hid + out) * sizeof(float); }
-
-int cy_proj_head_bwd(const float* dz, const float* pooled, const float* y1, const float* y2, const float* norms,
-                     const float* w1, const float* w2, void* dfeat, float* dw1, float* db1, float* dw2, float* db2,
-                     int accumulate, void* ws, size_t ws_bytes, int B, int HW, int C, int hid, int out, float slope,
-                     float eps, int dtype, void* stream) {
-  if (!dz || !pooled || !y1 || !y2 || !norms || !w1 || !w2 || !ws || B <= 0 || HW <= 0) return CY_ERR_ARG;
-  if (C <= 0 || C > PH_MAXC || C % 8 || hid <= 0 || hid > PH_MAXH || hid % 4 || out <= 0 || out > PH_MAXH)
-    return CY_ERR_SHAPE;
-  if (ws_bytes < cy_proj_head_bwd_ws_bytes(B, hid, out)) return CY_ERR_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  float* dy2 = (float*)ws;
-  float* dh = dy2 + (size_t)B * out;
-  if (dtype == CY_BF16)
-    hipLaunchKernelGGL(proj_head_bwd_kernel<bf16>, dim3(B), dim3(PH_NT), 0, st, dz, y1, y2, norms, w1, w2, dy2, dh,
-                       (bf16*)dfeat, HW, C, hid, out, slope, eps);
-  else if (dtype == CY_F16)
-    hipLaunchKernelGGL(proj_head_bwd_kernel<f16>, dim3(B), dim3(PH_NT), 0, st, dz, y1, y2, norms, w1, w2, dy2, dh,
-                       (f16*)dfeat, HW, C, hid, out, slope, eps);
-  else if (dtype == CY_F32)
-    hipLaunchKernelGGL(proj_head_bwd_kernel<float>, dim3(B), dim3(PH_NT), 0, st, dz, y1, y2, norms, w1, w2, dy2, dh,
-                       (float*)dfeat, HW, C, hid, out, slope, eps);
-  else
-    return CY_ERR_DTYPE;
-  CY_CHECK_LAUNCH();
-  if (dw1 || db1 || dw2 || db2) {
-    const long total = (long)out * hid + (long)hid * C;
-    hipLaunchKernelGGL(proj_head_dw_kernel, dim3(cy_cdiv(total, 256)), dim3(256), 0, st, (const float*)dy2,
-                       (const float*)dh, y1, pooled, dw1, db1, dw2, db2, B, C, hid, out, accumulate);
-    CY_CHECK_LAUNCH();
-  }
-  return CY_OK;
-}
-
-int cy_l2norm_fwd(const float* x, float* z, float* norms, int M, int D, float eps, void* stream) {
-  if (!x || !z || !norms || M <= 0 || D <= 0) return CY_ERR_ARG;
-  hipLaunchKernelGGL(l2norm_fwd_kernel, dim3(cy_cdiv(M, 4)), dim3(256), 0, (hipStream_t)stream, x,
-                     z, norms, M, D, eps);
-  CY_CHECK_LAUNCH();
-  return CY_OK;
-}
-
-int cy_l2norm_bwd(const float* x, const float* norms, const float* dz, float* dx, int M, int D,
-                  float eps, void* stream) {
-  if (!x || !norms || !dz || !dx || M <= 0 || D <= 0) return CY_ERR_ARG;
-  hipLaunchKernelGGL(l2norm_bwd_kernel, dim3(cy_cdiv(M, 4)), dim3(256), 0, (hipStream_t)stream, x,
-                     norms, dz, dx, M, D, eps);
   CY_CHECK_LAUNCH();
   return CY_OK;
 }

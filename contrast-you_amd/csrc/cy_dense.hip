@@ -10,7 +10,7 @@
 // This file therefore computes  hpool[bin][hid] = mean_{px in bin} lrelu(W1 x[px] + b1)  directly
 // from the NHWC feature map -- the [pixels][hid] intermediate (1.6 GB f32 at 32 x 256 x 224^2) is
 // never written -- and leaves the [bins][hid] x [hid][out] product and the normalisation to the
-// small dense kernels of cy_contrast.hip.  A bin list restricts the work to the bins the loss
+// small dense kernels of cy_proj_head.hip.  A bin list restricts the work to the bins the loss
 // actually samples (5 per image in the dense InfoNCE hook); null means all N*s*s bins.
 //
 // Adaptive pooling bins (torch semantics): rows [floor(i*H/s), ceil((i+1)*H/s)), same for

@@ -2185,7 +2185,7 @@ def linear_bwd(x: Tensor, w: Tensor, y: Tensor, dy: Tensor, act: int, slope: flo
 
 
 def proj_head_ok(x: Tensor, w1: Tensor, w2: Tensor) -> bool:
-    """shapes the one-launch projection head takes (csrc/cy_contrast.hip proj_head_*)"""
+    """shapes the one-launch projection head takes (csrc/cy_proj_head.hip proj_head_*)"""
     Cc, hid, out = x.shape[1], w1.shape[0], w2.shape[0]
     return (x.is_cuda and Cc % 8 == 0 and Cc <= 512 and hid % 4 == 0 and hid <= 512 and out <= 512
             and x.dtype in (torch.bfloat16, torch.float16, torch.float32))

@@ -1,6 +1,7 @@
 """The cases tests/test_gpu_contrast_dispatch.py is parametrised with, and what tests/test_contrast_plan_coverage.py
 requires of them: the kernels of csrc/cy_contrast.hip -- the f32 MFMA GEMM, the InfoNCE / SupCon loss on its three paths
-(materialised similarity matrix, fused, exclude_other_pos) and the projection head, piecewise and in one launch.
+(materialised similarity matrix, fused, exclude_other_pos) -- and of csrc/cy_proj_head.hip -- the projection head,
+piecewise and in one launch.
 A plain module: no GPU, no torch and no library call at import.
 
 Every shape is the smallest that reaches its branch.  The column-split count of the fused kernels is never restated
@@ -27,10 +28,10 @@ TOL_16 = {"f32": TOL_GRAD, "bf16": 1.2e-2, "f16": 2e-3}   # dfeat / dx in the st
 # ---------------------------------------------------------------- restated launch geometry (coverage only)
 SC_TM = 64          # cy_contrast.hip: constexpr int SC_TM, rows / columns of a fused tile
 SC_SPLIT_BUDGET = 256   # cy_contrast.hip: sc_nsplit(), `ns = 256 / rb`, at most rb, at least 1
-GRID_CAP = 8192     # cy_contrast.hip: `constexpr int GRID_CAP = 8192;`, cy_blocks(items, 256, GRID_CAP)
+GRID_CAP = 8192     # cy_contrast.hip and cy_proj_head.hip: `constexpr int GRID_CAP = 8192;`, cy_blocks(items, 256, GRID_CAP)
 SGEMM_KSTAGE = 16   # cy_contrast.hip: sgemm_kernel stages K 16 at a time
-DP_TILE = 32        # cy_contrast.hip: supcon_fused_bwd_kernel, `nct = (D + 31) / 32` column tiles of dP, 8 at most
-PH_NT, PH_NW = 1024, 16   # cy_contrast.hip: threads and waves of the one-launch head
+DP_TILE = 32        # cy_contrast.hip: sc_bwd_sweep, `nct = (D + 31) / 32` column tiles of dP, 8 at most
+PH_NT, PH_NW = 1024, 16   # cy_proj_head.hip: threads and waves of the one-launch head
 EPC = {"f32": 4, "bf16": 8, "f16": 8}   # cy_common.h: ElemTr<T>::EPC, elements per 16-byte chunk
 
 
@@ -39,13 +40,13 @@ def row_blocks(R):
 
 
 def split_blocks(R, ns):
-    """cy_contrast.hip, supcon_fused_*_kernel: split y takes column blocks [ncb * y / ns, ncb * (y + 1) / ns)"""
+    """cy_contrast.hip, sc_block(): split y takes column blocks [ncb * y / ns, ncb * (y + 1) / ns)"""
     ncb = row_blocks(R)
     return [ncb * (y + 1) // ns - ncb * y // ns for y in range(ns)]
 
 
 def pool_slices(C, dtype):
-    """cy_contrast.hip, proj_head_fwd_kernel: `nsl = PH_NT / G < PH_NW ? PH_NT / G : PH_NW`, G = C / EPC"""
+    """cy_proj_head.hip, proj_head_fwd_kernel: `nsl = PH_NT / G < PH_NW ? PH_NT / G : PH_NW`, G = C / EPC"""
     return min(PH_NT // (C // EPC[dtype]), PH_NW)
 
 

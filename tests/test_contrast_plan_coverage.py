@@ -1,5 +1,5 @@
 """tests/test_gpu_contrast_dispatch.py claims to reach every host-side branch and every capped loop of
-csrc/cy_contrast.hip.  The claim is checked here on the CPU, against the same tables (tests/contrast_cases.py).  The
+csrc/cy_contrast.hip and csrc/cy_proj_head.hip.  The claim is checked here on the CPU, against the same tables (tests/contrast_cases.py).  The
 column-split count of the fused SupCon kernels comes from the library's own workspace query; the geometry the library
 does not export is restated in the case module next to its source line.  Each assertion names its branch: deleting a
 case fails here, by name, without a GPU.  The rejections of these entry points are asserted here too: a refused call

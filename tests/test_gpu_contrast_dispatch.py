@@ -1,7 +1,8 @@
-"""Parity of csrc/cy_contrast.hip on every branch and past every cap: cy_sgemm, the InfoNCE / SupCon loss on its three
-paths (materialised similarity matrix, fused, exclude_other_pos) with labels and with the reference's general mask --
-1 positive, 0 negative, anything else neither, never transposed -- the projector pieces (average pool, linear, L2
-normalise) and the one-launch projection head.  The cases are those of tests/contrast_cases.py;
+"""Parity of csrc/cy_contrast.hip and csrc/cy_proj_head.hip on every branch and past every cap: cy_sgemm, the InfoNCE /
+SupCon loss on its three paths (materialised similarity matrix, fused, exclude_other_pos) with labels and with the
+reference's general mask -- 1 positive, 0 negative, anything else neither, never transposed -- (cy_contrast.hip); the
+projector pieces (average pool, linear, L2 normalise) and the one-launch projection head (cy_proj_head.hip).  The cases
+are those of tests/contrast_cases.py;
 tests/test_contrast_plan_coverage.py checks on the CPU that they reach every branch and cap, and the rejections.
 
 Reference: the same operation in float64, torch on the CPU or the oracle, with autograd, on inputs already rounded to

@@ -1,7 +1,7 @@
 """Parity of the kernels behind the decoder on every dispatch branch and past every launch cap: the 1x1 head
 (cy_head1x1_fwd / _bwd / _bwd_into), softmax-KL, softmax-MSE, dice counts (csrc/cy_head_loss.hip), the cluster head in
 its softmax mode (csrc/cy_cluster_head.hip) and the projection head with the separate kernels it fuses
-(csrc/cy_contrast.hip).  The cases are those of tests/head_cases.py; tests/test_head_plan_coverage.py checks on the CPU
+(csrc/cy_proj_head.hip).  The cases are those of tests/head_cases.py; tests/test_head_plan_coverage.py checks on the CPU
 that they reach every branch and cap.
 
 Reference: torch on the CPU in float64, with autograd, on inputs already rounded to the storage type.  Tolerances, on
