@@ -78,7 +78,11 @@ class DenseProjectionHead(nn.Module):
     pool_name "adaptive_max": the projector runs on every pixel and the map is max-pooled (`_rows_max`); points are
     gathered from the pooled rows.  pool_name "identical" / "none" / None (projectors/nn.py:16-23): no pooling, one
     vector per pixel of the feature map's own grid, by one launch of the per-row projector (`PixelMLPFn`), which for
-    points computes the listed pixels only."""
+    points computes the listed pixels only.
+
+    "adaptive_avg" with more than 256 hidden units, or with channels that are no multiple of 8, is outside the fused
+    kernels' range (`_fused_hidden`) and is composed from the Linear and the average-pool kernels (`_hidden_composed`).
+    A `spatial_size` larger than the feature map raises a ValueError: the pooling kernels do not upsample."""
 
     def __init__(self, *, input_dim: int, hidden_dim=128, output_dim: int, head_type: str, normalize: bool,
                  pool_name="adaptive_avg", spatial_size=(16, 16)):
@@ -153,11 +157,38 @@ class DenseProjectionHead(nn.Module):
             rows = LinearFn.apply(rows, w1, b1, 0, 0.0)
         return L2NormFn.apply(rows) if self._normalize else rows
 
+    # cy_dense_proj_bwd: a thread of its 256 per hidden unit (CY_ERR_SHAPE above that); both entry points load the
+    # channels of a pixel 16 bytes at a time (C % 8)
+    FUSED_MAX_HIDDEN, FUSED_CHANNEL_STEP = 256, 8
+
+    def _fused_hidden(self) -> bool:
+        """whether cy_dense_proj_fwd AND cy_dense_proj_bwd take this head (decided before any launch: the forward
+        entry point alone accepts more hidden units than the backward does)"""
+        hid, cin = self._projector[0].weight.shape[:2]
+        return hid <= self.FUSED_MAX_HIDDEN and cin % self.FUSED_CHANNEL_STEP == 0
+
+    def _hidden_composed(self, features: Tensor) -> Tensor:
+        """outside the fused range (more than 256 hidden units, or channels that are no multiple of 8): the first conv
+        and the LeakyReLU on pixel rows through the Linear kernels, as `_rows_max` does, then the average pool of the
+        [N, H, W, hidden] map -> [N * sh * sw, hidden], every bin"""
+        pr = self._projector
+        x = ops.to_nhwc(features)
+        N, Cc, H, W = x.shape
+        rows = x.permute(0, 2, 3, 1).reshape(N * H * W, Cc)
+        rows = LinearFn.apply(rows, pr[0].weight.reshape(pr[0].weight.shape[0], -1), pr[0].bias, 1, 0.01)
+        fmap = rows.view(N, H, W, -1).permute(0, 3, 1, 2)  # NHWC memory
+        return AdaptiveAvgPoolFn.apply(fmap, self._spatial_size)
+
     def _rows(self, features: Tensor, bins: Optional[np.ndarray]) -> Tensor:
         """bins: host int32 [nb, 3] = (image, row, col) on the output grid, or None (the whole grid)"""
         pr = self._projector
         dev = features.device
         gh, gw = self.output_size(features)
+        if not self._unpooled and (gh > features.shape[2] or gw > features.shape[3]):
+            # (nn.AdaptiveAvgPool2d / nn.AdaptiveMaxPool2d repeat pixels there; the pooling kernels take bins of at
+            #  least one pixel that overlap by at most one)
+            raise ValueError(f"DenseProjectionHead: spatial_size {(gh, gw)} is larger than the feature map "
+                             f"{(int(features.shape[2]), int(features.shape[3]))}; the pooling kernels do not upsample")
         flat = None  # the listed cells as rows of the [N * gh * gw, .] grid
         if bins is not None:
             assert (bins >= 0).all() and (bins[:, 0] < features.shape[0]).all() and (bins[:, 1] < gh).all() \
@@ -171,9 +202,14 @@ class DenseProjectionHead(nn.Module):
             rows = self._rows_max(features)
             return rows if flat is None else GatherRowsFn.apply(rows, flat)
         if self._head_type == "mlp":
-            hp = DenseProjHiddenFn.apply(features, pr[0].weight, pr[0].bias, self._spatial_size,
-                                         ops._bins_tensor(bins, dev))
             w2 = pr[2].weight.reshape(pr[2].weight.shape[0], -1)
+            if self._fused_hidden():
+                hp = DenseProjHiddenFn.apply(features, pr[0].weight, pr[0].bias, self._spatial_size,
+                                             ops._bins_tensor(bins, dev))
+            else:
+                hp = self._hidden_composed(features)
+                if flat is not None:
+                    hp = GatherRowsFn.apply(hp, flat)
             rows = LinearFn.apply(hp, w2, pr[2].bias, 0, 0.0)
         else:
             pooled = AdaptiveAvgPoolFn.apply(features, self._spatial_size)

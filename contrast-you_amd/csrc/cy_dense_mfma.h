@@ -36,6 +36,7 @@
 //     of an MFMA may be any permutation as long as A and B agree: lane-half h, slot i <-> pixel row
 //     16s + 4h + i (+4 for i >= 4)); A = x^T comes from a per-wave LDS copy of the 32 x 32 pixel block through
 //     ds_read_b64_tr_b16, whose four row addresses per 16-lane group are free to follow that permutation.
+//     bf16: g enters this product as two 16-bit terms (rounded value + remainder), see the kernel.
 //   dx^T[c][p] = sum_o W1[o][c] g[p][o]: contraction over the lane index of g -- g goes through a per-wave LDS
 //     tile [o][p] (8-byte writes of four consecutive pixels) and comes back as the B operand by transposed reads;
 //     A = W1^T fragments live in registers.  The output leaves lane p with 16 channels of ITS pixel: NHWC stores.
@@ -370,6 +371,7 @@ __global__ void __launch_bounds__(256, 2)
                               float slope, int cbs) {
   using M = Mma<T>;
   constexpr int HB = 4;
+  constexpr bool SPLIT = sizeof(T) == 2 && !__is_same(T, f16);  // bf16: g goes into the dW1 product as two 16-bit terms
   __shared__ __attribute__((aligned(16))) float red[2 * DPM_PART];  // (the x tiles alias its head)
   __shared__ __attribute__((aligned(16))) unsigned char sw1[CB * 256 * 64];
   const int lane = threadIdx.x & 63;
@@ -432,6 +434,11 @@ __global__ void __launch_bounds__(256, 2)
     float dneg[HB];
 #pragma unroll
     for (int hb = 0; hb < HB; ++hb) dneg[hb] = slope * dpos[hb];
+    // bf16 only (SPLIT): all pixels of a bin carry the same g, so its rounding error (up to 2^-8) is the same in
+    // every term of dW1 and does not average out -- a whole row of dW1 was off by 3e-3 with one bin per image.  What
+    // the 8-bit mantissa drops from the two values g takes goes through a second pair of MFMAs (what that drops in
+    // turn is 2^-16); the two remainders are formed per block, not held across the job: 254 registers at C = 64.
+    // f16 (2^-11) keeps the single product.
 
     auto block = [&](const u32x4 (&f)[CB][2]) {
       // (the x tile of the second product: the selected channel block's 32 channels)
@@ -471,6 +478,15 @@ __global__ void __launch_bounds__(256, 2)
           const DpFrag<T> g0 = dpm_frag<T>(Chunk<T>::pack(g)), g1 = dpm_frag<T>(Chunk<T>::pack(g + 8));
           M::mma(xt[0], g0, dw[hb]);
           M::mma(xt[1], g1, dw[hb]);
+          if constexpr (SPLIT) {  // (a pass of its own over the accumulators; both terms from one compare measured the same)
+            __builtin_amdgcn_sched_barrier(0);
+            const float lpos = dpos[hb] - round_through<T>(dpos[hb]), lneg = dneg[hb] - round_through<T>(dneg[hb]);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) g[i] = acc[k][i] > nbias[hb] ? lpos : lneg;
+            const DpFrag<T> l0 = dpm_frag<T>(Chunk<T>::pack(g)), l1 = dpm_frag<T>(Chunk<T>::pack(g + 8));
+            M::mma(xt[0], l0, dw[hb]);
+            M::mma(xt[1], l1, dw[hb]);
+          }
         }
         __builtin_amdgcn_sched_barrier(0);
       }
