@@ -90,35 +90,88 @@ __global__ void __launch_bounds__(256)
 }
 
 // ---------------------------------------------------------------- joint forward
-// part[blockIdx.y = displacement][blockIdx.x][k*k]
-__global__ void __launch_bounds__(256)
-    joint_fwd_kernel(const float* __restrict__ x1, const float* __restrict__ x2,
-                     float* __restrict__ part, int N, int H, int W, int k, int pad) {
+// Both forward forms work on a WINDOW of the maps, origin (h0, w0) and extent eh x ew, and are written once, as a body:
+//   J[q][d][i][j] = sum_n sum_{(h,w) in q, (h+du,w+dv) in q} x1[n][h+du][w+dv][i] * x2[n][h][w][j]
+// A displaced read that leaves the window is zero.  The whole image is the window {0, 0, H, W} with q = 0
+// (joint_fwd_kernel, joint_fwd_multi_kernel); the patches of the patch-wise loss are P windows of one extent, q the
+// patch (joint_patch_fwd1_kernel, joint_patch_fwd_kernel further down).  A block's sums go to
+// part[q][d][blockIdx.x][k*k]; where the caller gives J (its one block along x holds the whole sum) they go straight to
+// J[q][d][k*k], times scale and rounded as joint_reduce_kernel rounds.
+struct joint_window {
+  int h0, w0, eh, ew;
+};
+
+// thread -> (pixel slice sl of nsl, 4x4 tile (ti, tj) of the kp x kp joint); threads past the last slice idle
+struct joint_lanes {
+  int kp, nsl, sl, ti, tj;
+  bool active;
+};
+__device__ __forceinline__ joint_lanes joint_lanes_of(int k) {
+  joint_lanes L;
+  L.kp = (k + 3) & ~3;
+  const int k4 = L.kp >> 2, tps = k4 * k4;  // threads per pixel slice
+  L.nsl = 256 / tps;                        // slices (>= 1 because k <= 64)
+  L.sl = (int)threadIdx.x / tps;
+  const int tt = (int)threadIdx.x - L.sl * tps;
+  L.ti = tt / k4;
+  L.tj = tt - L.ti * k4;
+  L.active = L.sl < L.nsl;
+  return L;
+}
+
+// One joint of the block leaves the registers: the slices meet in red[nsl][kp*kp] and are summed in slice order.
+__device__ __forceinline__ void joint_write_out(const float (&acc)[4][4], float* red, const joint_lanes& L,
+                                                float* __restrict__ part, float* __restrict__ J, double scale,
+                                                size_t qd, int k) {
+  const int kp = L.kp;
+  __syncthreads();
+  if (L.active) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) red[L.sl * kp * kp + (4 * L.ti + i) * kp + 4 * L.tj + j] = acc[i][j];
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < k * k; e += 256) {
+    const int i = e / k, j = e - i * k;
+    float s = 0.f;
+    for (int u = 0; u < L.nsl; ++u) s += red[u * kp * kp + i * kp + j];
+    if (J)
+      J[qd * (k * k) + e] = (float)((double)s * scale);
+    else
+      part[(qd * gridDim.x + blockIdx.x) * (k * k) + e] = s;
+  }
+}
+
+// The per-displacement form: one displacement per block (blockIdx.y), 64-pixel tiles of the window's N*eh*ew pixels
+// split evenly over gridDim.x, the displaced read bounds-tested against the window.
+// WHOLE: the window is the whole map, so a tile is one contiguous span of both maps and, with pad == 0 and k % 4 == 0
+// (the padding-0 segmentation joint), is staged in 16-byte copies.
+template <bool WHOLE>
+__device__ __forceinline__ void joint_tile_body(const float* __restrict__ x1, const float* __restrict__ x2,
+                                                float* __restrict__ part, float* __restrict__ J, double scale, int N,
+                                                int H, int W, int k, int pad, const joint_window win, int q) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int kp = (k + 3) & ~3, k4 = kp >> 2;
-  const int tps = k4 * k4;           // threads per pixel slice
-  const int nsl = 256 / tps;         // slices (>= 1 because k <= 64)
-  float* xs1 = sm;                   // [J_P][kp]
-  float* xs2 = sm + J_P * kp;        // [J_P][kp]
-  float* red = sm + 2 * J_P * kp;    // [nsl][kp*kp]
+  const joint_lanes L = joint_lanes_of(k);
+  const int kp = L.kp;
+  float* xs1 = sm;                 // [J_P][kp]
+  float* xs2 = sm + J_P * kp;      // [J_P][kp]
+  float* red = sm + 2 * J_P * kp;  // [nsl][kp*kp]
   const int tid = threadIdx.x;
   const int T = 2 * pad + 1;
   const int du = (int)blockIdx.y / T - pad, dv = (int)blockIdx.y % T - pad;
-  const int sl = tid / tps, tt = tid - sl * tps;
-  const int ti = tt / k4, tj = tt - ti * k4;
-  const bool active = sl < nsl;
   float acc[4][4];
 #pragma unroll
   for (int a = 0; a < 4; ++a)
 #pragma unroll
     for (int b = 0; b < 4; ++b) acc[a][b] = 0.f;
-  const long npix = (long)N * H * W;
+  const long npix = (long)N * win.eh * win.ew;
   const long per = ((npix + gridDim.x - 1) / gridDim.x + J_P - 1) / J_P * J_P;
   const long p0 = (long)blockIdx.x * per;
   const long p1 = p0 + per < npix ? p0 + per : npix;
   for (long pt = p0; pt < p1; pt += J_P) {
     __syncthreads();
-    if (pad == 0 && kp == k) {  // the tile is one contiguous span of both maps: 16-byte copies
+    if (WHOLE && pad == 0 && kp == k) {
       const long lim = (p1 - pt) * k;  // floats of this tile that exist
       for (int e4 = tid; e4 < J_P * k / 4; e4 += 256) {
         f32x4 a = {0.f, 0.f, 0.f, 0.f}, b = {0.f, 0.f, 0.f, 0.f};
@@ -129,31 +182,30 @@ __global__ void __launch_bounds__(256)
         *reinterpret_cast<f32x4*>(xs1 + 4 * e4) = a;
         *reinterpret_cast<f32x4*>(xs2 + 4 * e4) = b;
       }
-    } else
-    for (int e = tid; e < J_P * kp; e += 256) {
-      const int p = e / kp, c = e - p * kp;
-      const long pix = pt + p;
-      float a = 0.f, b = 0.f;
-      if (pix < p1 && c < k) {
-        b = x2[pix * k + c];
-        if (pad == 0) {
-          a = x1[pix * k + c];
-        } else {
-          const int w = (int)(pix % W);
-          const long t = pix / W;
-          const int h = (int)(t % H);
-          const int hh = h + du, ww = w + dv;
-          if (hh >= 0 && hh < H && ww >= 0 && ww < W) a = x1[(pix + (long)du * W + dv) * k + c];
+    } else {
+      for (int e = tid; e < J_P * kp; e += 256) {
+        const int p = e / kp, c = e - p * kp;
+        const long pp = pt + p;
+        float a = 0.f, b = 0.f;
+        if (pp < p1 && c < k) {
+          const int wl = (int)(pp % win.ew);
+          const long t = pp / win.ew;
+          const int hl = (int)(t % win.eh);
+          const long n = t / win.eh;
+          b = x2[((n * H + win.h0 + hl) * W + win.w0 + wl) * k + c];
+          const int hh = hl + du, ww = wl + dv;
+          if (hh >= 0 && hh < win.eh && ww >= 0 && ww < win.ew)
+            a = x1[((n * H + win.h0 + hh) * W + win.w0 + ww) * k + c];
         }
+        xs1[e] = a;
+        xs2[e] = b;
       }
-      xs1[e] = a;
-      xs2[e] = b;
     }
     __syncthreads();
-    if (active) {
-      for (int p = sl; p < J_P; p += nsl) {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(xs1 + p * kp + 4 * ti);
-        const f32x4 b = *reinterpret_cast<const f32x4*>(xs2 + p * kp + 4 * tj);
+    if (L.active) {
+      for (int p = L.sl; p < J_P; p += L.nsl) {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(xs1 + p * kp + 4 * L.ti);
+        const f32x4 b = *reinterpret_cast<const f32x4*>(xs2 + p * kp + 4 * L.tj);
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -161,49 +213,42 @@ __global__ void __launch_bounds__(256)
       }
     }
   }
-  __syncthreads();
-  if (active) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) red[sl * kp * kp + (4 * ti + i) * kp + 4 * tj + j] = acc[i][j];
-  }
-  __syncthreads();
-  float* dst = part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * (k * k);
-  for (int e = tid; e < k * k; e += 256) {
-    const int i = e / k, j = e - i * k;
-    float s = 0.f;
-    for (int q = 0; q < nsl; ++q) s += red[q * kp * kp + i * kp + j];
-    dst[e] = s;
-  }
+  joint_write_out(acc, red, L, part, J, scale, (size_t)q * T * T + blockIdx.y, k);
 }
 
-// Displaced joints (padding > 0) in ONE pass over the maps: the kernel above is launched per displacement and reads
-// both maps (2p+1)^2 times (9 displacements: 266 GB/s of algorithmic traffic).  Here a block stages R image rows of
-// x2 and the R + 2p rows of x1 around them, with p zero columns on both sides (so a displaced read is an address
-// shift, no bounds test), and every thread keeps one 4x4 tile of the joint per displacement: up to JM_D = 9 tiles,
-// 144 accumulators; (2p+1)^2 > 9 runs in groups of nine (blockIdx.y).  Same partial layout and fixed-order
-// reduction as above.
+// part[blockIdx.y = displacement][blockIdx.x][k*k]
+__global__ void __launch_bounds__(256)
+    joint_fwd_kernel(const float* __restrict__ x1, const float* __restrict__ x2,
+                     float* __restrict__ part, int N, int H, int W, int k, int pad) {
+  joint_tile_body<true>(x1, x2, part, nullptr, 1.0, N, H, W, k, pad, joint_window{0, 0, H, W}, 0);
+}
+
+// The staged form, displaced joints (padding > 0) in ONE pass over the maps: the form above runs per displacement and
+// reads both maps (2p+1)^2 times (9 displacements: 266 GB/s of algorithmic traffic).  Here a block owns a group of up to
+// JM_D = 9 displacements (blockIdx.y) and walks the (image, tile of R window rows) pairs with stride gridDim.x.  It
+// stages the R rows of x2 and the R + 2p rows of x1 around them, with p zero columns on both sides and rows outside the
+// window zero (so a displaced read is an address shift, no bounds test), and every thread keeps one 4x4 tile of the
+// joint per displacement: up to 144 accumulators.  The reduction buffer lies over the tiles once they are done (72 KB at
+// W = 224, k = 20: two workgroups per CU, one stages while the other computes).
+// SPAN: the window is as wide as the map, so its R rows of x2 are one span of memory as they are of the staged tile.
 constexpr int JM_D = 9;
 
-__global__ void __launch_bounds__(256, 2)
-    joint_fwd_multi_kernel(const float* __restrict__ x1, const float* __restrict__ x2, float* __restrict__ part,
-                           int N, int H, int W, int k, int pad, int R) {
+template <bool SPAN>
+__device__ __forceinline__ void joint_staged_body(const float* __restrict__ x1, const float* __restrict__ x2,
+                                                  float* __restrict__ part, float* __restrict__ J, double scale, int N,
+                                                  int H, int W, int k, int pad, int R, const joint_window win, int q) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int kp = (k + 3) & ~3, k4 = kp >> 2;
-  const int tps = k4 * k4, nsl = 256 / tps;
-  const int Wp = W + 2 * pad, Rp = R + 2 * pad;
-  float* xs1 = sm;                       // [Rp][Wp][kp]
-  float* xs2 = xs1 + (size_t)Rp * Wp * kp;  // [R][W][kp]
-  float* red = sm;                          // [nsl][kp*kp]: over the tiles once they are done (72 KB at W = 224,
-                                            // k = 20: two workgroups per CU, one stages while the other computes)
+  const joint_lanes L = joint_lanes_of(k);
+  const int kp = L.kp, nsl = L.nsl;
+  const int h0 = win.h0, w0 = win.w0, eh = win.eh, ew = win.ew;
+  const int Wp = ew + 2 * pad, Rp = R + 2 * pad;
+  float* xs1 = sm;                          // [Rp][Wp][kp]
+  float* xs2 = xs1 + (size_t)Rp * Wp * kp;  // [R][ew][kp]
+  float* red = sm;                          // [nsl][kp*kp]
   const int tid = threadIdx.x;
-  const int T = 2 * pad + 1;
+  const int T = 2 * pad + 1, TT = T * T;
   const int d0 = (int)blockIdx.y * JM_D;
-  const int nd = T * T - d0 < JM_D ? T * T - d0 : JM_D;
-  const int sl = tid / tps, tt = tid - sl * tps;
-  const int ti = tt / k4, tj = tt - ti * k4;
-  const bool active = sl < nsl;
+  const int nd = TT - d0 < JM_D ? TT - d0 : JM_D;
   float acc[JM_D][4][4];
 #pragma unroll
   for (int d = 0; d < JM_D; ++d)
@@ -217,26 +262,26 @@ __global__ void __launch_bounds__(256, 2)
     const int dd = d0 + (d < nd ? d : 0);
     doff[d] = ((dd / T - pad) * Wp + (dd % T - pad)) * kp;
   }
-  const int tiles_h = (H + R - 1) / R;
+  const int tiles_h = (eh + R - 1) / R;
   const int ntile = N * tiles_h;
   if (kp == k)  // the zero columns left and right of every staged x1 row
     for (int e = tid; e < Rp * 2 * pad * kp; e += 256) {
-      const int r = e / (2 * pad * kp), q = e - r * (2 * pad * kp);
-      const int col = q / kp < pad ? q / kp : W + q / kp;  // 0..pad-1 | W+pad..W+2pad-1
-      xs1[(r * Wp + col) * kp + q % kp] = 0.f;
+      const int r = e / (2 * pad * kp), c = e - r * (2 * pad * kp);
+      const int col = c / kp < pad ? c / kp : ew + c / kp;  // 0..pad-1 | ew+pad..ew+2pad-1
+      xs1[(r * Wp + col) * kp + c % kp] = 0.f;
     }
   for (int t = blockIdx.x; t < ntile; t += gridDim.x) {
-    const int n = t / tiles_h, h0 = (t - n * tiles_h) * R;
-    const int rows = H - h0 < R ? H - h0 : R;
+    const int n = t / tiles_h, r0 = (t - n * tiles_h) * R;
+    const int rows = eh - r0 < R ? eh - r0 : R;
     __syncthreads();
     if (kp == k) {
-      // an image row is one contiguous span of W*k floats in memory and in the staged tile: 16-byte copies, no
-      // index arithmetic (the pad columns were zeroed once, rows outside the image are zeroed here)
-      const int row4 = W * k / 4;
+      // a window row is one contiguous, 16-byte aligned span of ew*k floats in memory and in the staged tile: 16-byte
+      // copies (the pad columns were zeroed once, rows outside the window are zeroed here)
+      const int row4 = ew * k / 4;
       for (int r = 0; r < Rp; ++r) {
-        const int hh = h0 - pad + r;
-        const bool ok = r < rows + 2 * pad && hh >= 0 && hh < H;
-        const float* src = x1 + ((long)n * H + (ok ? hh : 0)) * W * k;
+        const int pr = r0 - pad + r;
+        const bool ok = r < rows + 2 * pad && pr >= 0 && pr < eh;
+        const float* src = x1 + (((long)n * H + h0 + (ok ? pr : 0)) * W + w0) * k;
         float* dst = xs1 + (r * Wp + pad) * kp;
         for (int e4 = tid; e4 < row4; e4 += 256) {
           f32x4 v = {0.f, 0.f, 0.f, 0.f};
@@ -244,37 +289,42 @@ __global__ void __launch_bounds__(256, 2)
           *reinterpret_cast<f32x4*>(dst + 4 * e4) = v;
         }
       }
-      const float* src2 = x2 + ((long)n * H + h0) * W * k;
+      const float* src2 = x2 + (((long)n * H + h0 + r0) * W + w0) * k;  // the tile's first row of x2
       for (int e4 = tid; e4 < R * row4; e4 += 256) {
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (e4 < rows * row4) v = *reinterpret_cast<const f32x4*>(src2 + 4 * e4);
+        if (SPAN) {  // the rows follow each other in memory as they do in the tile
+          if (e4 < rows * row4) v = *reinterpret_cast<const f32x4*>(src2 + 4 * e4);
+        } else {
+          const int r = e4 / row4, c4 = e4 - r * row4;
+          if (r < rows) v = *reinterpret_cast<const f32x4*>(src2 + (long)r * W * k + 4 * c4);
+        }
         *reinterpret_cast<f32x4*>(xs2 + 4 * e4) = v;
       }
     } else {
       for (int e = tid; e < Rp * Wp * kp; e += 256) {
         const int c = e % kp;
-        const int q = e / kp;
-        const int cw = q % Wp, r = q / Wp;
-        const int hh = h0 - pad + r, ww = cw - pad;
+        const int p = e / kp;
+        const int cw = p % Wp, r = p / Wp;
+        const int pr = r0 - pad + r, pc = cw - pad;
         float v = 0.f;
-        if (c < k && r < rows + 2 * pad && hh >= 0 && hh < H && ww >= 0 && ww < W)
-          v = x1[(((long)n * H + hh) * W + ww) * k + c];
+        if (c < k && r < rows + 2 * pad && pr >= 0 && pr < eh && pc >= 0 && pc < ew)
+          v = x1[(((long)n * H + h0 + pr) * W + w0 + pc) * k + c];
         xs1[e] = v;
       }
-      for (int e = tid; e < R * W * kp; e += 256) {
+      for (int e = tid; e < R * ew * kp; e += 256) {
         const int c = e % kp;
-        const int q = e / kp;
-        const int w = q % W, r = q / W;
-        xs2[e] = (c < k && r < rows) ? x2[(((long)n * H + h0 + r) * W + w) * k + c] : 0.f;
+        const int p = e / kp;
+        const int w = p % ew, r = p / ew;
+        xs2[e] = (c < k && r < rows) ? x2[(((long)n * H + h0 + r0 + r) * W + w0 + w) * k + c] : 0.f;
       }
     }
     __syncthreads();
-    if (active) {
-      int r = 0, w = sl;
-      while (w >= W) w -= W, ++r;
+    if (L.active) {
+      int r = 0, w = L.sl;
+      while (w >= ew) w -= ew, ++r;
       for (; r < rows;) {
-        const f32x4 b = *reinterpret_cast<const f32x4*>(xs2 + (r * W + w) * kp + 4 * tj);
-        const float* a0 = xs1 + ((r + pad) * Wp + (w + pad)) * kp + 4 * ti;
+        const f32x4 b = *reinterpret_cast<const f32x4*>(xs2 + (r * ew + w) * kp + 4 * L.tj);
+        const float* a0 = xs1 + ((r + pad) * Wp + (w + pad)) * kp + 4 * L.ti;
 #pragma unroll
         for (int d = 0; d < JM_D; ++d) {
           if (d < nd) {  // wave-uniform
@@ -286,30 +336,24 @@ __global__ void __launch_bounds__(256, 2)
           }
         }
         w += nsl;
-        while (w >= W) w -= W, ++r;
+        while (w >= ew) w -= ew, ++r;
       }
     }
   }
 #pragma unroll
   for (int d = 0; d < JM_D; ++d) {  // (no early exit: the accumulators must stay statically indexed = in registers)
     if (d >= nd) continue;          // block-uniform
-    __syncthreads();
-    if (active) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) red[sl * kp * kp + (4 * ti + i) * kp + 4 * tj + j] = acc[d][i][j];
-    }
-    __syncthreads();
-    float* dst = part + ((size_t)(d0 + d) * gridDim.x + blockIdx.x) * (k * k);
-    for (int e = tid; e < k * k; e += 256) {
-      const int i = e / k, j = e - i * k;
-      float s = 0.f;
-      for (int q = 0; q < nsl; ++q) s += red[q * kp * kp + i * kp + j];
-      dst[e] = s;
-    }
+    joint_write_out(acc[d], red, L, part, J, scale, (size_t)q * TT + d0 + d, k);
   }
 }
+
+// part[displacement][blockIdx.x][k*k]
+__global__ void __launch_bounds__(256, 2)
+    joint_fwd_multi_kernel(const float* __restrict__ x1, const float* __restrict__ x2, float* __restrict__ part,
+                           int N, int H, int W, int k, int pad, int R) {
+  joint_staged_body<true>(x1, x2, part, nullptr, 1.0, N, H, W, k, pad, R, joint_window{0, 0, H, W}, 0);
+}
+
 
 // J[e] = scale * sum_b part[d][b][r]: 4 elements per block, 64 slices of the block partials each,
 // fixed slice order (deterministic)
@@ -339,75 +383,74 @@ __global__ void __launch_bounds__(256)
 // dJ is staged in LDS dchunk displacements at a time (the launch plan: as many as fit 64 KB).  With one chunk, which is
 // every padding-0 launch and padding 1 up to k = 42, it is staged once per block; otherwise once per chunk and trip of
 // the grid-stride loop, whose trip count is the same for every thread of a block (the barriers are block-uniform).
+
+// The product both adjoints (this one and the patch-wise gather) are made of, for one displacement: m = its k x k dJ,
+// o = the other map's pixel, c = the thread's first output channel.
+//   which = 0: s[u] += sum_j m[c+u][j] * o[j]      which = 1: s[u] += sum_i m[i][c+u] * o[i]
+// V = 4 (k % 4 == 0): 16-byte reads of m and o; V = 1: scalar.  s: the thread's V sums.
+template <int V>
+__device__ __forceinline__ void joint_bwd_dot(float* s, const float* m, const float* o, int k, int c, int which) {
+  if (V == 4) {
+    for (int j4 = 0; j4 < k / 4; ++j4) {
+      const f32x4 ov = *reinterpret_cast<const f32x4*>(o + 4 * j4);
+      if (which) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          const f32x4 mv = *reinterpret_cast<const f32x4*>(m + (4 * j4 + t) * k + c);
+#pragma unroll
+          for (int u = 0; u < V; ++u) s[u] = fmaf(mv[u], ov[t], s[u]);
+        }
+      } else {
+#pragma unroll
+        for (int u = 0; u < V; ++u) {
+          const f32x4 mv = *reinterpret_cast<const f32x4*>(m + (c + u) * k + 4 * j4);
+#pragma unroll
+          for (int t = 0; t < 4; ++t) s[u] = fmaf(mv[t], ov[t], s[u]);
+        }
+      }
+    }
+  } else if (which) {
+    for (int i = 0; i < k; ++i) s[0] = fmaf(m[i * k + c], o[i], s[0]);
+  } else {
+    for (int j = 0; j < k; ++j) s[0] = fmaf(m[c * k + j], o[j], s[0]);
+  }
+}
+
+// dx[pix][c..c+V) = g * s, as one 16-byte store for V = 4
+template <int V>
+__device__ __forceinline__ void joint_bwd_store(float* __restrict__ dx, long at, const float (&s)[V], float g) {
+  if (V == 4) {
+    f32x4 r = {g * s[0], g * s[V > 1 ? 1 : 0], g * s[V > 2 ? 2 : 0], g * s[V > 3 ? 3 : 0]};
+    *reinterpret_cast<f32x4*>(dx + at) = r;
+  } else {
+    dx[at] = g * s[0];
+  }
+}
+
+template <int V>  // V = 4: one thread per (pixel, 4 channels), k % 4 == 0; V = 1: one thread per (pixel, channel)
 __global__ void __launch_bounds__(256)
     joint_bwd_kernel(const float* __restrict__ other, const float* __restrict__ dJ,
                      const float* __restrict__ gscale, float* __restrict__ dx, int N, int H, int W,
                      int k, int pad, float scale, int which, int dchunk) {
-  extern __shared__ float sdj[];  // [min(dchunk, T*T)][k][k]
-  const int T = 2 * pad + 1, TT = T * T, kk = k * k;
-  const bool once = dchunk >= TT;
-  if (once) {
-    for (int e = threadIdx.x; e < TT * kk; e += 256) sdj[e] = dJ[e];
-    __syncthreads();
-  }
-  const float g = gscale[0] * scale;
-  const long total = (long)N * H * W * k;
-  for (long base = blockIdx.x * 256L; base < total; base += (long)gridDim.x * 256L) {
-    const long e = base + threadIdx.x;
-    const bool live = e < total;
-    const int c = (int)(e % k);
-    const long pix = e / k;
-    const int w = (int)(pix % W);
-    const int h = (int)((pix / W) % H);
-    float s = 0.f;
-    for (int d0 = 0; d0 < TT; d0 += dchunk) {
-      const int d1 = d0 + dchunk < TT ? d0 + dchunk : TT;
-      if (!once) {
-        __syncthreads();
-        for (int q = threadIdx.x; q < (d1 - d0) * kk; q += 256) sdj[q] = dJ[(size_t)d0 * kk + q];
-        __syncthreads();
-      }
-      if (!live) continue;
-      for (int d = d0; d < d1; ++d) {
-        const int du = d / T - pad, dv = d % T - pad;
-        const int hh = which ? h + du : h - du, ww = which ? w + dv : w - dv;
-        if (hh < 0 || hh >= H || ww < 0 || ww >= W) continue;
-        const long q = which ? pix + (long)du * W + dv : pix - (long)du * W - dv;
-        const float* o = other + q * k;
-        const float* m = sdj + (d - d0) * kk;
-        if (which) {
-          for (int i = 0; i < k; ++i) s = fmaf(m[i * k + c], o[i], s);
-        } else {
-          for (int j = 0; j < k; ++j) s = fmaf(m[c * k + j], o[j], s);
-        }
-      }
-    }
-    if (live) dx[e] = g * s;
-  }
-}
-
-// k % 4 == 0: one thread per (pixel, 4 output channels), 16-byte global and LDS accesses
-__global__ void __launch_bounds__(256)
-    joint_bwd4_kernel(const float* __restrict__ other, const float* __restrict__ dJ,
-                      const float* __restrict__ gscale, float* __restrict__ dx, int N, int H, int W,
-                      int k, int pad, float scale, int which, int dchunk) {
   extern __shared__ __attribute__((aligned(16))) float sdj[];  // [min(dchunk, T*T)][k][k]
-  const int T = 2 * pad + 1, TT = T * T, k4 = k >> 2, kk = k * k;
+  const int T = 2 * pad + 1, TT = T * T, kv = k / V, kk = k * k;
   const bool once = dchunk >= TT;
   if (once) {
     for (int e = threadIdx.x; e < TT * kk; e += 256) sdj[e] = dJ[e];
     __syncthreads();
   }
   const float g = gscale[0] * scale;
-  const long total = (long)N * H * W * k4;
+  const long total = (long)N * H * W * kv;
   for (long base = blockIdx.x * 256L; base < total; base += (long)gridDim.x * 256L) {
     const long e = base + threadIdx.x;
     const bool live = e < total;
-    const int c = (int)(e % k4) * 4;
-    const long pix = e / k4;
+    const int c = (int)(e % kv) * V;
+    const long pix = e / kv;
     const int w = (int)(pix % W);
     const int h = (int)((pix / W) % H);
-    f32x4 s = {0.f, 0.f, 0.f, 0.f};
+    float s[V];
+#pragma unroll
+    for (int u = 0; u < V; ++u) s[u] = 0.f;
     for (int d0 = 0; d0 < TT; d0 += dchunk) {
       const int d1 = d0 + dchunk < TT ? d0 + dchunk : TT;
       if (!once) {
@@ -421,32 +464,10 @@ __global__ void __launch_bounds__(256)
         const int hh = which ? h + du : h - du, ww = which ? w + dv : w - dv;
         if (hh < 0 || hh >= H || ww < 0 || ww >= W) continue;
         const long q = which ? pix + (long)du * W + dv : pix - (long)du * W - dv;
-        const float* o = other + q * k;
-        const float* m = sdj + (d - d0) * kk;
-        for (int j4 = 0; j4 < k4; ++j4) {
-          const f32x4 ov = *reinterpret_cast<const f32x4*>(o + 4 * j4);
-          if (which) {  // s[c..c+3] += sum_i M[i][c..c+3] * o[i]
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-              const f32x4 mv = *reinterpret_cast<const f32x4*>(m + (4 * j4 + t) * k + c);
-#pragma unroll
-              for (int u = 0; u < 4; ++u) s[u] = fmaf(mv[u], ov[t], s[u]);
-            }
-          } else {  // s[c+u] += sum_j M[c+u][j] * o[j]
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-              const f32x4 mv = *reinterpret_cast<const f32x4*>(m + (c + u) * k + 4 * j4);
-#pragma unroll
-              for (int t = 0; t < 4; ++t) s[u] = fmaf(mv[t], ov[t], s[u]);
-            }
-          }
-        }
+        joint_bwd_dot<V>(s, sdj + (d - d0) * kk, other + q * k, k, c, which);
       }
     }
-    if (live) {
-      f32x4 r = {g * s[0], g * s[1], g * s[2], g * s[3]};
-      *reinterpret_cast<f32x4*>(dx + pix * k + c) = r;
-    }
+    if (live) joint_bwd_store<V>(dx, pix * k + c, s, g);
   }
 }
 
@@ -578,8 +599,8 @@ constexpr int JOINT_GRID_CAP = 2048;  // 256 CUs x 8
 // IIDSegmentationSmallPathLoss / patch_generator (contrastyou/losses/discreteMI.py:173-198,264-272): the loss of
 // IIDSegmentationLoss on every square patch of the maps (side `patch`, step patch / 2), averaged.  Patch origins along an
 // axis of length L: 0, s, 2s, ... below L - p, then max(L - p, 0); every patch is clipped to the map, so all patches of
-// one call have the same extents eh x ew.  The zero padding of a displaced read is at the PATCH border.
-//   J[q][d][i][j] = sum_n sum_{(h,w) in q, (h+du,w+dv) in q} x1[n][h+du][w+dv][i] * x2[n][h][w][j]
+// one call have the same extents eh x ew.  A patch is a window of the forward bodies above: the zero padding of a
+// displaced read is at the PATCH border.
 __host__ __device__ inline int patch_count(int L, int p) {
   const int s = p / 2;
   return L > p ? (L - p + s - 1) / s + 1 : 1;
@@ -588,216 +609,29 @@ __host__ __device__ inline int patch_origin(int i, int n, int L, int p) {
   return i < n - 1 ? i * (p / 2) : (L > p ? L - p : 0);
 }
 
-// joint_fwd_multi_kernel on a patch: a block owns (patch blockIdx.z, group of <= 9 displacements blockIdx.y) and walks
-// the (image, tile of R patch rows) pairs with stride gridDim.x.  It stages the R rows of x2 and the R + 2 pad rows of x1
-// around them with pad zero columns on both sides; rows and columns outside the patch are zero.  With gridDim.x == 1 the
-// block's sums are the joint and go straight to J (times scale, rounded as joint_reduce_kernel rounds); otherwise to
-// part[q][d][blockIdx.x][k*k].
+__device__ __forceinline__ joint_window patch_window(int q, int H, int W, int patch, int nph, int npw, int eh, int ew) {
+  return joint_window{patch_origin(q / npw, nph, H, patch), patch_origin(q % npw, npw, W, patch), eh, ew};
+}
+
+// The two forward bodies on the window of patch blockIdx.z.  With gridDim.x == 1 the block's sums are the joint and go
+// straight to J; otherwise to part[q][d][blockIdx.x][k*k].  The staged form:
 __global__ void __launch_bounds__(256, 2)
     joint_patch_fwd_kernel(const float* __restrict__ x1, const float* __restrict__ x2, float* __restrict__ part,
                            float* __restrict__ J, int N, int H, int W, int k, int pad, int R, int patch, int nph,
                            int npw, int eh, int ew, double scale) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int kp = (k + 3) & ~3, k4 = kp >> 2;
-  const int tps = k4 * k4, nsl = 256 / tps;
-  const int Wp = ew + 2 * pad, Rp = R + 2 * pad;
-  float* xs1 = sm;                          // [Rp][Wp][kp]
-  float* xs2 = xs1 + (size_t)Rp * Wp * kp;  // [R][ew][kp]
-  float* red = sm;                          // [nsl][kp*kp]: over the tiles once they are done
-  const int tid = threadIdx.x;
-  const int T = 2 * pad + 1, TT = T * T;
   const int q = (int)blockIdx.z;
-  const int h0 = patch_origin(q / npw, nph, H, patch), w0 = patch_origin(q % npw, npw, W, patch);
-  const int d0 = (int)blockIdx.y * JM_D;
-  const int nd = TT - d0 < JM_D ? TT - d0 : JM_D;
-  const int sl = tid / tps, tt = tid - sl * tps;
-  const int ti = tt / k4, tj = tt - ti * k4;
-  const bool active = sl < nsl;
-  float acc[JM_D][4][4];
-#pragma unroll
-  for (int d = 0; d < JM_D; ++d)
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int b = 0; b < 4; ++b) acc[d][a][b] = 0.f;
-  int doff[JM_D];
-#pragma unroll
-  for (int d = 0; d < JM_D; ++d) {
-    const int dd = d0 + (d < nd ? d : 0);
-    doff[d] = ((dd / T - pad) * Wp + (dd % T - pad)) * kp;
-  }
-  const int tiles_h = (eh + R - 1) / R;
-  const int ntile = N * tiles_h;
-  if (kp == k)  // the zero columns left and right of every staged x1 row
-    for (int e = tid; e < Rp * 2 * pad * kp; e += 256) {
-      const int r = e / (2 * pad * kp), c = e - r * (2 * pad * kp);
-      const int col = c / kp < pad ? c / kp : ew + c / kp;
-      xs1[(r * Wp + col) * kp + c % kp] = 0.f;
-    }
-  for (int t = blockIdx.x; t < ntile; t += gridDim.x) {
-    const int n = t / tiles_h, r0 = (t - n * tiles_h) * R;
-    const int rows = eh - r0 < R ? eh - r0 : R;
-    __syncthreads();
-    if (kp == k) {  // a patch row is one contiguous, 16-byte aligned span of ew*k floats in memory and in the tile
-      const int row4 = ew * k / 4;
-      for (int r = 0; r < Rp; ++r) {
-        const int pr = r0 - pad + r;
-        const bool ok = r < rows + 2 * pad && pr >= 0 && pr < eh;
-        const float* src = x1 + (((long)n * H + h0 + (ok ? pr : 0)) * W + w0) * k;
-        float* dst = xs1 + (r * Wp + pad) * kp;
-        for (int e4 = tid; e4 < row4; e4 += 256) {
-          f32x4 v = {0.f, 0.f, 0.f, 0.f};
-          if (ok) v = *reinterpret_cast<const f32x4*>(src + 4 * e4);
-          *reinterpret_cast<f32x4*>(dst + 4 * e4) = v;
-        }
-      }
-      for (int e4 = tid; e4 < R * row4; e4 += 256) {
-        const int r = e4 / row4, c4 = e4 - r * row4;
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (r < rows) v = *reinterpret_cast<const f32x4*>(x2 + (((long)n * H + h0 + r0 + r) * W + w0) * k + 4 * c4);
-        *reinterpret_cast<f32x4*>(xs2 + 4 * e4) = v;
-      }
-    } else {
-      for (int e = tid; e < Rp * Wp * kp; e += 256) {
-        const int c = e % kp;
-        const int p = e / kp;
-        const int cw = p % Wp, r = p / Wp;
-        const int pr = r0 - pad + r, pc = cw - pad;
-        float v = 0.f;
-        if (c < k && r < rows + 2 * pad && pr >= 0 && pr < eh && pc >= 0 && pc < ew)
-          v = x1[(((long)n * H + h0 + pr) * W + w0 + pc) * k + c];
-        xs1[e] = v;
-      }
-      for (int e = tid; e < R * ew * kp; e += 256) {
-        const int c = e % kp;
-        const int p = e / kp;
-        const int w = p % ew, r = p / ew;
-        xs2[e] = (c < k && r < rows) ? x2[(((long)n * H + h0 + r0 + r) * W + w0 + w) * k + c] : 0.f;
-      }
-    }
-    __syncthreads();
-    if (active) {
-      int r = 0, w = sl;
-      while (w >= ew) w -= ew, ++r;
-      for (; r < rows;) {
-        const f32x4 b = *reinterpret_cast<const f32x4*>(xs2 + (r * ew + w) * kp + 4 * tj);
-        const float* a0 = xs1 + ((r + pad) * Wp + (w + pad)) * kp + 4 * ti;
-#pragma unroll
-        for (int d = 0; d < JM_D; ++d) {
-          if (d < nd) {  // wave-uniform
-            const f32x4 a = *reinterpret_cast<const f32x4*>(a0 + doff[d]);
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-              for (int j = 0; j < 4; ++j) acc[d][i][j] = fmaf(a[i], b[j], acc[d][i][j]);
-          }
-        }
-        w += nsl;
-        while (w >= ew) w -= ew, ++r;
-      }
-    }
-  }
-#pragma unroll
-  for (int d = 0; d < JM_D; ++d) {  // (no early exit: the accumulators must stay statically indexed = in registers)
-    if (d >= nd) continue;          // block-uniform
-    __syncthreads();
-    if (active) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) red[sl * kp * kp + (4 * ti + i) * kp + 4 * tj + j] = acc[d][i][j];
-    }
-    __syncthreads();
-    const size_t qd = (size_t)q * TT + d0 + d;
-    for (int e = tid; e < k * k; e += 256) {
-      const int i = e / k, j = e - i * k;
-      float s = 0.f;
-      for (int u = 0; u < nsl; ++u) s += red[u * kp * kp + i * kp + j];
-      if (gridDim.x == 1)
-        J[qd * (k * k) + e] = (float)((double)s * scale);
-      else
-        part[(qd * gridDim.x + blockIdx.x) * (k * k) + e] = s;
-    }
-  }
+  joint_staged_body<false>(x1, x2, part, gridDim.x == 1 ? J : nullptr, scale, N, H, W, k, pad, R,
+                           patch_window(q, H, W, patch, nph, npw, eh, ew), q);
 }
 
-// The fallback, joint_fwd_kernel on a patch: one displacement per block (blockIdx.y), 64-pixel tiles of the patch's
-// N*eh*ew pixels, the displaced read bounds-tested against the patch.  Same partial layout.
+// The fallback, the per-displacement form:
 __global__ void __launch_bounds__(256)
     joint_patch_fwd1_kernel(const float* __restrict__ x1, const float* __restrict__ x2, float* __restrict__ part,
                             float* __restrict__ J, int N, int H, int W, int k, int pad, int patch, int nph, int npw,
                             int eh, int ew, double scale) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int kp = (k + 3) & ~3, k4 = kp >> 2;
-  const int tps = k4 * k4, nsl = 256 / tps;
-  float* xs1 = sm;                 // [J_P][kp]
-  float* xs2 = sm + J_P * kp;      // [J_P][kp]
-  float* red = sm + 2 * J_P * kp;  // [nsl][kp*kp]
-  const int tid = threadIdx.x;
-  const int T = 2 * pad + 1, TT = T * T;
   const int q = (int)blockIdx.z;
-  const int h0 = patch_origin(q / npw, nph, H, patch), w0 = patch_origin(q % npw, npw, W, patch);
-  const int du = (int)blockIdx.y / T - pad, dv = (int)blockIdx.y % T - pad;
-  const int sl = tid / tps, tt = tid - sl * tps;
-  const int ti = tt / k4, tj = tt - ti * k4;
-  const bool active = sl < nsl;
-  float acc[4][4];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 4; ++b) acc[a][b] = 0.f;
-  const long npp = (long)N * eh * ew;
-  const long per = ((npp + gridDim.x - 1) / gridDim.x + J_P - 1) / J_P * J_P;
-  const long p0 = (long)blockIdx.x * per;
-  const long p1 = p0 + per < npp ? p0 + per : npp;
-  for (long pt = p0; pt < p1; pt += J_P) {
-    __syncthreads();
-    for (int e = tid; e < J_P * kp; e += 256) {
-      const int p = e / kp, c = e - p * kp;
-      const long pp = pt + p;
-      float a = 0.f, b = 0.f;
-      if (pp < p1 && c < k) {
-        const int wl = (int)(pp % ew);
-        const long t = pp / ew;
-        const int hl = (int)(t % eh);
-        const long n = t / eh;
-        b = x2[((n * H + h0 + hl) * W + w0 + wl) * k + c];
-        const int hh = hl + du, ww = wl + dv;
-        if (hh >= 0 && hh < eh && ww >= 0 && ww < ew) a = x1[((n * H + h0 + hh) * W + w0 + ww) * k + c];
-      }
-      xs1[e] = a;
-      xs2[e] = b;
-    }
-    __syncthreads();
-    if (active) {
-      for (int p = sl; p < J_P; p += nsl) {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(xs1 + p * kp + 4 * ti);
-        const f32x4 b = *reinterpret_cast<const f32x4*>(xs2 + p * kp + 4 * tj);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(a[i], b[j], acc[i][j]);
-      }
-    }
-  }
-  __syncthreads();
-  if (active) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) red[sl * kp * kp + (4 * ti + i) * kp + 4 * tj + j] = acc[i][j];
-  }
-  __syncthreads();
-  const size_t qd = (size_t)q * TT + blockIdx.y;
-  for (int e = tid; e < k * k; e += 256) {
-    const int i = e / k, j = e - i * k;
-    float s = 0.f;
-    for (int u = 0; u < nsl; ++u) s += red[u * kp * kp + i * kp + j];
-    if (gridDim.x == 1)
-      J[qd * (k * k) + e] = (float)((double)s * scale);
-    else
-      part[(qd * gridDim.x + blockIdx.x) * (k * k) + e] = s;
-  }
+  joint_tile_body<false>(x1, x2, part, gridDim.x == 1 ? J : nullptr, scale, N, H, W, k, pad,
+                         patch_window(q, H, W, patch, nph, npw, eh, ew), q);
 }
 
 // one block per patch on J[P][TT][k][k]: losses[q], Pj[q] (may be NULL) and dJ[q] (may be NULL) = (1/P) dloss_q/dJ_q
@@ -855,41 +689,12 @@ __global__ void __launch_bounds__(256)
         const int vlo = which ? max(-pad, -lw) : max(-pad, lw - ew + 1), vhi = which ? min(pad, ew - 1 - lw) : min(pad, lw);
         for (int du = ulo; du <= uhi; ++du)
           for (int dv = vlo; dv <= vhi; ++dv) {
-            const float* o = other + (pix + sgn * ((long)du * W + dv)) * k;
-            const float* m = dq + ((du + pad) * T + dv + pad) * kk;
-            if (V == 4) {
-              for (int j4 = 0; j4 < kv; ++j4) {
-                const f32x4 ov = *reinterpret_cast<const f32x4*>(o + 4 * j4);
-                if (which) {
-#pragma unroll
-                  for (int t = 0; t < 4; ++t) {
-                    const f32x4 mv = *reinterpret_cast<const f32x4*>(m + (4 * j4 + t) * k + c);
-#pragma unroll
-                    for (int u = 0; u < V; ++u) s[u] = fmaf(mv[u], ov[t], s[u]);
-                  }
-                } else {
-#pragma unroll
-                  for (int u = 0; u < V; ++u) {
-                    const f32x4 mv = *reinterpret_cast<const f32x4*>(m + (c + u) * k + 4 * j4);
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) s[u] = fmaf(mv[t], ov[t], s[u]);
-                  }
-                }
-              }
-            } else if (which) {
-              for (int i = 0; i < k; ++i) s[0] = fmaf(m[i * k + c], o[i], s[0]);
-            } else {
-              for (int j = 0; j < k; ++j) s[0] = fmaf(m[c * k + j], o[j], s[0]);
-            }
+            joint_bwd_dot<V>(s, dq + ((du + pad) * T + dv + pad) * kk, other + (pix + sgn * ((long)du * W + dv)) * k, k,
+                             c, which);
           }
       }
     }
-    if (V == 4) {
-      f32x4 r = {g * s[0], g * s[V > 1 ? 1 : 0], g * s[V > 2 ? 2 : 0], g * s[V > 3 ? 3 : 0]};
-      *reinterpret_cast<f32x4*>(dx + pix * k + c) = r;
-    } else {
-      dx[e] = g * s[0];
-    }
+    joint_bwd_store<V>(dx, pix * k + c, s, g);
   }
 }
 
@@ -905,6 +710,52 @@ constexpr int J_FWD_LDS = 150 * 1024;  // the staged tile of joint_fwd_multi_ker
 constexpr int J_BWD_LDS = 64 * 1024;   // the dJ chunk of the backward kernels (default limit)
 constexpr int GS_LDS = 64 * 1024;      // the softmax tiles (default limit)
 
+// The host's half of the launch rules that the whole-image and the patch-wise plans share (the kernels recompute kp and
+// nsl from k, see joint_lanes_of).
+struct joint_split {
+  int kp, k4, nsl;
+  size_t red;   // bytes of the reduction buffer [nsl][kp*kp]
+  size_t tile;  // dynamic LDS of the per-displacement form: two 64-pixel tiles and the reduction buffer
+};
+joint_split joint_split_of(int k) {
+  joint_split s;
+  s.kp = (k + 3) & ~3;
+  s.k4 = s.kp / 4;
+  s.nsl = 256 / (s.k4 * s.k4);
+  s.red = (size_t)s.nsl * s.kp * s.kp * sizeof(float);
+  s.tile = 2 * J_P * s.kp * sizeof(float) + s.red;
+  return s;
+}
+
+// The staged form on a window of eh x ew pixels: R rows of it per tile and the bytes of the staged tile (the reduction
+// buffer lies over it); the form is taken where they fit J_FWD_LDS.
+struct joint_staged {
+  int R;
+  size_t lds;
+};
+joint_staged joint_staged_of(int eh, int ew, int k, int pad) {
+  const joint_split s = joint_split_of(k);
+  joint_staged t;
+  t.R = 256 / ew;
+  t.R = t.R < 1 ? 1 : (t.R > eh ? eh : t.R);
+  t.lds = ((size_t)(t.R + 2 * pad) * (ew + 2 * pad) * s.kp + (size_t)t.R * ew * s.kp) * sizeof(float);
+  if (t.lds < s.red) t.lds = s.red;
+  return t;
+}
+
+// The backward kernels, whole-image and patch-wise: the 16-byte form where k % 4 == 0, one thread per (pixel, V channels)
+struct joint_bwd_rule {
+  int vec, grid;
+  long work;  // threads' worth of outputs
+};
+joint_bwd_rule joint_bwd_rule_of(long npix, int k) {
+  joint_bwd_rule b;
+  b.vec = (k & 3) == 0;
+  b.work = b.vec ? npix * (k / 4) : npix * k;
+  b.grid = cy_blocks(b.work, 256, GRID_CAP);
+  return b;
+}
+
 }  // namespace
 
 extern "C" {
@@ -917,40 +768,36 @@ int cy_joint_plan(int N, int H, int W, int k, int pad, cy_joint_plan_t* out) {
   cy_joint_plan_t p = {};
   const long npix = (long)N * H * W;
   const int T = 2 * pad + 1, TT = T * T;
-  const int kp = (k + 3) & ~3, k4 = kp / 4, nsl = 256 / (k4 * k4);
-  p.kp = kp;
-  p.nsl = nsl;
-  p.idle = 256 - nsl * k4 * k4;
+  const joint_split s = joint_split_of(k);
+  p.kp = s.kp;
+  p.nsl = s.nsl;
+  p.idle = 256 - s.nsl * s.k4 * s.k4;
   p.nblk = cy_blocks(npix, JOINT_PIX, JOINT_GRID_CAP);
   p.reduce_trips = cy_cdiv(p.nblk, 64);
-  const size_t red = (size_t)nsl * kp * kp * sizeof(float);
   // padding > 0: every displacement from one staged tile of R rows, if it fits the LDS
-  int R = 256 / W;
-  R = R < 1 ? 1 : (R > H ? H : R);
-  size_t smem_multi = ((size_t)(R + 2 * pad) * (W + 2 * pad) * kp + (size_t)R * W * kp) * sizeof(float);
-  if (smem_multi < red) smem_multi = red;
-  if (pad > 0 && smem_multi <= (size_t)J_FWD_LDS) {
+  const joint_staged st = joint_staged_of(H, W, k, pad);
+  if (pad > 0 && st.lds <= (size_t)J_FWD_LDS) {
     p.fwd_kernel = 1;
-    p.fwd_vec = kp == k;
-    p.R = R;
-    p.tiles_h = cy_cdiv(H, R);
+    p.fwd_vec = s.kp == k;
+    p.R = st.R;
+    p.tiles_h = cy_cdiv(H, st.R);
     p.ntile = N * p.tiles_h;
     p.grid_y = cy_cdiv(TT, JM_D);
     p.nd_last = TT - (p.grid_y - 1) * JM_D;
-    p.fwd_lds = (int)smem_multi;
+    p.fwd_lds = (int)st.lds;
   } else {
     p.fwd_kernel = 0;
-    p.fwd_vec = pad == 0 && kp == k;
+    p.fwd_vec = pad == 0 && s.kp == k;
     p.per = (int)(((npix + p.nblk - 1) / p.nblk + J_P - 1) / J_P * J_P);
     p.ntile = cy_cdiv(npix, J_P);
     p.grid_y = TT;
     p.nd_last = 1;
-    p.fwd_lds = (int)(2 * J_P * kp * sizeof(float) + red);
+    p.fwd_lds = (int)s.tile;
   }
-  p.bwd_kernel = (k & 3) == 0;
-  const long work = p.bwd_kernel ? npix * (k / 4) : npix * k;
-  p.bwd_grid = cy_blocks(work, 256, GRID_CAP);
-  p.bwd_trips = cy_cdiv(work, 256L * p.bwd_grid);
+  const joint_bwd_rule b = joint_bwd_rule_of(npix, k);
+  p.bwd_kernel = b.vec;
+  p.bwd_grid = b.grid;
+  p.bwd_trips = cy_cdiv(b.work, 256L * p.bwd_grid);
   const int fit = J_BWD_LDS / (k * k * (int)sizeof(float));  // >= 4 because k <= 64
   p.bwd_dchunk = fit < TT ? fit : TT;
   p.bwd_nchunk = cy_cdiv(TT, p.bwd_dchunk);
@@ -1053,10 +900,10 @@ int cy_joint_bwd(const float* x1, const float* x2, const float* dJ, const float*
     const float* other = which ? x1 : x2;
     if (!dst) continue;
     if (p.bwd_kernel)
-      hipLaunchKernelGGL(joint_bwd4_kernel, dim3(p.bwd_grid), dim3(256), (size_t)p.bwd_lds, st, other, dJ, gscale,
+      hipLaunchKernelGGL(joint_bwd_kernel<4>, dim3(p.bwd_grid), dim3(256), (size_t)p.bwd_lds, st, other, dJ, gscale,
                          dst, N, H, W, k, pad, scale, which, p.bwd_dchunk);
     else
-      hipLaunchKernelGGL(joint_bwd_kernel, dim3(p.bwd_grid), dim3(256), (size_t)p.bwd_lds, st, other, dJ, gscale,
+      hipLaunchKernelGGL(joint_bwd_kernel<1>, dim3(p.bwd_grid), dim3(256), (size_t)p.bwd_lds, st, other, dJ, gscale,
                          dst, N, H, W, k, pad, scale, which, p.bwd_dchunk);
     CY_CHECK_LAUNCH();
   }
@@ -1096,37 +943,34 @@ int patch_plan_of(int N, int H, int W, int k, int pad, int patch, int kernel, pa
   p.P = p.nph * p.npw;
   const int T = 2 * pad + 1, TT = T * T;
   if ((long)p.P * TT * k * k > 0x7fffffffL) return CY_ERR_SHAPE;  // J is indexed with 32 bits in the reduction
-  const int kp = (k + 3) & ~3, k4 = kp / 4, nsl = 256 / (k4 * k4);
-  const size_t red = (size_t)nsl * kp * kp * sizeof(float);
-  int R = 256 / p.ew;
-  R = R < 1 ? 1 : (R > p.eh ? p.eh : R);
-  size_t smem = ((size_t)(R + 2 * pad) * (p.ew + 2 * pad) * kp + (size_t)R * p.ew * kp) * sizeof(float);
-  if (smem < red) smem = red;
-  p.staged_fits = smem <= (size_t)J_FWD_LDS;
+  const joint_split s = joint_split_of(k);
+  const joint_staged st = joint_staged_of(p.eh, p.ew, k, pad);
+  p.staged_fits = st.lds <= (size_t)J_FWD_LDS;
   if (kernel == 1 && !p.staged_fits) return CY_ERR_SHAPE;
   p.kernel = kernel < 0 ? p.staged_fits : kernel;
-  const int tiles_h = cy_cdiv(p.eh, R), ntile = N * tiles_h, groups = cy_cdiv(TT, JM_D);
+  const int tiles_h = cy_cdiv(p.eh, st.R), ntile = N * tiles_h, groups = cy_cdiv(TT, JM_D);
   int nbx1 = cy_cdiv(JP_TARGET, (long)p.P * groups);
   nbx1 = nbx1 > ntile ? ntile : nbx1;
   const int nbx0 = cy_blocks((long)N * p.eh * p.ew, JOINT_PIX, JOINT_GRID_CAP);
   if (p.kernel == 1) {
-    p.R = R;
+    p.R = st.R;
     p.tiles_h = tiles_h;
     p.ntile = ntile;
     p.nbx = nbx1;
     p.grid_y = groups;
-    p.fwd_lds = (int)smem;
-    p.fwd_vec = kp == k;
+    p.fwd_lds = (int)st.lds;
+    p.fwd_vec = s.kp == k;
   } else {
     p.ntile = cy_cdiv((long)N * p.eh * p.ew, J_P);
     p.nbx = nbx0;
     p.grid_y = TT;
-    p.fwd_lds = (int)(2 * J_P * kp * sizeof(float) + red);
+    p.fwd_lds = (int)s.tile;
   }
   // the partial joints of the forward; a forward with one block per (patch, group) writes J itself
   p.ws_bytes = p.nbx > 1 ? (size_t)p.P * TT * p.nbx * k * k * sizeof(float) : 16;
-  p.bwd_kernel = (k & 3) == 0;
-  p.bwd_grid = cy_blocks(p.bwd_kernel ? (long)N * H * W * (k / 4) : (long)N * H * W * k, 256, GRID_CAP);
+  const joint_bwd_rule b = joint_bwd_rule_of((long)N * H * W, k);
+  p.bwd_kernel = b.vec;
+  p.bwd_grid = b.grid;
   *out = p;
   return CY_OK;
 }

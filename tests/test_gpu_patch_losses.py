@@ -162,6 +162,38 @@ def test_one_clipped_patch_is_the_single_map_loss(npz, tol):
         assert torch.equal(u, v), name
 
 
+# (shape, k, pad, normalise, forward kernel of both sides)
+WHOLE_IMAGE_CASES = (
+    [((1, 33, 37), k, 0, norm, "per_displacement") for k in (5, 20) for norm in (True, False)]
+    + [((1, 8, 64), 64, 1, False, "per_displacement")]
+    + [((1, 6, 40), k, 1, False, "staged") for k in (8, 21)])  # one row tile: one block per displacement group
+
+
+@pytest.mark.parametrize("shape,k,pad,normalise,kernel", WHOLE_IMAGE_CASES,
+                         ids=[f"{n}x{h}x{w}-k{k}-pad{p}-{'norm' if nm else 'raw'}-{kn}"
+                              for (n, h, w), k, p, nm, kn in WHOLE_IMAGE_CASES])
+def test_whole_image_joint_is_the_one_patch_joint(shape, k, pad, normalise, kernel):
+    """a whole image is the window of origin (0, 0) and extent H x W: with one patch that covers the map, the patch-wise
+    kernel and the whole-image kernel run the same body on the same window -- the same bits, given the same forward
+    kernel, rows per tile and block count along x (asserted first, from the two plan queries)"""
+    from cyhip import ops
+    N, H, W = shape
+    patch = max(H, W)
+    whole = ops.joint_plan(N, H, W, k, pad)
+    one = ops.joint_patch_plan(N, H, W, k, pad, patch, kernel)
+    print("whole", whole, "\none patch", one)
+    assert one["P"] == 1 and (one["eh"], one["ew"]) == (H, W)
+    assert whole["fwd_kernel"] == one["fwd_kernel"] == ops.JOINT_PATCH_KERNELS[kernel]
+    assert whole["R"] == one["R"]
+    assert whole["nblk"] == one["nbx"]
+    g = torch.Generator().manual_seed(11)
+    x1, x2 = (nhwc(torch.softmax(torch.randn(N, k, H, W, generator=g) * 2, 1)) for _ in range(2))
+    J = ops.joint_fwd(x1, x2, N, H, W, k, pad, normalise)
+    Jp = ops.joint_patch_fwd(x1, x2, pad, patch, normalise, kernel=kernel)
+    print("max |difference|", float((J.double() - Jp[0].double()).abs().max()))
+    assert J.shape == Jp[0].shape and torch.equal(J, Jp[0])
+
+
 @pytest.mark.parametrize("tag", ["A", "B", "C", "E"])
 def test_the_fallback_forward_agrees_with_the_staged_one(npz, tol, patch_refs, tag):
     """the per-displacement kernel, which the rule takes where the staged tile exceeds the LDS cap, forced through the
