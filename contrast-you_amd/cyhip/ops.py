@@ -2140,6 +2140,96 @@ def surface_stats(pred: Tensor, target: Tensor, classes, ndim: int = 3, maps: bo
     return count, total, maxd2
 
 
+# --------------------------------------------------------------------------- SLIC superpixels (csrc/cy_slic.hip)
+SLIC_PLAN_FIELDS = ("status", "r", "S", "start", "Ky", "Kx", "K", "M", "min_size", "blur_form", "blur_grid_x",
+                    "blur_grid_y", "blur_lds_h", "blur_lds_w", "pixel_grid_x", "assign_lds", "update_grid",
+                    "scan_tiles", "launches")
+_SLIC_WS = {}  # (device, N, H, W, n_segments) -> workspace; the calls of one shape are ordered by the stream they share
+
+
+def slic_plan(N: int, H: int, W: int, n_segments: int = 40, sigma: float = 5.0, compactness: float = 0.1,
+              max_iter: int = 10) -> dict:
+    """what cy_slic would do for these sizes: geometry (r, S, start, Ky, Kx, K, M, min_size), kernel form, grids and
+    LDS per stage; `status` is the refusal (0: none), nothing is launched and no GPU is needed"""
+    plan = (C.c_int32 * _lib.CY_SLIC_PLAN_LEN)()
+    _lib.load().cy_slic_plan(int(N), int(H), int(W), int(n_segments), float(sigma), float(compactness),
+                             int(max_iter), plan)
+    return {f: int(plan[getattr(_lib, "CY_SLIC_PLAN_" + f.upper())]) for f in SLIC_PLAN_FIELDS}
+
+
+def _slic_images(images: Tensor) -> Tensor:
+    require_gpu(images)
+    if images.dim() == 4:
+        if images.shape[1] != 1:
+            raise ValueError(f"superpixels are computed on single-channel images, given {tuple(images.shape)}")
+        images = images[:, 0]
+    if images.dim() != 3:
+        raise ValueError(f"images are [N,1,H,W] or [N,H,W], given {tuple(images.shape)}")
+    return images.detach().float().contiguous()
+
+
+def _slic_ws(dev, N: int, H: int, W: int, n_segments: int):
+    key = (dev, N, H, W, int(n_segments))
+    hit = _SLIC_WS.get(key)
+    if hit is None:
+        nbytes = _lib.load().cy_slic_ws_bytes(N, H, W, int(n_segments))
+        hit = _SLIC_WS[key] = (_ws(nbytes, dev), nbytes)
+    return hit
+
+
+def slic_blur_q(images: Tensor, sigma: float = 5.0) -> Tensor:
+    """stage 1: Gaussian blur (reflect boundary) and 16-bit quantisation -> q int32 [N,H,W]"""
+    x = _slic_images(images)
+    N, H, W = x.shape
+    q = torch.empty((N, H, W), dtype=torch.int32, device=x.device)
+    ws = _ws(4 * N * H * W + 256, x.device)
+    _lib.call("cy_slic_blur_q", x.data_ptr(), q.data_ptr(), N, H, W, float(sigma), ws.data_ptr(), ws.numel(),
+              _stream())
+    return q
+
+
+def slic_cluster(q: Tensor, n_segments: int = 40, compactness: float = 0.1, max_iter: int = 10):
+    """stage 2: windowed k-means on the quantised image -> (labels int32 [N,H,W], centres int32 [N,K,3] = cy, cx, cq)"""
+    require_gpu(q)
+    assert q.dtype == torch.int32 and q.dim() == 3, "q is int32 [N,H,W]"
+    q = q.contiguous()
+    N, H, W = q.shape
+    K = max(slic_plan(N, H, W, n_segments, 0.0, compactness, max_iter)["K"], 1)
+    labels = torch.empty((N, H, W), dtype=torch.int32, device=q.device)
+    centres = torch.empty((N, K, 3), dtype=torch.int32, device=q.device)
+    ws, nbytes = _slic_ws(q.device, N, H, W, n_segments)
+    _lib.call("cy_slic_cluster", q.data_ptr(), labels.data_ptr(), centres.data_ptr(), N, H, W, int(n_segments),
+              float(compactness), int(max_iter), ws.data_ptr(), nbytes, _stream())
+    return labels, centres
+
+
+def slic_connect(labels: Tensor, n_segments: int = 40):
+    """stage 3: 4-connected components of a label map, the small ones merged -> (ids uint8 [N,H,W], count int32 [N])"""
+    require_gpu(labels)
+    assert labels.dtype == torch.int32 and labels.dim() == 3, "labels are int32 [N,H,W]"
+    labels = labels.contiguous()
+    N, H, W = labels.shape
+    ids = torch.empty((N, H, W), dtype=torch.uint8, device=labels.device)
+    count = torch.empty((N,), dtype=torch.int32, device=labels.device)
+    ws, nbytes = _slic_ws(labels.device, N, H, W, n_segments)
+    _lib.call("cy_slic_connect", labels.data_ptr(), ids.data_ptr(), count.data_ptr(), N, H, W, int(n_segments),
+              ws.data_ptr(), nbytes, _stream())
+    return ids, count
+
+
+def slic(images: Tensor, n_segments: int = 40, sigma: float = 5.0, compactness: float = 0.1, max_iter: int = 10):
+    """SLIC superpixels of single-channel images in 0..1 ([N,1,H,W] or [N,H,W]; bf16 / f16 are converted) ->
+    (ids uint8 [N,H,W], count int32 [N]).  All on the current stream, no host read; the workspace is kept per shape."""
+    x = _slic_images(images)
+    N, H, W = x.shape
+    ids = torch.empty((N, H, W), dtype=torch.uint8, device=x.device)
+    count = torch.empty((N,), dtype=torch.int32, device=x.device)
+    ws, nbytes = _slic_ws(x.device, N, H, W, n_segments)
+    _lib.call("cy_slic", x.data_ptr(), ids.data_ptr(), count.data_ptr(), N, H, W, int(n_segments), float(sigma),
+              float(compactness), int(max_iter), ws.data_ptr(), nbytes, _stream())
+    return ids, count
+
+
 # --------------------------------------------------------------------------- projector pieces
 def avgpool_fwd(x: Tensor) -> Tensor:
     N, Cc, H, W = x.shape

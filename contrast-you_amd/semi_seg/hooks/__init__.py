@@ -11,8 +11,8 @@ from .creator import (create_consistency_hook, create_cross_correlation_hooks2, 
 from .dmt import DifferentiableMeanTeacherTrainerHook  # noqa: F401
 from .discretemi import DiscreteIMSATTrainHook, DiscreteMITrainHook  # noqa: F401
 from .entmin import EntropyMinTrainerHook  # noqa: F401
-from .infonce import (INFONCEHook, PScheduler, SelfPacedINFONCEHook, SuperPixelInfoNCEHook,  # noqa: F401
-                      region_extractor)
+from .infonce import (INFONCEHook, OnlineSuperPixelInfoNCEHook, PScheduler, SelfPacedINFONCEHook,  # noqa: F401
+                      SuperPixelInfoNCEHook, region_extractor)
 from .midl import IIDSegmentationTrainerHook, IMSATTrainHook  # noqa: F401
 from .mixup import MixUpTrainHook  # noqa: F401
 from .mt import (EMAUpdater, ICTMeanTeacherTrainerHook, MeanTeacherTrainerHook,  # noqa: F401

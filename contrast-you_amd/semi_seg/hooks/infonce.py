@@ -1,7 +1,8 @@
 """InfoNCE regulariser on an encoder feature map (semi_seg/hooks/infonce.py:84-245), its dense
 variant on decoder feature maps (`_INFONCEDenseHook`, infonce.py:251-279; `region_extractor`,
 infonce.py:31-46), the self-paced variant (`SelfPacedINFONCEHook` + `PScheduler`, infonce.py:58-80,146-178,
-281-305) and the superpixel-labelled dense variant (`SuperPixelInfoNCEHook`, infonce.py:180-194,308-340).
+281-305), the superpixel-labelled dense variant (`SuperPixelInfoNCEHook`, infonce.py:180-194,308-340) and
+`OnlineSuperPixelInfoNCEHook`, the same with the superpixel map computed on the device instead of loaded.
 
 `INFONCEHook` (TrainerHook) owns the feature tap, the projection head and the SupCon criterion;
 once per epoch it hands out an `_INFONCEEpochHook` whose `_call_implementation`:
@@ -28,6 +29,7 @@ from contrastyou.utils.utils import fix_all_seed_for_transforms
 from cyhip import ops, parallel
 from cyhip.functions import GatherRowsFn
 
+from ..superpixel import as_batch_entry, slic_superpixels
 from .utils import get_label
 
 
@@ -170,6 +172,25 @@ class SuperPixelInfoNCEHook(INFONCEHook):
                                            label_generator=self._label_generator)
 
 
+class OnlineSuperPixelInfoNCEHook(SuperPixelInfoNCEHook):
+    """`SuperPixelInfoNCEHook` that needs no `superpixel/` folder: a batch that carries no map gets one computed on
+    the device from its `unlabeled_image` (semi_seg/superpixel.py; the reference's offline pass is
+    script/create_superpixel.py:27, whose parameters are the defaults here).  Works without `batch_data`, so also
+    inside `SemiSupervisedEpocher`."""
+
+    def __init__(self, *, name, model: nn.Module, feature_name: str, weight: float = 1.0,
+                 spatial_size: t.Sequence[int] = None, data_name: str, contrast_on: str, n_segments: int = 40,
+                 sigma: float = 5.0, compactness: float = 0.1) -> None:
+        super().__init__(name=name, model=model, feature_name=feature_name, weight=weight, spatial_size=spatial_size,
+                         data_name=data_name, contrast_on=contrast_on)
+        self._slic_params = dict(n_segments=int(n_segments), sigma=float(sigma), compactness=float(compactness))
+
+    def __call__(self) -> "_OnlineSuperPixelInfoNCEEpochHook":
+        return _OnlineSuperPixelInfoNCEEpochHook(name=self._hook_name, weight=self._weight, extractor=self._extractor,
+                                                 projector=self._projector, criterion=self._criterion,
+                                                 label_generator=self._label_generator, slic_params=self._slic_params)
+
+
 class _INFONCEEpochHook(EpocherHook):
 
     def __init__(self, *, name: str, weight: float, extractor, projector,
@@ -284,6 +305,23 @@ class _SuperPixelInfoNCEEPochHook(_INFONCEEpochHook):
         self.meters["loss"].add(loss.detach())
         self._n += 1
         return loss * self._weight
+
+
+class _OnlineSuperPixelInfoNCEEpochHook(_SuperPixelInfoNCEEPochHook):
+    """the batch's own superpixel map where it has one, else the map of `unlabeled_image` computed on the device"""
+
+    def __init__(self, *, slic_params: t.Dict[str, t.Any], **kwargs) -> None:
+        super().__init__(**kwargs)
+        self._slic_params = slic_params
+
+    def _call_implementation(self, *, unlabeled_image=None, batch_data: t.Dict[str, t.Any] = None, **kwargs):
+        if batch_data is None or "superpixel" not in batch_data:
+            if unlabeled_image is None or unlabeled_image.dim() != 4 or unlabeled_image.shape[1] != 1:
+                raise ValueError("superpixels are computed on single-channel images [N,1,H,W], given "
+                                 f"{None if unlabeled_image is None else tuple(unlabeled_image.shape)}")
+            ids = slic_superpixels(unlabeled_image, **self._slic_params)
+            batch_data = {**(batch_data or {}), "superpixel": as_batch_entry(ids)}
+        return super()._call_implementation(unlabeled_image=unlabeled_image, batch_data=batch_data, **kwargs)
 
 
 class _INFONCEDenseHook(_INFONCEEpochHook):

@@ -1637,6 +1637,79 @@ int cy_softmax_mixmse_row_bwd(const float* student, const float* teacher, const 
                               float w_other, const float* gscale, float* dstudent, int N, long HW, int K,
                               void* stream);
 
+/* ------------------------------------------------------------------------
+ * On-device SLIC superpixels (csrc/cy_slic.hip; 6 entries added to ABI v18 -- no existing signature changed, so
+ * cy_abi_version() stays 18).  Replaces the offline pass the superpixel InfoNCE hook depends on:
+ * skimage.segmentation.slic(img, n_segments=40, sigma=5, compactness=0.1) of script/create_superpixel.py:27
+ * (compactness 0.001 in semi_seg/postprocess/superpixel.py:23) and the `superpixel/` folder read by
+ * _load_superpixel_image (semi_seg/hooks/infonce.py:24-27).  Not label-for-label skimage: DESIGN.md "On-device
+ * superpixels" lists the deviations.  images: f32 [N][H][W] in 0..1.
+ *   blur_q   separable Gaussian along H then W, radius r = int(4 sigma + 0.5), weights exp(-0.5 (i/sigma)^2)
+ *            normalised in f64 then cast to f32, scipy.ndimage's `reflect` boundary, taps i = -r..r accumulated in
+ *            order in f32 (product and sum rounded separately); sigma == 0 skips the blur.
+ *            q = floor(clamp(v,0,1) * 65535 + 0.5) of the f32 value v, evaluated exactly (in f64);
+ *            int32 [N][H][W].
+ *   grid     s = sqrt(H W / n_segments) (f64), S = s rounded half to even, start = floor(s / 2); centres at
+ *            y = start + i S < H, x = start + j S < W, k row-major, K of them; cq_k = q there.
+ *   cluster  max_iter rounds, all of them.  Labels start at 0.  Assignment: among the centres with |y - cy_k| <= 2S and
+ *            |x - cx_k| <= 2S the smallest (q - cq_k)^2 S^2 + (dy^2 + dx^2) M^2 (int64), M = compactness * 65535 rounded
+ *            half to even, ties to the smallest k; a pixel no window covers keeps its label.  Update: cnt and the int64
+ *            sums of y, x, q per label; c = (2 sum + cnt) / (2 cnt); cnt == 0 leaves the centre.
+ *            labels int32 [N][H][W]; centres int32 [N][K][3] = (cy, cx, cq) after the last update.
+ *   connect  4-connected components of equal label, root = smallest linear index; min_size = (H W) / (2 K); a
+ *            component with size >= min_size or root 0 is kept, any other takes the final id of the component owning the
+ *            pixel left of its root (above it when the root is in column 0); sizes are each component's own; kept
+ *            components are numbered 0, 1, ... by increasing root.  ids uint8 [N][H][W], count int32 [N] (< 208).
+ *            Any int32 label map is accepted.
+ * cy_slic is the three stages through the workspace.  Everything goes onto `stream`; no host read, no allocation;
+ * integer sums only after the blur, so two runs give the same bits.
+ * Checked before any launch, in this order: a NULL pointer or max_iter < 0 -> CY_ERR_ARG; N < 1 -> CY_ERR_ARG, H or W
+ * outside 1..CY_SLIC_MAX_SIDE or N > 65535 -> CY_ERR_SHAPE; a negative or NaN sigma -> CY_ERR_ARG, sigma >
+ * CY_SLIC_MAX_SIGMA or r > min(H, W) -> CY_ERR_SHAPE; a non-finite compactness or M outside 1..65535 -> CY_ERR_ARG;
+ * n_segments < 1 -> CY_ERR_ARG, S < 1, K outside 1..CY_SLIC_MAX_K or H W < 64 K -> CY_ERR_SHAPE; a short workspace ->
+ * CY_ERR_WORKSPACE.  Each stage checks the arguments it takes.  cy_slic_ws_bytes (one size for all four entries;
+ * blur_q alone needs N H W 4 bytes) is 0 where the sizes are refused.
+ * cy_slic_plan fills plan[CY_SLIC_PLAN_LEN] (the CY_SLIC_PLAN_* indices; the rest 0) and returns the status cy_slic
+ * would: the geometry, the blur form with its grid and LDS bytes per pass, the grid of the per-pixel kernels
+ * (assignment and the components; blocks of 256, grid.y = N), the tiles of 1024 pixels the numbering block steps
+ * through and the number of launches.
+ * ------------------------------------------------------------------------ */
+#define CY_SLIC_MAX_SIDE 1024
+#define CY_SLIC_MAX_K 100
+#define CY_SLIC_MAX_SIGMA 16
+#define CY_SLIC_BLUR_QUANT 0    /* sigma == 0: slic_quant_kernel */
+#define CY_SLIC_BLUR_TWO_PASS 1 /* slic_blur_kernel along H, then along W with the quantisation */
+#define CY_SLIC_PLAN_LEN 24
+#define CY_SLIC_PLAN_STATUS 0
+#define CY_SLIC_PLAN_R 1
+#define CY_SLIC_PLAN_S 2
+#define CY_SLIC_PLAN_START 3
+#define CY_SLIC_PLAN_KY 4
+#define CY_SLIC_PLAN_KX 5
+#define CY_SLIC_PLAN_K 6
+#define CY_SLIC_PLAN_M 7
+#define CY_SLIC_PLAN_MIN_SIZE 8
+#define CY_SLIC_PLAN_BLUR_FORM 9
+#define CY_SLIC_PLAN_BLUR_GRID_X 10
+#define CY_SLIC_PLAN_BLUR_GRID_Y 11
+#define CY_SLIC_PLAN_BLUR_LDS_H 12
+#define CY_SLIC_PLAN_BLUR_LDS_W 13
+#define CY_SLIC_PLAN_PIXEL_GRID_X 14
+#define CY_SLIC_PLAN_ASSIGN_LDS 15
+#define CY_SLIC_PLAN_UPDATE_GRID 16
+#define CY_SLIC_PLAN_SCAN_TILES 17
+#define CY_SLIC_PLAN_LAUNCHES 18
+size_t cy_slic_ws_bytes(int N, int H, int W, int n_segments);
+int cy_slic_plan(int N, int H, int W, int n_segments, double sigma, double compactness, int max_iter, int32_t* plan);
+int cy_slic_blur_q(const float* images, int32_t* q, int N, int H, int W, double sigma, void* ws, size_t ws_bytes,
+                   void* stream);
+int cy_slic_cluster(const int32_t* q, int32_t* labels, int32_t* centres, int N, int H, int W, int n_segments,
+                    double compactness, int max_iter, void* ws, size_t ws_bytes, void* stream);
+int cy_slic_connect(const int32_t* labels, uint8_t* ids, int32_t* count, int N, int H, int W, int n_segments, void* ws,
+                    size_t ws_bytes, void* stream);
+int cy_slic(const float* images, uint8_t* ids, int32_t* count, int N, int H, int W, int n_segments, double sigma,
+            double compactness, int max_iter, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
