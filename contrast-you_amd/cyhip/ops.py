@@ -2230,6 +2230,85 @@ def slic(images: Tensor, n_segments: int = 40, sigma: float = 5.0, compactness: 
     return ids, count
 
 
+# --------------------------------------------------------------------------- loader augmentation (csrc/cy_augment.hip)
+AUG_MAX_SIDE, AUG_MAX_OUT, AUG_MAX_VIEWS = _lib.CY_AUG_MAX_SIDE, _lib.CY_AUG_MAX_OUT, _lib.CY_AUG_MAX_VIEWS
+AUG_IP_LEN, AUG_FP_LEN = _lib.CY_AUG_IP_LEN, _lib.CY_AUG_FP_LEN
+AUG_BRIGHTNESS, AUG_CONTRAST = _lib.CY_AUG_BRIGHTNESS, _lib.CY_AUG_CONTRAST
+AUG_PLAN_FIELDS = ("status", "form", "geo_grid_x", "geo_grid_y", "geo_grid_z", "jit_grid", "jit_trips", "jit_lds",
+                   "scratch_bytes", "launches")
+_AUG_LUTS = {}  # device -> (ToTensor's table, the identity label table)
+
+
+def augment_plan(views: int, out_h: int, out_w: int) -> dict:
+    """what cy_aug_views would launch for these sizes: kernel form, both grids, the trips of the jitter block over a
+    view, its LDS bytes, the scratch bytes; `status` is the refusal (0: none); nothing is launched, no GPU needed"""
+    plan = (C.c_int32 * _lib.CY_AUG_PLAN_LEN)()
+    _lib.load().cy_aug_plan(int(views), int(out_h), int(out_w), plan)
+    return {f: int(plan[getattr(_lib, "CY_AUG_PLAN_" + f.upper())]) for f in AUG_PLAN_FIELDS}
+
+
+def augment_luts(device):
+    """(ToTensor's 256 values exactly as torch computes them, uint8 -> float -> / 255; the identity label table)"""
+    hit = _AUG_LUTS.get(device)
+    if hit is None:
+        ramp = torch.arange(256, dtype=torch.uint8)
+        hit = _AUG_LUTS[device] = (ramp.float().div(255).to(device), ramp.to(device))
+    return hit
+
+
+def augment_views(store_images: Tensor, store_labels: Optional[Tensor], table: Tensor, int_params: Tensor,
+                  f64_params: Tensor, label_lut: Optional[Tensor], out_hw, *, labels: bool = True):
+    """The views the records describe, cut from a resident store -> (images f32 [B,1,h,w] in 0..1, labels int64
+    [B,1,h,w] or None with labels=False).
+
+    store_images / store_labels: uint8 arenas on the GPU; table: int64 [S,3] = (byte offset, H, W) on the HOST, where
+    the records are checked against it before anything is launched.  The device reads no table: the row of each
+    view's slice is written into its record here (the OFF_LO, OFF_HI, SRC_H, SRC_W columns of a copy; the caller's
+    tensor is left as it is).  int_params int32 [B, AUG_IP_LEN] and f64_params float64 [B, AUG_FP_LEN] are HOST tensors
+    (the records of include/contrastyou_hip.h, as contrastyou.augment.device draws them); they go up through `pinned`,
+    whose ring makes the host wait only once it is a ring's worth of uploads ahead of the device.  label_lut: uint8
+    [256] on the GPU, None for the identity.  Two launches on the current stream."""
+    for name, t, dt in (("table", table, torch.int64), ("int_params", int_params, torch.int32),
+                        ("f64_params", f64_params, torch.float64)):
+        if t.is_cuda or t.dtype != dt or not t.is_contiguous():
+            raise ValueError(f"{name} is a contiguous host tensor of {dt}, given {t.dtype} on {t.device}")
+    B = int_params.shape[0]
+    if tuple(int_params.shape) != (B, AUG_IP_LEN) or tuple(f64_params.shape) != (B, AUG_FP_LEN):
+        raise ValueError(f"one record per view: int_params [B,{AUG_IP_LEN}] and f64_params [B,{AUG_FP_LEN}], given "
+                         f"{tuple(int_params.shape)} and {tuple(f64_params.shape)}")
+    if table.dim() != 2 or table.shape[1] != 3 or table.shape[0] < 1:
+        raise ValueError(f"table is [S,3] = (byte offset, H, W), given {tuple(table.shape)}")
+    if store_images.dtype != torch.uint8 or store_images.dim() != 1 or (
+            labels and (store_labels is None or store_labels.dtype != torch.uint8
+                        or store_labels.shape != store_images.shape)):
+        raise ValueError("the store is two flat uint8 arenas of one size")
+    if label_lut is not None and (label_lut.dtype != torch.uint8 or label_lut.numel() != 256):
+        raise ValueError("label_lut is uint8 [256]")
+    require_gpu(store_images, store_labels if labels else None, label_lut)
+    dev = store_images.device
+    h, w = int(out_hw[0]), int(out_hw[1])
+    tensor_lut, identity = augment_luts(dev)
+    lut = identity if label_lut is None else label_lut
+    _lib.check(augment_plan(B, h, w)["status"], "cy_aug_views")  # sizes it refuses are not allocated first
+    # each record takes the table row of its slice along; an index outside the table keeps the row of the nearest
+    # slice and is refused by the library, which checks SLICE itself
+    rows = table[int_params[:, _lib.CY_AUG_IP_SLICE].long().clamp(0, table.shape[0] - 1)]
+    int_params = int_params.clone()
+    int_params[:, _lib.CY_AUG_IP_OFF_LO] = (rows[:, 0] & 0xffffffff).to(torch.int32)  # wraps to the low word's bits
+    int_params[:, _lib.CY_AUG_IP_OFF_HI] = (rows[:, 0] >> 32).to(torch.int32)
+    int_params[:, _lib.CY_AUG_IP_SRC_H] = rows[:, 1].to(torch.int32)
+    int_params[:, _lib.CY_AUG_IP_SRC_W] = rows[:, 2].to(torch.int32)
+    images = torch.empty((B, 1, h, w), dtype=torch.float32, device=dev)
+    gts = torch.empty((B, 1, h, w), dtype=torch.int64, device=dev) if labels else None
+    scratch = _ws(B * h * w, dev)
+    ip_dev, fp_dev = pinned.upload(int_params, dev), pinned.upload(f64_params, dev)
+    _lib.call("cy_aug_views", store_images.data_ptr(), store_labels.data_ptr() if labels else None, table.data_ptr(),
+              table.shape[0], store_images.numel(), ip_dev.data_ptr(), int_params.data_ptr(), fp_dev.data_ptr(), B, h, w,
+              lut.data_ptr(), tensor_lut.data_ptr(), images.data_ptr(), _ptr(gts), scratch.data_ptr(), scratch.numel(),
+              _stream())
+    return images, gts
+
+
 # --------------------------------------------------------------------------- projector pieces
 def avgpool_fwd(x: Tensor) -> Tensor:
     N, Cc, H, W = x.shape

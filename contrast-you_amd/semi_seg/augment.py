@@ -8,17 +8,23 @@ vendored and unpinned, so its RNG consumption cannot be reproduced: this class d
 parameter families from its own seeded generator and resamples with the HIP nearest-neighbour
 kernels (cyhip.functions.AffineFn).  What IS preserved is the contract the hooks rely on: the
 same `seed` gives the same geometry for images, logits and feature maps of any resolution.
+
+`augment_zoo` is the loader-side augmentation of the same reference module (semi_seg/augment.py:36-325): its ten
+keys, each with the four pipelines `.pretrain`, `.label`, `.val`, `.trainval` as `DevicePipeline`s -- descriptions the
+kernels of csrc/cy_augment.hip apply to a store of slices on the device (semi_seg/data).
 """
 from __future__ import annotations
 
 import math
 from contextlib import contextmanager
+from functools import partial
 from typing import Optional, Tuple
 
 import numpy as np
 import torch
 from torch import Tensor
 
+from contrastyou.augment.device import DevicePipeline
 from cyhip.functions import AffineFn
 
 
@@ -83,3 +89,74 @@ class AffineAugment:
 
 # name kept so that code written against the reference keeps importing
 RisingWrapper = AffineAugment
+
+
+# ---- loader-side pipelines ------------------------------------------------------------------------------------------
+_ACDC_JITTER = ((0.5, 1.5), (0.5, 1.5), (0.5, 1.5))
+_MILD_JITTER = ((0.9, 1.1), (0.9, 1.1), (0.9, 1.1))
+
+
+class ZooEntry:
+    """the four pipelines of one dataset.  `presize` is the `Resize` its pipelines start with (an int: the smaller
+    edge; a pair: (h, w); None: none): it draws nothing, so `DeviceSliceStore.from_arrays(presize=...)` applies it
+    once when the store is built instead of once per sample.  The reference's prostate and hippocampus `trainval`
+    pipelines are the only ones of their datasets without it; their `DevicePipeline.presize` is None."""
+    presize = None
+    mapping = None
+
+    def _pipe(self, presize="dataset", **kw) -> DevicePipeline:
+        return DevicePipeline(mapping=self.mapping, presize=self.presize if presize == "dataset" else presize, **kw)
+
+
+class ACDCTransforms2(ZooEntry):  # semi_seg/augment.py:36-102
+
+    def __init__(self, mapping=None) -> None:
+        self.mapping = mapping
+
+    pretrain = property(lambda self: self._pipe(rotation=45, vflip=True, hflip=True, crop=224, jitter=_ACDC_JITTER,
+                                                total_freedom=True))
+    label = property(lambda self: self._pipe(pre_crop=224, rotation=30))
+    val = property(lambda self: self._pipe(center_crop=224))
+    trainval = property(lambda self: self._pipe(center_crop=224, total_freedom=True))
+
+
+class ProstateTransforms(ZooEntry):  # :105-161
+    presize = 224
+    pretrain = property(lambda self: self._pipe(rotation=10, vflip=True, hflip=True, crop=224, padding=20,
+                                                jitter=_MILD_JITTER, total_freedom=True))
+    label = property(lambda self: self._pipe(crop=224))
+    val = property(lambda self: self._pipe())
+    trainval = property(lambda self: self._pipe(presize=None, center_crop=224, total_freedom=True))
+
+
+class SpleenTransforms(ZooEntry):  # :164-221
+    presize = 320
+    pretrain = property(lambda self: self._pipe(rotation=30, vflip=True, hflip=True, crop=256, padding=20,
+                                                jitter=_MILD_JITTER, total_freedom=True))
+    label = property(lambda self: self._pipe(rotation=10, crop=256, padding=20))
+    val = property(lambda self: self._pipe(center_crop=256))
+    trainval = property(lambda self: self._pipe(center_crop=256, total_freedom=True))
+
+
+class HippocampusTransforms(ZooEntry):  # :224-283
+    presize = (64, 64)
+    pretrain = property(lambda self: self._pipe(rotation=10, vflip=True, hflip=True, crop=64, padding=20,
+                                                jitter=_MILD_JITTER, total_freedom=True))
+    label = property(lambda self: self._pipe(pre_crop=64, padding=20, rotation=10))
+    val = property(lambda self: self._pipe())
+    trainval = property(lambda self: self._pipe(presize=None, center_crop=64, total_freedom=True))
+
+
+# :314-325.  A value is called to get the entry, as the reference's classes and partials are: augment_zoo["acdc"]().label
+augment_zoo = {
+    "acdc": partial(ACDCTransforms2, mapping=None),
+    "acdc_lv": partial(ACDCTransforms2, mapping={0: 0, 1: 0, 2: 0, 3: 1}),
+    "acdc_rv": partial(ACDCTransforms2, mapping={0: 0, 1: 1, 2: 0, 3: 0}),
+    "acdc_myo": partial(ACDCTransforms2, mapping={0: 0, 1: 0, 2: 1, 3: 0}),
+    "spleen": SpleenTransforms,
+    "prostate": ProstateTransforms,
+    "mmwhsct": partial(ACDCTransforms2, mapping=None),
+    "mmwhsmr": partial(ACDCTransforms2, mapping=None),
+    "prostate_md": ProstateTransforms,
+    "hippocampus": HippocampusTransforms,
+}

@@ -1710,6 +1710,102 @@ int cy_slic_connect(const int32_t* labels, uint8_t* ids, int32_t* count, int N, 
 int cy_slic(const float* images, uint8_t* ids, int32_t* count, int N, int H, int W, int n_segments, double sigma,
             double compactness, int max_iter, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------
+ * On-device loader augmentation (csrc/cy_augment.hip; 2 entries added to ABI v18 -- no existing signature changed, so
+ * cy_abi_version() stays 18).  Replaces the host-side Pillow / torchvision pipelines of semi_seg/augment.py:36-283
+ * (augment_zoo) as contrastyou/augment/synchronize.py:76-165 applies them: the *application* of given parameters is
+ * Pillow's bit for bit (Image.rotate BILINEAR / NEAREST, transpose, ImageOps.expand, crop, ImageEnhance.Brightness and
+ * .Contrast, ToTensor, ToLabel); the parameters are drawn on the host (contrastyou/augment/device.py).
+ * Store: store_img / store_lab are uint8 arenas of arena_bytes each; slice s is the H x W row-major block at byte
+ * h_table[3s] with (H, W) = h_table[3s+1], h_table[3s+2] in both arenas (int64 [slices][3], on the HOST: the device
+ * never reads a table, each record carries the row of its slice).
+ * One record per output view v, the same for the image and for the label of the view:
+ *   ip[v][CY_AUG_IP_LEN] int32   SLICE, and its table row as OFF_LO, OFF_HI (the low and high 32 bits of the byte
+ *                                offset), SRC_H, SRC_W: what the kernel reads; the pre-window PY, PX, CH, CW: canvas c[y][x] = source[y+PY][x+PX], 0 outside
+ *                                the source; ROT 0/1 with A0..A5 = Pillow's FIX() of the matrix (below); FLIPV, FLIPH
+ *                                0/1, applied to the rotated canvas; the post-window QY, QX: out[y][x] = pixel
+ *                                (y+QY, x+QX) of the rotated and flipped canvas, 0 outside it; NJIT 0..3 and KIND0..2
+ *                                (CY_AUG_BRIGHTNESS / CY_AUG_CONTRAST) in the order they are applied.
+ *   fp[v][CY_AUG_FP_LEN] double  M0..M5, the matrix exactly as Image.rotate computes it for the CH x CW canvas
+ *                                (x_in = M0 x + M1 y + M2, y_in = M3 x + M4 y + M5); F0..F2, the jitter factors (f32
+ *                                values held in doubles).
+ * Stage A (aug_geometry_kernel, blocks of CY_AUG_GEO_BLOCK output pixels, grid.y = views, grid.z = image / label):
+ * walks output -> post-window -> flips -> rotation -> canvas -> source.
+ *   label, ROT:  xin = (A2 + y A1 + x A0) >> 16, yin = (A5 + y A4 + x A3) >> 16 (int64, arithmetic shift); c[yin][xin]
+ *                inside the canvas, else 0 (affine_fixed, nearest).  A0, A1, A3, A4 = FIX(M0, M1, M3, M4),
+ *                A2 = FIX(M2 + M0 0.5 + M1 0.5), A5 = FIX(M5 + M3 0.5 + M4 0.5), FIX(v) = floor(v 65536 + 0.5): the
+ *                host computes them, the kernel holds integers only.
+ *   image, ROT:  xin = M0 (x+0.5) + M1 (y+0.5) + M2, yin likewise (f64, every product and sum rounded on its own, no
+ *                fma); outside [0,CW) x [0,CH) -> 0; else xin -= 0.5, yin -= 0.5, x0 = floor(xin), dx = xin - x0 (y
+ *                alike), columns and the first row clamped to the canvas, v1 = a + dx (b - a) on row y0, v2 the same on
+ *                row y0+1 when that is inside the canvas, else v1; (uint8)(v1 + dy (v2 - v1)) (bilinear_filter8).
+ *   labels go through label_lut (uint8 [256]: ToLabel's mapping) into labels int64 [views][out_h][out_w]; images as
+ *   uint8 into scratch [views][out_h][out_w].
+ * Stage B (aug_jitter_kernel, one block of CY_AUG_JIT_BLOCK threads per view): the jitter steps are maps of 0..255, so
+ * the block composes them into one 256-entry table and reads the scratch once per contrast step (its mean) and once to
+ * write.  Brightness: t = (uint8) clip(trunc(F (float)t), 0, 255).  Contrast: mean = (2 sum + count) / (2 count) of
+ * the current image in integers, t = (uint8) clip(trunc((float)mean + F ((float)t - (float)mean)), 0, 255), f32, each
+ * operation rounded on its own.  images[v] = tensor_lut[t[scratch]] (f32 [256]: ToTensor's i / 255, computed by the
+ * caller) as f32 [views][out_h][out_w].
+ * store_lab and labels may both be NULL: image views only.  Everything goes onto `stream`; no host read of device
+ * memory, no allocation, no atomics; two runs give the same bits.
+ * Checked on the host before any launch, from h_table and h_ip (the host copy of ip; nothing is read through the
+ * device pointers, and what the kernel reads of the store is in the records that were checked): a NULL pointer (but the label pair), or only one of store_lab / labels -> CY_ERR_ARG; views
+ * outside 1..CY_AUG_MAX_VIEWS, out_h or out_w outside 1..CY_AUG_MAX_OUT, slices < 1 -> CY_ERR_SHAPE; per view: SLICE
+ * outside the table, a table row with H or W outside 1..CY_AUG_MAX_SIDE or leaving the arena, CH or CW outside
+ * 1..CY_AUG_MAX_SIDE, an offset beyond +-CY_AUG_MAX_OFFSET -> CY_ERR_SHAPE; OFF_LO, OFF_HI, SRC_H, SRC_W that are not
+ * the table row of SLICE, a flag that is not 0 / 1, NJIT outside 0..3, an unknown KIND -> CY_ERR_ARG; scratch_bytes < views out_h out_w -> CY_ERR_WORKSPACE.
+ * cy_aug_plan fills plan[CY_AUG_PLAN_LEN] (the CY_AUG_PLAN_* indices, the rest 0) and returns the status the sizes
+ * alone decide: the kernel form, both grids, the trips of stage B's block over a view, its LDS bytes, the scratch
+ * bytes and the number of launches.
+ * ------------------------------------------------------------------------ */
+#define CY_AUG_MAX_SIDE 1024
+#define CY_AUG_MAX_OUT 512
+#define CY_AUG_MAX_VIEWS 4096
+#define CY_AUG_MAX_OFFSET 4096
+#define CY_AUG_GEO_BLOCK 256
+#define CY_AUG_JIT_BLOCK 1024
+#define CY_AUG_BRIGHTNESS 1
+#define CY_AUG_CONTRAST 2
+#define CY_AUG_FORM_TWO_STAGE 0 /* aug_geometry_kernel then aug_jitter_kernel: the only form */
+#define CY_AUG_IP_LEN 24
+#define CY_AUG_IP_SLICE 0
+#define CY_AUG_IP_PY 1
+#define CY_AUG_IP_PX 2
+#define CY_AUG_IP_CH 3
+#define CY_AUG_IP_CW 4
+#define CY_AUG_IP_ROT 5
+#define CY_AUG_IP_FLIPV 6
+#define CY_AUG_IP_FLIPH 7
+#define CY_AUG_IP_QY 8
+#define CY_AUG_IP_QX 9
+#define CY_AUG_IP_NJIT 10
+#define CY_AUG_IP_KIND0 11
+#define CY_AUG_IP_A0 14
+#define CY_AUG_IP_OFF_LO 20
+#define CY_AUG_IP_OFF_HI 21
+#define CY_AUG_IP_SRC_H 22
+#define CY_AUG_IP_SRC_W 23
+#define CY_AUG_FP_LEN 9
+#define CY_AUG_FP_M0 0
+#define CY_AUG_FP_F0 6
+#define CY_AUG_PLAN_LEN 16
+#define CY_AUG_PLAN_STATUS 0
+#define CY_AUG_PLAN_FORM 1
+#define CY_AUG_PLAN_GEO_GRID_X 2
+#define CY_AUG_PLAN_GEO_GRID_Y 3
+#define CY_AUG_PLAN_GEO_GRID_Z 4 /* 2: the plan is that of the call with labels; without them the launch has 1 */
+#define CY_AUG_PLAN_JIT_GRID 5
+#define CY_AUG_PLAN_JIT_TRIPS 6
+#define CY_AUG_PLAN_JIT_LDS 7
+#define CY_AUG_PLAN_SCRATCH_BYTES 8
+#define CY_AUG_PLAN_LAUNCHES 9
+int cy_aug_plan(int views, int out_h, int out_w, int32_t* plan);
+int cy_aug_views(const uint8_t* store_img, const uint8_t* store_lab, const int64_t* h_table, int slices,
+                 long long arena_bytes, const int32_t* ip, const int32_t* h_ip, const double* fp, int views, int out_h,
+                 int out_w, const uint8_t* label_lut, const float* tensor_lut, float* images, int64_t* labels,
+                 uint8_t* scratch, size_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
