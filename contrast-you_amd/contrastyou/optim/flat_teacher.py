@@ -14,7 +14,7 @@ running statistics for the U-Net):
     perturb(a)                data += a * grad, one cy_axpy (manually_forward_with_grad, dmt.py:22-28)
     adam_step(lr, wd)         one cy_adam_step
     ema_from(student, upd)    EMAUpdater(update_bn=True): one cy_ema_update over the parameters when the student's are
-                              slices of one flat buffer in the same order (FusedRAdam), else one cy_ema_update_multi;
+                              slices of one flat buffer in the same order (a FlatOptimizer), else one cy_ema_update_multi;
                               one cy_ema_update_multi over the running statistics
 
 Works on a plain torch.nn model on the GPU as well: there autograd accumulates into the same .grad views.  The Adam

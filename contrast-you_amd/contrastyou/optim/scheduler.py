@@ -5,7 +5,7 @@ base lrs are rescaled by `multiplier` at the hand-over.
 Same constructor, `get_lr()` law, hand-over rule and `state_dict` nesting as
 contrastyou/optim/scheduler.py:19-104 (config/base.yaml:14-17: multiplier 300, warmup_max 10,
 followed by CosineAnnealingLR(T_max=max_epoch-warmup_max, eta_min=1e-7), trainer/base.py:77-89).
-The scheduler only writes `param_group["lr"]`; FusedRAdam reads it on every step.
+The scheduler only writes `param_group["lr"]`; the flat-buffer optimizers read it on every step.
 """
 from __future__ import annotations
 

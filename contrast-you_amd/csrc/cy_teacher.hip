@@ -10,29 +10,14 @@
 // loss: [npix][K] f32 rows, one thread per pixel, grid-stride, one f64 partial per block, a fixed-order finalize, no
 // atomics; neither softmax, nor the warped tensor, nor the difference is stored.
 #include "cy_common.h"
+#include "cy_flat.h"
 #include "cy_pixel_loss.h"
 #include "cy_reduce.h"
 
 namespace {
 
-constexpr int FLAT_GRID_CAP = 2048;   // blocks of the flat sweeps (256 CUs x 8), the rest is grid-stride
 constexpr int EMA_MULTI_MAX = 4096;   // tensors of one multi-tensor launch
 constexpr int EMA_MULTI_BLOCKS = 8192;  // about this many blocks in all: grid.x = clamp(8192 / count, 2, 64)
-
-struct AdamScalars {
-  float beta1, beta2, eps, wd;
-  float step_size;  // lr / (1 - beta1^t)
-  float sqrt_bc2;   // sqrt(1 - beta2^t)
-};
-
-// one element of torch's single-tensor Adam: lerp for the first moment, sqrt(v) / sqrt(bc2) + eps for the denominator
-__device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, const AdamScalars& s) {
-  if (s.wd != 0.f) g = fmaf(s.wd, p, g);
-  m = m + (g - m) * (1.f - s.beta1);
-  v = s.beta2 * v + (1.f - s.beta2) * g * g;
-  const float denom = sqrtf(v) / s.sqrt_bc2 + s.eps;
-  p = p - s.step_size * (m / denom);
-}
 
 // VEC == 4: n4 = n / 4 groups of four, then the n % 4 tail by the first threads of block 0
 template <int VEC>
@@ -176,13 +161,6 @@ __global__ void __launch_bounds__(256)
 }
 
 // ---------------------------------------------------------------- the launch rule
-inline int ptr_align(const void* p) {
-  const uintptr_t v = (uintptr_t)p;
-  return (v % 16 == 0) ? 16 : (v % 8 == 0) ? 8 : (v % 4 == 0) ? 4 : 1;
-}
-
-inline int min_int(int a, int b) { return a < b ? a : b; }
-
 struct TeacherPlan {
   int variant, vec, fwd_grid, fwd_trips, bwd_grid, bwd_trips, rows;
 };
@@ -192,10 +170,9 @@ int teacher_plan(int form, long n, int K, int align, TeacherPlan* pl) {
   if (!pl || n < 1 || align < 1 || align % 4 != 0) return CY_ERR_ARG;
   pl->variant = 0, pl->bwd_grid = pl->bwd_trips = 0, pl->rows = 0;
   if (form == CY_TEACHER_ADAM || form == CY_TEACHER_AXPY) {
-    pl->vec = (align % 16 == 0 && n >= 4) ? 4 : 1;
-    const long groups = n / pl->vec;
-    pl->fwd_grid = cy_blocks(groups, 256, FLAT_GRID_CAP);
-    pl->fwd_trips = cy_trips(groups, pl->fwd_grid, 256);
+    FlatPlan fp;  // cy_flat.h: the rule cy_optim_plan gives too
+    flat_plan(n, align, &fp);
+    pl->vec = fp.vec, pl->fwd_grid = fp.grid, pl->fwd_trips = fp.trips;
     return CY_OK;
   }
   if (form == CY_TEACHER_EMA_MULTI) {  // n: the tensors
@@ -263,11 +240,7 @@ int cy_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg
   TeacherPlan pl;
   const int rc = teacher_plan(CY_TEACHER_ADAM, n, 0, align, &pl);
   if (rc != CY_OK) return rc;
-  AdamScalars s;
-  s.beta1 = beta1, s.beta2 = beta2, s.eps = eps, s.wd = weight_decay;
-  const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
-  s.step_size = (float)((double)lr / bc1);
-  s.sqrt_bc2 = (float)sqrt(bc2);
+  const AdamScalars s = adam_scalars(lr, beta1, beta2, eps, weight_decay, step);
   hipStream_t st = (hipStream_t)stream;
   if (pl.vec == 4)
     hipLaunchKernelGGL(adam_kernel<4>, dim3(pl.fwd_grid), dim3(256), 0, st, param, grad, exp_avg, exp_avg_sq, n, s);

@@ -22,8 +22,8 @@ captured backward contains exactly the eager one.  Detached outputs are returned
 autograd node that raises if a later loss does try to differentiate through them.
 
 Conditions (checked per call; otherwise the eager two-stream path runs): every model parameter has
-a live f32 `.grad` buffer that the kernels accumulate into (FusedRAdam's flat buffers), so that no
-parameter gradient flows through autograd; bench instrumentation is off.  `CY_GRAPH_STEP=0`
+a live f32 `.grad` buffer that the kernels accumulate into (the flat buffers of contrastyou.optim's
+optimizers), so that no parameter gradient flows through autograd; bench instrumentation is off.  `CY_GRAPH_STEP=0`
 disables the capture; a failed capture warns once and training continues eagerly.
 """
 from __future__ import annotations

@@ -2011,6 +2011,39 @@ def axpy(y: Tensor, x: Tensor, a: float) -> None:
     _lib.call("cy_axpy", y.data_ptr(), x.data_ptr(), n, float(a), _stream())
 
 
+# --------------------------------------------------------------------------- SGD / Adam / AdamW on flat buffers (csrc/cy_optim.hip)
+OPTIM_FORMS = {"sgd": _lib.CY_OPTIM_SGD, "adamw": _lib.CY_OPTIM_ADAMW}
+_OPTIM_PLAN = ("vec", "grid", "trips", "tail")
+
+
+def optim_plan(form: str, n: int, align: int = 16) -> dict:
+    """the launch rule of cy_sgd_step / cy_adamw_step (host-side query, no GPU needed): the values of cy_optim_plan by
+    name -- the rule teacher_plan("adam", ...) gives.  What the launches refuse raises HipKernelError with their
+    status."""
+    plan = (C.c_int32 * 4)()
+    _lib.call("cy_optim_plan", OPTIM_FORMS[form], int(n), int(align), plan)
+    return dict(zip(_OPTIM_PLAN, (int(v) for v in plan)))
+
+
+def sgd_step(p: Tensor, g: Tensor, buf: Optional[Tensor], lr: float, momentum: float, dampening: float, wd: float,
+             nesterov: bool, first: bool) -> None:
+    """one torch.optim.SGD update (maximize=False) of flat f32 buffers, in place; `buf` is None exactly when
+    momentum == 0; `first`: this is the update that copies the gradient into the momentum buffer"""
+    n = _flat_f32(p, g) if buf is None else _flat_f32(p, g, buf)
+    _lib.call("cy_sgd_step", p.data_ptr(), g.data_ptr(), None if buf is None else buf.data_ptr(), n, float(lr),
+              float(momentum), float(dampening), float(wd), int(bool(nesterov)), int(bool(first)), _stream())
+
+
+def adamw_step(p: Tensor, g: Tensor, m: Tensor, v: Tensor, vmax: Optional[Tensor], lr: float, beta1: float,
+               beta2: float, eps: float, wd: float, decoupled: bool, step: int) -> None:
+    """one torch.optim.AdamW (`decoupled`) or torch.optim.Adam update (maximize=False) of flat f32 buffers, in place;
+    a `vmax` buffer is amsgrad; `step` is the 1-based count after this update"""
+    n = _flat_f32(p, g, m, v) if vmax is None else _flat_f32(p, g, m, v, vmax)
+    _lib.call("cy_adamw_step", p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(),
+              None if vmax is None else vmax.data_ptr(), n, float(lr), float(beta1), float(beta2), float(eps),
+              float(wd), int(bool(decoupled)), int(step), _stream())
+
+
 def ema_table(pairs, device) -> Tensor:
     """the int64 [count, 3] device table of cy_ema_update_multi for (teacher, student) f32 tensor pairs: the two
     addresses and the element count of each.  Built on the host and uploaded once; the caller caches it and rebuilds

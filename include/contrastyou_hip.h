@@ -1588,6 +1588,42 @@ int cy_softmax_gathermse_bwd(const float* teacher, const int32_t* map, const flo
                              float* dstudent, int N, long HW, int K, void* stream);
 
 /* ------------------------------------------------------------------------
+ * SGD, Adam and AdamW on the flat buffers (csrc/cy_optim.hip; entries added to ABI v18 -- no existing signature changed
+ * and no struct added, so cy_abi_version() stays 18).  They replace torch.optim.SGD / Adam / AdamW's per-tensor (or
+ * foreach) step in contrastyou/optim: FusedSGD, FusedAdam(amsgrad=True) and FusedAdamW launch them once per run of
+ * updated parameters (contrastyou/optim/flat_optimizer.py: FlatOptimizer.step); FusedAdam(amsgrad=False) keeps
+ * cy_adam_step.  Every entry checks its arguments before any launch: a NULL pointer, n < 1, step < 1, a base that is
+ * not 4-byte aligned -> CY_ERR_ARG, as cy_adam_step answers.  The gradient is read only.  No atomics: two runs give the
+ * same bits.  HBM-bound: 20 B/element for SGD with momentum (12 without), 28 for Adam(W), 36 with amsgrad.
+ * ------------------------------------------------------------------------ */
+#define CY_OPTIM_SGD 0   /* cy_sgd_step */
+#define CY_OPTIM_ADAMW 1 /* cy_adamw_step */
+/* The launch rule of the two (host-side only, launches nothing; the launches take every decision from it): the rule
+ * cy_teacher_plan gives CY_TEACHER_ADAM.  `align`: the bytes every buffer base of the call is aligned to (16 and more
+ * count as 16).
+ *   plan[0] vec: floats per memory access: 4 where align is a multiple of 16 and n >= 4, else 1 -- a run of touched
+ *           parameters starts at an arbitrary parameter offset, so training reaches both
+ *   plan[1] grid: min(2048, ceil(n / vec / 256)) blocks of 256
+ *   plan[2] trips: loop trips of the busiest block
+ *   plan[3] tail: the n % 4 elements that the first threads of block 0 finish one float at a time (vec == 4), else 0
+ * CY_ERR_ARG for a NULL `plan`, an unknown form, n < 1 or an align that is no multiple of 4. */
+int cy_optim_plan(int form, long n, int align, int32_t* plan /* [4] */);
+/* torch.optim.SGD(maximize=False) on flat f32 buffers of n elements.  g += wd p (wd != 0); with momentum:
+ * buf = g when `first` (the buffer's content is not read), else buf = momentum buf + (1 - dampening) g; then
+ * g += momentum buf (nesterov) or g = buf;  p -= lr g.  `momentum_buf` is NULL exactly when momentum == 0: any other
+ * pairing is CY_ERR_ARG. */
+int cy_sgd_step(float* param, const float* grad, float* momentum_buf, long n, float lr, float momentum,
+                float dampening, float weight_decay, int nesterov, int first, void* stream);
+/* torch.optim.AdamW (decoupled = 1: p *= 1 - lr wd first, no L2 term) or torch.optim.Adam (decoupled = 0: g += wd p) on
+ * flat f32 buffers of n elements; `step` is the 1-based count after this update.  A non-NULL `max_exp_avg_sq` is
+ * amsgrad: vmax = max(vmax, v) and the denominator is sqrt(vmax) / sqrt(bc2) + eps.  Moments, bias corrections and the
+ * update are cy_adam_step's, term for term (bc_i in f64 on the host, lr / bc1 and sqrt(bc2) rounded to f32 once);
+ * 1 - lr wd is formed in f64 and rounded to f32 once. */
+int cy_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq, long n,
+                  float lr, float beta1, float beta2, float eps, float weight_decay, int decoupled, long step,
+                  void* stream);
+
+/* ------------------------------------------------------------------------
  * Wide-K regularisers (csrc/cy_wide_reg.hip; entries added to ABI v18 -- no existing signature changed and no struct
  * added, so cy_abi_version() stays 18).  The entropy, self-MSE, UA-MT and ICT losses above on multi-prototype logits,
  * 16 < K <= 64: the same arguments, values and launch counts as cy_softmax_entropy_*, cy_softmax_selfmse_*,
