@@ -186,22 +186,22 @@ int aug_check_views(const int64_t* h_table, int slices, long long arena_bytes, c
 
 extern "C" {
 
-int cy_aug_plan(int views, int out_h, int out_w, int32_t* plan) {
-  if (!plan) return CY_ERR_ARG;
-  for (int i = 0; i < CY_AUG_PLAN_LEN; ++i) plan[i] = 0;
+int cy_aug_plan(int views, int out_h, int out_w, cy_aug_plan_t* out) {
+  if (!out) return CY_ERR_ARG;
+  *out = {};
   const int rc = aug_check_sizes(views, out_h, out_w);
-  plan[CY_AUG_PLAN_STATUS] = rc;
+  out->status = rc;
   if (rc != CY_OK) return rc;
   const int hw = out_h * out_w;
-  plan[CY_AUG_PLAN_FORM] = CY_AUG_FORM_TWO_STAGE;
-  plan[CY_AUG_PLAN_GEO_GRID_X] = cy_cdiv(hw, CY_AUG_GEO_BLOCK);
-  plan[CY_AUG_PLAN_GEO_GRID_Y] = views;
-  plan[CY_AUG_PLAN_GEO_GRID_Z] = 2;
-  plan[CY_AUG_PLAN_JIT_GRID] = views;
-  plan[CY_AUG_PLAN_JIT_TRIPS] = cy_cdiv(hw, CY_AUG_JIT_BLOCK);
-  plan[CY_AUG_PLAN_JIT_LDS] = 256 + 256 * 4 + (CY_AUG_JIT_BLOCK / CY_WAVE) * 4;
-  plan[CY_AUG_PLAN_SCRATCH_BYTES] = views * hw;  // <= 4096 * 512 * 512 = 2^30
-  plan[CY_AUG_PLAN_LAUNCHES] = 2;
+  out->form = CY_AUG_FORM_TWO_STAGE;
+  out->geo_grid_x = cy_cdiv(hw, CY_AUG_GEO_BLOCK);
+  out->geo_grid_y = views;
+  out->geo_grid_z = 2;
+  out->jit_grid = views;
+  out->jit_trips = cy_cdiv(hw, CY_AUG_JIT_BLOCK);
+  out->jit_lds = 256 + 256 * 4 + (CY_AUG_JIT_BLOCK / CY_WAVE) * 4;
+  out->scratch_bytes = views * hw;  // <= 4096 * 512 * 512 = 2^30
+  out->launches = 2;
   return CY_OK;
 }
 

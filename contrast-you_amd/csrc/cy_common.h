@@ -132,6 +132,12 @@ __device__ __forceinline__ void st16(void* p, const u32x4& v) {
 
 static inline int cy_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 static inline int cy_roundup(int a, int b) { return ((a + b - 1) / b) * b; }
+static inline int min_int(int a, int b) { return a < b ? a : b; }
+// the bytes a base pointer is aligned to, as the launch rules count them: 16 (and more), 8, 4 or 1
+static inline int ptr_align(const void* p) {
+  const uintptr_t v = (uintptr_t)p;
+  return (v % 16 == 0) ? 16 : (v % 8 == 0) ? 8 : (v % 4 == 0) ? 4 : 1;
+}
 
 // launch size of a grid-stride kernel: blocks of `per_block` items for `items`, at least 1, at most `cap`
 constexpr int cy_blocks(long items, long per_block, long cap) {

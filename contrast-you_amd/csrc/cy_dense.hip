@@ -438,14 +438,15 @@ int cy_dense_proj_fwd(const void* x, const float* w1, const float* b1, const int
   return CY_OK;
 }
 
-int cy_dense_proj_plan(int C, int hid, int dtype, float slope, int32_t* plan) {
-  if (!plan) return CY_ERR_ARG;
+int cy_dense_proj_plan(int C, int hid, int dtype, float slope, cy_dense_proj_plan_t* out) {
+  if (!out) return CY_ERR_ARG;
   DpPlan P;
   const int rc = dp_plan(C, hid, dtype, slope, P);
   if (rc != CY_OK) return rc;
-  plan[0] = P.form, plan[1] = P.cb, plan[2] = P.fwd_pass, plan[3] = P.dw_pass;
-  plan[4] = P.lds_fwd > P.lds_dx ? P.lds_fwd : P.lds_dx;
-  plan[5] = dp_plan_launches(P, false), plan[6] = dp_plan_launches(P, true), plan[7] = P.w_global;
+  out->form = P.form, out->channel_blocks = P.cb, out->fwd_passes = P.fwd_pass, out->dw_passes = P.dw_pass;
+  out->lds_bytes = P.lds_fwd > P.lds_dx ? P.lds_fwd : P.lds_dx;
+  out->bwd_launches = dp_plan_launches(P, false), out->bwd_launches_list = dp_plan_launches(P, true);
+  out->w1_image_in_ws = P.w_global;
   return CY_OK;
 }
 

@@ -8,13 +8,6 @@ namespace {
 
 constexpr int FLAT_GRID_CAP = 2048;  // blocks of the flat sweeps (256 CUs x 8), the rest is grid-stride
 
-inline int ptr_align(const void* p) {
-  const uintptr_t v = (uintptr_t)p;
-  return (v % 16 == 0) ? 16 : (v % 8 == 0) ? 8 : (v % 4 == 0) ? 4 : 1;
-}
-
-inline int min_int(int a, int b) { return a < b ? a : b; }
-
 struct FlatPlan {
   int vec, grid, trips;
 };

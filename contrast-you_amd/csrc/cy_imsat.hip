@@ -30,7 +30,7 @@ constexpr int IMSAT_FWD_CAP = 1024;  // blocks; the forward writes one row of pa
 constexpr int IMSAT_BWD_CAP = 2048;
 
 // ---------------------------------------------------------------- the launch rule (host)
-// what cy_imsat_plan answers: `status`, then the nine values of its array in their order
+// what cy_imsat_plan answers: `status`, then the fields of cy_imsat_plan_t
 struct ImsatPlan {
   int32_t status, vec, kt, threads, tile, fwd_grid, fwd_trips, bwd_grid, bwd_trips, slots;
 };
@@ -404,13 +404,13 @@ int sweep_bwd(const float* x1, const float* x2, const float* coef, const float* 
 
 extern "C" {
 
-int cy_imsat_plan(int form, long R, int K, int align, int32_t* plan) {
+int cy_imsat_plan(int form, long R, int K, int align, cy_imsat_plan_t* out) {
   ImsatPlan p;
-  if (!plan) return CY_ERR_ARG;
+  if (!out) return CY_ERR_ARG;
   const int rc = plan_fill(form, R, K, align, &p);
   if (rc != CY_OK || p.status != CY_OK) return rc != CY_OK ? rc : p.status;
-  const int32_t v[9] = {p.vec, p.kt, p.threads, p.tile, p.fwd_grid, p.fwd_trips, p.bwd_grid, p.bwd_trips, p.slots};
-  for (int i = 0; i < 9; ++i) plan[i] = v[i];
+  out->vec = p.vec, out->kt = p.kt, out->threads = p.threads, out->tile = p.tile, out->slots = p.slots;
+  out->fwd_grid = p.fwd_grid, out->fwd_trips = p.fwd_trips, out->bwd_grid = p.bwd_grid, out->bwd_trips = p.bwd_trips;
   return CY_OK;
 }
 

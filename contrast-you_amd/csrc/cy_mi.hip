@@ -698,7 +698,6 @@ __global__ void __launch_bounds__(256)
   }
 }
 
-constexpr int JP_PLAN = 16;       // values of cy_joint_patch_plan
 constexpr int JP_TARGET = 1024;   // blocks the staged forward aims at (4 per CU) before a block walks several tiles
 
 struct patch_plan {
@@ -979,14 +978,15 @@ int patch_plan_of(int N, int H, int W, int k, int pad, int patch, int kernel, pa
 
 extern "C" {
 
-int cy_joint_patch_plan(int N, int H, int W, int k, int pad, int patch, int kernel, int32_t* plan) {
-  if (!plan) return CY_ERR_ARG;
+int cy_joint_patch_plan(int N, int H, int W, int k, int pad, int patch, int kernel, cy_joint_patch_plan_t* out) {
+  if (!out) return CY_ERR_ARG;
   patch_plan p;
   const int rc = patch_plan_of(N, H, W, k, pad, patch, kernel, &p);
   if (rc != CY_OK) return rc;
-  const int v[JP_PLAN] = {p.P, p.nph, p.npw, p.eh, p.ew, p.kernel, p.R, p.tiles_h, p.ntile, p.nbx, p.grid_y, p.fwd_lds,
-                          p.fwd_vec, p.staged_fits, p.bwd_kernel, p.bwd_grid};
-  for (int i = 0; i < JP_PLAN; ++i) plan[i] = v[i];
+  out->P = p.P, out->nph = p.nph, out->npw = p.npw, out->eh = p.eh, out->ew = p.ew, out->fwd_kernel = p.kernel;
+  out->R = p.R, out->tiles_h = p.tiles_h, out->ntile = p.ntile, out->nbx = p.nbx, out->grid_y = p.grid_y;
+  out->fwd_lds = p.fwd_lds, out->fwd_vec = p.fwd_vec, out->staged_fits = p.staged_fits;
+  out->bwd_kernel = p.bwd_kernel, out->bwd_grid = p.bwd_grid;
   return CY_OK;
 }
 

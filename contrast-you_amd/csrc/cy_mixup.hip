@@ -191,19 +191,9 @@ __global__ void __launch_bounds__(256)
 }
 
 // ---------------------------------------------------------------- the launch rule
-inline int ptr_align(const void* p) {
-  const uintptr_t v = (uintptr_t)p;
-  return (v % 16 == 0) ? 16 : (v % 8 == 0) ? 8 : (v % 4 == 0) ? 4 : 1;
-}
-
-inline int min_int(int a, int b) { return a < b ? a : b; }
-
-struct MixPlan {
-  int vec, kt, fwd_grid, fwd_trips, bwd_grid, bwd_trips, rows;
-};
-
-// the one place the three groups take their kernel form and grid from; a status as the launches return it
-int mix_plan(int form, int N, long per_image, int K, int align, MixPlan* pl) {
+// the one place the three groups take their kernel form and grid from; a status as the launches return it, and nothing
+// is written to `pl` before the last refusal
+int mix_plan(int form, int N, long per_image, int K, int align, cy_mix_plan_t* pl) {
   if (!pl || N < 1 || per_image < 1 || align < 1) return CY_ERR_ARG;
   if (form == CY_MIX_IMAGES) {
     if (align % 4 != 0) return CY_ERR_ARG;
@@ -221,9 +211,10 @@ int mix_plan(int form, int N, long per_image, int K, int align, MixPlan* pl) {
   if (form != CY_MIX_KL && form != CY_MIX_MSE) return CY_ERR_ARG;
   if (K < 2 || K > KMAX) return CY_ERR_SHAPE;
   const int row = K == 2 ? 8 : 16;  // bytes of a row access of the compiled forms
-  pl->kt = ((K == 2 || K == 4 || K == 8) && align % row == 0) ? K : 0;
-  if (K == 4 && !pl->kt) return CY_ERR_ARG;  // K == 4 rows are read 16 bytes at a time in the run-time form too
+  const int kt = ((K == 2 || K == 4 || K == 8) && align % row == 0) ? K : 0;
+  if (K == 4 && !kt) return CY_ERR_ARG;  // K == 4 rows are read 16 bytes at a time in the run-time form too
   if (align % 4 != 0) return CY_ERR_ARG;
+  pl->kt = kt;
   pl->vec = pl->kt == 2 ? 2 : pl->kt ? 4 : 1;
   const long npix = (long)N * per_image;
   pl->fwd_grid = cy_blocks(npix, 256, LOSS_GRID_CAP);
@@ -257,20 +248,14 @@ inline size_t mix_ws_bytes(int N, long HW) {
 
 extern "C" {
 
-int cy_mix_plan(int form, int N, long per_image, int K, int align, int32_t* plan) {
-  if (!plan) return CY_ERR_ARG;
-  MixPlan pl;
-  const int rc = mix_plan(form, N, per_image, K, align, &pl);
-  if (rc != CY_OK) return rc;
-  plan[0] = pl.vec, plan[1] = pl.kt, plan[2] = pl.fwd_grid, plan[3] = pl.fwd_trips;
-  plan[4] = pl.bwd_grid, plan[5] = pl.bwd_trips, plan[6] = pl.rows;
-  return CY_OK;
+int cy_mix_plan(int form, int N, long per_image, int K, int align, cy_mix_plan_t* out) {
+  return mix_plan(form, N, per_image, K, align, out);  // (a NULL `out` is the rule's first refusal)
 }
 
 int cy_mix_images(const float* x, const int32_t* index, float w_self, float w_other, float* out, int N, long E,
                   void* stream) {
   if (!x || !index || !out || N < 1 || E < 1 || x == out) return CY_ERR_ARG;
-  MixPlan pl;
+  cy_mix_plan_t pl;
   const int rc = mix_plan(CY_MIX_IMAGES, N, E, 0, min_int(ptr_align(x), ptr_align(out)), &pl);
   if (rc != CY_OK) return rc;
   const dim3 grid(pl.fwd_grid / pl.rows, pl.rows);
@@ -288,7 +273,7 @@ size_t cy_softmax_mixkl_ws_bytes(int N, long HW) { return mix_ws_bytes(N, HW); }
 int cy_softmax_mixkl_fwd(const float* logits, const int64_t* target, const int32_t* index, float w_self, float w_other,
                          float* loss, int N, long HW, int K, float eps, void* ws, size_t ws_bytes, void* stream) {
   if (!logits || !target || !index || !loss || !ws || N < 1 || HW < 1) return CY_ERR_ARG;
-  MixPlan pl;
+  cy_mix_plan_t pl;
   const int rc = mix_plan(CY_MIX_KL, N, HW, K, ptr_align(logits), &pl);
   if (rc != CY_OK) return rc;
   if (ws_bytes < mix_ws_bytes(N, HW)) return CY_ERR_WORKSPACE;
@@ -305,7 +290,7 @@ int cy_softmax_mixkl_fwd(const float* logits, const int64_t* target, const int32
 int cy_softmax_mixkl_bwd(const float* logits, const int64_t* target, const int32_t* index, float w_self, float w_other,
                          const float* gscale, float* dlogits, int N, long HW, int K, float eps, void* stream) {
   if (!logits || !target || !index || !gscale || !dlogits || N < 1 || HW < 1) return CY_ERR_ARG;
-  MixPlan pl;
+  cy_mix_plan_t pl;
   const int rc = mix_plan(CY_MIX_KL, N, HW, K, min_int(ptr_align(logits), ptr_align(dlogits)), &pl);
   if (rc != CY_OK) return rc;
   CY_MIX_LAUNCH(softmax_mixkl_bwd_kernel, pl.kt, pl.bwd_grid, (hipStream_t)stream, logits, target, index, w_self,
@@ -318,7 +303,7 @@ size_t cy_softmax_mixmse_ws_bytes(int N, long HW) { return mix_ws_bytes(N, HW); 
 int cy_softmax_mixmse_fwd(const float* student, const float* teacher, const int32_t* index, float w_self,
                           float w_other, float* loss, int N, long HW, int K, void* ws, size_t ws_bytes, void* stream) {
   if (!student || !teacher || !index || !loss || !ws || N < 1 || HW < 1) return CY_ERR_ARG;
-  MixPlan pl;
+  cy_mix_plan_t pl;
   const int rc = mix_plan(CY_MIX_MSE, N, HW, K, min_int(ptr_align(student), ptr_align(teacher)), &pl);
   if (rc != CY_OK) return rc;
   if (ws_bytes < mix_ws_bytes(N, HW)) return CY_ERR_WORKSPACE;
@@ -335,7 +320,7 @@ int cy_softmax_mixmse_fwd(const float* student, const float* teacher, const int3
 int cy_softmax_mixmse_bwd(const float* student, const float* teacher, const int32_t* index, float w_self,
                           float w_other, const float* gscale, float* dstudent, int N, long HW, int K, void* stream) {
   if (!student || !teacher || !index || !gscale || !dstudent || N < 1 || HW < 1) return CY_ERR_ARG;
-  MixPlan pl;
+  cy_mix_plan_t pl;
   const int rc = mix_plan(CY_MIX_MSE, N, HW, K,
                           min_int(min_int(ptr_align(student), ptr_align(teacher)), ptr_align(dstudent)), &pl);
   if (rc != CY_OK) return rc;

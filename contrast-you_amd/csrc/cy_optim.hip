@@ -132,12 +132,12 @@ int optim_plan(int form, long n, int align, FlatPlan* pl) {
 
 extern "C" {
 
-int cy_optim_plan(int form, long n, int align, int32_t* plan) {
-  if (!plan) return CY_ERR_ARG;
+int cy_optim_plan(int form, long n, int align, cy_optim_plan_t* out) {
+  if (!out) return CY_ERR_ARG;
   FlatPlan pl;
   const int rc = optim_plan(form, n, align, &pl);
   if (rc != CY_OK) return rc;
-  plan[0] = pl.vec, plan[1] = pl.grid, plan[2] = pl.trips, plan[3] = pl.vec == 4 ? (int)(n % 4) : 0;
+  out->vec = pl.vec, out->grid = pl.grid, out->trips = pl.trips, out->tail = pl.vec == 4 ? (int)(n % 4) : 0;
   return CY_OK;
 }
 

@@ -523,13 +523,14 @@ int pm_launch_bwd(const PmPlan& P, const void* x, const int32_t* idx, const floa
 
 extern "C" {
 
-int cy_pixel_mlp_plan(long M, int C, int hid, int out, int dtype, int32_t* plan) {
+int cy_pixel_mlp_plan(long M, int C, int hid, int out, int dtype, cy_pixel_mlp_plan_t* plan) {
   if (!plan) return CY_ERR_ARG;
   PmPlan P;
   const int rc = pm_plan(M, C, hid, out, dtype, P);
   if (rc != CY_OK) return rc;
-  plan[0] = P.form, plan[1] = P.tm, plan[2] = P.fwd_wgs, plan[3] = P.fwd_trips, plan[4] = P.bwd_wgs, plan[5] = P.bwd_trips;
-  plan[6] = P.slabs, plan[7] = P.lds_fwd > P.lds_bwd ? P.lds_fwd : P.lds_bwd;
+  plan->form = P.form, plan->rows_per_tile = P.tm, plan->slabs = P.slabs;
+  plan->fwd_grid = P.fwd_wgs, plan->fwd_trips = P.fwd_trips, plan->bwd_grid = P.bwd_wgs, plan->bwd_trips = P.bwd_trips;
+  plan->lds_bytes = P.lds_fwd > P.lds_bwd ? P.lds_fwd : P.lds_bwd;
   return CY_OK;
 }
 

@@ -277,22 +277,12 @@ __global__ void __launch_bounds__(256)
 }
 
 // ---------------------------------------------------------------- the launch rule
-inline int ptr_align(const void* p) {
-  const uintptr_t v = (uintptr_t)p;
-  return (v % 16 == 0) ? 16 : (v % 8 == 0) ? 8 : (v % 4 == 0) ? 4 : 1;
-}
-
-inline int min_int(int a, int b) { return a < b ? a : b; }
-
-struct PriorPlan {
-  int variant, vec, fwd_grid, fwd_trips, bwd_grid, bwd_trips, k_chunks, fwd_lds, bwd_lds, aux;
-};
-
 // the most dynamic LDS a launch asks for: the backward's rows and Gram matrix at K = 64, C = 256 (80 KB of the CU's 160)
 constexpr int ORTHO_LDS_MAX = (ORTHO_ELEMS + PRIOR_KMAX * PRIOR_KMAX) * 4;
 
-// the one place every launch takes its kernel form, grid and LDS from; a status as the launches return it
-int prior_plan(int form, long n, int K, int C, int align, PriorPlan* pl) {
+// the one place every launch takes its kernel form, grid and LDS from; a status as the launches return it, and nothing
+// is written to `pl` before the last refusal
+int prior_plan(int form, long n, int K, int C, int align, cy_prior_plan_t* pl) {
   if (!pl) return CY_ERR_ARG;
   if (form == CY_PRIOR_DAE) {
     if (n < 1 || align < 1 || align % 4 != 0) return CY_ERR_ARG;
@@ -363,14 +353,8 @@ inline bool dae_act_ok(int act) { return act == CY_PRIOR_ACT_SIGMOID || act == C
 
 extern "C" {
 
-int cy_prior_plan(int form, long n, int K, int C, int align, int32_t* plan) {
-  if (!plan) return CY_ERR_ARG;
-  PriorPlan pl;
-  const int rc = prior_plan(form, n, K, C, align, &pl);
-  if (rc != CY_OK) return rc;
-  plan[0] = pl.variant, plan[1] = pl.vec, plan[2] = pl.fwd_grid, plan[3] = pl.fwd_trips, plan[4] = pl.bwd_grid;
-  plan[5] = pl.bwd_trips, plan[6] = pl.k_chunks, plan[7] = pl.fwd_lds, plan[8] = pl.bwd_lds, plan[9] = pl.aux;
-  return CY_OK;
+int cy_prior_plan(int form, long n, int K, int C, int align, cy_prior_plan_t* out) {
+  return prior_plan(form, n, K, C, align, out);  // (a NULL `out` is the rule's first refusal)
 }
 
 size_t cy_dae_ws_bytes(long npix, int K, int backward) { return dae_ws_bytes(npix, K, backward); }
@@ -379,7 +363,7 @@ int cy_dae_fwd(const float* logits, const float* w, const float* b, const float*
                int K, int Cimg, int act, void* ws, size_t ws_bytes, void* stream) {
   if (!logits || !w || !b || !image || !loss || !ws || N < 1 || HW < 1) return CY_ERR_ARG;
   const long npix = (long)N * HW;
-  PriorPlan pl;
+  cy_prior_plan_t pl;
   const int rc = prior_plan(CY_PRIOR_DAE, npix, K, Cimg, min_int(ptr_align(logits), 16), &pl);
   if (rc != CY_OK) return rc;
   if (!dae_act_ok(act)) return CY_ERR_SHAPE;
@@ -398,7 +382,7 @@ int cy_dae_bwd(const float* logits, const float* w, const float* b, const float*
                size_t ws_bytes, void* stream) {
   if (!logits || !w || !b || !image || !gscale || !dlogits || !dw || !db || !ws || N < 1 || HW < 1) return CY_ERR_ARG;
   const long npix = (long)N * HW;
-  PriorPlan pl;
+  cy_prior_plan_t pl;
   const int rc = prior_plan(CY_PRIOR_DAE, npix, K, Cimg, min_int(ptr_align(logits), 16), &pl);
   if (rc != CY_OK) return rc;
   if (!dae_act_ok(act)) return CY_ERR_SHAPE;
@@ -415,7 +399,7 @@ int cy_dae_bwd(const float* logits, const float* w, const float* b, const float*
 
 int cy_ortho_fwd(const float* prototypes, float* loss, int K, int C, void* stream) {
   if (!prototypes || !loss) return CY_ERR_ARG;
-  PriorPlan pl;
+  cy_prior_plan_t pl;
   const int rc = prior_plan(CY_PRIOR_ORTHO, 0, K, C, 4, &pl);
   if (rc != CY_OK) return rc;
   if (ptr_align(prototypes) < 4) return CY_ERR_ARG;
@@ -431,7 +415,7 @@ int cy_ortho_fwd(const float* prototypes, float* loss, int K, int C, void* strea
 
 int cy_ortho_bwd(const float* prototypes, const float* gscale, float* dprototypes, int K, int C, void* stream) {
   if (!prototypes || !gscale || !dprototypes) return CY_ERR_ARG;
-  PriorPlan pl;
+  cy_prior_plan_t pl;
   const int rc = prior_plan(CY_PRIOR_ORTHO, 0, K, C, 4, &pl);
   if (rc != CY_OK) return rc;
   if (ptr_align(prototypes) < 4 || ptr_align(dprototypes) < 4) return CY_ERR_ARG;

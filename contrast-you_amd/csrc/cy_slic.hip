@@ -411,30 +411,31 @@ size_t cy_slic_ws_bytes(int N, int H, int W, int n_segments) {
   return 6 * slic_plane(N, H, W) + slic_acc_bytes(N, g.K) + slic_align((size_t)N * g.K * 3 * 4);
 }
 
-int cy_slic_plan(int N, int H, int W, int n_segments, double sigma, double compactness, int max_iter, int32_t* plan) {
-  if (!plan) return CY_ERR_ARG;
-  for (int i = 0; i < CY_SLIC_PLAN_LEN; ++i) plan[i] = 0;
+int cy_slic_plan(int N, int H, int W, int n_segments, double sigma, double compactness, int max_iter,
+                 cy_slic_plan_t* out) {
+  if (!out) return CY_ERR_ARG;
+  *out = {};
   SlicGeom g = {};
   int rc = max_iter < 0 ? CY_ERR_ARG : slic_check_shape(N, H, W);
   if (rc == CY_OK) rc = slic_blur_radius(H, W, sigma, &g.r);
   if (rc == CY_OK) rc = slic_compactness(compactness, &g.M);
   if (rc == CY_OK) rc = slic_grid(H, W, n_segments, &g);
-  plan[CY_SLIC_PLAN_STATUS] = rc;
+  out->status = rc;
   if (rc != CY_OK) return rc;
   const int HW = H * W;
-  plan[CY_SLIC_PLAN_R] = g.r, plan[CY_SLIC_PLAN_S] = g.S, plan[CY_SLIC_PLAN_START] = g.start;
-  plan[CY_SLIC_PLAN_KY] = g.Ky, plan[CY_SLIC_PLAN_KX] = g.Kx, plan[CY_SLIC_PLAN_K] = g.K;
-  plan[CY_SLIC_PLAN_M] = g.M, plan[CY_SLIC_PLAN_MIN_SIZE] = g.min_size;
-  plan[CY_SLIC_PLAN_BLUR_FORM] = sigma == 0.0 ? CY_SLIC_BLUR_QUANT : CY_SLIC_BLUR_TWO_PASS;
-  plan[CY_SLIC_PLAN_BLUR_GRID_X] = sigma == 0.0 ? cy_cdiv(HW, 256) : cy_cdiv(W, CY_SLIC_TW);
-  plan[CY_SLIC_PLAN_BLUR_GRID_Y] = sigma == 0.0 ? N : cy_cdiv(H, CY_SLIC_TH);
-  plan[CY_SLIC_PLAN_BLUR_LDS_H] = sigma == 0.0 ? 0 : (CY_SLIC_TH + 2 * g.r) * CY_SLIC_TW * 4;
-  plan[CY_SLIC_PLAN_BLUR_LDS_W] = sigma == 0.0 ? 0 : CY_SLIC_TH * (CY_SLIC_TW + 2 * g.r) * 4;
-  plan[CY_SLIC_PLAN_PIXEL_GRID_X] = cy_cdiv(HW, 256);
-  plan[CY_SLIC_PLAN_ASSIGN_LDS] = 12 * CY_SLIC_MAX_K;
-  plan[CY_SLIC_PLAN_UPDATE_GRID] = cy_cdiv((long)N * g.K, 256);
-  plan[CY_SLIC_PLAN_SCAN_TILES] = cy_cdiv(HW, CY_SLIC_SCAN);
-  plan[CY_SLIC_PLAN_LAUNCHES] = (sigma == 0.0 ? 1 : 2) + 1 + 2 * max_iter + 5;
+  out->r = g.r, out->S = g.S, out->start = g.start;
+  out->Ky = g.Ky, out->Kx = g.Kx, out->K = g.K;
+  out->M = g.M, out->min_size = g.min_size;
+  out->blur_form = sigma == 0.0 ? CY_SLIC_BLUR_QUANT : CY_SLIC_BLUR_TWO_PASS;
+  out->blur_grid_x = sigma == 0.0 ? cy_cdiv(HW, 256) : cy_cdiv(W, CY_SLIC_TW);
+  out->blur_grid_y = sigma == 0.0 ? N : cy_cdiv(H, CY_SLIC_TH);
+  out->blur_lds_h = sigma == 0.0 ? 0 : (CY_SLIC_TH + 2 * g.r) * CY_SLIC_TW * 4;
+  out->blur_lds_w = sigma == 0.0 ? 0 : CY_SLIC_TH * (CY_SLIC_TW + 2 * g.r) * 4;
+  out->pixel_grid_x = cy_cdiv(HW, 256);
+  out->assign_lds = 12 * CY_SLIC_MAX_K;
+  out->update_grid = cy_cdiv((long)N * g.K, 256);
+  out->scan_tiles = cy_cdiv(HW, CY_SLIC_SCAN);
+  out->launches = (sigma == 0.0 ? 1 : 2) + 1 + 2 * max_iter + 5;
   return CY_OK;
 }
 

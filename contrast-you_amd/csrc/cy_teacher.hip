@@ -161,13 +161,13 @@ __global__ void __launch_bounds__(256)
 }
 
 // ---------------------------------------------------------------- the launch rule
-struct TeacherPlan {
-  int variant, vec, fwd_grid, fwd_trips, bwd_grid, bwd_trips, rows;
-};
-
-// the one place the four families take their kernel form and grid from; a status as the launches return it
-int teacher_plan(int form, long n, int K, int align, TeacherPlan* pl) {
+// the one place the four families take their kernel form and grid from; a status as the launches return it, and nothing
+// is written to `pl` before the last refusal
+int teacher_plan(int form, long n, int K, int align, cy_teacher_plan_t* pl) {
   if (!pl || n < 1 || align < 1 || align % 4 != 0) return CY_ERR_ARG;
+  if (form < CY_TEACHER_ADAM || form > CY_TEACHER_GATHERMSE) return CY_ERR_ARG;
+  if (form == CY_TEACHER_EMA_MULTI && n > EMA_MULTI_MAX) return CY_ERR_SHAPE;
+  if (form == CY_TEACHER_GATHERMSE && (K < 2 || K > KMAX)) return CY_ERR_SHAPE;
   pl->variant = 0, pl->bwd_grid = pl->bwd_trips = 0, pl->rows = 0;
   if (form == CY_TEACHER_ADAM || form == CY_TEACHER_AXPY) {
     FlatPlan fp;  // cy_flat.h: the rule cy_optim_plan gives too
@@ -176,7 +176,6 @@ int teacher_plan(int form, long n, int K, int align, TeacherPlan* pl) {
     return CY_OK;
   }
   if (form == CY_TEACHER_EMA_MULTI) {  // n: the tensors
-    if (n > EMA_MULTI_MAX) return CY_ERR_SHAPE;
     long gx = EMA_MULTI_BLOCKS / n;
     gx = gx < 2 ? 2 : gx > 64 ? 64 : gx;
     pl->vec = 1;
@@ -185,18 +184,15 @@ int teacher_plan(int form, long n, int K, int align, TeacherPlan* pl) {
     pl->fwd_trips = (int)gx * 256;  // elements of a tensor that one trip covers
     return CY_OK;
   }
-  if (form == CY_TEACHER_GATHERMSE) {  // n: the pixels
-    if (K < 2 || K > KMAX) return CY_ERR_SHAPE;
-    const int row = K == 2 ? 8 : 16;  // bytes of a row access of the compiled forms
-    pl->variant = ((K == 2 || K == 4 || K == 8) && align % row == 0) ? K : 0;
-    pl->vec = pl->variant == 2 ? 2 : pl->variant ? 4 : 1;
-    pl->fwd_grid = cy_blocks(n, 256, LOSS_GRID_CAP);
-    pl->bwd_grid = pl->fwd_grid * 2;
-    pl->fwd_trips = cy_trips(n, pl->fwd_grid, 256);
-    pl->bwd_trips = cy_trips(n, pl->bwd_grid, 256);
-    return CY_OK;
-  }
-  return CY_ERR_ARG;
+  // CY_TEACHER_GATHERMSE, n: the pixels
+  const int row = K == 2 ? 8 : 16;  // bytes of a row access of the compiled forms
+  pl->variant = ((K == 2 || K == 4 || K == 8) && align % row == 0) ? K : 0;
+  pl->vec = pl->variant == 2 ? 2 : pl->variant ? 4 : 1;
+  pl->fwd_grid = cy_blocks(n, 256, LOSS_GRID_CAP);
+  pl->bwd_grid = pl->fwd_grid * 2;
+  pl->fwd_trips = cy_trips(n, pl->fwd_grid, 256);
+  pl->bwd_trips = cy_trips(n, pl->bwd_grid, 256);
+  return CY_OK;
 }
 
 // launch `KERNEL<variant>` of the gather-MSE pair
@@ -222,14 +218,8 @@ inline size_t gather_ws_bytes(int N, long HW) {
 
 extern "C" {
 
-int cy_teacher_plan(int form, long n, int K, int align, int32_t* plan) {
-  if (!plan) return CY_ERR_ARG;
-  TeacherPlan pl;
-  const int rc = teacher_plan(form, n, K, align, &pl);
-  if (rc != CY_OK) return rc;
-  plan[0] = pl.variant, plan[1] = pl.vec, plan[2] = pl.fwd_grid, plan[3] = pl.fwd_trips;
-  plan[4] = pl.bwd_grid, plan[5] = pl.bwd_trips, plan[6] = pl.rows;
-  return CY_OK;
+int cy_teacher_plan(int form, long n, int K, int align, cy_teacher_plan_t* out) {
+  return teacher_plan(form, n, K, align, out);  // (a NULL `out` is the rule's first refusal)
 }
 
 int cy_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long n, float lr, float beta1,
@@ -237,7 +227,7 @@ int cy_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg
   if (!param || !grad || !exp_avg || !exp_avg_sq || n <= 0 || step < 1) return CY_ERR_ARG;
   const int align =
       min_int(min_int(ptr_align(param), ptr_align(grad)), min_int(ptr_align(exp_avg), ptr_align(exp_avg_sq)));
-  TeacherPlan pl;
+  cy_teacher_plan_t pl;
   const int rc = teacher_plan(CY_TEACHER_ADAM, n, 0, align, &pl);
   if (rc != CY_OK) return rc;
   const AdamScalars s = adam_scalars(lr, beta1, beta2, eps, weight_decay, step);
@@ -252,7 +242,7 @@ int cy_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg
 
 int cy_axpy(float* y, const float* x, long n, float a, void* stream) {
   if (!y || !x || n <= 0) return CY_ERR_ARG;
-  TeacherPlan pl;
+  cy_teacher_plan_t pl;
   const int rc = teacher_plan(CY_TEACHER_AXPY, n, 0, min_int(ptr_align(y), ptr_align(x)), &pl);
   if (rc != CY_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
@@ -268,7 +258,7 @@ int cy_ema_update_multi(const int64_t* table, int count, float alpha, float weig
   if (!table) return CY_ERR_ARG;
   if (count < 1 || count > EMA_MULTI_MAX) return CY_ERR_SHAPE;
   if (ptr_align(table) < 8) return CY_ERR_ARG;
-  TeacherPlan pl;
+  cy_teacher_plan_t pl;
   const int rc = teacher_plan(CY_TEACHER_EMA_MULTI, count, 0, 4, &pl);
   if (rc != CY_OK) return rc;
   hipLaunchKernelGGL(ema_multi_kernel, dim3(pl.fwd_grid, pl.rows), dim3(256), 0, (hipStream_t)stream, table, alpha,
@@ -283,7 +273,7 @@ int cy_softmax_gathermse_fwd(const float* teacher, const int32_t* map, const flo
                              long HW, int K, void* ws, size_t ws_bytes, void* stream) {
   if (!teacher || !map || !student || !loss || !ws || N < 1 || HW < 1) return CY_ERR_ARG;
   const long npix = (long)N * HW;
-  TeacherPlan pl;
+  cy_teacher_plan_t pl;
   const int rc = teacher_plan(CY_TEACHER_GATHERMSE, npix, K, min_int(ptr_align(teacher), ptr_align(student)), &pl);
   if (rc != CY_OK) return rc;
   if (ptr_align(map) < 4 || ptr_align(ws) < 8) return CY_ERR_ARG;
@@ -300,7 +290,7 @@ int cy_softmax_gathermse_bwd(const float* teacher, const int32_t* map, const flo
                              float* dstudent, int N, long HW, int K, void* stream) {
   if (!teacher || !map || !student || !gscale || !dstudent || N < 1 || HW < 1) return CY_ERR_ARG;
   const long npix = (long)N * HW;
-  TeacherPlan pl;
+  cy_teacher_plan_t pl;
   const int rc = teacher_plan(CY_TEACHER_GATHERMSE, npix, K,
                               min_int(min_int(ptr_align(teacher), ptr_align(student)), ptr_align(dstudent)), &pl);
   if (rc != CY_OK) return rc;

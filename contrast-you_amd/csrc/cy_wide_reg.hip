@@ -286,24 +286,14 @@ __global__ void __launch_bounds__(256)
 }
 
 // ---------------------------------------------------------------- the launch rule
-inline int ptr_align(const void* p) {
-  const uintptr_t v = (uintptr_t)p;
-  return (v % 16 == 0) ? 16 : (v % 8 == 0) ? 8 : (v % 4 == 0) ? 4 : 1;
-}
-
-inline int min_int(int a, int b) { return a < b ? a : b; }
-
-struct WidePlan {
-  int vec, rows, fwd_grid, fwd_trips, bwd_grid, bwd_trips;
-};
-
-// the one place the four families take their kernel form and grid from; a status as the launches return it
-int wide_plan(int family, long npix, int K, int align, WidePlan* pl) {
+// the one place the four families take their kernel form and grid from; a status as the launches return it, and nothing
+// is written to `pl` before the last refusal
+int wide_plan(int family, long npix, int K, int align, cy_wide_reg_plan_t* pl) {
   if (!pl || family < CY_WIDE_ENTROPY || family > CY_WIDE_MIXMSE || npix < 1 || align < 1) return CY_ERR_ARG;
   if (K < WIDE_KMIN || K > KROW) return CY_ERR_SHAPE;
   if (align % 4 != 0) return CY_ERR_ARG;
   pl->vec = (K % 4 == 0 && align % 16 == 0) ? 4 : 1;
-  pl->rows = ROWS;
+  pl->rows_per_block = ROWS;
   pl->fwd_grid = pl->bwd_grid = cy_blocks(npix, ROWS, WIDE_GRID_CAP);
   pl->fwd_trips = pl->bwd_trips = cy_trips(npix, pl->fwd_grid, ROWS);
   return CY_OK;
@@ -329,14 +319,8 @@ inline size_t wide_ws_bytes(long npix, int per_block) {
 
 extern "C" {
 
-int cy_wide_reg_plan(int family, long npix, int K, int align, int32_t* plan) {
-  if (!plan) return CY_ERR_ARG;
-  WidePlan pl;
-  const int rc = wide_plan(family, npix, K, align, &pl);
-  if (rc != CY_OK) return rc;
-  plan[0] = pl.vec, plan[1] = pl.rows, plan[2] = pl.fwd_grid, plan[3] = pl.fwd_trips;
-  plan[4] = pl.bwd_grid, plan[5] = pl.bwd_trips;
-  return CY_OK;
+int cy_wide_reg_plan(int family, long npix, int K, int align, cy_wide_reg_plan_t* out) {
+  return wide_plan(family, npix, K, align, out);  // (a NULL `out` is the rule's first refusal)
 }
 
 size_t cy_softmax_entropy_row_ws_bytes(long npix) { return wide_ws_bytes(npix, 1); }
@@ -344,7 +328,7 @@ size_t cy_softmax_entropy_row_ws_bytes(long npix) { return wide_ws_bytes(npix, 1
 int cy_softmax_entropy_row_fwd(const float* logits, float* loss, long npix, int K, float eps, void* ws,
                                size_t ws_bytes, void* stream) {
   if (!logits || !loss || !ws) return CY_ERR_ARG;
-  WidePlan pl;
+  cy_wide_reg_plan_t pl;
   const int rc = wide_plan(CY_WIDE_ENTROPY, npix, K, ptr_align(logits), &pl);
   if (rc != CY_OK) return rc;
   if (ws_bytes < wide_ws_bytes(npix, 1)) return CY_ERR_WORKSPACE;
@@ -359,7 +343,7 @@ int cy_softmax_entropy_row_fwd(const float* logits, float* loss, long npix, int 
 int cy_softmax_entropy_row_bwd(const float* logits, const float* gscale, float* dlogits, long npix, int K, float eps,
                                void* stream) {
   if (!logits || !gscale || !dlogits) return CY_ERR_ARG;
-  WidePlan pl;
+  cy_wide_reg_plan_t pl;
   const int rc = wide_plan(CY_WIDE_ENTROPY, npix, K, min_int(ptr_align(logits), ptr_align(dlogits)), &pl);
   if (rc != CY_OK) return rc;
   CY_WIDE_LAUNCH(softmax_entropy_bwd_row_kernel, pl.vec, pl.bwd_grid, (hipStream_t)stream, logits, gscale, dlogits,
@@ -372,7 +356,7 @@ size_t cy_softmax_selfmse_row_ws_bytes(long npix) { return wide_ws_bytes(npix, 1
 int cy_softmax_selfmse_row_fwd(const float* logits, float* loss, long npix, int K, void* ws, size_t ws_bytes,
                                void* stream) {
   if (!logits || !loss || !ws) return CY_ERR_ARG;
-  WidePlan pl;
+  cy_wide_reg_plan_t pl;
   const int rc = wide_plan(CY_WIDE_SELFMSE, npix, K, ptr_align(logits), &pl);
   if (rc != CY_OK) return rc;
   if (ws_bytes < wide_ws_bytes(npix, 1)) return CY_ERR_WORKSPACE;
@@ -387,7 +371,7 @@ int cy_softmax_selfmse_row_fwd(const float* logits, float* loss, long npix, int 
 int cy_softmax_selfmse_row_bwd(const float* logits, const float* gscale, float* dlogits, long npix, int K,
                                void* stream) {
   if (!logits || !gscale || !dlogits) return CY_ERR_ARG;
-  WidePlan pl;
+  cy_wide_reg_plan_t pl;
   const int rc = wide_plan(CY_WIDE_SELFMSE, npix, K, min_int(ptr_align(logits), ptr_align(dlogits)), &pl);
   if (rc != CY_OK) return rc;
   CY_WIDE_LAUNCH(softmax_selfmse_bwd_row_kernel, pl.vec, pl.bwd_grid, (hipStream_t)stream, logits, gscale, dlogits,
@@ -400,7 +384,7 @@ size_t cy_uamt_mse_row_ws_bytes(long npix) { return wide_ws_bytes(npix, 2); }
 int cy_uamt_mse_row_fwd(const float* teacher, const float* student, float* result, long npix, int K, float thr,
                         int hard, void* ws, size_t ws_bytes, void* stream) {
   if (!teacher || !student || !result || !ws) return CY_ERR_ARG;
-  WidePlan pl;
+  cy_wide_reg_plan_t pl;
   const int rc = wide_plan(CY_WIDE_UAMT, npix, K, min_int(ptr_align(teacher), ptr_align(student)), &pl);
   if (rc != CY_OK) return rc;
   if (ws_bytes < wide_ws_bytes(npix, 2)) return CY_ERR_WORKSPACE;
@@ -415,7 +399,7 @@ int cy_uamt_mse_row_fwd(const float* teacher, const float* student, float* resul
 int cy_uamt_mse_row_bwd(const float* teacher, const float* student, const float* result, const float* gscale,
                         float* dstudent, long npix, int K, float thr, int hard, void* stream) {
   if (!teacher || !student || !result || !gscale || !dstudent) return CY_ERR_ARG;
-  WidePlan pl;
+  cy_wide_reg_plan_t pl;
   const int rc = wide_plan(CY_WIDE_UAMT, npix, K,
                            min_int(min_int(ptr_align(teacher), ptr_align(student)), ptr_align(dstudent)), &pl);
   if (rc != CY_OK) return rc;
@@ -431,7 +415,7 @@ int cy_softmax_mixmse_row_fwd(const float* student, const float* teacher, const 
                               void* stream) {
   if (!student || !teacher || !index || !loss || !ws || N < 1 || HW < 1) return CY_ERR_ARG;
   const long npix = (long)N * HW;
-  WidePlan pl;
+  cy_wide_reg_plan_t pl;
   const int rc = wide_plan(CY_WIDE_MIXMSE, npix, K, min_int(ptr_align(student), ptr_align(teacher)), &pl);
   if (rc != CY_OK) return rc;
   if (ws_bytes < wide_ws_bytes(npix, 1)) return CY_ERR_WORKSPACE;
@@ -449,7 +433,7 @@ int cy_softmax_mixmse_row_bwd(const float* student, const float* teacher, const 
                               void* stream) {
   if (!student || !teacher || !index || !gscale || !dstudent || N < 1 || HW < 1) return CY_ERR_ARG;
   const long npix = (long)N * HW;
-  WidePlan pl;
+  cy_wide_reg_plan_t pl;
   const int rc = wide_plan(CY_WIDE_MIXMSE, npix, K,
                            min_int(min_int(ptr_align(student), ptr_align(teacher)), ptr_align(dstudent)), &pl);
   if (rc != CY_OK) return rc;

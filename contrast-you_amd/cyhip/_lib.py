@@ -100,6 +100,17 @@ ClusterPlan = _struct("cy_cluster_plan")
 JointPlan = _struct("cy_joint_plan_t")
 GroupSoftmaxPlan = _struct("cy_group_softmax_plan_t")
 NormActPlan = _struct("cy_norm_act_plan_t")
+DenseProjPlan = _struct("cy_dense_proj_plan_t")
+JointPatchPlan = _struct("cy_joint_patch_plan_t")
+PixelMlpPlan = _struct("cy_pixel_mlp_plan_t")
+ImsatPlan = _struct("cy_imsat_plan_t")
+MixPlan = _struct("cy_mix_plan_t")
+PriorPlan = _struct("cy_prior_plan_t")
+TeacherPlan = _struct("cy_teacher_plan_t")
+OptimPlan = _struct("cy_optim_plan_t")
+WideRegPlan = _struct("cy_wide_reg_plan_t")
+SlicPlan = _struct("cy_slic_plan_t")  # (and AugPlan: a refusal is their `status` field, the struct zeroed)
+AugPlan = _struct("cy_aug_plan_t")
 WgradReduceEntry = _struct("cy_wgrad_reduce_entry")
 BnAcc = _struct("cy_bn_acc")
 BnFold = _struct("cy_bn_fold")

@@ -265,11 +265,19 @@ def _desc(N, H, W, C1, C2, Cout, mode, prologue, dt, ld1, ld2, ldo, split_c=0, l
     return p
 
 
-def _query(struct, name: str, *args, skip=()) -> dict:
-    """a host-side query whose last argument is a `struct` the library fills in: the fields it answers, by name"""
+def _query(struct, name: str, *args, skip=(), check: bool = True) -> dict:
+    """a host-side query whose last argument is a `struct` the library fills in: the fields it answers, by name.
+    `check` False: for the queries that answer a refusal in the struct's `status` field, nothing is raised"""
     s = struct()
-    _lib.call(name, *args, C.byref(s))
+    if check:
+        _lib.call(name, *args, C.byref(s))
+    else:
+        getattr(_lib.load(), name)(*args, C.byref(s))
     return {f: getattr(s, f) for f, _ in s._fields_ if f not in skip}
+
+
+def _fields(struct) -> tuple:
+    return tuple(f for f, _ in struct._fields_)
 
 
 # cy_conv_plan.kernel
@@ -1636,16 +1644,13 @@ def softmax_mix_kl_bwd(logits: Tensor, target: Tensor, mix: Tensor, gscale: Tens
 WIDE_REG_KMIN, WIDE_REG_KMAX = 17, 64
 WIDE_REG_FAMILIES = {"entropy": _lib.CY_WIDE_ENTROPY, "selfmse": _lib.CY_WIDE_SELFMSE, "uamt": _lib.CY_WIDE_UAMT,
                      "mixmse": _lib.CY_WIDE_MIXMSE}
-_WIDE_REG_PLAN = ("vec", "rows_per_block", "fwd_grid", "fwd_trips", "bwd_grid", "bwd_trips")
 
 
 def wide_reg_plan(family: str, npix: int, K: int, align: int = 16) -> dict:
     """the launch rule of the wide-K regularisers (host-side query, no GPU needed): the values of cy_wide_reg_plan by
     name.  `align`: the bytes every base pointer of the call is aligned to.  What the launches refuse raises
     HipKernelError with their status."""
-    plan = (C.c_int32 * 6)()
-    _lib.call("cy_wide_reg_plan", WIDE_REG_FAMILIES[family], int(npix), int(K), int(align), plan)
-    return dict(zip(_WIDE_REG_PLAN, (int(v) for v in plan)))
+    return _query(_lib.WideRegPlan, "cy_wide_reg_plan", WIDE_REG_FAMILIES[family], int(npix), int(K), int(align))
 
 
 def _by_k(name: str, K: int) -> str:
@@ -1715,16 +1720,11 @@ IMSAT_FORMS = {"rows": _lib.CY_IMSAT_ROWS, "pair": _lib.CY_IMSAT_PAIR, "logits":
 IMSAT_LOGITS_KMAX = 16  # classes of cy_softmax_imsat_*
 
 
-_IMSAT_PLAN = ("vec", "kt", "threads", "tile", "fwd_grid", "fwd_trips", "bwd_grid", "bwd_trips", "slots")
-
-
 def imsat_plan(form: str, R: int, K: int, align: int = 16) -> dict:
     """the launch rule of the IMSAT kernels (host-side query, no GPU needed): the values of cy_imsat_plan by name, and
     "ws_bytes", the forward's workspace.  `align`: the bytes every base pointer of the call is aligned to.  What the
     launches refuse raises HipKernelError with their status."""
-    plan = (C.c_int32 * 9)()
-    _lib.call("cy_imsat_plan", IMSAT_FORMS[form], int(R), int(K), int(align), plan)
-    out = dict(zip(_IMSAT_PLAN, (int(v) for v in plan)))
+    out = _query(_lib.ImsatPlan, "cy_imsat_plan", IMSAT_FORMS[form], int(R), int(K), int(align))
     query = {"rows": "cy_imsat_ws_bytes", "pair": "cy_imsat_pair_ws_bytes", "logits": "cy_softmax_imsat_ws_bytes"}
     out["ws_bytes"] = int(getattr(_lib.load(), query[form])(int(R), int(K)))
     return out
@@ -1806,16 +1806,13 @@ def softmax_imsat_bwd(logits: Tensor, coef: Tensor, g: Tensor) -> Tensor:
 
 # --------------------------------------------------------------------------- MixUp and ICT (csrc/cy_mixup.hip)
 MIX_FORMS = {"images": _lib.CY_MIX_IMAGES, "mixkl": _lib.CY_MIX_KL, "mixmse": _lib.CY_MIX_MSE}
-_MIX_PLAN = ("vec", "kt", "fwd_grid", "fwd_trips", "bwd_grid", "bwd_trips", "rows")
 
 
 def mix_plan(form: str, N: int, per_image: int, K: int = 0, align: int = 16) -> dict:
     """the launch rule of the mixing kernels (host-side query, no GPU needed): the values of cy_mix_plan by name.
     `per_image`: the elements of an image (form "images") or its pixels (the losses).  What the launches refuse raises
     HipKernelError with their status."""
-    plan = (C.c_int32 * 7)()
-    _lib.call("cy_mix_plan", MIX_FORMS[form], int(N), int(per_image), int(K), int(align), plan)
-    return dict(zip(_MIX_PLAN, (int(v) for v in plan)))
+    return _query(_lib.MixPlan, "cy_mix_plan", MIX_FORMS[form], int(N), int(per_image), int(K), int(align))
 
 
 def mix_weights(lam: float) -> Tuple[float, float]:
@@ -1910,17 +1907,13 @@ def softmax_mixmse_bwd(student: Tensor, teacher: Tensor, index: Tensor, w_self: 
 # --------------------------------------------------------------------------- DAE prior, orthogonal prototypes (csrc/cy_prior.hip)
 PRIOR_FORMS = {"dae": _lib.CY_PRIOR_DAE, "ortho": _lib.CY_PRIOR_ORTHO}
 PRIOR_ACTS = {"sigmoid": _lib.CY_PRIOR_ACT_SIGMOID, "tanh": _lib.CY_PRIOR_ACT_TANH}
-_PRIOR_PLAN = ("variant", "vec", "fwd_grid", "fwd_trips", "bwd_grid", "bwd_trips", "k_chunks", "fwd_lds", "bwd_lds",
-               "aux")
 
 
 def prior_plan(form: str, K: int, Cc: int, npix: int = 0, align: int = 16) -> dict:
     """the launch rule of the DAE ("dae": K classes, Cc image channels, npix pixels, the logits' base aligned to `align`
     bytes) and orthogonality ("ortho": K prototypes of Cc floats) kernels: the values of cy_prior_plan by name.  A
     host-side query, no GPU needed; what the launches refuse raises HipKernelError with their status."""
-    plan = (C.c_int32 * 10)()
-    _lib.call("cy_prior_plan", PRIOR_FORMS[form], int(npix), int(K), int(Cc), int(align), plan)
-    return dict(zip(_PRIOR_PLAN, (int(v) for v in plan)))
+    return _query(_lib.PriorPlan, "cy_prior_plan", PRIOR_FORMS[form], int(npix), int(K), int(Cc), int(align))
 
 
 def _dae_args(logits: Tensor, weight: Tensor, bias: Tensor, image: Tensor):
@@ -1974,7 +1967,6 @@ def ortho_bwd(prototypes: Tensor, gscale: Tensor) -> Tensor:
 # --------------------------------------------------------------------------- differentiable mean teacher (csrc/cy_teacher.hip)
 TEACHER_FORMS = {"adam": _lib.CY_TEACHER_ADAM, "axpy": _lib.CY_TEACHER_AXPY, "ema_multi": _lib.CY_TEACHER_EMA_MULTI,
                  "gathermse": _lib.CY_TEACHER_GATHERMSE}
-_TEACHER_PLAN = ("variant", "vec", "fwd_grid", "fwd_trips", "bwd_grid", "bwd_trips", "rows")
 EMA_MULTI_MAX = 4096  # tensors of one cy_ema_update_multi launch
 SOURCE_MAP_MAX = 1 << 24  # pixel indices an f32 image carries exactly
 
@@ -1983,9 +1975,7 @@ def teacher_plan(form: str, n: int, K: int = 0, align: int = 16) -> dict:
     """the launch rule of the teacher kernels (host-side query, no GPU needed): the values of cy_teacher_plan by name.
     `n`: elements ("adam", "axpy"), tensors ("ema_multi") or pixels ("gathermse").  What the launches refuse raises
     HipKernelError with their status."""
-    plan = (C.c_int32 * 7)()
-    _lib.call("cy_teacher_plan", TEACHER_FORMS[form], int(n), int(K), int(align), plan)
-    return dict(zip(_TEACHER_PLAN, (int(v) for v in plan)))
+    return _query(_lib.TeacherPlan, "cy_teacher_plan", TEACHER_FORMS[form], int(n), int(K), int(align))
 
 
 def _flat_f32(*ts: Tensor) -> int:
@@ -2013,16 +2003,13 @@ def axpy(y: Tensor, x: Tensor, a: float) -> None:
 
 # --------------------------------------------------------------------------- SGD / Adam / AdamW on flat buffers (csrc/cy_optim.hip)
 OPTIM_FORMS = {"sgd": _lib.CY_OPTIM_SGD, "adamw": _lib.CY_OPTIM_ADAMW}
-_OPTIM_PLAN = ("vec", "grid", "trips", "tail")
 
 
 def optim_plan(form: str, n: int, align: int = 16) -> dict:
     """the launch rule of cy_sgd_step / cy_adamw_step (host-side query, no GPU needed): the values of cy_optim_plan by
     name -- the rule teacher_plan("adam", ...) gives.  What the launches refuse raises HipKernelError with their
     status."""
-    plan = (C.c_int32 * 4)()
-    _lib.call("cy_optim_plan", OPTIM_FORMS[form], int(n), int(align), plan)
-    return dict(zip(_OPTIM_PLAN, (int(v) for v in plan)))
+    return _query(_lib.OptimPlan, "cy_optim_plan", OPTIM_FORMS[form], int(n), int(align))
 
 
 def sgd_step(p: Tensor, g: Tensor, buf: Optional[Tensor], lr: float, momentum: float, dampening: float, wd: float,
@@ -2174,9 +2161,7 @@ def surface_stats(pred: Tensor, target: Tensor, classes, ndim: int = 3, maps: bo
 
 
 # --------------------------------------------------------------------------- SLIC superpixels (csrc/cy_slic.hip)
-SLIC_PLAN_FIELDS = ("status", "r", "S", "start", "Ky", "Kx", "K", "M", "min_size", "blur_form", "blur_grid_x",
-                    "blur_grid_y", "blur_lds_h", "blur_lds_w", "pixel_grid_x", "assign_lds", "update_grid",
-                    "scan_tiles", "launches")
+SLIC_PLAN_FIELDS = _fields(_lib.SlicPlan)
 _SLIC_WS = {}  # (device, N, H, W, n_segments) -> workspace; the calls of one shape are ordered by the stream they share
 
 
@@ -2184,10 +2169,8 @@ def slic_plan(N: int, H: int, W: int, n_segments: int = 40, sigma: float = 5.0, 
               max_iter: int = 10) -> dict:
     """what cy_slic would do for these sizes: geometry (r, S, start, Ky, Kx, K, M, min_size), kernel form, grids and
     LDS per stage; `status` is the refusal (0: none), nothing is launched and no GPU is needed"""
-    plan = (C.c_int32 * _lib.CY_SLIC_PLAN_LEN)()
-    _lib.load().cy_slic_plan(int(N), int(H), int(W), int(n_segments), float(sigma), float(compactness),
-                             int(max_iter), plan)
-    return {f: int(plan[getattr(_lib, "CY_SLIC_PLAN_" + f.upper())]) for f in SLIC_PLAN_FIELDS}
+    return _query(_lib.SlicPlan, "cy_slic_plan", int(N), int(H), int(W), int(n_segments), float(sigma),
+                  float(compactness), int(max_iter), check=False)
 
 
 def _slic_images(images: Tensor) -> Tensor:
@@ -2267,17 +2250,14 @@ def slic(images: Tensor, n_segments: int = 40, sigma: float = 5.0, compactness: 
 AUG_MAX_SIDE, AUG_MAX_OUT, AUG_MAX_VIEWS = _lib.CY_AUG_MAX_SIDE, _lib.CY_AUG_MAX_OUT, _lib.CY_AUG_MAX_VIEWS
 AUG_IP_LEN, AUG_FP_LEN = _lib.CY_AUG_IP_LEN, _lib.CY_AUG_FP_LEN
 AUG_BRIGHTNESS, AUG_CONTRAST = _lib.CY_AUG_BRIGHTNESS, _lib.CY_AUG_CONTRAST
-AUG_PLAN_FIELDS = ("status", "form", "geo_grid_x", "geo_grid_y", "geo_grid_z", "jit_grid", "jit_trips", "jit_lds",
-                   "scratch_bytes", "launches")
+AUG_PLAN_FIELDS = _fields(_lib.AugPlan)
 _AUG_LUTS = {}  # device -> (ToTensor's table, the identity label table)
 
 
 def augment_plan(views: int, out_h: int, out_w: int) -> dict:
     """what cy_aug_views would launch for these sizes: kernel form, both grids, the trips of the jitter block over a
     view, its LDS bytes, the scratch bytes; `status` is the refusal (0: none); nothing is launched, no GPU needed"""
-    plan = (C.c_int32 * _lib.CY_AUG_PLAN_LEN)()
-    _lib.load().cy_aug_plan(int(views), int(out_h), int(out_w), plan)
-    return {f: int(plan[getattr(_lib, "CY_AUG_PLAN_" + f.upper())]) for f in AUG_PLAN_FIELDS}
+    return _query(_lib.AugPlan, "cy_aug_plan", int(views), int(out_h), int(out_w), check=False)
 
 
 def augment_luts(device):
@@ -2618,16 +2598,10 @@ def _bins_tensor(bins, device) -> Optional[Tensor]:
     return pinned.upload(torch.as_tensor(bins, dtype=torch.int32).reshape(-1, 3).contiguous(), device)
 
 
-_DENSE_PROJ_PLAN = ("form", "channel_blocks", "fwd_passes", "dw_passes", "lds_bytes", "bwd_launches", "bwd_launches_list",
-                    "w1_image_in_ws")
-
-
 def dense_proj_plan(C_in: int, hid: int, dtype: torch.dtype = torch.bfloat16, slope: float = 0.01) -> dict:
     """which kernels cy_dense_proj_fwd / _bwd run for this map (host-side query, no GPU needed): form is
     _lib.CY_DENSE_PROJ_VALU, _MFMA_REG (C = 32 / 64 / 128) or _MFMA_STREAM (C = 256 / 512)"""
-    plan = (C.c_int32 * 8)()
-    _lib.call("cy_dense_proj_plan", int(C_in), int(hid), dtype_code(dtype), float(slope), plan)
-    return dict(zip(_DENSE_PROJ_PLAN, (int(v) for v in plan)))
+    return _query(_lib.DenseProjPlan, "cy_dense_proj_plan", int(C_in), int(hid), dtype_code(dtype), float(slope))
 
 
 def dense_proj_fwd(x: Tensor, w1: Tensor, b1: Tensor, size: Tuple[int, int], bins: Optional[Tensor],
@@ -2715,9 +2689,6 @@ def gather_rows_bwd(dout: Tensor, idx: Tensor, rows: int) -> Tensor:
 
 
 # --------------------------------------------------------------------------- per-row projector (csrc/cy_pixel_mlp.hip)
-_PIXEL_MLP_PLAN = ("form", "rows_per_tile", "fwd_grid", "fwd_trips", "bwd_grid", "bwd_trips", "slabs", "lds_bytes")
-
-
 def pixel_mlp_ok(C_in: int, hid: int, out: int) -> bool:
     """the fused range of cy_pixel_mlp_* (hid == 0: the linear head)"""
     return 1 <= C_in <= 256 and 0 <= hid <= 256 and 1 <= out <= 256
@@ -2725,9 +2696,7 @@ def pixel_mlp_ok(C_in: int, hid: int, out: int) -> bool:
 
 def pixel_mlp_plan(M: int, C_in: int, hid: int, out: int, dtype: torch.dtype = torch.float32) -> dict:
     """the launch shape of cy_pixel_mlp_fwd / _bwd (host-side query, no GPU needed)"""
-    plan = (C.c_int32 * 8)()
-    _lib.call("cy_pixel_mlp_plan", int(M), int(C_in), int(hid), int(out), dtype_code(dtype), plan)
-    return dict(zip(_PIXEL_MLP_PLAN, (int(v) for v in plan)))
+    return _query(_lib.PixelMlpPlan, "cy_pixel_mlp_plan", int(M), int(C_in), int(hid), int(out), dtype_code(dtype))
 
 
 def _pixel_rows(x: Tensor) -> Tuple[int, int]:
@@ -2877,8 +2846,6 @@ def iid_loss(J: Tensor, mode: int, symmetric: bool, lamda: float, eps: float, wa
     return out2, P, dJ
 
 
-_JOINT_PATCH_PLAN = ("P", "nph", "npw", "eh", "ew", "fwd_kernel", "R", "tiles_h", "ntile", "nbx", "grid_y", "fwd_lds",
-                     "fwd_vec", "staged_fits", "bwd_kernel", "bwd_grid")
 JOINT_PATCH_KERNELS = {None: -1, "per_displacement": 0, "staged": 1}  # the forward kernel: the rule's choice, or forced
 
 
@@ -2886,10 +2853,8 @@ def joint_patch_plan(N: int, H: int, W: int, k: int, pad: int, patch: int, kerne
     """the launch rule of the patch-wise joint kernels (host-side query, no GPU needed): the values of
     cy_joint_patch_plan by name, and "ws_bytes", the forward's workspace.  What the launches refuse raises
     HipKernelError with their status."""
-    plan = (C.c_int32 * 16)()
-    _lib.call("cy_joint_patch_plan", int(N), int(H), int(W), int(k), int(pad), int(patch),
-              JOINT_PATCH_KERNELS[kernel], plan)
-    out = dict(zip(_JOINT_PATCH_PLAN, (int(v) for v in plan)))
+    out = _query(_lib.JointPatchPlan, "cy_joint_patch_plan", int(N), int(H), int(W), int(k), int(pad), int(patch),
+                 JOINT_PATCH_KERNELS[kernel])
     out["ws_bytes"] = int(_lib.load().cy_joint_patch_ws_bytes(int(N), int(H), int(W), int(k), int(pad), int(patch),
                                                               JOINT_PATCH_KERNELS[kernel]))
     return out

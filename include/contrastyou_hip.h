@@ -48,7 +48,7 @@ extern "C" {
 
 /* ABI version; bumped whenever a signature changes.  This line is the only place the number is written: the library
  * returns it and the Python binding (cyhip/_lib.py, derived from this header) reads it from here. */
-#define CY_ABI_VERSION 18
+#define CY_ABI_VERSION 19
 int cy_abi_version(void);
 /* name of the offload arch the library was built for ("gfx950"). */
 const char* cy_build_arch(void);
@@ -595,7 +595,7 @@ int cy_l2norm_bwd(const float* x, const float* norms, const float* dz, float* dx
  * cy_supcon_matrices reports it in neither mask.  The pair (i, j) of the 2n x 2n problem reads pos_mask[i mod n][j mod n];
  * the mask is taken as given and need not be symmetric (the gradient's transposed term reads [j mod n][i mod n]).
  * The diagonal i == j is left out whatever its code.  No signature changed with this contract (codes 1 and 0 mean what
- * they meant), so cy_abi_version() stays 18.
+ * they meant).
  * S: f32 [R][R] buffer that receives P P^T / t (kept for backward). */
 int cy_supcon_fwd(const float* P, const int32_t* labels, const uint8_t* pos_mask, float* S,
                   float* loss, float* row_stats, int n, int D, float t, void* stream);
@@ -785,8 +785,7 @@ int cy_uamt_mse_bwd(const float* teacher, const float* student, const float* res
                     float* dstudent, long npix, int K, float thr, int hard, void* stream);
 
 /* ------------------------------------------------------------------------
- * Supervised criteria on the segmentation output (csrc/cy_seg_loss.hip; entries added to ABI v18 -- no existing
- * signature changed, so cy_abi_version() stays 18): class-weighted KL_div with any reduction
+ * Supervised criteria on the segmentation output (csrc/cy_seg_loss.hip; entries added to ABI v18): class-weighted KL_div with any reduction
  * (contrastyou/losses/kl.py:94-125, the criterion of semi_seg/epochers/epocher.py:317-318) and the soft Dice loss
  * (contrastyou/losses/dice_loss.py:46-105), both of softmax(logits) against integer labels.  Logits are [npix][K] f32
  * (NHWC), labels int64 in [0, K), 1 <= K <= 16.  Every entry checks its arguments before any launch: a NULL pointer
@@ -862,20 +861,26 @@ int cy_dense_proj_bwd(const void* x, const float* w1, const float* b1, const int
                       int H, int W, int C, int ldx, int hid, int sh, int sw, float slope, int dtype,
                       void* ws, size_t ws_bytes, void* stream);
 /* cy_dense_proj_plan (host side, no GPU needed) is the rule cy_dense_proj_fwd, cy_dense_proj_bwd and
- * cy_dense_proj_bwd_ws_bytes follow when they choose their kernels (an added entry: no signature changed):
- *   plan[0] kernel form (CY_DENSE_PROJ_*), [1] channel blocks of 32 (VALU: staged chunks), [2] passes over the hidden
- *   units of the forward kernel, [3] ... of the dW1 kernel, [4] dynamic LDS bytes (the largest of the three kernels';
- *   <= 160 KiB), [5] launches of a backward with all bins that asks for dx and the parameter gradients, [6] ... with a
- *   bin list, [7] 1 when the dx kernel reads W1 from a 16-bit image in the workspace (hid * C * 2 bytes behind the
- *   partials and the job table, counted by cy_dense_proj_bwd_ws_bytes), else 0.
+ * cy_dense_proj_bwd_ws_bytes follow when they choose their kernels.
  * The matrix-core forms take 16-bit maps, 128 or 256 hidden units and slope <= 1: C = 32, 64, 128 the register-resident
  * form, C = 256, 512 the streamed form (forward and dx; its dW1 / db1 run the VALU kernel: one pass); everything else, and every call when CY_DENSE_MFMA=0 is set (read once per
- * process), runs the VALU kernels.  plan == NULL -> CY_ERR_ARG; C < 1, C % 8 != 0 or hid < 1 -> CY_ERR_SHAPE; an
+ * process), runs the VALU kernels.  out == NULL -> CY_ERR_ARG; C < 1, C % 8 != 0 or hid < 1 -> CY_ERR_SHAPE; an
  * unknown dtype -> CY_ERR_DTYPE. */
 #define CY_DENSE_PROJ_VALU 0        /* any dtype, any C % 8 == 0 */
 #define CY_DENSE_PROJ_MFMA_REG 1    /* pixel rows and W1 resident in registers / static LDS */
 #define CY_DENSE_PROJ_MFMA_STREAM 2 /* forward, dx: accumulator resident, rows streamed, W1 in dynamic LDS per pass */
-int cy_dense_proj_plan(int C, int hid, int dtype, float slope, int32_t* plan /* [8] */);
+typedef struct cy_dense_proj_plan_t {
+  int32_t form;              /* kernel form (CY_DENSE_PROJ_*) */
+  int32_t channel_blocks;    /* channel blocks of 32 (VALU: staged chunks) */
+  int32_t fwd_passes;        /* passes over the hidden units of the forward kernel */
+  int32_t dw_passes;         /* ... of the dW1 kernel */
+  int32_t lds_bytes;         /* dynamic LDS bytes (the largest of the three kernels'; <= 160 KiB) */
+  int32_t bwd_launches;      /* launches of a backward with all bins that asks for dx and the parameter gradients */
+  int32_t bwd_launches_list; /* ... with a bin list */
+  int32_t w1_image_in_ws;    /* 1 when the dx kernel reads W1 from a 16-bit image in the workspace (hid * C * 2 bytes
+                                behind the partials and the job table, counted by cy_dense_proj_bwd_ws_bytes), else 0 */
+} cy_dense_proj_plan_t;
+int cy_dense_proj_plan(int C, int hid, int dtype, float slope, cy_dense_proj_plan_t* out);
 /* nn.AdaptiveAvgPool2d((sh,sw)) on an NHWC map -> f32 [nb][C] (same bin list
  * convention); backward for the all-bins case (gather form, deterministic). */
 int cy_adaptive_avgpool_fwd(const void* x, const int32_t* bins, int nb, float* out, int N, int H,
@@ -995,7 +1000,7 @@ size_t cy_iid_loss_ws_bytes(int TT, int k);
 int cy_iid_loss(const float* J, float* out2, float* P, float* dJ, int TT, int k, int mode,
                 int symmetric, float lamda, float eps, void* ws, size_t ws_bytes, void* stream);
 /* Patch-wise IIC (IIDSegmentationSmallPathLoss / patch_generator, contrastyou/losses/discreteMI.py:173-198,264-272;
- * entries added to ABI v18 -- no existing signature changed and no struct added).  The maps are cut into square patches
+ * entries added to ABI v18).  The maps are cut into square patches
  * of side `patch` with step patch / 2: the origins along an axis of length L are 0, s, 2s, ... below L - patch, then
  * max(L - patch, 0); every patch is clipped to the map, so all P = nph * npw patches have the same extents eh x ew =
  * min(patch, H) x min(patch, W).  Patch q = ih * npw + iw.  With d = (du+pad)*T + (dv+pad), T = 2 pad + 1:
@@ -1005,20 +1010,30 @@ int cy_iid_loss(const float* J, float* out2, float* P, float* dJ, int TT, int k,
  * patch < 2, pad >= min(eh, ew), more than 65535 patches, J of 2^31 elements or more, or a forced staged kernel whose
  * tile exceeds 150 KB of LDS ->
  * CY_ERR_SHAPE; a short workspace -> CY_ERR_WORKSPACE.  No atomics anywhere: two runs give the same bits.
- * cy_joint_patch_plan (host-side only, launches nothing) writes the launch rule:
- *   plan[0] P, [1] nph, [2] npw, [3] eh, [4] ew
- *   plan[5] forward kernel: 1 = a block owns (patch, group of <= 9 displacements) and walks the (image, R patch rows)
- *           tiles staged in LDS with their zero border; 0 = one displacement per block, 64-pixel tiles, bounds-tested
- *           reads (where the staged tile exceeds 150 KB).  `kernel` = -1 asks for the rule's choice, 0 / 1 force one
- *   plan[6] R = min(eh, max(1, 256 / ew)), [7] tiles_h = ceil(eh / R) (kernel 1; else 0, 0)
- *   plan[8] tiles: N * tiles_h (kernel 1), ceil(N eh ew / 64) (kernel 0)
- *   plan[9] nbx, blocks per (patch, group) = partial joints: kernel 1 min(tiles, ceil(1024 / (P * groups))), kernel 0
- *           min(2048, ceil(N eh ew / 1024)); 1 = the forward writes J itself and no reduction is launched
- *   plan[10] gridDim.y: ceil(T*T / 9) (kernel 1), T*T (kernel 0); [11] dynamic LDS bytes; [12] 16-byte staging (k % 4 == 0)
- *   plan[13] 1 if the staged tile fits; [14] backward kernel: 1 = four channels per thread (k % 4 == 0); [15] its grid
+ * cy_joint_patch_plan (host-side only, launches nothing) writes the launch rule; `kernel` = -1 asks for the rule's
+ * choice of forward kernel, 0 / 1 force one.
  * cy_joint_patch_ws_bytes = 4 P T*T k*k nbx, the partial joints of that `kernel`, or 16 with nbx = 1 (0 where the sizes
  * are refused). */
-int cy_joint_patch_plan(int N, int H, int W, int k, int pad, int patch, int kernel, int32_t* plan /* [16] */);
+typedef struct cy_joint_patch_plan_t {
+  int32_t P, nph, npw; /* the patches, and their rows and columns */
+  int32_t eh, ew;      /* the extents of every patch */
+  int32_t fwd_kernel;  /* 1 = a block owns (patch, group of <= 9 displacements) and walks the (image, R patch rows) tiles
+                          staged in LDS with their zero border; 0 = one displacement per block, 64-pixel tiles,
+                          bounds-tested reads (where the staged tile exceeds 150 KB) */
+  int32_t R;           /* min(eh, max(1, 256 / ew)) (kernel 1; else 0) */
+  int32_t tiles_h;     /* ceil(eh / R) (kernel 1; else 0) */
+  int32_t ntile;       /* tiles: N * tiles_h (kernel 1), ceil(N eh ew / 64) (kernel 0) */
+  int32_t nbx;         /* blocks per (patch, group) = partial joints: kernel 1 min(tiles, ceil(1024 / (P * groups))),
+                          kernel 0 min(2048, ceil(N eh ew / 1024)); 1 = the forward writes J itself and no reduction is
+                          launched */
+  int32_t grid_y;      /* gridDim.y: ceil(T*T / 9) (kernel 1), T*T (kernel 0) */
+  int32_t fwd_lds;     /* dynamic LDS bytes */
+  int32_t fwd_vec;     /* 16-byte staging (k % 4 == 0) */
+  int32_t staged_fits; /* 1 if the staged tile fits */
+  int32_t bwd_kernel;  /* 1 = four channels per thread (k % 4 == 0) */
+  int32_t bwd_grid;    /* the backward's grid */
+} cy_joint_patch_plan_t;
+int cy_joint_patch_plan(int N, int H, int W, int k, int pad, int patch, int kernel, cy_joint_patch_plan_t* out);
 size_t cy_joint_patch_ws_bytes(int N, int H, int W, int k, int pad, int patch, int kernel);
 int cy_joint_patch_fwd(const float* x1, const float* x2, float* J, int N, int H, int W, int k, int pad, int patch,
                        int normalise, int kernel, void* ws, size_t ws_bytes, void* stream);
@@ -1322,7 +1337,7 @@ int cy_surface_stats(const int64_t* pred, const int64_t* target, const int32_t* 
 
 /* ------------------------------------------------------------------------
  * Per-row projector: the dense projection head without pooling, and point evaluation of it (csrc/cy_pixel_mlp.hip;
- * 4 entries added to ABI v18 -- no existing signature changed, so cy_abi_version() stays 18).  Replaces, for
+ * 4 entries added to ABI v18).  Replaces, for
  * pool_name in ("identical", "none", None), the Conv2d(1x1) -> LeakyReLU -> Conv2d(1x1) -> Identical -> F.normalize of
  * DenseProjectionHead.forward (contrastyou/projectors/heads.py:99-123, projectors/nn.py:16-23) on every pixel, or on
  * the pixels the dense InfoNCE hook samples (semi_seg/hooks/infonce.py:31-46).
@@ -1339,17 +1354,25 @@ int cy_surface_stats(const int64_t* pred, const int64_t* target, const int32_t* 
  * (zero it first), as cy_dense_proj_bwd does; dw1, db1, dw2, db2 (f32, each may be NULL) are written, or added to
  * with `accumulate`.  The parameter gradients go through one partial slab per workgroup in ws and a second launch that
  * adds the slabs in slab order: no atomics, two runs give the same bits.
- * cy_pixel_mlp_plan (host side, no GPU needed) is the launch rule both launches and the workspace query follow:
- *   plan[0] kernel form (CY_PIXEL_MLP_*), [1] rows per tile, [2] forward workgroups (<= 1024), [3] forward loop trips,
- *   [4] backward workgroups (<= 256), [5] backward loop trips, [6] partial slabs, [7] dynamic LDS bytes (the larger of
- *   the two kernels').  ws_bytes = 4 * slabs * (J Cp + J + (hid ? Op Hp + Op : 0)) with Cp, Hp, Op the sizes rounded up
+ * cy_pixel_mlp_plan (host side, no GPU needed) is the launch rule both launches and the workspace query follow.
+ *   ws_bytes = 4 * slabs * (J Cp + J + (hid ? Op Hp + Op : 0)) with Cp, Hp, Op the sizes rounded up
  *   to 32 and J = hid ? Hp : Op: it does not grow with M past the cap (0 where the sizes are refused).
  * Checked before any launch: a NULL required pointer -> CY_ERR_ARG; M < 1, a size outside the fused range or
  * ldx < C -> CY_ERR_SHAPE; a short workspace (when a parameter gradient is asked for) -> CY_ERR_WORKSPACE.
  * ------------------------------------------------------------------------ */
 #define CY_PIXEL_MLP_MFMA16 1 /* bf16 / f16 rows: 64 rows per tile */
 #define CY_PIXEL_MLP_MFMA32 2 /* f32 rows: 32 rows per tile */
-int cy_pixel_mlp_plan(long M, int C, int hid, int out, int dtype, int32_t* plan /* [8] */);
+typedef struct cy_pixel_mlp_plan_t {
+  int32_t form;          /* kernel form (CY_PIXEL_MLP_*) */
+  int32_t rows_per_tile; /* rows per tile */
+  int32_t fwd_grid;      /* forward workgroups (<= 1024) */
+  int32_t fwd_trips;     /* forward loop trips */
+  int32_t bwd_grid;      /* backward workgroups (<= 256) */
+  int32_t bwd_trips;     /* backward loop trips */
+  int32_t slabs;         /* partial slabs */
+  int32_t lds_bytes;     /* dynamic LDS bytes (the larger of the two kernels') */
+} cy_pixel_mlp_plan_t;
+int cy_pixel_mlp_plan(long M, int C, int hid, int out, int dtype, cy_pixel_mlp_plan_t* plan);
 int cy_pixel_mlp_fwd(const void* x, const int32_t* idx, const float* w1, const float* b1, const float* w2,
                      const float* b2, float* y, float* inv, long M, int C, int ldx, int hid, int out, float slope,
                      int normalize, int dtype, void* stream);
@@ -1360,8 +1383,7 @@ int cy_pixel_mlp_bwd(const void* x, const int32_t* idx, const float* w1, const f
                      int dtype, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
- * IMSAT: marginal and conditional entropy of probability rows (csrc/cy_imsat.hip; entries added to ABI v18 -- no
- * existing signature changed, so cy_abi_version() stays 18).  For p [R][K] f32, every row a probability simplex, and
+ * IMSAT: marginal and conditional entropy of probability rows (csrc/cy_imsat.hip; entries added to ABI v18).  For p [R][K] f32, every row a probability simplex, and
  * eps the module-level entropy_criterion's 1e-8 (semi_seg/hooks/midl.py:13; not IMSATLoss.eps, which the reference
  * never reads):
  *   cond = (1/R) sum_r -sum_k p_rk log(p_rk + eps)      m_k = (1/R) sum_r p_rk      marg = -sum_k m_k log(m_k + eps)
@@ -1387,16 +1409,20 @@ int cy_pixel_mlp_bwd(const void* x, const int32_t* idx, const float* w1, const f
  * vec = 4 where align is a multiple of 16, else 1 -- the only two kernel forms.  Logits: one thread per pixel; kt = K
  * for the compiled K = 2, 4, 8 where the rows are aligned to their 8 / 16 bytes, else 0 (run-time K, one float at a
  * time).  K == 4 rows are read 16 bytes at a time in both forms: a misaligned base is CY_ERR_ARG.
- *   plan[0] vec: floats per memory access (rows / pair 4 or 1; logits 2 (kt 2), 4 (kt 4, 8) or 1)
- *   plan[1] kt: logits: the compiled K (2, 4, 8) or 0; rows / pair: 0
- *   plan[2] threads: working threads of the 256 of a block
- *   plan[3] tile: rows / pair: floats per block and trip = threads * vec * 4; logits: pixels = 256
- *   plan[4] fwd_grid = min(1024, tiles) blocks = rows of partials, [5] fwd_trips of the busiest block
- *   plan[6] bwd_grid = min(2048, tiles), [7] bwd_trips
- *   plan[8] slots: f64 partials per block = 1 + K, pair 3 + 2 K
- * Returns what the launches answer: CY_ERR_ARG for a NULL `plan`, an unknown form, R < 1, align < 1 or misaligned
+ * Returns what the launches answer: CY_ERR_ARG for a NULL `out`, an unknown form, R < 1, align < 1 or misaligned
  * K == 4 logits; CY_ERR_SHAPE for K out of range; otherwise CY_OK. */
-int cy_imsat_plan(int form, long R, int K, int align, int32_t* plan /* [9] */);
+typedef struct cy_imsat_plan_t {
+  int32_t vec;       /* floats per memory access (rows / pair 4 or 1; logits 2 (kt 2), 4 (kt 4, 8) or 1) */
+  int32_t kt;        /* logits: the compiled K (2, 4, 8) or 0; rows / pair: 0 */
+  int32_t threads;   /* working threads of the 256 of a block */
+  int32_t tile;      /* rows / pair: floats per block and trip = threads * vec * 4; logits: pixels = 256 */
+  int32_t fwd_grid;  /* min(1024, tiles) blocks = rows of partials */
+  int32_t fwd_trips; /* of the busiest block */
+  int32_t bwd_grid;  /* min(2048, tiles) */
+  int32_t bwd_trips;
+  int32_t slots;     /* f64 partials per block = 1 + K, pair 3 + 2 K */
+} cy_imsat_plan_t;
+int cy_imsat_plan(int form, long R, int K, int align, cy_imsat_plan_t* out);
 /* imsat_with_entropy(p) / imsat_loss(p, lamda) = cond - lamda * marg / IMSATDynamicWeight's -w * marg + cond
  * (contrastyou/losses/discreteMI.py:20-87,275-297; the combination is left to the caller, on the two device scalars).
  * ws_bytes >= 8 * (1 + K) * min(1024, ceil(R K / (4 K floor(256 / K)))) = cy_imsat_ws_bytes(R, K): the grid of
@@ -1427,8 +1453,8 @@ int cy_softmax_imsat_bwd(const float* logits, const float* coef, const float* g,
                          float eps, void* stream);
 
 /* ------------------------------------------------------------------------
- * MixUp and interpolation-consistency training (csrc/cy_mixup.hip; entries added to ABI v18 -- no existing signature
- * changed, so cy_abi_version() stays 18).  Image n of a batch of N is mixed with image index[n]; `index` is int32 [N]
+ * MixUp and interpolation-consistency training (csrc/cy_mixup.hip; entries added to ABI v18).
+ * Image n of a batch of N is mixed with image index[n]; `index` is int32 [N]
  * in device memory and a gather: any values in [0, N), not only permutations (the caller checks the range; the kernels
  * trust it).  w_self and w_other are lam and 1 - lam, formed in f64 on the host and rounded to f32 each, which is what
  * `lam * x + (1 - lam) * x[index]` (semi_seg/hooks/utils.py:284-297) does; no kernel forms 1 - w.  Logits are
@@ -1444,19 +1470,22 @@ int cy_softmax_imsat_bwd(const float* logits, const float* coef, const float* g,
 /* The launch rule of the three groups (host-side only, launches nothing; the launches take every decision from it), in
  * the style of cy_imsat_plan.  `per_image`: E of cy_mix_images, HW of the losses.  `align`: the bytes every tensor base
  * pointer of the call is aligned to (the launches work it out from their pointers; 16 and more count as 16).
- *   plan[0] vec: floats per memory access.  Images: 4 where per_image % 4 == 0 and align is a multiple of 16, else 1.
- *           Losses: 2 (kt 2), 4 (kt 4, 8) or 1
- *   plan[1] kt: losses: the compiled K (2, 4, 8) where the rows are aligned to their 8 / 16 bytes, else 0 (run-time K,
- *           one float at a time; K == 4 rows are read 16 bytes at a time in both forms: a misaligned base is
- *           CY_ERR_ARG).  Images: 0
- *   plan[2] fwd_grid: losses min(1024, ceil(npix / 256)) blocks = the f64 partials; images rows * columns, with
- *           columns = min(ceil(per_image / vec / 256), 2048 / rows) blocks striding over one image
- *   plan[3] fwd_trips: loop trips of the busiest block
- *   plan[4] bwd_grid = 2 * fwd_grid, plan[5] bwd_trips (images: 0, 0)
- *   plan[6] rows: images: min(N, 1024) grid rows striding over the images; losses: 0
- * Returns what the launches answer: CY_ERR_ARG for a NULL `plan`, an unknown form, N < 1, per_image < 1 or such an
+ * Returns what the launches answer: CY_ERR_ARG for a NULL `out`, an unknown form, N < 1, per_image < 1 or such an
  * align; CY_ERR_SHAPE for K out of range (losses; images ignore K); otherwise CY_OK. */
-int cy_mix_plan(int form, int N, long per_image, int K, int align, int32_t* plan /* [7] */);
+typedef struct cy_mix_plan_t {
+  int32_t vec;       /* floats per memory access.  Images: 4 where per_image % 4 == 0 and align is a multiple of 16,
+                        else 1.  Losses: 2 (kt 2), 4 (kt 4, 8) or 1 */
+  int32_t kt;        /* losses: the compiled K (2, 4, 8) where the rows are aligned to their 8 / 16 bytes, else 0
+                        (run-time K, one float at a time; K == 4 rows are read 16 bytes at a time in both forms: a
+                        misaligned base is CY_ERR_ARG).  Images: 0 */
+  int32_t fwd_grid;  /* losses min(1024, ceil(npix / 256)) blocks = the f64 partials; images rows * columns, with
+                        columns = min(ceil(per_image / vec / 256), 2048 / rows) blocks striding over one image */
+  int32_t fwd_trips; /* loop trips of the busiest block */
+  int32_t bwd_grid;  /* 2 * fwd_grid (images: 0) */
+  int32_t bwd_trips; /* (images: 0) */
+  int32_t rows;      /* images: min(N, 1024) grid rows striding over the images; losses: 0 */
+} cy_mix_plan_t;
+int cy_mix_plan(int form, int N, long per_image, int K, int align, cy_mix_plan_t* out);
 /* out[n][e] = w_self * x[n][e] + w_other * x[index[n]][e], E contiguous f32 elements per image (any memory format, the
  * same for x and out; out must not be x).  Two correctly rounded products and one correctly rounded sum, never an
  * FMA: the bits of torch's CPU f32 evaluation of the reference expression. */
@@ -1484,8 +1513,8 @@ int cy_softmax_mixmse_bwd(const float* student, const float* teacher, const int3
                           float w_other, const float* gscale, float* dstudent, int N, long HW, int K, void* stream);
 
 /* ------------------------------------------------------------------------
- * DAE prior and orthogonal prototypes (csrc/cy_prior.hip; entries added to ABI v18 -- no existing signature changed,
- * so cy_abi_version() stays 18).  Every entry checks its arguments before any launch: a NULL pointer, a count < 1 or a
+ * DAE prior and orthogonal prototypes (csrc/cy_prior.hip; entries added to ABI v18).
+ * Every entry checks its arguments before any launch: a NULL pointer, a count < 1 or a
  * base that is not 4-byte aligned -> CY_ERR_ARG; K, Cimg, the activation or K * C out of range -> CY_ERR_SHAPE; a short
  * workspace -> CY_ERR_WORKSPACE.  No atomics: two runs give the same bits.  Upstream gradients are device memory.
  * ------------------------------------------------------------------------ */
@@ -1496,22 +1525,28 @@ int cy_softmax_mixmse_bwd(const float* student, const float* teacher, const int3
 /* The launch rule of both groups (host-side only, launches nothing; the launches take every decision from it), in the
  * style of cy_mix_plan.  DAE: n = npix, C = Cimg, `align` = the bytes the logits' base is aligned to (16 and more count
  * as 16).  Orthogonality: K prototypes of C floats; n and align are not looked at.
- *   plan[0] variant.  DAE: the compiled K (2, 4, 8) where the rows are aligned to their 8 / 16 bytes, else 0 (run-time
- *           K, the row read 16 floats at a time).  Orthogonality: 0 = a thread per Gram entry (C <= 64), 1 = a wave
- *   plan[1] vec: floats per access of a logits row: 2 (variant 2), 4 (variants 4, 8; variant 0 where K % 4 == 0 on a
- *           16-byte base), else 1.  Orthogonality: 1
- *   plan[2] fwd_grid, plan[4] bwd_grid.  DAE: min(1024, ceil(npix / 256)) blocks = the f64 partials per quantity.
- *           Orthogonality: 1
- *   plan[3] fwd_trips, plan[5] bwd_trips.  DAE: loop trips of the busiest block.  Orthogonality: trips of the Gram
- *           loop (ceil(K^2 / 256), or ceil(K^2 / 4) for the wave form) and of the sweeps over [K][C] (ceil(K C / 256))
- *   plan[6] k_chunks.  DAE: 16-float pieces a row is read in: ceil(K / 16) for variant 0, else 1.  Orthogonality: 0
- *   plan[7] fwd_lds, plan[8] bwd_lds: bytes of LDS per block: static for DAE, dynamic for orthogonality (rows, and
- *           backward the K x K matrix)
- *   plan[9] DAE: the threads of a block that work in the backward's flat sweep, floor(256 / K) * K.  Orthogonality: the
- *           floats between two rows in LDS (C | 1 for the thread form, C for the wave form)
- * Returns what the launches answer: CY_ERR_ARG for a NULL `plan`, an unknown form, npix < 1, C < 1 (orthogonality) or
+ * Returns what the launches answer: CY_ERR_ARG for a NULL `out`, an unknown form, npix < 1, C < 1 (orthogonality) or
  * an align that is no multiple of 4; CY_ERR_SHAPE for K outside 2..64, Cimg outside 1..4 or K * C > 16384. */
-int cy_prior_plan(int form, long n, int K, int C, int align, int32_t* plan /* [10] */);
+typedef struct cy_prior_plan_t {
+  int32_t variant;   /* DAE: the compiled K (2, 4, 8) where the rows are aligned to their 8 / 16 bytes, else 0 (run-time
+                        K, the row read 16 floats at a time).  Orthogonality: 0 = a thread per Gram entry (C <= 64),
+                        1 = a wave */
+  int32_t vec;       /* floats per access of a logits row: 2 (variant 2), 4 (variants 4, 8; variant 0 where K % 4 == 0
+                        on a 16-byte base), else 1.  Orthogonality: 1 */
+  int32_t fwd_grid;  /* DAE: min(1024, ceil(npix / 256)) blocks = the f64 partials per quantity.  Orthogonality: 1 */
+  int32_t fwd_trips; /* DAE: loop trips of the busiest block.  Orthogonality: trips of the Gram loop (ceil(K^2 / 256),
+                        or ceil(K^2 / 4) for the wave form) */
+  int32_t bwd_grid;  /* as fwd_grid */
+  int32_t bwd_trips; /* DAE: loop trips of the busiest block.  Orthogonality: trips of the sweeps over [K][C]
+                        (ceil(K C / 256)) */
+  int32_t k_chunks;  /* DAE: 16-float pieces a row is read in: ceil(K / 16) for variant 0, else 1.  Orthogonality: 0 */
+  int32_t fwd_lds;   /* bytes of LDS per block: static for DAE, dynamic for orthogonality (rows) */
+  int32_t bwd_lds;   /* ... (orthogonality: rows and the K x K matrix) */
+  int32_t aux;       /* DAE: the threads of a block that work in the backward's flat sweep, floor(256 / K) * K.
+                        Orthogonality: the floats between two rows in LDS (C | 1 for the thread form, C for the wave
+                        form) */
+} cy_prior_plan_t;
+int cy_prior_plan(int form, long n, int K, int C, int align, cy_prior_plan_t* out);
 /* The denoising-auto-encoder prior (semi_seg/hooks/autoencoder.py:52-57: F.mse_loss(AuxiliaryLayer(logits), image),
  * the layer a 1x1 convolution K -> 1 and a sigmoid or tanh).  Logits are [npix][K] f32 rows (NHWC), npix = N * HW,
  * 2 <= K <= 64; w[K], b[1] f32; image [N][Cimg][HW] f32 planar, 1 <= Cimg <= 4; act CY_PRIOR_ACT_*.
@@ -1535,8 +1570,8 @@ int cy_ortho_fwd(const float* prototypes, float* loss, int K, int C, void* strea
 int cy_ortho_bwd(const float* prototypes, const float* gscale, float* dprototypes, int K, int C, void* stream);
 
 /* ------------------------------------------------------------------------
- * Differentiable mean teacher (csrc/cy_teacher.hip; entries added to ABI v18 -- no existing signature changed and no
- * struct added, so cy_abi_version() stays 18).  The teacher's state lives in flat f32 buffers; every update of it is one
+ * Differentiable mean teacher (csrc/cy_teacher.hip; entries added to ABI v18).
+ * The teacher's state lives in flat f32 buffers; every update of it is one
  * streaming launch.  Every entry checks its arguments before any launch: a NULL pointer, a count < 1, step < 1 or a
  * base that is not 4-byte aligned -> CY_ERR_ARG; K or the tensor count out of range -> CY_ERR_SHAPE; a short workspace
  * -> CY_ERR_WORKSPACE.  No atomics: two runs give the same bits.
@@ -1549,19 +1584,24 @@ int cy_ortho_bwd(const float* prototypes, const float* gscale, float* dprototype
  * the style of cy_mix_plan.  `n`: the elements (Adam, axpy), the tensors (multi-tensor EMA) or the pixels N * HW
  * (gather-MSE).  `align`: the bytes every tensor base of the call is aligned to (16 and more count as 16).  K is looked
  * at by gather-MSE only.
- *   plan[0] variant: gather-MSE: the compiled K (2, 4, 8) where the rows are aligned to their 8 / 16 bytes, else 0
- *           (run-time K, one float at a time, any 4-byte-aligned base).  Otherwise 0
- *   plan[1] vec: floats per memory access.  Adam, axpy: 4 where align is a multiple of 16 and n >= 4 (the n % 4 tail
- *           goes one float at a time), else 1.  Multi-tensor EMA: 1.  Gather-MSE: 2 (variant 2), 4 (variants 4, 8), 1
- *   plan[2] fwd_grid: Adam, axpy: min(2048, ceil(n / vec / 256)) blocks.  Multi-tensor EMA: the blocks striding over one
- *           tensor, clamp(8192 / n, 2, 64).  Gather-MSE: min(1024, ceil(n / 256)) blocks = the f64 partials
- *   plan[3] fwd_trips: loop trips of the busiest block; multi-tensor EMA (the sizes are device data): the elements of a
- *           tensor that one trip covers, 256 * plan[2]
- *   plan[4] bwd_grid = 2 * fwd_grid, plan[5] bwd_trips: gather-MSE; otherwise 0, 0
- *   plan[6] rows: multi-tensor EMA: the grid's second dimension = n; otherwise 0
- * Returns what the launches answer: CY_ERR_ARG for a NULL `plan`, an unknown form, n < 1 or an align that is no multiple
+ * Returns what the launches answer: CY_ERR_ARG for a NULL `out`, an unknown form, n < 1 or an align that is no multiple
  * of 4; CY_ERR_SHAPE for more than 4096 tensors or K outside 2..16. */
-int cy_teacher_plan(int form, long n, int K, int align, int32_t* plan /* [7] */);
+typedef struct cy_teacher_plan_t {
+  int32_t variant;   /* gather-MSE: the compiled K (2, 4, 8) where the rows are aligned to their 8 / 16 bytes, else 0
+                        (run-time K, one float at a time, any 4-byte-aligned base).  Otherwise 0 */
+  int32_t vec;       /* floats per memory access.  Adam, axpy: 4 where align is a multiple of 16 and n >= 4 (the n % 4
+                        tail goes one float at a time), else 1.  Multi-tensor EMA: 1.  Gather-MSE: 2 (variant 2),
+                        4 (variants 4, 8), 1 */
+  int32_t fwd_grid;  /* Adam, axpy: min(2048, ceil(n / vec / 256)) blocks.  Multi-tensor EMA: the blocks striding over
+                        one tensor, clamp(8192 / n, 2, 64).  Gather-MSE: min(1024, ceil(n / 256)) blocks = the f64
+                        partials */
+  int32_t fwd_trips; /* loop trips of the busiest block; multi-tensor EMA (the sizes are device data): the elements of
+                        a tensor that one trip covers, 256 * fwd_grid */
+  int32_t bwd_grid;  /* gather-MSE: 2 * fwd_grid; otherwise 0 */
+  int32_t bwd_trips; /* gather-MSE; otherwise 0 */
+  int32_t rows;      /* multi-tensor EMA: the grid's second dimension = n; otherwise 0 */
+} cy_teacher_plan_t;
+int cy_teacher_plan(int form, long n, int K, int align, cy_teacher_plan_t* out);
 /* torch.optim.Adam(amsgrad=False, maximize=False) on flat f32 buffers of n elements; `step` is the 1-based count after
  * this update.  g += wd p (wd != 0);  m += (g - m)(1 - beta1);  v = beta2 v + (1 - beta2) g^2;
  * p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps), bc_i = 1 - beta_i^step formed in f64 on the host as cy_radam_step
@@ -1588,8 +1628,7 @@ int cy_softmax_gathermse_bwd(const float* teacher, const int32_t* map, const flo
                              float* dstudent, int N, long HW, int K, void* stream);
 
 /* ------------------------------------------------------------------------
- * SGD, Adam and AdamW on the flat buffers (csrc/cy_optim.hip; entries added to ABI v18 -- no existing signature changed
- * and no struct added, so cy_abi_version() stays 18).  They replace torch.optim.SGD / Adam / AdamW's per-tensor (or
+ * SGD, Adam and AdamW on the flat buffers (csrc/cy_optim.hip; entries added to ABI v18).  They replace torch.optim.SGD / Adam / AdamW's per-tensor (or
  * foreach) step in contrastyou/optim: FusedSGD, FusedAdam(amsgrad=True) and FusedAdamW launch them once per run of
  * updated parameters (contrastyou/optim/flat_optimizer.py: FlatOptimizer.step); FusedAdam(amsgrad=False) keeps
  * cy_adam_step.  Every entry checks its arguments before any launch: a NULL pointer, n < 1, step < 1, a base that is
@@ -1601,13 +1640,15 @@ int cy_softmax_gathermse_bwd(const float* teacher, const int32_t* map, const flo
 /* The launch rule of the two (host-side only, launches nothing; the launches take every decision from it): the rule
  * cy_teacher_plan gives CY_TEACHER_ADAM.  `align`: the bytes every buffer base of the call is aligned to (16 and more
  * count as 16).
- *   plan[0] vec: floats per memory access: 4 where align is a multiple of 16 and n >= 4, else 1 -- a run of touched
- *           parameters starts at an arbitrary parameter offset, so training reaches both
- *   plan[1] grid: min(2048, ceil(n / vec / 256)) blocks of 256
- *   plan[2] trips: loop trips of the busiest block
- *   plan[3] tail: the n % 4 elements that the first threads of block 0 finish one float at a time (vec == 4), else 0
- * CY_ERR_ARG for a NULL `plan`, an unknown form, n < 1 or an align that is no multiple of 4. */
-int cy_optim_plan(int form, long n, int align, int32_t* plan /* [4] */);
+ * CY_ERR_ARG for a NULL `out`, an unknown form, n < 1 or an align that is no multiple of 4. */
+typedef struct cy_optim_plan_t {
+  int32_t vec;   /* floats per memory access: 4 where align is a multiple of 16 and n >= 4, else 1 -- a run of touched
+                    parameters starts at an arbitrary parameter offset, so training reaches both */
+  int32_t grid;  /* min(2048, ceil(n / vec / 256)) blocks of 256 */
+  int32_t trips; /* loop trips of the busiest block */
+  int32_t tail;  /* the n % 4 elements that the first threads of block 0 finish one float at a time (vec == 4), else 0 */
+} cy_optim_plan_t;
+int cy_optim_plan(int form, long n, int align, cy_optim_plan_t* out);
 /* torch.optim.SGD(maximize=False) on flat f32 buffers of n elements.  g += wd p (wd != 0); with momentum:
  * buf = g when `first` (the buffer's content is not read), else buf = momentum buf + (1 - dampening) g; then
  * g += momentum buf (nesterov) or g = buf;  p -= lr g.  `momentum_buf` is NULL exactly when momentum == 0: any other
@@ -1624,8 +1665,7 @@ int cy_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_av
                   void* stream);
 
 /* ------------------------------------------------------------------------
- * Wide-K regularisers (csrc/cy_wide_reg.hip; entries added to ABI v18 -- no existing signature changed and no struct
- * added, so cy_abi_version() stays 18).  The entropy, self-MSE, UA-MT and ICT losses above on multi-prototype logits,
+ * Wide-K regularisers (csrc/cy_wide_reg.hip; entries added to ABI v18).  The entropy, self-MSE, UA-MT and ICT losses above on multi-prototype logits,
  * 16 < K <= 64: the same arguments, values and launch counts as cy_softmax_entropy_*, cy_softmax_selfmse_*,
  * cy_uamt_mse_* and cy_softmax_mixmse_*, in the sixteen-lanes-per-pixel form of cy_softmax_group_kl_* (lane j of a row
  * holds logits 4j..4j+3; 16 pixels per block and loop trip).  The arg-max of self-MSE and hard UA-MT is the first
@@ -1641,14 +1681,17 @@ int cy_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_av
 /* The launch rule of the four families (host-side only, launches nothing; the launches take every decision from it), in
  * the style of cy_mix_plan.  `npix`: the pixels N * HW.  `align`: the bytes every tensor base pointer of the call is
  * aligned to (the launches work it out from their pointers; 16 and more count as 16).
- *   plan[0] vec: floats per memory access: 4 where K % 4 == 0 and align is a multiple of 16, else 1
- *   plan[1] rows_per_block: pixels a block covers per loop trip, 16
- *   plan[2] fwd_grid: min(4096, ceil(npix / 16)) blocks = the f64 partials (UA-MT: two per block)
- *   plan[3] fwd_trips: loop trips of every block
- *   plan[4] bwd_grid = fwd_grid, plan[5] bwd_trips
- * Returns what the launches answer: CY_ERR_ARG for a NULL `plan`, an unknown family, npix < 1 or an align that is no
+ * Returns what the launches answer: CY_ERR_ARG for a NULL `out`, an unknown family, npix < 1 or an align that is no
  * multiple of 4; CY_ERR_SHAPE for K outside 17..64; otherwise CY_OK. */
-int cy_wide_reg_plan(int family, long npix, int K, int align, int32_t* plan /* [6] */);
+typedef struct cy_wide_reg_plan_t {
+  int32_t vec;            /* floats per memory access: 4 where K % 4 == 0 and align is a multiple of 16, else 1 */
+  int32_t rows_per_block; /* pixels a block covers per loop trip, 16 */
+  int32_t fwd_grid;       /* min(4096, ceil(npix / 16)) blocks = the f64 partials (UA-MT: two per block) */
+  int32_t fwd_trips;      /* loop trips of every block */
+  int32_t bwd_grid;       /* = fwd_grid */
+  int32_t bwd_trips;
+} cy_wide_reg_plan_t;
+int cy_wide_reg_plan(int family, long npix, int K, int align, cy_wide_reg_plan_t* out);
 /* ws_bytes >= 8 * fwd_grid (16 * fwd_grid for UA-MT) = the *_row_ws_bytes queries (0 for a count < 1). */
 size_t cy_softmax_entropy_row_ws_bytes(long npix);
 int cy_softmax_entropy_row_fwd(const float* logits, float* loss, long npix, int K, float eps, void* ws,
@@ -1674,8 +1717,8 @@ int cy_softmax_mixmse_row_bwd(const float* student, const float* teacher, const 
                               void* stream);
 
 /* ------------------------------------------------------------------------
- * On-device SLIC superpixels (csrc/cy_slic.hip; 6 entries added to ABI v18 -- no existing signature changed, so
- * cy_abi_version() stays 18).  Replaces the offline pass the superpixel InfoNCE hook depends on:
+ * On-device SLIC superpixels (csrc/cy_slic.hip; 6 entries added to ABI v18).
+ * Replaces the offline pass the superpixel InfoNCE hook depends on:
  * skimage.segmentation.slic(img, n_segments=40, sigma=5, compactness=0.1) of script/create_superpixel.py:27
  * (compactness 0.001 in semi_seg/postprocess/superpixel.py:23) and the `superpixel/` folder read by
  * _load_superpixel_image (semi_seg/hooks/infonce.py:24-27).  Not label-for-label skimage: DESIGN.md "On-device
@@ -1705,7 +1748,7 @@ int cy_softmax_mixmse_row_bwd(const float* student, const float* teacher, const 
  * n_segments < 1 -> CY_ERR_ARG, S < 1, K outside 1..CY_SLIC_MAX_K or H W < 64 K -> CY_ERR_SHAPE; a short workspace ->
  * CY_ERR_WORKSPACE.  Each stage checks the arguments it takes.  cy_slic_ws_bytes (one size for all four entries;
  * blur_q alone needs N H W 4 bytes) is 0 where the sizes are refused.
- * cy_slic_plan fills plan[CY_SLIC_PLAN_LEN] (the CY_SLIC_PLAN_* indices; the rest 0) and returns the status cy_slic
+ * cy_slic_plan fills a cy_slic_plan_t (all 0 but `status` where the call is refused) and returns the status cy_slic
  * would: the geometry, the blur form with its grid and LDS bytes per pass, the grid of the per-pixel kernels
  * (assignment and the components; blocks of 256, grid.y = N), the tiles of 1024 pixels the numbering block steps
  * through and the number of launches.
@@ -1715,28 +1758,21 @@ int cy_softmax_mixmse_row_bwd(const float* student, const float* teacher, const 
 #define CY_SLIC_MAX_SIGMA 16
 #define CY_SLIC_BLUR_QUANT 0    /* sigma == 0: slic_quant_kernel */
 #define CY_SLIC_BLUR_TWO_PASS 1 /* slic_blur_kernel along H, then along W with the quantisation */
-#define CY_SLIC_PLAN_LEN 24
-#define CY_SLIC_PLAN_STATUS 0
-#define CY_SLIC_PLAN_R 1
-#define CY_SLIC_PLAN_S 2
-#define CY_SLIC_PLAN_START 3
-#define CY_SLIC_PLAN_KY 4
-#define CY_SLIC_PLAN_KX 5
-#define CY_SLIC_PLAN_K 6
-#define CY_SLIC_PLAN_M 7
-#define CY_SLIC_PLAN_MIN_SIZE 8
-#define CY_SLIC_PLAN_BLUR_FORM 9
-#define CY_SLIC_PLAN_BLUR_GRID_X 10
-#define CY_SLIC_PLAN_BLUR_GRID_Y 11
-#define CY_SLIC_PLAN_BLUR_LDS_H 12
-#define CY_SLIC_PLAN_BLUR_LDS_W 13
-#define CY_SLIC_PLAN_PIXEL_GRID_X 14
-#define CY_SLIC_PLAN_ASSIGN_LDS 15
-#define CY_SLIC_PLAN_UPDATE_GRID 16
-#define CY_SLIC_PLAN_SCAN_TILES 17
-#define CY_SLIC_PLAN_LAUNCHES 18
+typedef struct cy_slic_plan_t {
+  int32_t status;                   /* the refusal (CY_OK: none) */
+  int32_t r, S, start, Ky, Kx, K, M, min_size; /* the geometry */
+  int32_t blur_form;                /* CY_SLIC_BLUR_* */
+  int32_t blur_grid_x, blur_grid_y; /* the blur's grid */
+  int32_t blur_lds_h, blur_lds_w;   /* LDS bytes of the pass along H and of the pass along W */
+  int32_t pixel_grid_x;             /* the grid of the per-pixel kernels (blocks of 256, grid.y = N) */
+  int32_t assign_lds;               /* LDS bytes of the assignment */
+  int32_t update_grid;              /* blocks of the centre update */
+  int32_t scan_tiles;               /* tiles of 1024 pixels the numbering block steps through */
+  int32_t launches;
+} cy_slic_plan_t;
 size_t cy_slic_ws_bytes(int N, int H, int W, int n_segments);
-int cy_slic_plan(int N, int H, int W, int n_segments, double sigma, double compactness, int max_iter, int32_t* plan);
+int cy_slic_plan(int N, int H, int W, int n_segments, double sigma, double compactness, int max_iter,
+                 cy_slic_plan_t* out);
 int cy_slic_blur_q(const float* images, int32_t* q, int N, int H, int W, double sigma, void* ws, size_t ws_bytes,
                    void* stream);
 int cy_slic_cluster(const int32_t* q, int32_t* labels, int32_t* centres, int N, int H, int W, int n_segments,
@@ -1747,8 +1783,7 @@ int cy_slic(const float* images, uint8_t* ids, int32_t* count, int N, int H, int
             double compactness, int max_iter, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
- * On-device loader augmentation (csrc/cy_augment.hip; 2 entries added to ABI v18 -- no existing signature changed, so
- * cy_abi_version() stays 18).  Replaces the host-side Pillow / torchvision pipelines of semi_seg/augment.py:36-283
+ * On-device loader augmentation (csrc/cy_augment.hip; 2 entries added to ABI v18).  Replaces the host-side Pillow / torchvision pipelines of semi_seg/augment.py:36-283
  * (augment_zoo) as contrastyou/augment/synchronize.py:76-165 applies them: the *application* of given parameters is
  * Pillow's bit for bit (Image.rotate BILINEAR / NEAREST, transpose, ImageOps.expand, crop, ImageEnhance.Brightness and
  * .Contrast, ToTensor, ToLabel); the parameters are drawn on the host (contrastyou/augment/device.py).
@@ -1791,7 +1826,7 @@ int cy_slic(const float* images, uint8_t* ids, int32_t* count, int N, int H, int
  * outside the table, a table row with H or W outside 1..CY_AUG_MAX_SIDE or leaving the arena, CH or CW outside
  * 1..CY_AUG_MAX_SIDE, an offset beyond +-CY_AUG_MAX_OFFSET -> CY_ERR_SHAPE; OFF_LO, OFF_HI, SRC_H, SRC_W that are not
  * the table row of SLICE, a flag that is not 0 / 1, NJIT outside 0..3, an unknown KIND -> CY_ERR_ARG; scratch_bytes < views out_h out_w -> CY_ERR_WORKSPACE.
- * cy_aug_plan fills plan[CY_AUG_PLAN_LEN] (the CY_AUG_PLAN_* indices, the rest 0) and returns the status the sizes
+ * cy_aug_plan fills a cy_aug_plan_t (all 0 but `status` where the sizes are refused) and returns the status the sizes
  * alone decide: the kernel form, both grids, the trips of stage B's block over a view, its LDS bytes, the scratch
  * bytes and the number of launches.
  * ------------------------------------------------------------------------ */
@@ -1825,18 +1860,18 @@ int cy_slic(const float* images, uint8_t* ids, int32_t* count, int N, int H, int
 #define CY_AUG_FP_LEN 9
 #define CY_AUG_FP_M0 0
 #define CY_AUG_FP_F0 6
-#define CY_AUG_PLAN_LEN 16
-#define CY_AUG_PLAN_STATUS 0
-#define CY_AUG_PLAN_FORM 1
-#define CY_AUG_PLAN_GEO_GRID_X 2
-#define CY_AUG_PLAN_GEO_GRID_Y 3
-#define CY_AUG_PLAN_GEO_GRID_Z 4 /* 2: the plan is that of the call with labels; without them the launch has 1 */
-#define CY_AUG_PLAN_JIT_GRID 5
-#define CY_AUG_PLAN_JIT_TRIPS 6
-#define CY_AUG_PLAN_JIT_LDS 7
-#define CY_AUG_PLAN_SCRATCH_BYTES 8
-#define CY_AUG_PLAN_LAUNCHES 9
-int cy_aug_plan(int views, int out_h, int out_w, int32_t* plan);
+typedef struct cy_aug_plan_t {
+  int32_t status;                 /* the refusal (CY_OK: none) */
+  int32_t form;                   /* CY_AUG_FORM_* */
+  int32_t geo_grid_x, geo_grid_y; /* stage A: blocks of CY_AUG_GEO_BLOCK output pixels, the views */
+  int32_t geo_grid_z;             /* 2: the plan is that of the call with labels; without them the launch has 1 */
+  int32_t jit_grid;               /* stage B: one block per view */
+  int32_t jit_trips;              /* trips of stage B's block over a view */
+  int32_t jit_lds;                /* its LDS bytes */
+  int32_t scratch_bytes;
+  int32_t launches;
+} cy_aug_plan_t;
+int cy_aug_plan(int views, int out_h, int out_w, cy_aug_plan_t* out);
 int cy_aug_views(const uint8_t* store_img, const uint8_t* store_lab, const int64_t* h_table, int slices,
                  long long arena_bytes, const int32_t* ip, const int32_t* h_ip, const double* fp, int views, int out_h,
                  int out_w, const uint8_t* label_lut, const float* tensor_lut, float* images, int64_t* labels,

@@ -142,9 +142,9 @@ def test_abi_version_has_one_source():
     one place a test pins it: an ABI bump edits the header's define and this line"""
     from cyhip import _lib
     macro = int(re.search(r"^#define CY_ABI_VERSION (\d+)$", HEADER.read_text(), flags=re.M).group(1))
-    assert macro == 18
-    assert _lib.load().cy_abi_version() == 18
-    assert _lib.ABI_VERSION == 18
+    assert macro == 19
+    assert _lib.load().cy_abi_version() == 19
+    assert _lib.ABI_VERSION == 19
 
 
 def test_pinned_signatures():
@@ -205,14 +205,56 @@ MIRRORS = {"cy_conv_desc": "ConvDesc", "cy_pack_item": "PackItem", "cy_conv_plan
            "cy_joint_plan_t": "JointPlan", "cy_group_softmax_plan_t": "GroupSoftmaxPlan",
            "cy_norm_act_plan_t": "NormActPlan", "cy_wgrad_reduce_entry": "WgradReduceEntry", "cy_bn_acc": "BnAcc",
            "cy_bn_fold": "BnFold", "cy_bn_bwd_in": "BnBwdIn", "cy_bn_dz_out": "BnDzOut", "cy_bn_run_item": "BnRunItem",
-           "cy_mat_layout": "MatLayout"}
+           "cy_mat_layout": "MatLayout",
+           "cy_dense_proj_plan_t": "DenseProjPlan", "cy_joint_patch_plan_t": "JointPatchPlan",
+           "cy_pixel_mlp_plan_t": "PixelMlpPlan", "cy_imsat_plan_t": "ImsatPlan", "cy_mix_plan_t": "MixPlan",
+           "cy_prior_plan_t": "PriorPlan", "cy_teacher_plan_t": "TeacherPlan", "cy_optim_plan_t": "OptimPlan",
+           "cy_wide_reg_plan_t": "WideRegPlan", "cy_slic_plan_t": "SlicPlan", "cy_aug_plan_t": "AugPlan"}
+
+# the eleven plan structs of ABI v19: (struct, the ops function that reads it, one accepted call, the documented extras)
+FAMILY_PLANS = [
+    ("cy_dense_proj_plan_t", "dense_proj_plan", (64, 128), ()),
+    ("cy_joint_patch_plan_t", "joint_patch_plan", (2, 24, 20, 5, 1, 16), ("ws_bytes",)),
+    ("cy_pixel_mlp_plan_t", "pixel_mlp_plan", (100, 32, 64, 16), ()),
+    ("cy_imsat_plan_t", "imsat_plan", ("rows", 100, 10), ("ws_bytes",)),
+    ("cy_mix_plan_t", "mix_plan", ("mixkl", 2, 100, 4), ()),
+    ("cy_prior_plan_t", "prior_plan", ("dae", 4, 1, 100), ()),
+    ("cy_teacher_plan_t", "teacher_plan", ("gathermse", 100, 4), ()),
+    ("cy_optim_plan_t", "optim_plan", ("sgd", 1000), ()),
+    ("cy_wide_reg_plan_t", "wide_reg_plan", ("entropy", 286, 20), ()),
+    ("cy_slic_plan_t", "slic_plan", (2, 64, 64, 16), ()),
+    ("cy_aug_plan_t", "augment_plan", (4, 32, 32), ()),
+]
+
+
+@pytest.mark.parametrize("struct,fn,args,extras", FAMILY_PLANS, ids=[f[0] for f in FAMILY_PLANS])
+def test_family_plan_layouts_match_header_and_ops(struct, fn, args, extras):
+    """the plan structs of ABI v19 and their ctypes mirrors name the same int32 fields in order, and the dict the
+    matching ops function answers has exactly those fields as its leading keys, in order"""
+    from cyhip import _lib, ops
+    fields = _check_plan_layout(struct, MIRRORS[struct])
+    plan = getattr(ops, fn)(*args)
+    assert list(plan) == fields + list(extras)
+    assert all(type(v) is int for v in plan.values())
+    assert plan.get("status", 0) == 0
+    assert _lib.ABI_VERSION == _lib.load().cy_abi_version()
+
+
+def test_header_has_no_array_plans():
+    """a plan query answers through a struct of the header: no int32 array named `plan`, no index macros"""
+    text = re.sub(r"/\*.*?\*/", "", HEADER.read_text(), flags=re.S)
+    assert not re.search(r"int32_t\s*\*\s*plan\b", text)
+    assert not re.search(r"CY_\w+_PLAN_LEN\b", text)
+    assert not re.search(r"#define\s+CY_(SLIC|AUG)_PLAN_", text)
+    for name, args in re.findall(r"\b(cy_\w+_plan)\s*\(([^()]*)\)\s*;", text):
+        assert re.search(r"\bcy_\w+\s*\*\s*\w+\s*$", args), (name, args)  # the last parameter: a struct of the header
 
 
 def test_every_struct_has_a_mirror_and_every_struct_pointer_resolves_to_it():
     from cyhip import _lib
     text = re.sub(r"/\*.*?\*/", "", HEADER.read_text(), flags=re.S)
     declared = re.findall(r"typedef struct[^{;]*\{[^}]*\}\s*(\w+)\s*;", text)
-    assert len(declared) == 16 and sorted(declared) == sorted(MIRRORS)
+    assert len(declared) == 27 and sorted(declared) == sorted(MIRRORS)
     for struct, mirror in MIRRORS.items():
         assert issubclass(getattr(_lib, mirror), ctypes.Structure), mirror
     seen = set()

@@ -80,7 +80,7 @@ def test_argument_errors_come_before_any_launch():
     lib = _lib.load()
     buf = (C.c_char * 64)()
     p = C.addressof(buf)
-    plan = (C.c_int32 * 8)()
+    plan = _lib.PixelMlpPlan()
     assert lib.cy_pixel_mlp_plan(10, 8, 16, 4, 0, plan) == 0 and lib.cy_pixel_mlp_plan(10, 8, 16, 4, 0, None) == ARG
     for name in ("x", "w1", "b1", "w2", "b2", "y", "inv"):
         assert _fwd(lib, p, **{name: False}) == ARG, name

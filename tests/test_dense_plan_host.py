@@ -78,14 +78,15 @@ def test_everything_else_stays_on_the_valu_kernels(cin, hid, dtype, slope):
 
 
 def test_bad_arguments_return_error_codes_not_a_plan(lib):
-    plan = (C.c_int32 * 8)(*([-7] * 8))
+    from cyhip import _lib
+    plan = _lib.DenseProjPlan(*([-7] * 8))
     assert lib.cy_dense_proj_plan(256, 256, 1, 0.01, None) == ARG
     for cin, hid in ((0, 256), (-32, 256), (100, 256), (256, 0), (256, -1)):
         assert lib.cy_dense_proj_plan(cin, hid, 1, 0.01, plan) == SHAPE, (cin, hid)
     for dt in (3, -1, 17):
         assert lib.cy_dense_proj_plan(256, 256, dt, 0.01, plan) == DTYPE, dt
-    assert list(plan) == [-7] * 8, "an error must not write a plan"
-    assert lib.cy_dense_proj_plan(256, 256, 1, 0.01, plan) == 0 and plan[0] == 2
+    assert [getattr(plan, f) for f, _ in plan._fields_] == [-7] * 8, "an error must not write a plan"
+    assert lib.cy_dense_proj_plan(256, 256, 1, 0.01, plan) == 0 and plan.form == 2
 
 
 @pytest.mark.parametrize("cin,hid", [(256, 256), (256, 128), (512, 256), (512, 128), (128, 256), (32, 128), (96, 64)])

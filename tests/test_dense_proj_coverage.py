@@ -312,11 +312,12 @@ def test_the_entry_points_refuse_before_any_launch():
     assert bwd(dtype=7, ws_bytes=ws_bytes - 1) == DTYPE and bwd(hid=257, ws_bytes=0) == SHAPE
     assert m.untouched()
 
-    plan = (C.c_int32 * 8)(*([-77] * 8))
+    plan = _lib.DenseProjPlan(*([-77] * 8))
     assert lib.cy_dense_proj_plan(32, 128, _lib.CY_BF16, 0.01, None) == ARG
     for args, rc in (((0, 128, _lib.CY_BF16), SHAPE), ((36, 128, _lib.CY_BF16), SHAPE), ((32, 0, _lib.CY_BF16), SHAPE),
                      ((32, 128, 7), DTYPE)):
-        assert lib.cy_dense_proj_plan(*args, 0.01, plan) == rc and list(plan) == [-77] * 8, args
+        assert lib.cy_dense_proj_plan(*args, 0.01, plan) == rc, args
+        assert [getattr(plan, f) for f, _ in plan._fields_] == [-77] * 8, args
 
     # the pools and the gather
     def avg_f(x="x", out="hpool", N=N, nb=nb, ldx=Cc, sh=sh, sw=sw, dtype=_lib.CY_BF16):

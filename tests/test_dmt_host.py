@@ -33,7 +33,7 @@ def test_exports(lib):
     assert set(ENTRIES) <= set(_lib.exported_names())
     for name in ENTRIES:
         assert hasattr(lib, name), name
-    assert _lib.ABI_VERSION == 18 == lib.cy_abi_version()
+    assert _lib.ABI_VERSION == 19 == lib.cy_abi_version()
     for name in ("adam_step", "axpy", "ema_update_multi", "ema_table", "softmax_gathermse_fwd", "softmax_gathermse_bwd",
                  "teacher_plan", "source_index_image", "source_map_from_warped"):
         assert callable(getattr(ops, name)), name
@@ -89,7 +89,8 @@ def test_gathermse_refusals(lib):
 
 
 def test_plan_refusals(lib):
-    plan = (C.c_int32 * 7)()
+    from cyhip import _lib
+    plan = _lib.TeacherPlan()
     assert lib.cy_teacher_plan(0, 8, 0, 16, None) == ARG
     assert lib.cy_teacher_plan(4, 8, 0, 16, plan) == ARG
     assert lib.cy_teacher_plan(-1, 8, 0, 16, plan) == ARG
@@ -102,7 +103,7 @@ def test_plan_refusals(lib):
     for K in (1, 17):
         assert lib.cy_teacher_plan(3, 8, K, 16, plan) == SHAPE
     for align in (4, 8):  # K == 4 on a base short of 16 bytes is the run-time form, as its neighbours are
-        assert lib.cy_teacher_plan(3, 8, 4, align, plan) == OK and (plan[0], plan[1]) == (0, 1)
+        assert lib.cy_teacher_plan(3, 8, 4, align, plan) == OK and (plan.variant, plan.vec) == (0, 1)
 
 
 def test_wrappers_refuse_cpu_tensors():

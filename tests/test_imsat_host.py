@@ -26,17 +26,16 @@ def lib():
 
 def test_entries_are_declared_exported_and_typed(lib):
     from cyhip import _lib
-    assert lib.cy_abi_version() == 18 == _lib.ABI_VERSION
+    assert lib.cy_abi_version() == 19 == _lib.ABI_VERSION
     for name, (res, nargs) in ENTRIES.items():
         assert name in _lib.exported_names(), name
         fn = getattr(lib, name)  # exported by the library
         assert fn.restype is res and len(fn.argtypes) == nargs, (name, fn.restype, fn.argtypes)
         assert (name in _lib._INT_FUNCS) == (res is C.c_int), name
     assert lib.cy_imsat_fwd.argtypes[4:7] == [C.c_long, C.c_int, C.c_float]
-    assert lib.cy_imsat_plan.argtypes == [C.c_int, C.c_long, C.c_int, C.c_int, C.c_void_p]
-    from cyhip import ops
-    assert ops._IMSAT_PLAN == ("vec", "kt", "threads", "tile", "fwd_grid", "fwd_trips", "bwd_grid", "bwd_trips",
-                               "slots")
+    assert lib.cy_imsat_plan.argtypes == [C.c_int, C.c_long, C.c_int, C.c_int, C.POINTER(_lib.ImsatPlan)]
+    assert tuple(f for f, _ in _lib.ImsatPlan._fields_) == ("vec", "kt", "threads", "tile", "fwd_grid", "fwd_trips",
+                                                            "bwd_grid", "bwd_trips", "slots")
     assert (_lib.CY_IMSAT_ROWS, _lib.CY_IMSAT_PAIR, _lib.CY_IMSAT_LOGITS) == (0, 1, 2)
 
 
@@ -84,7 +83,10 @@ def test_every_rejection_has_its_status_before_any_launch(lib, group):
 
 def test_plan_rejections(lib):
     from cyhip import _lib, ops
-    out = (C.c_int32 * 9)(*([-7] * 9))
+    out = _lib.ImsatPlan(*([-7] * 9))
+
+    def values():
+        return [getattr(out, f) for f, _ in out._fields_]
     assert lib.cy_imsat_plan(0, 10, 3, 16, None) == ARG
     for form, R, K, align in ((3, 10, 3, 16), (-1, 10, 3, 16), (0, 0, 3, 16), (0, 10, 3, 0)):
         assert lib.cy_imsat_plan(form, R, K, align, out) == ARG
@@ -95,8 +97,9 @@ def test_plan_rejections(lib):
         assert lib.cy_imsat_plan(2, 10, 4, align, out) == ARG
         assert lib.cy_softmax_imsat_fwd(P + align, P, P, P, 10, 4, 1e-8, P, 1 << 20, None) == ARG
         assert lib.cy_softmax_imsat_bwd(P, P, P, P + align, 10, 4, 1e-8, None) == ARG
-    assert list(out) == [-7] * 9, "a refused query writes nothing"
-    assert lib.cy_imsat_plan(2, 10, 4, 16, out) == OK and list(out) == [4, 4, 256, 256, 1, 1, 1, 1, 5]
+    assert values() == [-7] * 9, "a refused query writes nothing"
+    assert lib.cy_imsat_plan(2, 10, 4, 16, out) == OK and values() == [4, 4, 256, 256, 1, 1, 1, 1, 5]
+    assert (out.vec, out.kt, out.threads, out.tile, out.slots) == (4, 4, 256, 256, 5)
     with pytest.raises(_lib.HipKernelError, match="CY_ERR_SHAPE"):
         ops.imsat_plan("rows", 10, 65)
 

@@ -182,8 +182,8 @@ ENTRIES = {
 
 
 def test_entries_are_declared_exported_and_typed(lib):
-    from cyhip import _lib, ops
-    assert lib.cy_abi_version() == 18 == _lib.ABI_VERSION
+    from cyhip import _lib
+    assert lib.cy_abi_version() == 19 == _lib.ABI_VERSION
     for name, (res, nargs) in ENTRIES.items():
         assert name in _lib.exported_names(), name
         fn = getattr(lib, name)
@@ -191,8 +191,10 @@ def test_entries_are_declared_exported_and_typed(lib):
     assert lib.cy_mix_images.argtypes == [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_long,
                                           C.c_void_p]
     assert (_lib.CY_MIX_IMAGES, _lib.CY_MIX_KL, _lib.CY_MIX_MSE) == (0, 1, 2)
-    assert ops._MIX_PLAN == ("vec", "kt", "fwd_grid", "fwd_trips", "bwd_grid", "bwd_trips", "rows")
-    assert len(_lib._STRUCTS) == 16  # the plan is an int32 array: no struct joined the header
+    assert tuple(f for f, _ in _lib.MixPlan._fields_) == ("vec", "kt", "fwd_grid", "fwd_trips", "bwd_grid", "bwd_trips",
+                                                          "rows")
+    assert len(_lib._STRUCTS) == 27 and _lib._STRUCTS["cy_mix_plan_t"] is _lib.MixPlan  # the plan is a header struct
+    assert lib.cy_mix_plan.argtypes[-1] is C.POINTER(_lib.MixPlan)
 
 
 def _kl(lib, which, N=2, HW=10, K=3, null=None, ws_bytes=1 << 20):
@@ -253,7 +255,8 @@ def test_images_and_plan_reject_with_their_status(lib):
     assert img(P, P, 0.5, 0.5, P, 2, 4, None) == ARG  # out must not be x
     assert img(P, P, 0.5, 0.5, 2 * P, 0, 4, None) == ARG and img(P, P, 0.5, 0.5, 2 * P, 2, 0, None) == ARG
     assert img(P + 2, P, 0.5, 0.5, 2 * P, 2, 4, None) == ARG  # not a float's alignment
-    plan = (C.c_int32 * 7)()
+    from cyhip import _lib
+    plan = _lib.MixPlan()
     assert lib.cy_mix_plan(1, 2, 10, 3, 16, None) == ARG
     assert lib.cy_mix_plan(3, 2, 10, 3, 16, plan) == ARG and lib.cy_mix_plan(-1, 2, 10, 3, 16, plan) == ARG
     for form in (0, 1, 2):

@@ -81,8 +81,8 @@ def test_plans_and_their_coverage(lib):
 def test_plan_refusals(lib):
     from cyhip import _lib, ops
     assert (_lib.CY_OPTIM_SGD, _lib.CY_OPTIM_ADAMW) == (0, 1)
-    assert _lib.ABI_VERSION == 18 == lib.cy_abi_version()
-    plan = (C.c_int32 * 4)()
+    assert _lib.ABI_VERSION == 19 == lib.cy_abi_version()
+    plan = _lib.OptimPlan()
     assert lib.cy_optim_plan(0, 8, 16, None) == ARG
     for form in (-1, 2):
         assert lib.cy_optim_plan(form, 8, 16, plan) == ARG

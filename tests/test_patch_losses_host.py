@@ -46,7 +46,7 @@ def test_patch_origins_equal_the_reference(npz):
 
 
 def test_the_launch_rule_follows_the_origins(lib):
-    from cyhip import ops
+    from cyhip import _lib, ops
     for n, k, H, W, patch, pad in list(fx.PATCH_CASES.values()) + [pc.MULTI_TRIP, (16, 20, 224, 224, 32, 7)]:
         plan = ops.joint_patch_plan(n, H, W, k, pad, patch)
         oh, ow = pc.origins(H, patch), pc.origins(W, patch)
@@ -64,7 +64,7 @@ def test_the_launch_rule_follows_the_origins(lib):
     # a wide patch with large pad * k: the staged tile exceeds the LDS cap and the rule takes the fallback
     wide = ops.joint_patch_plan(1, 64, 64, 64, 7, 64)
     assert wide["staged_fits"] == 0 and wide["fwd_kernel"] == 0
-    out = (C.c_int32 * 16)()
+    out = _lib.JointPatchPlan()
     assert lib.cy_joint_patch_plan(1, 64, 64, 64, 7, 64, 1, out) == SHAPE
 
 
@@ -93,7 +93,7 @@ def _loss(lib, Pn=4, TT=9, k=5, mode=1, ws_bytes=None, null=None):
 
 def test_entries_are_declared_exported_and_typed(lib):
     from cyhip import _lib
-    assert lib.cy_abi_version() == 18 == _lib.ABI_VERSION
+    assert lib.cy_abi_version() == 19 == _lib.ABI_VERSION
     for name, (res, nargs) in ENTRIES.items():
         assert name in _lib.exported_names(), name
         fn = getattr(lib, name)
@@ -102,7 +102,8 @@ def test_entries_are_declared_exported_and_typed(lib):
 
 
 def test_every_rejection_has_its_status_before_any_launch(lib):
-    out = (C.c_int32 * 16)(*([-7] * 16))
+    from cyhip import _lib
+    out = _lib.JointPatchPlan(*([-7] * 16))
     # NULL pointers
     for null in range(3):
         assert _fwd(lib, null=null) == ARG
@@ -132,7 +133,7 @@ def test_every_rejection_has_its_status_before_any_launch(lib):
         assert lib.cy_joint_patch_plan(*a.values(), -1, out) == SHAPE
     # 4225 patches * 225 displacements * 64 * 64 elements of J: past 32-bit indexing
     assert lib.cy_joint_patch_plan(1, 2112, 2112, 64, 7, 64, -1, out) == SHAPE
-    assert list(out) == [-7] * 16, "a refused query writes nothing"
+    assert [getattr(out, f) for f, _ in out._fields_] == [-7] * 16, "a refused query writes nothing"
     for bad in (dict(k=65), dict(mode=2), dict(mode=-1)):
         assert _loss(lib, ws_bytes=1 << 30, **bad) == SHAPE, bad
     # a short workspace

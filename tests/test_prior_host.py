@@ -188,16 +188,17 @@ ENTRIES = {"cy_prior_plan": (C.c_int, 6), "cy_dae_ws_bytes": (C.c_size_t, 3), "c
 
 def test_entries_are_declared_exported_and_typed(lib):
     from cyhip import _lib, ops
-    assert lib.cy_abi_version() == 18 == _lib.ABI_VERSION
+    assert lib.cy_abi_version() == 19 == _lib.ABI_VERSION
     for name, (res, nargs) in ENTRIES.items():
         assert name in _lib.exported_names(), name
         fn = getattr(lib, name)
         assert fn.restype is res and len(fn.argtypes) == nargs, (name, fn.restype, fn.argtypes)
     assert (_lib.CY_PRIOR_DAE, _lib.CY_PRIOR_ORTHO, _lib.CY_PRIOR_ACT_SIGMOID, _lib.CY_PRIOR_ACT_TANH) == (0, 1, 0, 1)
     assert ops.PRIOR_ACTS == {"sigmoid": 0, "tanh": 1}
-    assert ops._PRIOR_PLAN == ("variant", "vec", "fwd_grid", "fwd_trips", "bwd_grid", "bwd_trips", "k_chunks",
-                               "fwd_lds", "bwd_lds", "aux")
-    assert len(_lib._STRUCTS) == 16  # the plan is an int32 array: no struct joined the header
+    assert tuple(f for f, _ in _lib.PriorPlan._fields_) == ("variant", "vec", "fwd_grid", "fwd_trips", "bwd_grid",
+                                                            "bwd_trips", "k_chunks", "fwd_lds", "bwd_lds", "aux")
+    assert len(_lib._STRUCTS) == 27 and _lib._STRUCTS["cy_prior_plan_t"] is _lib.PriorPlan  # the plan is a header struct
+    assert lib.cy_prior_plan.argtypes[-1] is C.POINTER(_lib.PriorPlan)
 
 
 def _dae(lib, which, N=2, HW=35, K=3, Cimg=1, act=0, null=None, ws_bytes=1 << 20):
@@ -257,7 +258,8 @@ def test_ortho_and_plan_reject_with_their_status(lib):
         assert lib.cy_ortho_fwd(P, P, K, Cc, None) == SHAPE and lib.cy_ortho_bwd(P, P, P, K, Cc, None) == SHAPE
     assert lib.cy_ortho_fwd(P, P, 4, 0, None) == ARG and lib.cy_ortho_bwd(P, P, P, 4, -1, None) == ARG
     assert lib.cy_ortho_fwd(P + 2, P, 4, 16, None) == ARG
-    plan = (C.c_int32 * 10)()
+    from cyhip import _lib
+    plan = _lib.PriorPlan()
     assert lib.cy_prior_plan(0, 70, 3, 1, 16, None) == ARG
     assert lib.cy_prior_plan(2, 70, 3, 1, 16, plan) == ARG and lib.cy_prior_plan(-1, 70, 3, 1, 16, plan) == ARG
     assert lib.cy_prior_plan(0, 0, 3, 1, 16, plan) == ARG and lib.cy_prior_plan(0, 70, 3, 1, 2, plan) == ARG

@@ -1,8 +1,6 @@
 """SLIC superpixels without a GPU: the properties of the NumPy restatement (tests/slic_cases.py) that make its output
 usable by the superpixel hook, the refusals and the launch plan of csrc/cy_slic.hip against the cases, and the
 kernel's f32 blur arithmetic against scipy's float64 blur."""
-import ctypes
-
 import numpy as np
 import pytest
 from scipy import ndimage
@@ -111,8 +109,8 @@ def test_entry_points_refuse_null_pointers_and_short_workspaces():
     assert lib.cy_slic_connect(p, p, p, N, H, W, 1000, p, need, None) == sc.ERR_SHAPE
     assert lib.cy_slic_connect(p, p, p, N, H, W, ns, p, need - 1, None) == sc.ERR_WORKSPACE
     assert lib.cy_slic_plan(N, H, W, ns, 1.0, 0.1, 10, None) == sc.ERR_ARG
-    plan = (ctypes.c_int32 * _lib.CY_SLIC_PLAN_LEN)()
-    assert lib.cy_slic_plan(N, H, W, ns, 1.0, 0.1, 10, plan) == sc.OK and plan[_lib.CY_SLIC_PLAN_K] == 16
+    plan = _lib.SlicPlan()
+    assert lib.cy_slic_plan(N, H, W, ns, 1.0, 0.1, 10, plan) == sc.OK and plan.K == 16
 
 
 def test_plan_matches_the_cases_and_the_cases_reach_every_form():

@@ -74,10 +74,10 @@ def test_the_twelve_entries_and_the_plan_are_exported_and_typed(lib):
             assert sigs[new] == sigs[old], new  # the arguments of the K <= 16 counterpart
             assert getattr(lib, new).argtypes == sigs[new][1]
         assert sigs[f"cy_{fam}_row_ws_bytes"][0] is C.c_size_t and sigs[f"cy_{fam}_row_fwd"][0] is C.c_int
-    assert sigs["cy_wide_reg_plan"] == (C.c_int, [C.c_int, C.c_long, C.c_int, C.c_int, C.c_void_p])
+    assert sigs["cy_wide_reg_plan"] == (C.c_int, [C.c_int, C.c_long, C.c_int, C.c_int, C.POINTER(_lib.WideRegPlan)])
     assert [_lib.CY_WIDE_ENTROPY, _lib.CY_WIDE_SELFMSE, _lib.CY_WIDE_UAMT, _lib.CY_WIDE_MIXMSE] == [0, 1, 2, 3]
-    assert lib.cy_abi_version() == _lib.ABI_VERSION == 18
-    assert len(_lib._STRUCTS) == 16  # the plan is an int32 array: no struct joined the header
+    assert lib.cy_abi_version() == _lib.ABI_VERSION == 19
+    assert len(_lib._STRUCTS) == 27 and _lib._STRUCTS["cy_wide_reg_plan_t"] is _lib.WideRegPlan  # a header struct
 
 
 # ---- 2. refusals ------------------------------------------------------------------------------------------------------
@@ -115,7 +115,8 @@ def test_a_short_workspace_is_refused(lib, P, fam):
 
 
 def test_the_plan_refuses_with_the_status_of_the_launches(lib):
-    plan = (C.c_int32 * 6)()
+    from cyhip import _lib
+    plan = _lib.WideRegPlan()
     assert lib.cy_wide_reg_plan(0, 286, 20, 16, None) == ARG
     assert lib.cy_wide_reg_plan(4, 286, 20, 16, plan) == ARG and lib.cy_wide_reg_plan(-1, 286, 20, 16, plan) == ARG
     for fam in range(4):
@@ -192,7 +193,8 @@ def test_the_old_entries_still_answer_k_17_as_they_did(lib, P):
     assert lib.cy_uamt_mse_bwd(P, P, P, P, P, 286, 17, 1.0, 0, None) == ARG
     assert lib.cy_softmax_mixmse_fwd(P, P, P, 0.5, 0.5, P, 2, 143, 17, P, BIG, None) == SHAPE
     assert lib.cy_softmax_mixmse_bwd(P, P, P, 0.5, 0.5, P, P, 2, 143, 17, None) == SHAPE
-    plan = (C.c_int32 * 7)()
+    from cyhip import _lib
+    plan = _lib.MixPlan()
     assert lib.cy_mix_plan(2, 2, 143, 17, 16, plan) == SHAPE
     for npix in (286, 16 * 224 * 224):  # and their workspace is what it was: a partial per block of 256 pixels
         blocks = min(max((npix + 255) // 256, 1), 1024)

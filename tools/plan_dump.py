@@ -2,6 +2,7 @@
 
     python tools/plan_dump.py [--lib PATH] [--print] [--reduced]      # the CY_* switches of the environment
     python tools/plan_dump.py [--lib PATH] --all-settings             # one child process per switch setting
+    python tools/plan_dump.py [--lib PATH] [--print] --families       # the eleven other families' plan queries
 
 Prints the number of records and their SHA-256 (--print: the records themselves, one line each).  The planner is a pure
 host function and needs no GPU, so two builds of the library are compared by diffing the output of this tool: identical
@@ -101,14 +102,91 @@ def dump(lib_path, show, reduced):
     return n, h.hexdigest()
 
 
+# ---- --families: the eleven plan queries of the loss, projector, optimiser and loader kernels, through cyhip.ops only
+# (the ops.*_plan interface does not change when the C side of a query does, so one file dumps two builds)
+KS = (1, 2, 3, 4, 8, 16, 17, 20, 64, 65)  # both sides of every K threshold: compiled K, the 16 / 17 split, the 64 cap
+ALIGNS = (1, 2, 4, 8, 16)
+COUNTS = (0, 1, 3, 4, 5, 15, 16, 17, 255, 256, 257, 1000, 4096, 4097, 65536, 65537, 262144, 262145, 2097152, 2097153,
+          10 ** 7)  # 0 and 1, and each grid cap (blocks x items per block) with the size one past it
+
+
+def family_calls():
+    """(family, ops function name, positional arguments) over the fixed grid, refused arguments included"""
+    import torch
+    dts = (torch.float32, torch.bfloat16, torch.float16)
+    P = itertools.product
+    for Cc, hid, dt, slope in P((0, 8, 12, 16, 32, 64, 128, 256, 512, 1024), (0, 1, 64, 128, 256, 512), dts,
+                                (0.01, 1.0, 1.5)):
+        yield "dense_proj", "dense_proj_plan", (Cc, hid, dt, slope)
+    for N, (H, W), k, pad, patch, kern in P((1, 3), ((24, 20), (64, 64), (33, 70), (256, 192)), KS, (0, 1, 3, 7),
+                                            (1, 2, 16, 64), (None, "per_displacement", "staged")):
+        yield "joint_patch", "joint_patch_plan", (N, H, W, k, pad, patch, kern)
+    for M, Cc, hid, out, dt in P((0, 1, 31, 32, 33, 64, 65, 16384, 16385, 65536, 65537, 10 ** 6), (0, 1, 32, 33, 256, 257),
+                                 (0, 16, 256, 257), (0, 1, 4, 256, 257), dts):
+        yield "pixel_mlp", "pixel_mlp_plan", (M, Cc, hid, out, dt)
+    for form, R, K, align in P(("rows", "pair", "logits"), COUNTS, KS, ALIGNS):
+        yield "imsat", "imsat_plan", (form, R, K, align)
+    for form, N, per, K, align in P(("images", "mixkl", "mixmse"), (0, 1, 2, 1024, 1025, 3000),
+                                    (0, 1, 10, 143, 4096, 1 << 20), KS, ALIGNS):
+        yield "mix", "mix_plan", (form, N, per, K, align)
+    for npix, K, Cc, align in P(COUNTS, KS, (0, 1, 4, 5), ALIGNS):
+        yield "prior", "prior_plan", ("dae", K, Cc, npix, align)
+    for K, Cc in P(KS, (0, 1, 16, 63, 64, 65, 256, 257, 512)):
+        yield "prior", "prior_plan", ("ortho", K, Cc, 0, 16)
+    for form, n, K, align in P(("adam", "axpy", "ema_multi", "gathermse"), COUNTS, (0,) + KS, ALIGNS):
+        yield "teacher", "teacher_plan", (form, n, K, align)
+    for form, n, align in P(("sgd", "adamw"), COUNTS, ALIGNS):
+        yield "optim", "optim_plan", (form, n, align)
+    for fam, npix, K, align in P(("entropy", "selfmse", "uamt", "mixmse"), COUNTS, KS, ALIGNS):
+        yield "wide_reg", "wide_reg_plan", (fam, npix, K, align)
+    for N, (H, W), ns, sigma, comp, it in P((0, 1, 3, 65535, 65536), ((8, 8), (32, 32), (64, 48), (224, 224), (1024, 1024),
+                                                                      (1025, 8)),
+                                            (0, 1, 16, 40, 100, 101, 400), (-1.0, 0.0, 1.0, 5.0, 16.0, 17.0),
+                                            (0.0, 0.1, 2.0), (-1, 0, 10)):
+        yield "slic", "slic_plan", (N, H, W, ns, sigma, comp, it)
+    for views, oh, ow in P((0, 1, 2, 4096, 4097), (0, 1, 8, 224, 512, 513), (0, 1, 8, 224, 512, 513)):
+        yield "augment", "augment_plan", (views, oh, ow)
+
+
+def dump_families(lib_path, show):
+    """per family: the record count and the SHA-256 of `arguments, then the refusal or key=value in the dict's order`"""
+    from cyhip import _lib
+    _lib.LIB_PATH = Path(lib_path)
+    from cyhip import ops
+    out = {}
+    for family, fn, args in family_calls():
+        try:
+            answer = " ".join(f"{k}={v}" for k, v in getattr(ops, fn)(*args).items())
+        except _lib.HipKernelError as e:
+            answer = "refused " + str(e).split("failed: ")[1]
+        line = f"{family} {' '.join(str(a).replace('torch.', '') for a in args)} : {answer}\n"
+        n, h = out.setdefault(family, [0, hashlib.sha256()])
+        out[family][0] = n + 1
+        h.update(line.encode())
+        if show:
+            sys.stdout.write(line)
+    return {family: (n, h.hexdigest()) for family, (n, h) in out.items()}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--families", action="store_true",
+                    help="the eleven ops.*_plan queries beside the conv planner's, count and hash per family")
     ap.add_argument("--lib", default=str(ROOT / "contrast-you_amd" / "lib" / "libcontrastyou_hip.so"))
     ap.add_argument("--print", action="store_true", dest="show", help="print every record instead of count and hash only")
     ap.add_argument("--reduced", action="store_true", help="unit leading dimensions and five batch sizes only")
     ap.add_argument("--all-settings", action="store_true", help="one run per switch setting of SETTINGS, count and hash each")
     ap.add_argument("--jobs", type=int, default=min(len(SETTINGS), os.cpu_count() or 1))
     a = ap.parse_args()
+    if a.families:
+        total = hashlib.sha256()
+        for family, (n, digest) in dump_families(a.lib, a.show).items():
+            total.update(digest.encode())
+            if not a.show:
+                print(f"{family:12s} {n} {digest}")
+        if not a.show:
+            print(f"{'(all)':12s} {total.hexdigest()}")
+        return
     if not a.all_settings:
         n, digest = dump(a.lib, a.show, a.reduced)
         if not a.show:
